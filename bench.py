@@ -9,10 +9,15 @@ SARS-CoV-2-shaped alignments (uvaia_amd/csrc/host/synth.c, seed 20241008) and ar
   python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: starts its own N rank processes)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-N=1 runs BASELINE.json config[1]: 1 000 queries x 100 000 references x 29 903 columns, 4-bit IUPAC planes, top-k 100, and adds
-to the same JSON line a `sweep` of other resident-query counts (1, 4, 16 queries x 1 M references: the HBM-bound regime) and
-BASELINE config[2] (10 000 x 1 000 000, --acgt), each with its own roofline.  With N>1 every rank holds its own 100 000-reference
+N=1 runs BASELINE.json config[1]: 1 000 queries x 100 000 references x 29 903 columns, 4-bit IUPAC planes, top-k 100.  A plain
+run does only what the headline needs: set-up, warm-up, the timed steps and the result line.  --full adds to the same JSON line
+the two parts of a step timed on their own, the CPU baseline, the in-run check against the oracle, a `sweep` of other
+resident-query counts (1, 4, 16, 64 queries x 1 M references: the HBM-bound regime) and BASELINE config[2] (10 000 x 1 000 000,
+--acgt), each with its own roofline, and the uvaiaball and uvaialign records.  With N>1 every rank holds its own 100 000-reference
 shard of the database (weak scaling).
+
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs) as DIR/<name>.npy, so that two builds can be
+compared output for output on the same seeded inputs.
 """
 import argparse
 import hashlib
@@ -76,7 +81,15 @@ def parse(argv=None):
     ap.add_argument("--align-only", action="store_true", help="only the uvaialign record (profiling runs); prints {\"align\": ...}")
     ap.add_argument("--ball-only", action="store_true", help="only the uvaiaball record (profiling runs); prints {\"ball\": ...}")
     ap.add_argument("--align-cpu-queries", type=int, default=1024, help="queries of the uvaialign CPU-baseline sample (0 = skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parts of a step timed on their own, the CPU baseline, the in-run oracle check, the sweep "
+                         "and the ball and align records (--no-sweep, --cpu-refs, --no-parity, --align-queries then select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; --gpus 1, headline search only)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.gpus > 1 or args.emulate_refshard > 1 or args.emulate_shard_of > 1 or args.align_only or args.ball_only):
+        ap.error("--dump-outputs writes the heaps of the single-GPU headline search: not with --gpus > 1, --emulate-*, --align-only or --ball-only")
+    return args
 
 
 def kernel_source_hash():
@@ -488,6 +501,33 @@ def parity_on_timed_path(O, capi, pq, gen, first, qseqs, qnames, mode, pool, nbe
                 and all(got[iq] == [(tuple(s), o) for o, _, s in gold.rows[iq]] for iq in range(oq.ntax)))
 
 
+DUMP_LIMIT_BYTES = 60 * 10**6         # --dump-outputs: the arrays stay under 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, capi, eng, seed):
+    """What a caller of the timed path receives after its last step: the heaps (uvaia_gpu_drain), finalised best-first as
+    heap_finalise_heap_qsort leaves them (capi.finalise_heaps), every array float64 (all values are integers below 2^53):
+      query_index [m]         the queries written (all of them unless the arrays would exceed DUMP_LIMIT_BYTES: then a seeded sample)
+      n_items [m]             heap[q]->n
+      max_incompatible [m]    heap[q]->max_incompatible, the query's final tolerance
+      scores [m, slots, 6]    the six scores of each heap entry, best first; -1 past n_items
+      ordinals [m, slots]     the reference ordinal of each heap entry, best first; -1 past n_items"""
+    n, T, sc, od = eng.drain()
+    nq, slots = len(n), sc.shape[1] - 1
+    per_query = 8 * (3 + slots * (sc.shape[2] + 1))
+    keep = min(nq, DUMP_LIMIT_BYTES // per_query)
+    pick = np.arange(nq) if keep == nq else np.sort(np.random.default_rng(seed).choice(nq, keep, replace=False))
+    scores = np.full((keep, slots, sc.shape[2]), -1.0)
+    ordinals = np.full((keep, slots), -1.0)
+    for i, rows in enumerate(capi.finalise_heaps(n[pick], sc[pick], od[pick])):
+        for j, (s, o) in enumerate(rows):
+            scores[i, j] = s
+            ordinals[i, j] = o
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("query_index", pick), ("n_items", n[pick]), ("max_incompatible", T[pick]), ("scores", scores), ("ordinals", ordinals)):
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def parity_on_refshard(O, capi, refshard, dist, pq, gen, qseqs, qnames, mode, nbest, world, rank, device, on_gpu):
     """N > 1: a sample of the stream through the protocol the timed step runs -- reference shards, pieces of two tiles so that there
     are several stripes, the exchange over the process group in use (RCCL on the node) -- and every rank compares the heaps and
@@ -732,9 +772,11 @@ def main():
     gc.enable()
     scan_ms, scan_launches, scan_bytes = eng.scan_stats(reset=True)
     admitted, demanded, dense_rescans = eng.replay_stats(reset=True)
-    # the two parts of a step on their own (untimed for `value`): derived planes only, scan + replay only
-    derive_ms = search_only_ms = 0.0
-    if world == 1:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, capi, eng, args.seed)
+    # the two parts of a step on their own (untimed for `value`, --full): derived planes only, scan + replay only
+    derive_ms = search_only_ms = None
+    if world == 1 and args.full:
         gc.disable()
         t_d = time.perf_counter()
         for _ in range(args.steps):
@@ -762,25 +804,25 @@ def main():
     derived_bytes = eng.derived_bytes_per_ref()
     packed_bytes = bytes_per_ref
 
-    # ---- CPU baseline and the in-run parity check (rank 0, N=1 only)
+    # ---- CPU baseline and the in-run parity check (--full; rank 0, N=1 only)
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not emu and (args.cpu_refs > 0 or not args.no_parity):
+    if args.full and rank == 0 and world == 1 and not emu and (args.cpu_refs > 0 or not args.no_parity):
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         if args.cpu_refs > 0:
             cpu = cpu_baseline(O, gen, first, qseqs, qnames, args.mode, pool, args.nbest, args.cpu_warm, args.cpu_refs, args.cpu_refs_1thread)
         if not args.no_parity:
             parity = parity_on_timed_path(O, capi, pq, gen, first, qseqs, qnames, args.mode, pool, args.nbest, min(args.parity_refs, args.refs), local_rank, args.qt)
-    if world > 1 and multi == "refshard" and not args.no_parity:      # every rank takes part; the oracle is the checker, as at N = 1
+    if args.full and world > 1 and multi == "refshard" and not args.no_parity:      # every rank takes part; the oracle is the checker, as at N = 1
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_lib as O
         parity = parity_on_refshard(O, capi, refshard, dist, pq, gen, qseqs, qnames, args.mode, args.nbest, world, rank, local_rank, on_gpu)
     cleanup.close()                    # disconnect_peers, then eng.close
 
-    # ---- other resident-query counts, driver-timed in the same run (rank 0, N=1 only)
+    # ---- other resident-query counts, driver-timed in the same run (--full; rank 0, N=1 only)
     sweep = ball = aligned = None
-    if rank == 0 and world == 1 and not emu and not args.no_sweep:
+    if args.full and rank == 0 and world == 1 and not emu and not args.no_sweep:
         sweep = []
         # (queries, mode, steps, references of the in-run oracle check: the oracle's cost grows with the query count)
         for nq_s, mode_s, steps_s, par_s in ((1, "iupac", 5, 4096), (4, "iupac", 5, 4096), (16, "iupac", 5, 4096), (64, "iupac", 5, 2048), (10000, "acgt", 2, 768)):
@@ -815,12 +857,13 @@ def main():
                        "queries": pq.ntax, "refs_per_gpu": args.refs, "nchar": args.nchar, "nbest": args.nbest, "pool": pool,
                        "mode": args.mode, "packed_bytes_per_ref": packed_bytes, "db_load_s": round(load_s, 2),
                        "query_prepare_s": round(t_q1 - t_q0, 2), "engine_open_s": round(t_q2 - t_q1, 2)},
-            "step_parts": {"includes_derived_planes": not args.search_only, "derived_planes_ms": round(derive_ms, 3), "scan_and_replay_ms": round(search_only_ms, 3),
+            "step_parts": {"includes_derived_planes": not args.search_only, "derived_planes_ms": None if derive_ms is None else round(derive_ms, 3),
+                           "scan_and_replay_ms": None if search_only_ms is None else round(search_only_ms, 3),
                            "derived_planes_kernel": {"kernel": "derive_all_kernel", "bound": "hbm", "read_bytes_per_ref": packed_bytes, "written_bytes_per_ref": derived_bytes,
-                                                     "achieved": round(local_refs * (packed_bytes + derived_bytes) / (derive_ms * 1e-3) / 1e9, 1) if (derive_ms > 0 and derived_bytes) else None,
+                                                     "achieved": round(local_refs * (packed_bytes + derived_bytes) / (derive_ms * 1e-3) / 1e9, 1) if (derive_ms and derived_bytes) else None,
                                                      "peak": HBM_PEAK_GBS, "unit": "GB/s (reads + writes, host-timed over its launches)"},
                            "note": "a step = planes derived from the resident packed records for this query set (uvaia_gpu_db_rederive) + pair scan + ordered replay; "
-                                   "the two parts timed on their own after the timed region (N = 1 only)"},
+                                   "the two parts timed on their own after the timed region (--full, N = 1 only)"},
             "roofline": roofline,
             "replay": {"admissions_per_step": admitted // max(1, args.steps + args.warmup + 1), "on_demand_per_step": demanded // max(1, args.steps + args.warmup + 1),
                        "dense_rescans_per_step": dense_rescans // max(1, args.steps + args.warmup + 1)},

@@ -14,7 +14,7 @@ for rep in 1 2; do
 for lib in uvaia_amd/lib/variants/libuvaia_gpu_*.so; do
   v=$(basename $lib .so); v=${v#libuvaia_gpu_}
   cp $lib uvaia_amd/lib/libuvaia_gpu.so || exit 1
-  timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-sweep --cpu-refs 0 --no-parity "$@" > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "variant $v failed"; tail -5 $O/${v}_$rep.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-sweep --cpu-refs 0 --no-parity "$@" > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "variant $v failed"; tail -5 $O/${v}_$rep.err; exit 1; }
   python - "$O/${v}_$rep.json" "$v" <<'P'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -o pipefail
 PART=${1:-ab}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/exp; mkdir -p $O
-C1="python bench.py --steps 10 --warmup 2 --no-sweep --cpu-refs 0"
+C1="python bench.py --full --steps 10 --warmup 2 --no-sweep --cpu-refs 0"
 show() { python - "$1" <<'P'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -36,7 +36,7 @@ for lab in s:
 P
 fi
 if [[ $PART == *d* ]]; then
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 python - <<'P'
 import json
 b = json.loads(open("gpurun_out/exp/bench_default.json").read().strip().splitlines()[-1])
@@ -49,7 +49,7 @@ fi
 
 if [[ $PART == *e* ]]; then
 for nq in 1 4 16 32; do for ph in 1; do
-  timeout -k 10 300 python bench.py --queries $nq --refs 1000000 --pool 1000000 --steps 5 --warmup 1 --no-sweep --cpu-refs 0 --parity-refs 4096  > $O/q${nq}_p$ph.json 2> $O/q${nq}_p$ph.err || { tail -5 $O/q${nq}_p$ph.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --queries $nq --refs 1000000 --pool 1000000 --steps 5 --warmup 1 --no-sweep --cpu-refs 0 --parity-refs 4096  > $O/q${nq}_p$ph.json 2> $O/q${nq}_p$ph.err || { tail -5 $O/q${nq}_p$ph.err; exit 1; }
   echo -n "queries $nq phases $ph: "; show $O/q${nq}_p$ph.json
 done; done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/q4trace -o q4 --output-format csv -- python bench.py --queries 4 --refs 1000000 --pool 1000000 --no-sweep --cpu-refs 0 --no-parity --steps 3 --warmup 1 > $O/q4trace.log 2>&1 || { tail -5 $O/q4trace.log; exit 1; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One measurement pass on the GPU box; everything lands in gpurun_out/measure/.  Usage: bash tools/measure_round.sh [a|b|c|e]
-#   a = the default bench.py run (config[1] + sweep + ball + align), kernel statistics and PMC passes of the config[1] step and of a config[2]-shaped step
+#   a = the full bench.py run (config[1] + sweep + ball + align), kernel statistics and PMC passes of the config[1] step and of a config[2]-shaped step
 #   b = --acgt config[1], the Q = 4 and config[1] kernel timelines, push-path and ingest timings
 #   c = reference-shard emulation (2, 4, 8 contexts on one GPU; 8 contexts with config[3]'s 10 000 --acgt queries)
 #   e = probes: dependent-load latency next to a streaming kernel, tiles the small-query replay opens, the replay's time split (timing build)
@@ -18,7 +18,7 @@ pmc() { name=$1; cfg=$2; shift 2
 if [[ $PART == *a* ]]; then
 [ -x tools/hbm_read ] || hipcc --offload-arch=gfx950 -O3 tools/hbm_read.hip -o tools/hbm_read || exit 1
 step hbm ceiling;    timeout -k 10 120 ./tools/hbm_read 4 > $O/hbm_read.txt 2>&1 || exit 1
-step bench default;  timeout -k 10 700 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
+step bench default;  timeout -k 10 700 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || { tail -5 $O/bench_default.err; exit 1; }
 step kernel stats;   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats -o c1 --output-format csv -- $C1 > $O/stats.log 2>&1 || exit 1
 step kernel stats config2; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats2 -o c2 --output-format csv -- $C2 > $O/stats2.log 2>&1 || exit 1
 pmc c1_fetch "$C1" FETCH_SIZE
@@ -40,7 +40,7 @@ step ball profile;   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/ba
 python tools/pmc_summary.py $(for d in c1_fetch c1_write c1_insts_a c1_waits c1_units c1_tcc c2_fetch c2_write c2_insts_a c2_waits c2_tcc q4_fetch q16_insts q16_waits; do echo $d=$(ls $O/pmc_$d/*counter_collection.csv | head -1); done) > $O/pmc_summary.json || exit 1
 fi
 if [[ $PART == *b* ]]; then
-step acgt config1;   timeout -k 10 300 python bench.py --mode acgt --steps 10 --warmup 2 --no-sweep --cpu-refs 2048 --align-queries 0 > $O/bench_acgt_c1.json 2> $O/bench_acgt_c1.err || exit 1
+step acgt config1;   timeout -k 10 300 python bench.py --full --mode acgt --steps 10 --warmup 2 --no-sweep --cpu-refs 2048 --align-queries 0 > $O/bench_acgt_c1.json 2> $O/bench_acgt_c1.err || exit 1
 step c1 timeline;    timeout -k 10 300 rocprofv3 --kernel-trace -d $O/c1trace -o c1 --output-format csv -- python bench.py --no-sweep --cpu-refs 0 --no-parity --align-queries 0 --steps 3 --warmup 1 > $O/c1trace.log 2>&1 || exit 1
 step q4 timeline;    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/q4 -o q4 --output-format csv -- python bench.py --queries 4 --refs 1000000 --pool 1000000 --no-sweep --cpu-refs 0 --no-parity --align-queries 0 --steps 5 --warmup 1 > $O/q4.log 2>&1 || exit 1
 step q16 timeline;   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/q16 -o q16 --output-format csv -- python bench.py --queries 16 --refs 1000000 --pool 1000000 --no-sweep --cpu-refs 0 --no-parity --align-queries 0 --steps 5 --warmup 1 > $O/q16.log 2>&1 || exit 1

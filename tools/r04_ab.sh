@@ -13,7 +13,7 @@ for lib in uvaia_amd/lib/variants/libuvaia_gpu_*.so; do
   v=$(basename $lib .so); v=${v#libuvaia_gpu_}
   [ "$v" = timing ] && continue
   cp $lib uvaia_amd/lib/libuvaia_gpu.so || exit 1
-  timeout -k 10 240 python bench.py --steps 10 --warmup 3 --no-sweep --cpu-refs 0 --no-parity --align-queries 0 "$@" > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "variant $v failed"; tail -3 $O/${v}_$rep.err; continue; }
+  timeout -k 10 240 python bench.py --full --steps 10 --warmup 3 --no-sweep --cpu-refs 0 --no-parity --align-queries 0 "$@" > $O/${v}_$rep.json 2> $O/${v}_$rep.err || { echo "variant $v failed"; tail -3 $O/${v}_$rep.err; continue; }
   python - "$O/${v}_$rep.json" "$v" <<'P'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; NQ=$2; shift; shift; O=gpurun_out/r04/$TAG; mkdir -p $O
 for tn in "$@"; do
   FL=""; if [ "$tn" != none ]; then for kv in ${tn//+/ }; do FL="$FL --tuning $kv"; done; fi
-  timeout -k 10 240 python bench.py --queries $NQ --refs 1000000 --pool 1000000 --steps 10 --warmup 2 --no-sweep --cpu-refs 0 --align-queries 0 $FL > $O/q${NQ}_$tn.json 2> $O/q${NQ}_$tn.err || { echo "$tn failed"; tail -5 $O/q${NQ}_$tn.err; exit 1; }
+  timeout -k 10 240 python bench.py --full --queries $NQ --refs 1000000 --pool 1000000 --steps 10 --warmup 2 --no-sweep --cpu-refs 0 --align-queries 0 $FL > $O/q${NQ}_$tn.json 2> $O/q${NQ}_$tn.err || { echo "$tn failed"; tail -5 $O/q${NQ}_$tn.err; exit 1; }
   python - $O/q${NQ}_$tn.json "$tn" <<'P'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 TAG=$1; shift; O=gpurun_out/r04/$TAG; mkdir -p $O
 for nq in "$@"; do
-  timeout -k 10 240 python bench.py --queries $nq --refs 1000000 --pool 1000000 --steps 10 --warmup 2 --no-sweep --cpu-refs 0 --align-queries 0 > $O/q$nq.json 2> $O/q$nq.err || { echo "q$nq failed"; tail -5 $O/q$nq.err; exit 1; }
+  timeout -k 10 240 python bench.py --full --queries $nq --refs 1000000 --pool 1000000 --steps 10 --warmup 2 --no-sweep --cpu-refs 0 --align-queries 0 > $O/q$nq.json 2> $O/q$nq.err || { echo "q$nq failed"; tail -5 $O/q$nq.err; exit 1; }
   python - $O/q$nq.json <<'P'
 import json, sys
 b = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,5 +1,5 @@
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-run() { python bench.py --refs 1000000 --steps 5 --warmup 1 --no-sweep --cpu-refs 0 --no-parity "$@" > /tmp/o.json 2>/tmp/o.err || { tail -3 /tmp/o.err; exit 1; }
+run() { python bench.py --full --refs 1000000 --steps 5 --warmup 1 --no-sweep --cpu-refs 0 --no-parity "$@" > /tmp/o.json 2>/tmp/o.err || { tail -3 /tmp/o.err; exit 1; }
   python - "$*" <<'P'
 import json, sys
 b = json.loads(open("/tmp/o.json").read().strip().splitlines()[-1])
