@@ -1,0 +1,79 @@
+/*
+ * uvaia_cluster.h -- C ABI of the MI355X (gfx950) one-pass canopy clustering behind `uvaiaclust`.
+ *
+ * What the reference's src/cluster.c computes (main 117-245, with src/fastaseq.c:127-260 and 522-560), restated from its code
+ * and not from its comments ("uvaiaclust", has the derivation; tests/cluster_restatement.c is the CPU restatement):
+ *
+ *   1. The site tables of src/utils.c:255-295 are never initialised by this program (initialise_acgt() is only called by the
+ *      query structure of uvaia/uvaiaball), so every pair of non-NUL bytes is "valid": every distance is the plain byte
+ *      inequality count.  'N' against 'A' counts, '-' against '-' does not.  The non-N count is the sequence length.
+ *   2. Hence the medoid-replacement test of add_seq_to_cluster (src/fastaseq.c:182) never holds: a cluster's medoid is its
+ *      first member, in both phases.
+ *   3. Phase 2 (check_seq_against_cluster, src/fastaseq.c:140-170), per queue, in push order.  A sequence's distance r to the
+ *      reference over the trimmed sites [trim, nchar - trim) and the positions p[0..n_score) of its first n_score differences
+ *      (relative to trim, -1 where there are fewer) are its scores.  Its candidates are, in medoid creation order: the first
+ *      medoid i1 with |r - stored(i1)| <= dist, then every later medoid i with 1 <= stored(i) <= 2 dist + 1 (score[0] is
+ *      overwritten by the truncated distance dist + 1 after the first failed comparison, src/fastaseq.c:158).  The first
+ *      candidate within dist wins; with none, the sequence founds a cluster and stores dist + 1 if any comparison happened,
+ *      else r.
+ *   4. The comparison window of phase 2 is [trim + m, nchar - trim + m) with m = max(0, min(p0_s, p0_medoid) - 1) (0 when
+ *      n_score is 0): the trimmed distance plus the differences in the tail [nchar - trim, nchar - trim + m).  Sites >= nchar
+ *      never count (the reference reads past the buffer there: undefined, so this is a defined choice).
+ *   5. The merge distance (merge_clusters, src/fastaseq.c:196-258) is the trimmed distance: equal, for the <= dist decision, to
+ *      the reference's count over the sites where any sequence differed from the reference.
+ *   6. The merge tree is for (c = Q; c > 1; c = c/2 + c%2): queue j < c/2 absorbs queue j + c/2 + c%2.  Both lists are stably
+ *      sorted by their score vectors, descending.  Each cluster of the absorbed list joins the first cluster of the other list
+ *      (sorted order, original clusters only) with |delta stored| <= dist and distance <= dist: its medoid, then its members,
+ *      are appended to that cluster's members.  Otherwise it is appended to the list.
+ *   7. The final order is the stable sort of queue 0 by member count descending, then the score vectors descending.
+ *   Defined choices where the reference has none: an empty absorbed queue merges as a no-op (the reference dereferences the
+ *   first element of the empty list) and an empty absorbing queue takes the other list as it is sorted; the out-of-bounds
+ *   write of src/fastaseq.c:160 has no effect; bytes 0 and >= 0x80 are refused (they index the site tables out of range).
+ *
+ * Conventions: plain C; 0 on success or a negative UVAIA_GPU_E* code, never exit(); uvaia_clust_last_error() gives the
+ * message.  One context = one GPU = one host thread at a time.  There is no CPU path: uvaia_clust_open fails with
+ * UVAIA_GPU_ENODEV without a gfx950 device.  Lower-case letters are upper-cased on the device (upper_kseq, src/fastaseq.c:151).
+ */
+#ifndef UVAIA_CLUSTER_H
+#define UVAIA_CLUSTER_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "uvaia_gpu.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct uvaia_clust_ctx uvaia_clust_ctx;
+
+/* new_cqueue (src/cluster.c:280-300) with its clamps already applied by the caller (dist <= nchar / 10, trim <= nchar / 2.1,
+ * negative values 0): the reference sequence (nchar bytes), the distance, the trim, n_score (-s) and the number of queues. */
+int  uvaia_clust_open (uvaia_clust_ctx **out, int device, const char *reference, int nchar, int dist, int trim, int n_score, int n_queues);
+void uvaia_clust_close (uvaia_clust_ctx *c);
+const char *uvaia_clust_last_error (const uvaia_clust_ctx *c);
+
+/* Phase 2 for n sequences of nchar bytes each (seq[i]); queue[i] in [0, n_queues) is the queue sequence i goes to.  Within a
+ * queue the order is push order.  Sequences are numbered by push ordinal from 0 across all calls.  A byte 0 or >= 0x80 fails
+ * the call with UVAIA_GPU_EALPHABET and leaves the context unusable (UVAIA_GPU_ESTATE afterwards). */
+int  uvaia_clust_push (uvaia_clust_ctx *c, int n, const char *const *seq, const int *queue);
+
+/* The merge tree and the final order.  No push after it. */
+int  uvaia_clust_finish (uvaia_clust_ctx *c);
+
+/* After finish: the number of clusters, and (each array nullable, sized by the caller)
+ *   medoid  [n_clusters]                   push ordinal of each cluster's medoid, in the final order
+ *   offsets [n_clusters + 1]               members of cluster k are members[offsets[k] .. offsets[k + 1])
+ *   members [pushed - n_clusters]          push ordinals of the other members, in member-list order (the csv line after the medoid)
+ *   scores  [n_clusters * (n_score + 2)]   the stored score vectors: stored distance, p[0..n_score), nchar */
+int  uvaia_clust_result (uvaia_clust_ctx *c, int *n_clusters, int64_t *medoid, int64_t *offsets, int64_t *members, int *scores);
+
+/* Kernel milliseconds of each phase so far: prep (distance to the reference), queue (phase 2), merge (the tree), and the
+ * number of sequences pushed. */
+int  uvaia_clust_stats (uvaia_clust_ctx *c, double *prep_ms, double *queue_ms, double *merge_ms, int64_t *pushed);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -1,0 +1,127 @@
+"""ctypes binding of include/uvaia_cluster.h (tests and tools reach the clustering of `uvaiaclust` through it)."""
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+# every symbol include/uvaia_cluster.h declares (tests check the library exports all of them)
+SYMBOLS = [
+    "uvaia_clust_open", "uvaia_clust_close", "uvaia_clust_last_error", "uvaia_clust_push", "uvaia_clust_finish", "uvaia_clust_result",
+    "uvaia_clust_stats",
+]
+
+
+class ClusterError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__("uvaia_clust error %d: %s" % (code, msg))
+        self.code = code
+
+
+_ready = False
+
+
+def _lib():
+    global _ready
+    L = capi.load_library()
+    if not _ready:
+        vp, pi, pl = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        L.uvaia_clust_open.argtypes = [C.POINTER(vp), C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.uvaia_clust_close.argtypes = [vp]
+        L.uvaia_clust_close.restype = None
+        L.uvaia_clust_last_error.argtypes = [vp]
+        L.uvaia_clust_last_error.restype = C.c_char_p
+        L.uvaia_clust_push.argtypes = [vp, C.c_int, C.POINTER(C.c_char_p), pi]
+        L.uvaia_clust_finish.argtypes = [vp]
+        L.uvaia_clust_result.argtypes = [vp, pi, pl, pl, pl, pi]
+        L.uvaia_clust_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), pl]
+        _ready = True
+    return L
+
+
+class Result:
+    """The clusters in their final order: medoid push ordinals, member lists (without the medoid) and stored score vectors."""
+
+    def __init__(self, medoid, offsets, members, scores):
+        self.medoid, self.offsets, self.members, self.scores = medoid, offsets, members, scores
+
+    def clusters(self):
+        """[(medoid, [members...]), ...] as Python ints"""
+        m, off, mem = self.medoid.tolist(), self.offsets.tolist(), self.members.tolist()
+        return [(m[k], mem[off[k]:off[k + 1]]) for k in range(len(m))]
+
+
+class Clusterer:
+    """One clustering on one GPU (new_cqueue, src/cluster.c:280-300): parameters already clamped by the caller."""
+
+    def __init__(self, reference, dist=1, trim=0, n_score=1, n_queues=1, device=0):
+        self.L = _lib()
+        self.n_score = n_score
+        self.ptr = C.c_void_p()
+        rc = self.L.uvaia_clust_open(C.byref(self.ptr), device, reference, len(reference), dist, trim, n_score, n_queues)
+        if rc:
+            raise ClusterError(rc, (self.L.uvaia_clust_last_error(None) or b"").decode())
+        self.pushed = 0
+
+    def _chk(self, rc):
+        if rc:
+            raise ClusterError(rc, (self.L.uvaia_clust_last_error(self.ptr) or b"").decode())
+
+    def close(self):
+        if self.ptr:
+            self.L.uvaia_clust_close(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def push(self, seqs, queues):
+        """seqs: list of bytes of the reference's length; queues: the queue of each"""
+        n = len(seqs)
+        if not n:
+            return
+        arr = (C.c_char_p * n)(*seqs)
+        q = np.ascontiguousarray(queues, dtype=np.int32)
+        self._chk(self.L.uvaia_clust_push(self.ptr, n, arr, q.ctypes.data_as(C.POINTER(C.c_int))))
+        self.pushed += n
+
+    def finish(self):
+        self._chk(self.L.uvaia_clust_finish(self.ptr))
+
+    def result(self):
+        nc = C.c_int(0)
+        self._chk(self.L.uvaia_clust_result(self.ptr, C.byref(nc), None, None, None, None))
+        k = nc.value
+        medoid = np.zeros(k, dtype=np.int64)
+        offsets = np.zeros(k + 1, dtype=np.int64)
+        members = np.zeros(max(self.pushed - k, 1), dtype=np.int64)
+        scores = np.zeros((max(k, 1), self.n_score + 2), dtype=np.int32)
+        pl = C.POINTER(C.c_int64)
+        self._chk(self.L.uvaia_clust_result(self.ptr, C.byref(nc), medoid.ctypes.data_as(pl), offsets.ctypes.data_as(pl), members.ctypes.data_as(pl),
+                                            scores.ctypes.data_as(C.POINTER(C.c_int))))
+        return Result(medoid, offsets, members[:self.pushed - k], scores[:k])
+
+    def stats(self):
+        a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
+        self._chk(self.L.uvaia_clust_stats(self.ptr, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return {"prep_ms": a.value, "queue_ms": b.value, "merge_ms": c.value, "pushed": n.value}
+
+
+def queues_round_robin(file_sizes, n_queues):
+    """src/cluster.c:164-181: within each input file sequence k goes to queue k mod Q; the next file starts again at queue 0"""
+    return np.concatenate([np.arange(n, dtype=np.int32) % n_queues for n in file_sizes]) if file_sizes else np.zeros(0, dtype=np.int32)
+
+
+def clamp_parameters(nchar, dist, trim, n_score):
+    """src/cluster.c:131-132 and new_cqueue (src/cluster.c:287-289)"""
+    dist = max(dist, 0)
+    n_score = max(n_score, 0)
+    trim = max(trim, 0)
+    if trim > nchar / 2.1:
+        trim = int(nchar / 2.1)
+    if dist > nchar // 10:
+        dist = nchar // 10
+    return dist, trim, n_score

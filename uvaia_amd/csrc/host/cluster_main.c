@@ -1,0 +1,199 @@
+/*
+ * cluster_main.c -- `uvaiaclust`: one-pass canopy deduplication of aligned sequences.  Same options, queue assignment and output
+ * files as the reference's src/cluster.c; phase 2 and the merge tree run on the GPU through include/uvaia_cluster.h, whose header
+ * states what is computed.  The partial saves of src/cluster.c:197-199,228-229 (their timing decides them) are not made: only the
+ * final <prefix>.csv.xz and <prefix>.aln.xz are written.
+ */
+#define _GNU_SOURCE
+#include <getopt.h>
+#include <libgen.h>
+#include <omp.h>
+
+#include "cli_common.h"
+#include "fastaseq.h"
+#include "../../../include/uvaia_cluster.h"
+
+/* read_reference_sequence (src/cluster.c:260-277): the first record of the file, filled by up to nseqs - 1 more while Ns remain
+   (accumulate_reference_sequence, src/fastaseq.c:488-512), remaining Ns replaced by A (src/fastaseq.c:514-520) */
+static char *
+read_reference (const char *filename, int nseqs, int *nchar)
+{
+  char *ref = NULL;
+  int count = 0xff, len = -1;
+  readfasta_t rfas = new_readfasta (filename);
+  fprintf (stderr, "Generating a reference from up to %d sequences in %s\n", nseqs, filename);
+  for (int i = 0; i < nseqs && count && readfasta_next (rfas) > 0; i++) {
+    if (len < 0) len = (int) rfas->seqlength;
+    else if (len != (int) rfas->seqlength) biomcmc_error ("Unaligned sequences: first seq has %d sites but %s has %lu sites\n", len, rfas->name, (unsigned long) rfas->seqlength);
+    const char *s = rfas->seq;
+    count = 0;
+    if (!ref) {
+      ref = (char *) biomcmc_malloc ((size_t) len + 1);
+      for (int k = 0; k < len; k++) {
+        ref[k] = s[k];
+        if (s[k] != 'A' && s[k] != 'C' && s[k] != 'G' && s[k] != 'T') { ref[k] = 'N'; count++; }
+      }
+      ref[len] = '\0';
+    } else for (int k = 0; k < len; k++) if (ref[k] == 'N') {
+      if (s[k] == 'A' || s[k] == 'C' || s[k] == 'G' || s[k] == 'T') ref[k] = s[k];
+      else count++;
+    }
+  }
+  del_readfasta (rfas);
+  if (!ref) biomcmc_error ("No sequence found in %s to build a reference from", filename);
+  count = 0;
+  for (int k = 0; k < len; k++) if (ref[k] == 'N') { ref[k] = 'A'; count++; }
+  if (count) fprintf (stderr, "Reference still had %d Ns or indels which were replaced arbitrarily (it only makes program a bit slower).", count);
+  *nchar = len;
+  return ref;
+}
+
+typedef struct { char **v; int64_t n, cap; } str_vec;
+
+static void
+str_vec_push (str_vec *s, char *x)
+{
+  if (s->n == s->cap) { s->cap = s->cap ? 2 * s->cap : 4096; s->v = (char **) biomcmc_realloc (s->v, (size_t) s->cap * sizeof (char *)); }
+  s->v[s->n++] = x;
+}
+
+typedef struct { int device, nchar, dist, trim, snps, n_clust; char *refseq; uvaia_clust_ctx *ctx; } gpu_state;
+
+/* the context is opened at the first push: errors in the input found by then are reported as such, GPU or not */
+static void
+open_context (gpu_state *g)
+{
+  if (g->ctx) return;
+  if (uvaia_clust_open (&g->ctx, g->device, g->refseq, g->nchar, g->dist, g->trim, g->snps, g->n_clust)) biomcmc_error ("%s", uvaia_clust_last_error (NULL));
+}
+
+static void
+push_batch (gpu_state *g, str_vec *seqs, int64_t from, int *queue, int n)
+{
+  if (!n) return;
+  open_context (g);
+  if (uvaia_clust_push (g->ctx, n, (const char *const *) seqs->v + from, queue)) biomcmc_error ("%s", uvaia_clust_last_error (g->ctx));
+}
+
+int
+main (int argc, char **argv)
+{
+  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, ch;   /* src/cluster.c:57-64 */
+  const char *out = "cluster_uvaia", *ref_file = NULL;
+  static const struct option longopts[] = {
+    {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
+    {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {0, 0, 0, 0}};
+  while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:", longopts, NULL)) != -1) switch (ch) {
+    case 'h': help = 1; break;
+    case 'v': version = 1; break;
+    case 'd': dist = atoi (optarg); break;
+    case 1000: trim = atoi (optarg); break;
+    case 'p': pool = atoi (optarg); break;
+    case 's': snps = atoi (optarg); break;
+    case 'r': if (ref_file) errors++; ref_file = optarg; break;
+    case 'o': out = optarg; break;
+    case 1001: device = atoi (optarg); break;
+    default: errors++;
+  }
+  const char **fasta = (const char **) argv + optind;
+  const int n_fasta = argc - optind;
+  if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
+  if (help || errors || n_fasta < 1 || n_fasta > 1024) {
+    printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... [-o <without suffix>]\n\n", basename (argv[0]));
+    printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
+    printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
+    printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
+    printf ("  -p, --pool=<int>                 Pool size, i.e. number of clustering queues (should be larger than avail threads)\n");
+    printf ("  -s, --snps=<int>                 how many SNPs w.r.t. reference it keeps track (default=1, should be small number)\n");
+    printf ("  -r, --reference=<ref.fa(.gz,.xz)> reference sequence (medoids are furthest from it)\n");
+    printf ("  <seqs.fa(.gz,.xz)>               alignments to merge\n");
+    printf ("  -o, --output=<without suffix>    prefix of xzipped output alignment and cluster table files\n");
+    printf ("  --device=<int>                   GPU to use (default 0)\n");
+    if (help) {
+      printf ("One-pass clustering similar to canopy clustering with single, tight distance, computed on the GPU.\n");
+      printf ("A pool of independent clustering queues is created, such that each sequence is compared to only one of them at first.\n\n");
+    }
+    return (help && !errors) ? EXIT_SUCCESS : EXIT_FAILURE;
+  }
+  if (dist < 0) dist = 0;                                                  /* src/cluster.c:131-132 */
+  if (snps < 0) snps = 0;
+  fprintf (stderr, "Experimental program: %s package: %s\n", basename (argv[0]), UVAIA_PACKAGE_STRING);
+  int n_clust = omp_get_max_threads ();                                    /* src/cluster.c:136-142 */
+  if (pool >= n_clust) n_clust = pool;
+  int64_t time0[2];
+  biomcmc_get_time (time0);
+
+  int nchar = 0;
+  char *refseq = ref_file ? read_reference (ref_file, 1, &nchar) : read_reference (fasta[0], 1024, &nchar);
+  if (trim < 0) trim = 0;                                                  /* new_cqueue, src/cluster.c:287-289 */
+  if (trim > nchar / 2.1) trim = (int) (nchar / 2.1);
+  if (dist > nchar / 10) dist = nchar / 10;
+  fprintf (stderr, "Creating a pool of %d cluster queues; maximum distance is %d, and %d SNP locations are kept\n", n_clust, dist, snps);
+  gpu_state g = {device, nchar, dist, trim, snps, n_clust, refseq, NULL};
+
+  /* read every file, sequence k of a file to queue k mod Q (src/cluster.c:164-181); push in batches of 4 Q */
+  str_vec names = {0}, seqs = {0};
+  const int batch = 4 * n_clust;
+  int *queue = (int *) biomcmc_malloc ((size_t) batch * sizeof (int));
+  int64_t count = 0;
+  for (int j = 0; j < n_fasta; j++) {
+    readfasta_t rfas = new_readfasta (fasta[j]);
+    int64_t k = 0, from = seqs.n;
+    int fill = 0;
+    while (readfasta_next (rfas) >= 0) {
+      if ((int64_t) rfas->seqlength != nchar)
+        biomcmc_error ("%s cannot work with unaligned sequences; sequence %s has %lu sites while reference has %d.", UVAIA_PACKAGE_STRING, rfas->name ? rfas->name : "(unnamed)", (unsigned long) rfas->seqlength, nchar);
+      for (int i = 0; i < nchar; i++) if ((unsigned char) rfas->seq[i] >= 0x80)   /* they index the reference's site tables out of range */
+        biomcmc_error ("sequence %s holds byte 0x%02x at site %d: only bytes 1-127 are defined", rfas->name ? rfas->name : "(unnamed)", (unsigned char) rfas->seq[i], i + 1);
+      str_vec_push (&seqs, rfas->seq); rfas->seq = NULL; rfas->seqlength = 0;
+      str_vec_push (&names, rfas->name); rfas->name = NULL;
+      queue[fill++] = (int) (k++ % n_clust);
+      count++;
+      if (fill == batch) { push_batch (&g, &seqs, from, queue, fill); from += fill; fill = 0; }
+    }
+    push_batch (&g, &seqs, from, queue, fill);
+    del_readfasta (rfas);
+    fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", fasta[j], biomcmc_update_elapsed_time (time0), (long) count);
+  }
+  open_context (&g);
+  free (refseq);
+  uvaia_clust_ctx *ctx = g.ctx;
+  if (uvaia_clust_finish (ctx)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
+  int n_out = 0;
+  uvaia_clust_result (ctx, &n_out, NULL, NULL, NULL, NULL);
+  int64_t *medoid = (int64_t *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int64_t)), *offsets = (int64_t *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int64_t));
+  int64_t *members = (int64_t *) biomcmc_malloc ((size_t) (count - n_out + 1) * sizeof (int64_t));
+  if (uvaia_clust_result (ctx, &n_out, medoid, offsets, members, NULL)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
+  double prep_ms = 0, queue_ms = 0, merge_ms = 0;
+  uvaia_clust_stats (ctx, &prep_ms, &queue_ms, &merge_ms, NULL);
+  uvaia_clust_close (ctx);
+
+  /* save_neighbours_to_xz_file and save_cluster_to_xz_file (src/fastaseq.c:293-392) for the final order */
+  size_t outlength = 0;
+  char *outfilename = outfile_from_prefix (out, &outlength);
+  strcpy (outfilename + outlength, ".csv.xz");
+  file_compress_t csv = biomcmc_open_compress (outfilename, "w");
+  int bad = 0;
+  for (int c = 0; c < n_out; c++) {
+    bad += biomcmc_write_compress (csv, names.v[medoid[c]]) != (int) strlen (names.v[medoid[c]]);
+    for (int64_t m = offsets[c]; m < offsets[c + 1]; m++) {
+      bad += biomcmc_write_compress (csv, ",") != 1;
+      bad += biomcmc_write_compress (csv, names.v[members[m]]) != (int) strlen (names.v[members[m]]);
+    }
+    bad += biomcmc_write_compress (csv, "\n") != 1;
+  }
+  biomcmc_close_compress (csv);
+  if (bad) fprintf (stderr, "File %s may not be correctly compressed, %d error%s occurred.\n", outfilename, bad, bad > 1 ? "s" : "");
+  strcpy (outfilename + outlength, ".aln.xz");
+  file_compress_t aln = biomcmc_open_compress (outfilename, "w");
+  for (int c = 0; c < n_out; c++) write_fasta_record (aln, names.v[medoid[c]], seqs.v[medoid[c]]);
+  biomcmc_close_compress (aln);
+  fprintf (stderr, "%d clusters from %ld sequences; GPU kernels: prep %.3lf ms, queues %.3lf ms, merge %.3lf ms\n", n_out, (long) count, prep_ms, queue_ms, merge_ms);
+  fprintf (stderr, "Finished sorting clusters and saving files in %lf secs\n", biomcmc_update_elapsed_time (time0));
+
+  for (int64_t i = 0; i < seqs.n; i++) { free (seqs.v[i]); free (names.v[i]); }
+  free (seqs.v); free (names.v); free (queue); free (medoid); free (offsets); free (members); free (outfilename);
+  return EXIT_SUCCESS;
+}

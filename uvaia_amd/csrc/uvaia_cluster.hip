@@ -1,0 +1,628 @@
+// uvaia_cluster.hip -- MI355X (gfx950 / CDNA4) one-pass canopy clustering behind include/uvaia_cluster.h (`uvaiaclust`).
+//
+// What it replaces in the reference: phase 2 of src/cluster.c:163-205 (check_seq_against_cluster, src/fastaseq.c:140-170, under
+// "#pragma omp parallel for" over the queues) and the merge tree of src/cluster.c:216-233 (merge_clusters, src/fastaseq.c:196-258).
+// The semantics are those the header states (the reference's code, not its comments); DESIGN.md "uvaiaclust" has the derivation.
+//
+// Design:
+//   * every pushed row stays resident (pitch padded to 64 B with zero bytes, which never differ).  A lane compares 16 B per load:
+//     the mismatching bytes of a 32-bit word are the high bits of ((x & 0x7f..) + 0x7f.. | x) & 0x80.. with x = a ^ b, counted by
+//     v_bcnt.  A wave compares 4 KB per round trip and stops once its count passes the distance.
+//   * prep: one wave per pushed row.  It upper-cases the row in place, flags bytes 0 and >= 0x80, counts the differences from the
+//     reference over the trimmed sites and records the first n_score of them (ballot-free: a wave prefix sum of the per-lane counts).
+//   * queue: one workgroup of four waves per queue, for the rows of one push in queue order.  The stored distances of the queue's
+//     medoids live in LDS (global memory past LDS_ST of them).  Wave 0 collects the next four candidates of the ordered candidate
+//     list (header, item 3) by ballots over the stored distances, each wave compares one of them, and the lowest matching wins.
+//   * merge: one launch per round of the tree, one wave per (pair, absorbed cluster): the host gives each its window of the
+//     absorbing list (binary search on the sorted stored distances), the wave compares in order and stops at the first match.
+//     The host does the stable sorts and splices the member lists.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/uvaia_cluster.h"
+
+namespace {
+
+constexpr int QTPB = 256;               // queue kernel: four waves, one candidate each
+constexpr int QW = QTPB / 64;
+constexpr int LDS_ST = 14336;           // stored distances of a queue's first medoids kept in LDS (56 KB)
+constexpr int PTPB = 256;               // prep and merge: one wave per row / item
+constexpr int UNROLL = 4;               // 16-B loads in flight per lane in a comparison: 4 KB per wave per round trip
+
+__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
+__device__ __forceinline__ uint32_t expand4(uint32_t b) { return ((b & 1u) << 7) | ((b & 2u) << 14) | ((b & 4u) << 21) | ((b & 8u) << 28); }
+__device__ __forceinline__ uint32_t pack4(uint32_t m) { return ((m >> 7) & 1u) | ((m >> 14) & 2u) | ((m >> 21) & 4u) | ((m >> 28) & 8u); }
+
+// bytes j of the 16-byte chunk at pos with lo <= pos + j < hi
+__device__ __forceinline__ uint32_t window16(int pos, int lo, int hi)
+{
+  const int a = max(lo - pos, 0), b = min(hi - pos, 16);
+  return b <= a ? 0u : (((1u << b) - 1u) & ~((1u << a) - 1u));
+}
+
+// 16-bit mask of the bytes that differ between two 16-byte chunks, inside the window w16
+__device__ __forceinline__ uint32_t diff_mask16(uint4 a, uint4 b, uint32_t w16)
+{
+  const uint32_t m = pack4(nz_bytes(a.x ^ b.x)) | (pack4(nz_bytes(a.y ^ b.y)) << 4) | (pack4(nz_bytes(a.z ^ b.z)) << 8) | (pack4(nz_bytes(a.w ^ b.w)) << 12);
+  return m & w16;
+}
+
+__device__ __forceinline__ int diff_count16(uint4 a, uint4 b, uint32_t w16)
+{
+  if (w16 == 0xffffu)
+    return __popc(nz_bytes(a.x ^ b.x)) + __popc(nz_bytes(a.y ^ b.y)) + __popc(nz_bytes(a.z ^ b.z)) + __popc(nz_bytes(a.w ^ b.w));
+  return __popc(nz_bytes(a.x ^ b.x) & expand4(w16)) + __popc(nz_bytes(a.y ^ b.y) & expand4(w16 >> 4)) +
+         __popc(nz_bytes(a.z ^ b.z) & expand4(w16 >> 8)) + __popc(nz_bytes(a.w ^ b.w) & expand4(w16 >> 12));
+}
+
+__device__ __forceinline__ int wave_sum(int v)
+{
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Differences between rows a and b over the sites [lo, hi), by one wave; stops once the count passes limit (the value returned is
+// then some count above limit).  Rows are 16-byte aligned and padded to a multiple of 64 bytes, hi <= the row's length.
+__device__ int wave_distance(const uint8_t *__restrict__ a, const uint8_t *__restrict__ b, int lo, int hi, int limit)
+{
+  const int lane = threadIdx.x & 63;
+  int total = 0;
+  for (int base = lo & ~15; base < hi; base += 64 * 16 * UNROLL) {
+    uint4 x[UNROLL], y[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int pos = base + (u * 64 + lane) * 16;
+      if (pos < hi) { x[u] = *(const uint4 *)(a + pos); y[u] = *(const uint4 *)(b + pos); }
+      else { x[u] = make_uint4(0, 0, 0, 0); y[u] = x[u]; }
+    }
+    int cnt = 0;
+#pragma unroll
+    for (int u = 0; u < UNROLL; u++) {
+      const int pos = base + (u * 64 + lane) * 16;
+      cnt += diff_count16(x[u], y[u], window16(pos, lo, hi));
+    }
+    total += wave_sum(cnt);
+    if (total > limit) break;
+  }
+  return total;
+}
+
+// One wave per pushed row (ordinals first .. first + n): upper-case in place, flag bytes 0 and >= 0x80 (bad_out = lowest such
+// row of the push), distance to the reference over [trim, nchar - trim) and the first n_score differing sites (relative to trim).
+__global__ __launch_bounds__(PTPB) void clust_prep_kernel(uint8_t *__restrict__ rows, size_t pitch, long long first, int n, const uint8_t *__restrict__ ref, int nchar,
+                                                          int trim, int n_score, int *__restrict__ dist_out, int *__restrict__ p_out, int *__restrict__ bad_out)
+{
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * (PTPB / 64) + (threadIdx.x >> 6);
+  if (w >= n) return;
+  const long long o = first + w;
+  uint8_t *row = rows + (size_t)o * pitch;
+  int *p = p_out + (size_t)o * n_score;
+  const int lo = trim, hi = nchar - trim;
+  int total = 0;
+  uint32_t bad = 0;
+  for (int base = 0; base < nchar; base += 64 * 16) {
+    const int pos = base + lane * 16;
+    uint32_t dm = 0;
+    if (pos < nchar) {
+      uint4 v = *(uint4 *)(row + pos);
+      const uint4 r = *(const uint4 *)(ref + pos);
+      const uint32_t vw = window16(pos, 0, nchar);
+      uint32_t *vv = &v.x;
+      uint32_t lower_any = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const uint32_t x = vv[k], in = expand4(vw >> (4 * k));
+        bad |= ((~nz_bytes(x) & 0x80808080u) | (x & 0x80808080u)) & in;          // a zero byte, or one >= 0x80
+        const uint32_t lower = (x + 0x1f1f1f1fu) & ~(x + 0x05050505u) & ~x & 0x80808080u & in;   // 'a'..'z' (no carries for bytes < 0x80)
+        vv[k] = x - (lower >> 2);
+        lower_any |= lower;
+      }
+      if (lower_any) *(uint4 *)(row + pos) = v;
+      dm = diff_mask16(v, r, window16(pos, lo, hi));
+    }
+    const int cnt = __popc(dm);
+    if (total < n_score) {            // wave-uniform: where the first n_score differences fall
+      int incl = cnt;
+      for (int s = 1; s < 64; s <<= 1) { const int t = __shfl_up(incl, s, 64); if (lane >= s) incl += t; }
+      int rank = total + incl - cnt;
+      for (uint32_t m = dm; m && rank < n_score; m &= m - 1, rank++) p[rank] = pos + __ffs(m) - 1 - trim;
+    }
+    total += wave_sum(cnt);
+  }
+  if (lane == 0) {
+    dist_out[o] = total;
+    for (int k = total; k < n_score; k++) p[k] = -1;
+  }
+  if (__ballot(bad != 0) && lane == 0) atomicMin(bad_out, w);
+}
+
+// Phase 2 for the rows of one push: workgroup q takes the ordinals qlist[qoff[q] .. qoff[q + 1]) in order against queue q's medoids
+// (m_ord / m_st: cap slots per queue, m_count of them used).  join[o] = slot of the medoid o joined, or -1 - slot if o founded one.
+__global__ __launch_bounds__(QTPB) void clust_queue_kernel(const uint8_t *__restrict__ rows, size_t pitch, int nchar, int trim, int d, int n_score,
+                                                           const int *__restrict__ dist, const int *__restrict__ p, const int *__restrict__ qoff,
+                                                           const int *__restrict__ qlist, int *__restrict__ m_count, int *__restrict__ m_ord_all,
+                                                           int *__restrict__ m_st_all, int cap, int *__restrict__ join)
+{
+  __shared__ int st[LDS_ST];
+  __shared__ int cand[QW], hit[QW];
+  __shared__ int s_ncand, s_next, s_after;
+  const int q = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k0 = qoff[q], k1 = qoff[q + 1];
+  if (k0 == k1) return;
+  int *m_ord = m_ord_all + (size_t)q * cap, *m_st = m_st_all + (size_t)q * cap;
+  int n = m_count[q];
+  for (int i = threadIdx.x; i < min(n, LDS_ST); i += QTPB) st[i] = m_st[i];
+  __syncthreads();
+  const int d2 = 2 * d + 1;
+
+  for (int k = k0; k < k1; k++) {
+    const int o = qlist[k];
+    const int r = dist[o];
+    const int ps = n_score ? p[(size_t)o * n_score] : 0;
+    int pos = 0, winner = -1;
+    bool compared = false;
+    if (threadIdx.x == 0) s_after = 0;
+    __syncthreads();
+    while (pos < n) {
+      if (wave == 0) {   // the next QW candidates in list order: the first medoid within the ring of r, then those with 1 <= stored <= 2d + 1
+        int got = 0, i = pos, last = pos;
+        bool after = s_after != 0;
+        while (got < QW && i < n) {
+          const int idx = i + lane;
+          bool pred = false;
+          if (idx < n) {
+            const int s = idx < LDS_ST ? st[idx] : m_st[idx];
+            pred = after ? (s >= 1 && s <= d2) : (abs(r - s) <= d);
+          }
+          unsigned long long m = __ballot(pred);
+          if (!m) { i += 64; continue; }
+          if (!after) {
+            const int b = __ffsll(m) - 1;
+            if (lane == 0) cand[got] = i + b;
+            got++; after = true; i = i + b + 1;
+            continue;
+          }
+          while (m && got < QW) { const int b = __ffsll(m) - 1; if (lane == 0) cand[got] = i + b; got++; last = i + b; m &= m - 1; }
+          i = got == QW ? last + 1 : i + 64;
+        }
+        if (lane == 0) { s_ncand = got; s_next = i; s_after = after; }
+      }
+      __syncthreads();
+      const int nc = s_ncand;
+      if (nc == 0) break;
+      compared = true;
+      if (wave < nc) {
+        const int slot = cand[wave];
+        const int m = m_ord[slot];
+        int minloc = 0;
+        if (n_score) minloc = max(0, min(ps, p[(size_t)m * n_score]) - 1);
+        const int lo = trim + minloc, hi = min(nchar, nchar - trim + minloc);
+        const int dd = wave_distance(rows + (size_t)o * pitch, rows + (size_t)m * pitch, lo, hi, d);
+        if (lane == 0) hit[wave] = dd <= d;
+      }
+      __syncthreads();
+      for (int w = 0; w < nc; w++) if (hit[w]) { winner = cand[w]; break; }
+      pos = s_next;
+      __syncthreads();     // cand / hit / s_next are rewritten by the next round
+      if (winner >= 0) break;
+    }
+    if (winner >= 0) {
+      if (threadIdx.x == 0) join[o] = winner;
+    } else {
+      if (threadIdx.x == 0) {
+        const int stored = compared ? d + 1 : r;
+        m_ord[n] = o; m_st[n] = stored;
+        if (n < LDS_ST) st[n] = stored;
+        join[o] = -1 - n;
+      }
+      n++;
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) m_count[q] = n;
+}
+
+// One wave per item of a merge round: item i compares row item_ord[i] with the rows list_ord[item_lo[i] .. item_hi[i]) in order over
+// the trimmed sites and writes the first position within d (or -1) to target[i].
+__global__ __launch_bounds__(PTPB) void clust_merge_kernel(const uint8_t *__restrict__ rows, size_t pitch, int nchar, int trim, int d, const int *__restrict__ item_ord,
+                                                           const int *__restrict__ item_lo, const int *__restrict__ item_hi, const int *__restrict__ list_ord,
+                                                           int n_items, int *__restrict__ target)
+{
+  const int w = blockIdx.x * (PTPB / 64) + (threadIdx.x >> 6);
+  if (w >= n_items) return;
+  const uint8_t *a = rows + (size_t)item_ord[w] * pitch;
+  int t = -1;
+  for (int j = item_lo[w], e = item_hi[w]; j < e; j++)
+    if (wave_distance(a, rows + (size_t)list_ord[j] * pitch, trim, nchar - trim, d) <= d) { t = j; break; }
+  if ((threadIdx.x & 63) == 0) target[w] = t;
+}
+
+thread_local std::string g_open_error;
+
+}  // namespace
+
+struct uvaia_clust_ctx {
+  int device = 0, nchar = 0, dist = 0, trim = 0, n_score = 0, n_queues = 0;
+  size_t pitch = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  uint8_t *d_ref = nullptr, *d_rows = nullptr;
+  int *d_dist = nullptr, *d_p = nullptr, *d_join = nullptr, *d_bad = nullptr;
+  int *d_qoff = nullptr, *d_qlist = nullptr, *d_mcount = nullptr, *d_mord = nullptr, *d_mst = nullptr;
+  size_t rows_cap = 0, qlist_cap = 0;
+  int m_cap = 0;
+  long long pushed = 0;
+  std::vector<long long> per_queue;        // rows pushed to each queue so far (bounds its medoid count)
+  std::vector<int> queue_of;               // queue of every pushed row
+  std::vector<uint8_t> h_rows;
+  double prep_ms = 0, queue_ms = 0, merge_ms = 0;
+  bool finished = false, broken = false;
+  // after finish: clusters in the final order
+  std::vector<long long> r_medoid, r_offsets, r_members;
+  std::vector<int> r_scores;
+  std::string err;
+};
+
+namespace {
+
+int cfail(uvaia_clust_ctx *c, int code, const char *fmt, ...)
+{
+  char buf[512];
+  va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+  if (c) c->err = buf; else g_open_error = buf;
+  return code;
+}
+
+#define CCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (c)->broken = true; \
+  return cfail((c), e_ == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
+
+// grows a device array to `want` bytes (at least doubling), keeping its first `keep` bytes
+int grow(uvaia_clust_ctx *c, void **ptr, size_t keep, size_t want)
+{
+  void *np = nullptr;
+  CCHK(c, hipMalloc(&np, want));
+  if (keep) CCHK(c, hipMemcpyAsync(np, *ptr, keep, hipMemcpyDeviceToDevice, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));
+  if (*ptr) hipFree(*ptr);
+  *ptr = np;
+  return 0;
+}
+
+int ensure_rows(uvaia_clust_ctx *c, size_t need)
+{
+  if (need <= c->rows_cap) return 0;
+  const size_t cap = std::max(need, std::max<size_t>(c->rows_cap * 2, 1024));
+  const size_t old = (size_t)c->pushed;
+  int rc;
+  if ((rc = grow(c, (void **)&c->d_rows, old * c->pitch, cap * c->pitch))) return rc;
+  if ((rc = grow(c, (void **)&c->d_dist, old * sizeof(int), cap * sizeof(int)))) return rc;
+  if ((rc = grow(c, (void **)&c->d_p, old * std::max(c->n_score, 1) * sizeof(int), cap * std::max(c->n_score, 1) * sizeof(int)))) return rc;
+  if ((rc = grow(c, (void **)&c->d_join, old * sizeof(int), cap * sizeof(int)))) return rc;
+  c->rows_cap = cap;
+  return 0;
+}
+
+// medoid slots per queue: at least as many as rows pushed to the busiest queue
+int ensure_medoids(uvaia_clust_ctx *c, long long need)
+{
+  if (need <= c->m_cap) return 0;
+  if (need > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences in one queue", INT_MAX / 2);
+  const int cap = (int)std::max<long long>(need, std::max(2LL * c->m_cap, 256LL));
+  int *no = nullptr, *ns = nullptr;
+  CCHK(c, hipMalloc(&no, (size_t)c->n_queues * cap * sizeof(int)));
+  CCHK(c, hipMalloc(&ns, (size_t)c->n_queues * cap * sizeof(int)));
+  if (c->m_cap) {
+    CCHK(c, hipMemcpy2DAsync(no, (size_t)cap * sizeof(int), c->d_mord, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
+    CCHK(c, hipMemcpy2DAsync(ns, (size_t)cap * sizeof(int), c->d_mst, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
+  }
+  CCHK(c, hipStreamSynchronize(c->stream));
+  hipFree(c->d_mord); hipFree(c->d_mst);
+  c->d_mord = no; c->d_mst = ns; c->m_cap = cap;
+  return 0;
+}
+
+struct Clust {
+  int ord;                          // push ordinal of the medoid
+  int stored;                       // score[0] as the reference leaves it
+  std::vector<long long> members;   // the nn list
+};
+
+// compare_fastaseq_score (src/fastaseq.c:31-40): score vectors descending; true when a goes strictly before b
+struct ScoreOrder {
+  const std::vector<int> *p; int n_score, nchar;
+  int key(const Clust &x, int i) const { return i == 0 ? x.stored : (i <= n_score ? (*p)[(size_t)x.ord * n_score + i - 1] : nchar); }
+  bool operator()(const Clust &a, const Clust &b) const
+  {
+    for (int i = 0; i < n_score + 2; i++) { const int ka = key(a, i), kb = key(b, i); if (ka != kb) return ka > kb; }
+    return false;
+  }
+};
+
+}  // namespace
+
+extern "C" {
+
+const char *uvaia_clust_last_error(const uvaia_clust_ctx *c) { return c ? c->err.c_str() : g_open_error.c_str(); }
+
+void uvaia_clust_close(uvaia_clust_ctx *c)
+{
+  if (!c) return;
+  hipSetDevice(c->device);
+  if (c->stream) hipStreamSynchronize(c->stream);
+  hipFree(c->d_ref); hipFree(c->d_rows); hipFree(c->d_dist); hipFree(c->d_p); hipFree(c->d_join); hipFree(c->d_bad);
+  hipFree(c->d_qoff); hipFree(c->d_qlist); hipFree(c->d_mcount); hipFree(c->d_mord); hipFree(c->d_mst);
+  if (c->ev_a) hipEventDestroy(c->ev_a);
+  if (c->ev_b) hipEventDestroy(c->ev_b);
+  if (c->stream) hipStreamDestroy(c->stream);
+  delete c;
+}
+
+int uvaia_clust_open(uvaia_clust_ctx **out, int device, const char *reference, int nchar, int dist, int trim, int n_score, int n_queues)
+{
+  if (!out) return cfail(nullptr, UVAIA_GPU_EINVAL, "null output pointer");
+  *out = nullptr;
+  if (!reference || nchar < 1) return cfail(nullptr, UVAIA_GPU_EINVAL, "empty reference sequence");
+  if (dist < 0 || trim < 0 || n_score < 0 || n_queues < 1 || 2LL * trim >= nchar)
+    return cfail(nullptr, UVAIA_GPU_EINVAL, "bad parameters: distance %d, trim %d (2 trim must stay below the %d sites), n_score %d, queues %d", dist, trim, nchar, n_score, n_queues);
+  for (int i = 0; i < nchar; i++) {
+    const unsigned char b = (unsigned char)reference[i];
+    if (b == 0 || b >= 0x80) return cfail(nullptr, UVAIA_GPU_EALPHABET, "reference site %d holds byte 0x%02x", i, b);
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return cfail(nullptr, UVAIA_GPU_ENODEV, "no HIP device: clustering runs on an MI355X (gfx950) and has no CPU path");
+  if (device < 0 || device >= ndev) return cfail(nullptr, UVAIA_GPU_EINVAL, "device %d out of range (%d devices)", device, ndev);
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return cfail(nullptr, UVAIA_GPU_ENODEV, "cannot query device %d", device);
+  if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return cfail(nullptr, UVAIA_GPU_ENODEV, "device %d is %s: this library is built for gfx950 only", device, prop.gcnArchName);
+  if (hipSetDevice(device) != hipSuccess) return cfail(nullptr, UVAIA_GPU_ENODEV, "cannot select device %d", device);
+  uvaia_clust_ctx *c = new uvaia_clust_ctx();
+  c->device = device; c->nchar = nchar; c->dist = dist; c->trim = trim; c->n_score = n_score; c->n_queues = n_queues;
+  c->pitch = ((size_t)nchar + 63) & ~(size_t)63;
+  c->per_queue.assign((size_t)n_queues, 0);
+  std::vector<uint8_t> ref(c->pitch, 0);
+  for (int i = 0; i < nchar; i++) { const uint8_t b = (uint8_t)reference[i]; ref[(size_t)i] = (b >= 'a' && b <= 'z') ? b - 32 : b; }
+#define OCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int rc_ = cfail(nullptr, e_ == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); uvaia_clust_close(c); return rc_; } } while (0)
+  OCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  OCHK(hipEventCreate(&c->ev_a)); OCHK(hipEventCreate(&c->ev_b));
+  OCHK(hipMalloc(&c->d_ref, c->pitch));
+  OCHK(hipMemcpy(c->d_ref, ref.data(), c->pitch, hipMemcpyHostToDevice));
+  OCHK(hipMalloc(&c->d_bad, sizeof(int)));
+  OCHK(hipMalloc(&c->d_qoff, ((size_t)n_queues + 1) * sizeof(int)));
+  OCHK(hipMalloc(&c->d_mcount, (size_t)n_queues * sizeof(int)));
+  OCHK(hipMemset(c->d_mcount, 0, (size_t)n_queues * sizeof(int)));
+#undef OCHK
+  *out = c;
+  return 0;
+}
+
+int uvaia_clust_push(uvaia_clust_ctx *c, int n, const char *const *seq, const int *queue)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "push after finish");
+  if (n < 0 || (n && (!seq || !queue))) return cfail(c, UVAIA_GPU_EINVAL, "bad push arguments");
+  if (!n) return 0;
+  if (c->pushed + n > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences", INT_MAX / 2);
+  for (int i = 0; i < n; i++) {
+    if (queue[i] < 0 || queue[i] >= c->n_queues) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: queue %d out of range [0, %d)", i, queue[i], c->n_queues);
+    if (!seq[i]) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push is null", i);
+  }
+  hipSetDevice(c->device);
+  int rc;
+  if ((rc = ensure_rows(c, (size_t)c->pushed + n))) return rc;
+  const long long first = c->pushed;
+  // rows, padded with zero bytes to the pitch
+  c->h_rows.assign((size_t)n * c->pitch, 0);
+  for (int i = 0; i < n; i++) memcpy(c->h_rows.data() + (size_t)i * c->pitch, seq[i], (size_t)c->nchar);
+  CCHK(c, hipMemcpyAsync(c->d_rows + (size_t)first * c->pitch, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
+  const int big = INT_MAX;
+  CCHK(c, hipMemcpyAsync(c->d_bad, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  // per-queue lists of this push's ordinals, in push order
+  std::vector<int> qoff((size_t)c->n_queues + 1, 0), qlist((size_t)n);
+  for (int i = 0; i < n; i++) qoff[(size_t)queue[i] + 1]++;
+  for (int q = 0; q < c->n_queues; q++) qoff[(size_t)q + 1] += qoff[(size_t)q];
+  { std::vector<int> fill(qoff.begin(), qoff.end() - 1); for (int i = 0; i < n; i++) qlist[(size_t)fill[(size_t)queue[i]]++] = (int)(first + i); }
+  long long busiest = 0;
+  for (int i = 0; i < n; i++) busiest = std::max(busiest, ++c->per_queue[(size_t)queue[i]]);
+  c->queue_of.insert(c->queue_of.end(), queue, queue + n);
+  if ((rc = ensure_medoids(c, busiest))) return rc;
+  if ((size_t)n > c->qlist_cap) {
+    hipFree(c->d_qlist); c->d_qlist = nullptr; c->qlist_cap = 0;
+    CCHK(c, hipMalloc(&c->d_qlist, (size_t)n * sizeof(int)));
+    c->qlist_cap = (size_t)n;
+  }
+  CCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  CCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+
+  float ms = 0;
+  CCHK(c, hipEventRecord(c->ev_a, c->stream));
+  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, first, n, c->d_ref,
+                     c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipEventRecord(c->ev_b, c->stream));
+  CCHK(c, hipEventSynchronize(c->ev_b));
+  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  c->prep_ms += ms;
+  int bad = big;
+  CCHK(c, hipMemcpy(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad != big) {
+    c->broken = true;
+    for (int k = 0; k < c->nchar; k++) {
+      const unsigned char b = (unsigned char)seq[bad][k];
+      if (b == 0 || b >= 0x80) return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds byte 0x%02x at site %d: only bytes 1-127 are defined", first + bad, b, k);
+    }
+    return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds a byte 0 or >= 0x80", first + bad);
+  }
+
+  CCHK(c, hipEventRecord(c->ev_a, c->stream));
+  hipLaunchKernelGGL(clust_queue_kernel, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar, c->trim, c->dist, c->n_score,
+                     c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipEventRecord(c->ev_b, c->stream));
+  CCHK(c, hipEventSynchronize(c->ev_b));
+  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  c->queue_ms += ms;
+  c->pushed += n;
+  return 0;
+}
+
+int uvaia_clust_finish(uvaia_clust_ctx *c)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "finish called twice");
+  hipSetDevice(c->device);
+  const int Q = c->n_queues, ns = c->n_score;
+  const size_t N = (size_t)c->pushed;
+  std::vector<int> mcount((size_t)Q), join(N), p(N * (size_t)ns);
+  CCHK(c, hipMemcpy(mcount.data(), c->d_mcount, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost));
+  if (N) CCHK(c, hipMemcpy(join.data(), c->d_join, N * sizeof(int), hipMemcpyDeviceToHost));
+  if (N && ns) CCHK(c, hipMemcpy(p.data(), c->d_p, N * ns * sizeof(int), hipMemcpyDeviceToHost));
+  std::vector<std::vector<Clust>> L((size_t)Q);
+  {
+    std::vector<int> mord, mst;
+    if (c->m_cap) {
+      mord.resize((size_t)Q * c->m_cap); mst.resize((size_t)Q * c->m_cap);
+      CCHK(c, hipMemcpy(mord.data(), c->d_mord, mord.size() * sizeof(int), hipMemcpyDeviceToHost));
+      CCHK(c, hipMemcpy(mst.data(), c->d_mst, mst.size() * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    for (int q = 0; q < Q; q++) {
+      L[(size_t)q].resize((size_t)mcount[(size_t)q]);
+      for (int s = 0; s < mcount[(size_t)q]; s++) {
+        Clust &k = L[(size_t)q][(size_t)s];
+        k.ord = mord[(size_t)q * c->m_cap + s]; k.stored = mst[(size_t)q * c->m_cap + s];
+      }
+    }
+    // members in push order, which is queue order: join[o] is a slot of o's own queue
+    for (size_t o = 0; o < N; o++) if (join[o] >= 0) L[(size_t)c->queue_of[o]][(size_t)join[o]].members.push_back((long long)o);
+  }
+  ScoreOrder by_score{&p, ns, c->nchar};
+  float ms = 0;
+  int *d_item_ord = nullptr, *d_item_lo = nullptr, *d_item_hi = nullptr, *d_list = nullptr, *d_target = nullptr;
+  size_t items_cap = 0, list_cap = 0;
+  auto free_merge = [&]() { hipFree(d_item_ord); hipFree(d_item_lo); hipFree(d_item_hi); hipFree(d_list); hipFree(d_target); };
+  for (int cc = Q; cc > 1; cc = cc / 2 + cc % 2) {
+    std::vector<int> item_ord, item_lo, item_hi, list;
+    std::vector<int> pair_item0, pair_list0;
+    for (int j = 0; j < cc / 2; j++) {
+      const int i = j + cc / 2 + cc % 2;
+      std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)i];
+      pair_item0.push_back((int)item_ord.size()); pair_list0.push_back((int)list.size());
+      if (B.empty()) continue;                                  // an empty absorbed queue: no-op
+      std::stable_sort(A.begin(), A.end(), by_score);
+      std::stable_sort(B.begin(), B.end(), by_score);
+      if (A.empty()) continue;                                  // spliced below: A takes B as it is sorted
+      const int base = (int)list.size();
+      for (const Clust &k : A) list.push_back(k.ord);
+      for (const Clust &k : B) {
+        // A is sorted by stored distance descending: the ring |stored - k.stored| <= d is one window
+        auto lo = std::partition_point(A.begin(), A.end(), [&](const Clust &x) { return x.stored > k.stored + c->dist; });
+        auto hi = std::partition_point(lo, A.end(), [&](const Clust &x) { return x.stored >= k.stored - c->dist; });
+        item_ord.push_back(k.ord); item_lo.push_back(base + (int)(lo - A.begin())); item_hi.push_back(base + (int)(hi - A.begin()));
+      }
+    }
+    const int n_items = (int)item_ord.size();
+    std::vector<int> target((size_t)n_items, -1);
+    if (n_items) {
+      if ((size_t)n_items > items_cap) {
+        hipFree(d_item_ord); hipFree(d_item_lo); hipFree(d_item_hi); hipFree(d_target);
+        d_item_ord = d_item_lo = d_item_hi = d_target = nullptr;
+        if (hipMalloc(&d_item_ord, n_items * sizeof(int)) != hipSuccess || hipMalloc(&d_item_lo, n_items * sizeof(int)) != hipSuccess ||
+            hipMalloc(&d_item_hi, n_items * sizeof(int)) != hipSuccess || hipMalloc(&d_target, n_items * sizeof(int)) != hipSuccess) {
+          free_merge(); c->broken = true;
+          return cfail(c, UVAIA_GPU_ENOMEM, "merge round of %d items: device allocation failed", n_items);
+        }
+        items_cap = (size_t)n_items;
+      }
+      if (list.size() > list_cap) {
+        hipFree(d_list); d_list = nullptr;
+        if (hipMalloc(&d_list, list.size() * sizeof(int)) != hipSuccess) { free_merge(); c->broken = true; return cfail(c, UVAIA_GPU_ENOMEM, "merge lists: device allocation failed"); }
+        list_cap = list.size();
+      }
+      hipError_t e = hipSuccess;
+      auto up = [&](int *dst, const std::vector<int> &v) { if (e == hipSuccess) e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, c->stream); };
+      up(d_item_ord, item_ord); up(d_item_lo, item_lo); up(d_item_hi, item_hi); up(d_list, list);
+      if (e == hipSuccess) e = hipEventRecord(c->ev_a, c->stream);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(clust_merge_kernel, dim3((unsigned)((n_items + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar,
+                           c->trim, c->dist, d_item_ord, d_item_lo, d_item_hi, d_list, n_items, d_target);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipEventRecord(c->ev_b, c->stream);
+      if (e == hipSuccess) e = hipMemcpyAsync(target.data(), d_target, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_a, c->ev_b);
+      if (e != hipSuccess) { free_merge(); c->broken = true; return cfail(c, UVAIA_GPU_EHIP, "merge round: %s", hipGetErrorString(e)); }
+      c->merge_ms += ms;
+    }
+    // splice, in the absorbed list's sorted order (src/fastaseq.c:228-253)
+    for (int j = 0; j < cc / 2; j++) {
+      const int i = j + cc / 2 + cc % 2;
+      std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)i];
+      if (B.empty()) continue;
+      if (A.empty()) { A.swap(B); continue; }
+      int it = pair_item0[(size_t)j];
+      const int base = pair_list0[(size_t)j];
+      for (Clust &k : B) {
+        const int t = target[(size_t)it++];
+        if (t >= 0) {
+          Clust &to = A[(size_t)(t - base)];
+          to.members.push_back(k.ord);
+          to.members.insert(to.members.end(), k.members.begin(), k.members.end());
+        } else A.push_back(std::move(k));
+      }
+      B.clear();
+    }
+  }
+  free_merge();
+  // final order (src/cluster.c:233, compare_fastaseq src/fastaseq.c:23-29): more members first, then the score vectors
+  std::vector<Clust> &F = L[0];
+  std::stable_sort(F.begin(), F.end(), [&](const Clust &a, const Clust &b) {
+    if (a.members.size() != b.members.size()) return a.members.size() > b.members.size();
+    return by_score(a, b);
+  });
+  c->r_medoid.clear(); c->r_offsets.assign(1, 0); c->r_members.clear(); c->r_scores.clear();
+  for (const Clust &k : F) {
+    c->r_medoid.push_back(k.ord);
+    c->r_members.insert(c->r_members.end(), k.members.begin(), k.members.end());
+    c->r_offsets.push_back((long long)c->r_members.size());
+    for (int s = 0; s < ns + 2; s++) c->r_scores.push_back(by_score.key(k, s));
+  }
+  c->finished = true;
+  return 0;
+}
+
+int uvaia_clust_result(uvaia_clust_ctx *c, int *n_clusters, int64_t *medoid, int64_t *offsets, int64_t *members, int *scores)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (!c->finished) return cfail(c, UVAIA_GPU_ESTATE, "result before finish");
+  const size_t nc = c->r_medoid.size();
+  if (n_clusters) *n_clusters = (int)nc;
+  if (medoid) for (size_t k = 0; k < nc; k++) medoid[k] = c->r_medoid[k];
+  if (offsets) for (size_t k = 0; k <= nc; k++) offsets[k] = c->r_offsets[k];
+  if (members) for (size_t k = 0; k < c->r_members.size(); k++) members[k] = c->r_members[k];
+  if (scores) memcpy(scores, c->r_scores.data(), c->r_scores.size() * sizeof(int));
+  return 0;
+}
+
+int uvaia_clust_stats(uvaia_clust_ctx *c, double *prep_ms, double *queue_ms, double *merge_ms, int64_t *pushed)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (prep_ms) *prep_ms = c->prep_ms;
+  if (queue_ms) *queue_ms = c->queue_ms;
+  if (merge_ms) *merge_ms = c->merge_ms;
+  if (pushed) *pushed = c->pushed;
+  return 0;
+}
+
+}  // extern "C"
