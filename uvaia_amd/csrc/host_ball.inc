@@ -2,8 +2,8 @@
 
 extern "C" {
 
-// radius search over references [r_lo, r_hi) (relative to tile tile_first of `tiles`): stage 1 for all, the queries for the few
-static int ball_range(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first, int n_tiles, int r_lo, int r_hi, int radius, int *mindist_host)
+// radius search over references [r_lo, r_hi) (relative to tile tile_first of the store): stage 1 for all, the queries for the few
+static int ball_range(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, int r_lo, int r_hi, int radius, int *mindist_host)
 {
   const int n = r_hi - r_lo;
   if (n <= 0) return 0;
@@ -39,7 +39,7 @@ static int ball_range(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first
     else { (void)hipGetLastError(); c->d_ball_ga = nullptr; fused = false; }
   }
   HIPCHK(c, hipEventRecord(c->ball_ev[0], c->stream));
-#define BALL_STAGE1(A, G) hipLaunchKernelGGL((ball_stage1_kernel<A, G>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, tiles, tile_first, n_tiles, c->W4, c->d_cp, c->d_cpm, radius, \
+#define BALL_STAGE1(A, G) hipLaunchKernelGGL((ball_stage1_kernel<A, G>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, s.planes, tile_first, n_tiles, c->W4, c->d_cp, c->d_cpm, radius, \
                                               r_lo, r_hi, c->d_mindist, c->d_ball_cdist, c->d_ball_list, c->d_ball_n, c->d_ball_masks, c->NH4, c->NG4, c->d_ball_ga, c->n_idx_c > 0, c->n_idx_m > 0)
   if (c->acgt) { if (fused) BALL_STAGE1(true, true); else BALL_STAGE1(true, false); }
   else         { if (fused) BALL_STAGE1(false, true); else BALL_STAGE1(false, false); }
@@ -68,8 +68,8 @@ static int ball_range(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first
       if (c->acgt) hipLaunchKernelGGL((ball_compact_kernel<3>), dim3(mt), dim3(64), 0, c->stream, c->d_ball_ga, c->d_ball_list, n_ask, c->NG4, c->d_ball_tiles);
       else         hipLaunchKernelGGL((ball_compact_kernel<4>), dim3(mt), dim3(64), 0, c->stream, c->d_ball_ga, c->d_ball_list, n_ask, c->NG4, c->d_ball_tiles);
     } else {
-      if (c->acgt) hipLaunchKernelGGL((ball_gather_cols_kernel<3>), dim3(mt), dim3(64), 0, c->stream, tiles, tile_first, c->W4, c->d_ball_masks, c->d_ball_list, n_ask, c->NH4, c->NG4, c->d_ball_tiles);
-      else         hipLaunchKernelGGL((ball_gather_cols_kernel<4>), dim3(mt), dim3(64), 0, c->stream, tiles, tile_first, c->W4, c->d_ball_masks, c->d_ball_list, n_ask, c->NH4, c->NG4, c->d_ball_tiles);
+      if (c->acgt) hipLaunchKernelGGL((ball_gather_cols_kernel<3>), dim3(mt), dim3(64), 0, c->stream, s.planes, tile_first, c->W4, c->d_ball_masks, c->d_ball_list, n_ask, c->NH4, c->NG4, c->d_ball_tiles);
+      else         hipLaunchKernelGGL((ball_gather_cols_kernel<4>), dim3(mt), dim3(64), 0, c->stream, s.planes, tile_first, c->W4, c->d_ball_masks, c->d_ball_list, n_ask, c->NH4, c->NG4, c->d_ball_tiles);
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ball_ev[2], c->stream));
@@ -103,9 +103,9 @@ int uvaia_gpu_ball(uvaia_gpu_ctx *c, const char *const *seq, int n_ref, int radi
   if (c->act_q0 != 0 || c->act_q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "the radius search acts on the whole query set");
   if (n_ref == 0) return 0;
   int rc = ensure_batch_buffers(c); if (rc) return rc;
-  rc = pack_rows(c, seq, nullptr, 0, nullptr, n_ref, c->d_batch, c->d_batch_nonn, c->d_batch_amb, c->d_batch_tot, 0);
+  rc = pack_rows(c, seq, nullptr, 0, nullptr, n_ref, c->batch, 0);
   if (rc) return rc;
-  return ball_range(c, c->d_batch, 0, (n_ref + 63) / 64, 0, n_ref, radius, mindist);
+  return ball_range(c, c->batch, 0, (n_ref + 63) / 64, 0, n_ref, radius, mindist);
 }
 
 // the same over references [first, first + n) of the resident database (uvaia_gpu_db_append*): mindist[i] for reference first + i
@@ -115,12 +115,12 @@ int uvaia_gpu_ball_resident(uvaia_gpu_ctx *c, size_t first, size_t n, int radius
   if (first + n > c->db_n) return fail(c, UVAIA_GPU_EINVAL, "range [%zu,+%zu) outside the database", first, n);
   if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only");
   if (c->act_q0 != 0 || c->act_q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "the radius search acts on the whole query set");
-  for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
+  if (int rc = sync_scan_streams(c)) return rc;
   const size_t step = (size_t)1 << 22;                       // stage 1 needs no more than 12 bytes per reference of work space
   for (size_t a = first; a < first + n; a += step) {
     const size_t b = std::min(first + n, a + step);
     const long long tf = (long long)(a / 64);
-    int rc = ball_range(c, c->d_db, tf, (int)((b + 63) / 64 - a / 64), (int)(a - (size_t)tf * 64), (int)(b - (size_t)tf * 64), radius, mindist ? mindist + (a - first) : nullptr);
+    int rc = ball_range(c, c->db, tf, (int)((b + 63) / 64 - a / 64), (int)(a - (size_t)tf * 64), (int)(b - (size_t)tf * 64), radius, mindist ? mindist + (a - first) : nullptr);
     if (rc) return rc;
   }
   return 0;

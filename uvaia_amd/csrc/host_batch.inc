@@ -9,13 +9,13 @@ int uvaia_gpu_agree_on_polymorphic(uvaia_gpu_ctx *c, const char *const *seq, int
   if ((size_t)n_seq > c->max_pool) return fail(c, UVAIA_GPU_ESTATE, "batch of %d exceeds max_pool %zu", n_seq, c->max_pool);
   if (n_seq == 0) return 0;
   int rc = ensure_batch_buffers(c); if (rc) return rc;
-  rc = pack_rows(c, seq, nullptr, 0, nullptr, n_seq, c->d_batch, c->d_batch_nonn, c->d_batch_amb, c->d_batch_tot, 0);
+  rc = pack_rows(c, seq, nullptr, 0, nullptr, n_seq, c->batch, 0);
   if (rc) return rc;
   const int n_tiles = (n_seq + 63) / 64, ppad = n_tiles * 64;
   rc = ensure_cnt4(c, (size_t)c->nq_pad * c->pool_pad); if (rc) return rc;
   const bool prof = c->profile; c->profile = false;     // not the nearest-neighbour scan the statistics describe
   rc = ensure_qpoly(c); if (rc) return rc;
-  rc = launch_scan(c, c->d_batch, 0, n_tiles, c->d_qpoly, c->nq, c->d_cnt, ppad, 0.0);
+  rc = launch_scan(c, c->batch, 0, n_tiles, c->d_qpoly, c->nq, c->d_cnt, ppad, 0.0);
   c->profile = prof;
   if (rc) return rc;
   uint8_t *d_out = nullptr;
@@ -99,11 +99,11 @@ int uvaia_gpu_push(uvaia_gpu_ctx *c, const char *const *seq, const int *non_n, i
   if (c->act_q0 != 0 || c->act_q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "streamed batches act on the whole query set: query shards use the resident calls");
   if (n_ref == 0) return 0;
   int rc = ensure_batch_buffers(c); if (rc) return rc;
-  rc = pack_rows(c, seq, nullptr, 0, non_n, n_ref, c->d_batch, c->d_batch_nonn, c->d_batch_amb, c->d_batch_tot, 0);
+  rc = pack_rows(c, seq, nullptr, 0, non_n, n_ref, c->batch, 0);
   if (rc) return rc;
   const int n_tiles = (n_ref + 63) / 64;
   HIPCHK(c, hipMemsetAsync(c->d_entered, 0, (size_t)n_tiles * 64, c->stream));
-  rc = run_batch(c, c->d_batch, c->d_batch_nonn, c->d_batch_amb, 0, n_tiles, 0, n_ref, ordinal0, c->d_entered);
+  rc = run_batch(c, c->batch, 0, n_tiles, 0, n_ref, ordinal0);
   if (rc) return rc;
   if (entered) HIPCHK(c, hipMemcpyAsync(entered, c->d_entered, (size_t)n_ref, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

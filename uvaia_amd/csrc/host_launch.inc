@@ -104,26 +104,47 @@ int ensure_qgather(uvaia_gpu_ctx *c)
   return 0;
 }
 
+void store_free(TileStore &s)
+{
+  for (void *p : {(void *)s.planes, (void *)s.nonn, (void *)s.amb, (void *)s.tot, (void *)s.ev, (void *)s.poly, (void *)s.grp, (void *)s.tote}) hipFree(p);
+  s = TileStore();
+}
+void slice_free(SliceBuf &b)
+{
+  for (void *p : {(void *)b.cnt, (void *)b.tmin, (void *)b.ext, (void *)b.rtp, (void *)b.tb8, (void *)b.rt, (void *)b.progress}) hipFree(p);
+  for (hipEvent_t e : {b.scan_done, b.scan_started, b.replay_done}) if (e) hipEventDestroy(e);
+  b = SliceBuf();
+}
+
+// a store of `tiles` tiles of 64 references (whatever it held before goes): packed planes, counts and side rows zeroed, the derived planes as they come
+int store_alloc(uvaia_gpu_ctx *c, TileStore &s, size_t tiles)
+{
+  store_free(s);
+  uint4 *planes = nullptr;
+  const size_t refs = tiles * 64, tile_u4 = (size_t)c->W4 * c->P * 64;
+  HIPCHK(c, hipMalloc(&s.nonn, refs * sizeof(int)));
+  HIPCHK(c, hipMemset(s.nonn, 0, refs * sizeof(int)));
+  HIPCHK(c, hipMalloc(&s.ev, tiles * (size_t)c->W4 * 2 * 64 * sizeof(uint4)));
+  HIPCHK(c, hipMalloc(&s.grp, tiles * (size_t)c->W4 * 64 * sizeof(uint32_t)));
+  HIPCHK(c, hipMalloc(&s.poly, tiles * (size_t)std::max(c->NP4 + c->NR4, 1) * 3 * 64 * sizeof(uint4)));
+  HIPCHK(c, hipMalloc(&s.tote, refs * sizeof(int)));
+  HIPCHK(c, hipMalloc(&s.tot, refs * sizeof(int)));
+  HIPCHK(c, hipMemset(s.tot, 0, refs * sizeof(int)));
+  HIPCHK(c, hipMalloc(&s.amb, refs * AMB_ROW * sizeof(int)));
+  HIPCHK(c, hipMemset(s.amb, 0, refs * AMB_ROW * sizeof(int)));
+  HIPCHK(c, hipMalloc(&planes, tiles * tile_u4 * sizeof(uint4)));
+  HIPCHK(c, hipMemset(planes, 0, tiles * tile_u4 * sizeof(uint4)));
+  s.planes = planes;                                      // last: its presence says all of them are there
+  return 0;
+}
+
 // Buffers of a streamed batch (uvaia_gpu_push, uvaia_gpu_ball, uvaia_gpu_agree_on_polymorphic): packed tiles of max_pool references,
 // the planes derived from them, side rows.  A context that only searches a resident database never needs them.
 int ensure_batch_buffers(uvaia_gpu_ctx *c)
 {
-  if (c->d_batch) return 0;
+  if (c->batch.planes) return 0;
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t tile_u4 = (size_t)c->W4 * c->P * 64, tiles = c->pool_pad / 64;
-  HIPCHK(c, hipMalloc(&c->d_batch_nonn, c->pool_pad * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_batch_nonn, 0, c->pool_pad * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_batch_ev, tiles * (size_t)c->W4 * 2 * 64 * sizeof(uint4)));
-  HIPCHK(c, hipMalloc(&c->d_batch_grp, tiles * (size_t)c->W4 * 64 * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&c->d_batch_poly, tiles * (size_t)std::max(c->NP4 + c->NR4, 1) * 3 * 64 * sizeof(uint4)));
-  HIPCHK(c, hipMalloc(&c->d_batch_tote, c->pool_pad * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_batch_tot, c->pool_pad * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_batch_tot, 0, c->pool_pad * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_batch_amb, c->pool_pad * AMB_ROW * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_batch_amb, 0, c->pool_pad * AMB_ROW * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_batch, tiles * tile_u4 * sizeof(uint4)));       // last: its presence says all of them are there
-  HIPCHK(c, hipMemset(c->d_batch, 0, tiles * tile_u4 * sizeof(uint4)));
-  return 0;
+  return store_alloc(c, c->batch, c->pool_pad / 64);
 }
 
 // Packs one character row restricted to `keep` (nullable: keep everything inside [lo,hi)) into query-plane words:
@@ -163,7 +184,7 @@ int take_scan_events(uvaia_gpu_ctx *c, ScanEvt &ev)
   return 0;
 }
 
-int launch_scan(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first, int n_tiles, const uint32_t *qp, int n_rows, int4 *out, int ppad, double bytes)
+int launch_scan(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, const uint32_t *qp, int n_rows, int4 *out, int ppad, double bytes)
 {
   if (n_tiles <= 0) return 0;
   dim3 grid((unsigned)((n_rows + c->qt - 1) / c->qt), (unsigned)((n_tiles + 3) / 4)), block(256);   // only tiles holding real queries
@@ -172,7 +193,7 @@ int launch_scan(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first, int 
     { int rc_ = take_scan_events(c, ev); if (rc_) return rc_; }
     HIPCHK(c, hipEventRecord(ev.a, c->stream));
   }
-#define LAUNCH(K, QT) hipLaunchKernelGGL((K<QT>), grid, block, 0, c->stream, tiles, tile_first, n_tiles, c->W4, qp, out, ppad)
+#define LAUNCH(K, QT) hipLaunchKernelGGL((K<QT>), grid, block, 0, c->stream, s.planes, tile_first, n_tiles, c->W4, qp, out, ppad)
   if (c->acgt) { switch (c->qt) { case 8: LAUNCH(scan_acgt_kernel, 8); break; case 32: LAUNCH(scan_acgt_kernel, 32); break; default: LAUNCH(scan_acgt_kernel, 16); } }
   else         { switch (c->qt) { case 8: LAUNCH(scan_iupac_kernel, 8); break; case 32: LAUNCH(scan_iupac_kernel, 32); break; default: LAUNCH(scan_iupac_kernel, 16); } }
 #undef LAUNCH
@@ -182,18 +203,18 @@ int launch_scan(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first, int 
 }
 
 // text - ACGT matches and partial - text matches of every pair of the slice, next to the column-compressed scan (pair_extras_kernel)
-int launch_pair_extras(uvaia_gpu_ctx *c, const uint4 *tiles, long long tile_first, int n_tiles, uint32_t *ext, int ppad, hipStream_t stream)
+int launch_pair_extras(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, uint32_t *ext, int ppad, hipStream_t stream)
 {
   if (n_tiles <= 0) return 0;
-  hipLaunchKernelGGL(pair_extras_kernel, dim3((unsigned)n_tiles, (unsigned)((c->nq + 15) / 16)), dim3(256), 0, stream, tiles, tile_first, n_tiles, c->W4,
-                     (tiles == c->d_db) ? c->d_db_amb : c->d_batch_amb, c->d_qp, c->d_amb_q, c->nq, ext, ppad);
+  hipLaunchKernelGGL(pair_extras_kernel, dim3((unsigned)n_tiles, (unsigned)((c->nq + 15) / 16)), dim3(256), 0, stream, s.planes, tile_first, n_tiles, c->W4,
+                     s.amb, c->d_qp, c->d_amb_q, c->nq, ext, ppad);
   HIPCHK(c, hipGetLastError());
   return 0;
 }
 
 // rt (nullable unless the query set has constant-and-complete columns): the untruncated consensus pre-score of the slice's references,
 // by the packed-plane scans themselves or, next to the column-compressed scan, by consensus_rt_kernel on the same stream
-int launch_scan2(uvaia_gpu_ctx *c, const uint4 *tiles, const int *tot_tile0, long long tile_first, int n_tiles, uint32_t *out, int ppad, double bytes, hipStream_t stream,
+int launch_scan2(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, uint32_t *out, int ppad, double bytes, hipStream_t stream,
                  int2 *tmin, int r_lo, int r_hi, int4 *rt, uint32_t *ext = nullptr /* default mode, packed-plane scan: the other two counters of every pair */, uint32_t *rtp = nullptr, uint4 *tb8 = nullptr,
                  unsigned *progress = nullptr /* column-compressed scan, pipelined search: zeroed counters, one per stripe of SCAN_STRIPE_TILES tiles */)
 {
@@ -201,6 +222,7 @@ int launch_scan2(uvaia_gpu_ctx *c, const uint4 *tiles, const int *tot_tile0, lon
   if (!stream) stream = c->stream;
   const bool cons = c->n_idx_c > 0;
   if (cons && !rt) return fail(c, UVAIA_GPU_ESTATE, "no buffer for the consensus pre-score");
+  const uint4 *tiles = s.planes; const int *tot_tile0 = s.tot + tile_first * 64;
   const long long ptile_first = tile_first;       // packed tiles (tile_first may be renumbered for the derived planes below)
   auto consensus_rt = [&]() {
     if (!cons) return;
@@ -220,16 +242,13 @@ int launch_scan2(uvaia_gpu_ctx *c, const uint4 *tiles, const int *tot_tile0, lon
   }
   const uint32_t *qp = c->acgt ? c->d_qp : c->d_qp2;
   if (c->scan_variant == 2) {
-    const bool is_db = (tiles == c->d_db);
-    const uint4 *ev = is_db ? c->d_db_ev : c->d_batch_ev, *poly = is_db ? c->d_db_poly : c->d_batch_poly;
-    const uint32_t *grp = is_db ? c->d_db_grp : c->d_batch_grp;
-    const int *tote = (is_db ? c->d_db_tote : c->d_batch_tote) + tile_first * 64;
+    const int *tote = s.tote + tile_first * 64;
     constexpr int QS = 64;                       // queries of a super-tile of scan3_kernel
     if (c->act_q0 % QS) return fail(c, UVAIA_GPU_ESTATE, "the scan works on super-tiles of %d queries: active queries start at a multiple of that", QS);
     const int st_first = c->act_q0 / QS, n_st = (c->act_q1 + QS - 1) / QS - st_first;
     const int R = c->scan_R;
     dim3 grid3(scan_grid_size(n_st, (n_tiles + R - 1) / R));
-#define SCAN3_LAUNCH(NWW, A, RR) hipLaunchKernelGGL((scan3_kernel<NWW, A, RR>), grid3, dim3(64 * NWW), 0, stream, ev, poly, tile_first, n_tiles, c->W4, c->NP4, c->NP4 + c->NR4, c->d_qpl, c->d_stream, c->d_sdir, grp, tote, tot_tile0, out, ppad, n_st, tmin, r_lo, r_hi, st_first, progress)
+#define SCAN3_LAUNCH(NWW, A, RR) hipLaunchKernelGGL((scan3_kernel<NWW, A, RR>), grid3, dim3(64 * NWW), 0, stream, s.ev, s.poly, tile_first, n_tiles, c->W4, c->NP4, c->NP4 + c->NR4, c->d_qpl, c->d_stream, c->d_sdir, s.grp, tote, tot_tile0, out, ppad, n_st, tmin, r_lo, r_hi, st_first, progress)
 #define SCAN3_NW(A, RR) { if (c->scan_NW == 8) SCAN3_LAUNCH(8, A, RR); else SCAN3_LAUNCH(4, A, RR); }
     if (progress) { consensus_rt(); HIPCHK(c, hipGetLastError()); }     // pipelined: the pre-score is complete before any block of the scan reports progress
     if (R == 4)      { if (c->acgt) SCAN3_LAUNCH(8, true, 4); else SCAN3_LAUNCH(8, false, 4); }     // four tiles per wave: eight waves only (open_tuned)
@@ -244,11 +263,11 @@ int launch_scan2(uvaia_gpu_ctx *c, const uint4 *tiles, const int *tot_tile0, lon
     if (tb8 && !c->acgt) {     // 33-128 queries, default mode: the sharp bounds replay3_kernel walks (the other two counters of every pair: launch_pair_extras)
       hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, out, ppad, n_tiles, c->nq, r_lo, r_hi, tb8, cons ? rt : (const int4 *)nullptr, rtp);
       HIPCHK(c, hipGetLastError());
-      if (ext) { int rc_ = launch_pair_extras(c, tiles, ptile_first, n_tiles, ext, ppad, stream); if (rc_) return rc_; }
+      if (ext) { int rc_ = launch_pair_extras(c, s, ptile_first, n_tiles, ext, ppad, stream); if (rc_) return rc_; }
     }
     return 0;
   }
-  const int *amb0 = (tiles == c->d_db) ? c->d_db_amb : c->d_batch_amb;       // side rows of tile 0 of `tiles`
+  const int *amb0 = s.amb;       // side rows of tile 0 of the store
 #define LAUNCH(K, QT, CN) hipLaunchKernelGGL((K<QT, CN>), grid, block, 0, stream, tiles, tile_first, n_tiles, c->W4, qp, out, ppad, n_qtiles, tot_tile0, tmin, r_lo, r_hi, c->d_cp, rt)
 #define LAUNCHX(K, QT, CN) hipLaunchKernelGGL((K<QT, CN>), grid, block, 0, stream, tiles, tile_first, n_tiles, c->W4, qp, out, ppad, n_qtiles, tot_tile0, tmin, r_lo, r_hi, c->d_cp, rt, ext, rtp, tb8, amb0, c->d_qp, c->d_amb_q, c->nq)
 #define LAUNCH_QT(L, K, CN) switch (qt2) { case 1: L(K, 1, CN); break; case 2: L(K, 2, CN); break; case 4: L(K, 4, CN); break; case 8: L(K, 8, CN); break; default: L(K, 16, CN); }
@@ -266,10 +285,6 @@ int launch_scan2(uvaia_gpu_ctx *c, const uint4 *tiles, const int *tot_tile0, lon
 // staging buffers of 32, 16 or 8 tiles (the context's staging depth) x 3 (4 with a consensus pre-score) arrays x 64 dwords
 size_t replay3_lds_bytes(const uvaia_gpu_ctx *c)
 { return (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int) + 128 + (size_t)16 * 1024 + (size_t)2 * c->replay_half * (c->n_idx_c > 0 ? 4 : 3) * 256; }
-// replay3_kernel with the context's staging depth
-#define REPLAY3_HALF(B, ...) do { if (c->replay_half == 32) hipLaunchKernelGGL((replay3_kernel<B, 32>), __VA_ARGS__); else if (c->replay_half == 16) hipLaunchKernelGGL((replay3_kernel<B, 16>), __VA_ARGS__); \
-                                  else hipLaunchKernelGGL((replay3_kernel<B, 8>), __VA_ARGS__); } while (0)
-
 int ensure_cnt4(uvaia_gpu_ctx *c, size_t elems)
 {
   if (c->cnt_cap >= elems) return 0;
@@ -291,63 +306,88 @@ int collect_events(uvaia_gpu_ctx *c)
   return 0;
 }
 
-// One batch = one pool of the reference (src/nearest.c:288-306), on tiles [tile_first, tile_first+n_tiles) of `tiles`;
-// references r_begin..r_end-1 (relative to the first tile) are the batch, in order.
-int run_batch(uvaia_gpu_ctx *c, const uint4 *tiles, const int *nonn_tile0, const int *amb_tile0, long long tile_first, int n_tiles, int r_begin, int r_end,
-              long long ord_base, uint8_t *entered_tile0, size_t cnt4_cols = 0 /* four-counter scan: columns its counter buffer is sized for (0: a whole pool) */)
+// One launch of the gate/heap replay over a scanned range: queries [q0, q1), one block each, over references rb .. re-1 (relative to
+// tile tile_first of `planes`).  The context decides the kernel: the four-counter replay (fullscan: counters, pre-score and entered
+// rows in d_cnt / d_rt / d_tr), replay3_kernel where the scan left the extras (ext), else replay2_kernel with its on-demand counters.
+struct ReplayLaunch {
+  hipStream_t stream; int q0, q1;
+  const uint32_t *cnt, *ext; int ppad; const int4 *rt; const uint32_t *rtp; const int2 *tmin; const uint4 *tb8;
+  const uint4 *planes; long long tile_first; const int *nonn, *amb; uint8_t *entered;
+  int rb, re; long long ord_base;
+  const uint32_t *qpl; const uint4 *poly; int nr4; const uint32_t *qrare;   // on-demand counters from the planes derived for the query set (null, 0: from the packed ones)
+  int prefetch;                                                             // candidates of a tile whose on-demand counters are requested ahead: 1, 2 or 3
+  const unsigned *progress; unsigned blocks_per_group; int scan_R; int *pipe_err;   // pipelined search (null, 0, 2, null otherwise: the kernel's defaults)
+};
+int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
 {
-  if (r_end <= r_begin) {   // an empty trailing batch only refreshes cq->max_incompatible (src/nearest.c:290-291)
-    return 0;
-  }
-  const int ppad = n_tiles * 64;
-  hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T, c->nq, c->d_snap);
-  if (c->n_idx_c > 0 && c->fullscan) {   // with no constant-and-complete column every pre-score counter is zero (common: gappy query sets)
-    if (c->acgt) hipLaunchKernelGGL((consensus_kernel<true>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, tiles, tile_first, n_tiles, c->W4, c->d_cp, c->d_snap, c->d_rt, c->d_tr);
-    else         hipLaunchKernelGGL((consensus_kernel<false>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, tiles, tile_first, n_tiles, c->W4, c->d_cp, c->d_snap, c->d_rt, c->d_tr);
-  }
-  HIPCHK(c, hipGetLastError());
-  const double bytes = (double)(r_end - r_begin) * (double)c->W4 * 16.0 * c->P + (double)c->nq * (double)c->W4 * 16.0 * c->P;
-  size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int);
-  const int lq_words = (c->replay_lq && !c->acgt && !c->fullscan && lds + (size_t)c->W4 * 4 * 6 * 4 + 128 <= 64 * 1024) ? c->W4 * 4 * 6 : 0;   // query planes cached in LDS
+  const dim3 grid(L.q1 - L.q0), block(64);
+  const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int);
   if (c->fullscan) {
-    int rc = ensure_cnt4(c, (size_t)c->nq_pad * (cnt4_cols ? std::max<size_t>(cnt4_cols, (size_t)ppad) : c->pool_pad)); if (rc) return rc;
-    rc = launch_scan(c, tiles, tile_first, n_tiles, c->d_qp, c->nq, c->d_cnt, ppad, bytes);
-    if (rc) return rc;
-    if (c->acgt) hipLaunchKernelGGL((replay_kernel<true>), dim3(c->nq), dim3(64), lds, c->stream, c->d_cnt, ppad, c->d_rt, c->d_tr, nonn_tile0, r_begin, r_end, ord_base, c->d_heap, c->d_n, c->d_T, c->d_snap, entered_tile0, c->k);
-    else         hipLaunchKernelGGL((replay_kernel<false>), dim3(c->nq), dim3(64), lds, c->stream, c->d_cnt, ppad, c->d_rt, c->d_tr, nonn_tile0, r_begin, r_end, ord_base, c->d_heap, c->d_n, c->d_T, c->d_snap, entered_tile0, c->k);
-  } else {
-    int rc = launch_scan2(c, tiles, (tiles == c->d_db ? c->d_db_tot : c->d_batch_tot) + tile_first * 64, tile_first, n_tiles, c->d_cnt2, ppad, bytes, nullptr, c->d_tmin[0], r_begin, r_end, c->d_rtb[0], c->use_ext ? c->d_extb[0] : nullptr, c->d_rtpb[0], c->d_tb8[0]);
-    if (rc) return rc;
-#define REPLAY3(B) REPLAY3_HALF(B, dim3(c->nq), dim3(64), replay3_lds_bytes(c), c->stream, c->d_cnt2, c->d_extb[0], ppad, c->d_rtb[0], c->d_rtpb[0], c->d_cp, nonn_tile0, amb_tile0, r_begin, r_end, ord_base, \
-                                    c->d_heap, c->d_n, c->d_T, c->d_snap, entered_tile0, c->k, tiles, tile_first, c->W4, c->d_qp, c->d_amb_q, c->d_stats, 0, c->d_tb8[0], c->replay_prio)
-    if (c->use_ext) { if (c->n_idx_c > 0) REPLAY3(true); else REPLAY3(false); } else
+#define REPLAY(A) hipLaunchKernelGGL((replay_kernel<A>), grid, block, lds, L.stream, c->d_cnt, L.ppad, c->d_rt, c->d_tr, L.nonn, L.rb, L.re, L.ord_base, c->d_heap, c->d_n, c->d_T, c->d_snap, L.entered, c->k)
+    if (c->acgt) REPLAY(true); else REPLAY(false);
+#undef REPLAY
+  } else if (L.ext) {     // the scan left every counter of every pair: the replay without a round trip per admission, with the context's staging depth
+#define REPLAY3(B, H) hipLaunchKernelGGL((replay3_kernel<B, H>), grid, block, replay3_lds_bytes(c), L.stream, L.cnt, L.ext, L.ppad, L.rt, L.rtp, c->d_cp, L.nonn, L.amb, L.rb, L.re, L.ord_base, \
+                                         c->d_heap, c->d_n, c->d_T, c->d_snap, L.entered, c->k, L.planes, L.tile_first, c->W4, c->d_qp, c->d_amb_q, c->d_stats, L.q0, L.tb8, c->replay_prio)
+#define REPLAY3_HALF(B) { if (c->replay_half == 32) REPLAY3(B, 32); else if (c->replay_half == 16) REPLAY3(B, 16); else REPLAY3(B, 8); }
+    if (c->n_idx_c > 0) REPLAY3_HALF(true) else REPLAY3_HALF(false)
+#undef REPLAY3_HALF
 #undef REPLAY3
-#define REPLAY2(A, B) hipLaunchKernelGGL((replay2_kernel<A, B>), dim3(c->nq), dim3(64), lds + (size_t)lq_words * 4 + 128, c->stream, c->d_cnt2, ppad, c->d_rtb[0], c->d_cp, nonn_tile0, amb_tile0, r_begin, r_end, ord_base, \
-                                    c->d_heap, c->d_n, c->d_T, c->d_snap, entered_tile0, c->k, tiles, tile_first, c->W4, c->d_qp, c->d_amb_q, c->d_stats, 0, (c->scan_variant == 2 || c->scan_variant == 0) ? c->d_tmin[0] : (const int2 *)nullptr, \
-                                    c->scan_variant == 2 ? c->d_qpl : (const uint32_t *)nullptr, lq_words, c->replay_prio, (tiles == c->d_db ? c->d_db_poly : c->d_batch_poly), c->NP4 + c->NR4, c->NP4, c->NR4, c->d_qrare)
-    { if (c->acgt) { if (c->n_idx_c > 0) REPLAY2(true, true); else REPLAY2(true, false); }
-      else         { if (c->n_idx_c > 0) REPLAY2(false, true); else REPLAY2(false, false); } }
+  } else {
+    const int lq_words = (c->replay_lq && !c->acgt && lds + (size_t)c->W4 * 4 * 6 * 4 + 128 <= 64 * 1024) ? c->W4 * 4 * 6 : 0;   // query planes cached in LDS
+    const int2 *tmin = (c->scan_variant == 2 || c->scan_variant == 0) ? L.tmin : nullptr;
+#define REPLAY2(A, B, PF_) hipLaunchKernelGGL((replay2_kernel<A, B, PF_>), grid, block, lds + (size_t)lq_words * 4 + 128, L.stream, L.cnt, L.ppad, L.rt, c->d_cp, L.nonn, L.amb, L.rb, L.re, L.ord_base, \
+                                              c->d_heap, c->d_n, c->d_T, c->d_snap, L.entered, c->k, L.planes, L.tile_first, c->W4, c->d_qp, c->d_amb_q, c->d_stats, L.q0, tmin, L.qpl, lq_words, c->replay_prio, \
+                                              L.poly, c->NP4 + c->NR4, c->NP4, L.nr4, L.qrare, L.progress, L.blocks_per_group, L.scan_R, L.pipe_err)
+#define REPLAY2_PF(A, B) { if (L.prefetch == 1) REPLAY2(A, B, 1); else if (L.prefetch == 2) REPLAY2(A, B, 2); else REPLAY2(A, B, 3); }
+    if (c->acgt) { if (c->n_idx_c > 0) REPLAY2_PF(true, true) else REPLAY2_PF(true, false) }
+    else         { if (c->n_idx_c > 0) REPLAY2_PF(false, true) else REPLAY2_PF(false, false) }
+#undef REPLAY2_PF
 #undef REPLAY2
   }
   HIPCHK(c, hipGetLastError());
-  c->last_tiles = tiles; c->last_nonn = nonn_tile0; c->last_n = r_end - r_begin; c->last_rbegin = r_begin; c->last_ppad = ppad; c->last_rt = c->fullscan ? c->d_rt : c->d_rtb[0];
-  c->last_ntiles = n_tiles; c->last_tile_first = tile_first;
+  return 0;
+}
+
+// One batch = one pool of the reference (src/nearest.c:288-306), on tiles [tile_first, tile_first+n_tiles) of the store;
+// references r_begin..r_end-1 (relative to the first tile) are the batch, in order.
+int run_batch(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, int r_begin, int r_end,
+              long long ord_base, size_t cnt4_cols = 0 /* four-counter scan: columns its counter buffer is sized for (0: a whole pool) */)
+{
+  if (r_end <= r_begin) return 0;   // an empty trailing batch only refreshes cq->max_incompatible (src/nearest.c:290-291)
+  const int ppad = n_tiles * 64;
+  const SliceBuf &b = c->slice[0];
+  hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T, c->nq, c->d_snap);
+  if (c->n_idx_c > 0 && c->fullscan) {   // with no constant-and-complete column every pre-score counter is zero (common: gappy query sets)
+    if (c->acgt) hipLaunchKernelGGL((consensus_kernel<true>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, s.planes, tile_first, n_tiles, c->W4, c->d_cp, c->d_snap, c->d_rt, c->d_tr);
+    else         hipLaunchKernelGGL((consensus_kernel<false>), dim3((n_tiles + 3) / 4), dim3(256), 0, c->stream, s.planes, tile_first, n_tiles, c->W4, c->d_cp, c->d_snap, c->d_rt, c->d_tr);
+  }
+  HIPCHK(c, hipGetLastError());
+  const double bytes = (double)(r_end - r_begin) * (double)c->W4 * 16.0 * c->P + (double)c->nq * (double)c->W4 * 16.0 * c->P;
+  uint32_t *ext = c->use_ext ? b.ext : nullptr;
+  int rc = 0;
+  if (c->fullscan) {
+    rc = ensure_cnt4(c, (size_t)c->nq_pad * (cnt4_cols ? std::max<size_t>(cnt4_cols, (size_t)ppad) : c->pool_pad)); if (rc) return rc;
+    rc = launch_scan(c, s, tile_first, n_tiles, c->d_qp, c->nq, c->d_cnt, ppad, bytes);
+  } else rc = launch_scan2(c, s, tile_first, n_tiles, b.cnt, ppad, bytes, nullptr, b.tmin, r_begin, r_end, b.rt, ext, b.rtp, b.tb8);
+  if (rc) return rc;
+  rc = launch_replay(c, {c->stream, 0, c->nq, b.cnt, ext, ppad, b.rt, b.rtp, b.tmin, b.tb8,
+                             s.planes, tile_first, s.nonn + tile_first * 64, s.amb + tile_first * 64 * AMB_ROW, c->d_entered + tile_first * 64, r_begin, r_end, ord_base,
+                             c->scan_variant == 2 ? c->d_qpl : nullptr, s.poly, c->NR4, c->d_qrare, 3, nullptr, 0, 2, nullptr});
+  if (rc) return rc;
+  c->last = {&s, tile_first, n_tiles, r_end - r_begin, r_begin, ppad, c->fullscan ? c->d_rt : b.rt};
   return 0;
 }
 
 // planes derived for the open query set (column-compressed scan) for the whole tiles that hold slots slot0 .. slot0 + n_ref - 1 of
-// `tiles` (resident database under reference shards: the context's own numbering of the tiles it keeps, see for_owned_tiles)
-int derive_rows(uvaia_gpu_ctx *c, uint4 *tiles, long long slot0, int n_ref, hipStream_t st = nullptr, bool v_in_place = false)
+// the store (resident database under reference shards: the context's own numbering of the tiles it keeps, see for_owned_tiles)
+int derive_rows(uvaia_gpu_ctx *c, const TileStore &s, long long slot0, int n_ref, hipStream_t st = nullptr, bool v_in_place = false)
 {
   if (!st) st = c->stream;
   if (c->fullscan || c->scan_variant != 2 || n_ref <= 0 || !c->d_split) return 0;     // only the column-compressed scan reads derived planes
-  const bool is_db = (tiles == c->d_db);
-  uint4 *ev = is_db ? c->d_db_ev : c->d_batch_ev, *poly = is_db ? c->d_db_poly : c->d_batch_poly;
-  int *tote = is_db ? c->d_db_tote : c->d_batch_tote;
-  uint32_t *grp = is_db ? c->d_db_grp : c->d_batch_grp;
   const long long a = slot0 / 64, t1 = (slot0 + n_ref - 1) / 64;
   const int nblk = (int)(t1 - a + 1);
-#define DERIVE_ALL(A, V) hipLaunchKernelGGL((derive_all_kernel<A, V>), dim3(nblk), dim3(256), 0, st, tiles, a, a, c->W4, c->d_cls, c->d_rmask, c->d_split, c->NP4, c->NR4, ev, tote, grp, poly)
+#define DERIVE_ALL(A, V) hipLaunchKernelGGL((derive_all_kernel<A, V>), dim3(nblk), dim3(256), 0, st, s.planes, a, a, c->W4, c->d_cls, c->d_rmask, c->d_split, c->NP4, c->NR4, s.ev, s.tote, s.grp, s.poly)
   if (c->acgt) { if (v_in_place) DERIVE_ALL(true, false); else DERIVE_ALL(true, true); }
   else         { if (v_in_place) DERIVE_ALL(false, false); else DERIVE_ALL(false, true); }
 #undef DERIVE_ALL
@@ -355,16 +395,41 @@ int derive_rows(uvaia_gpu_ctx *c, uint4 *tiles, long long slot0, int n_ref, hipS
   return 0;
 }
 
-// a rebuild of the derived planes still in flight (uvaia_gpu_db_rederive) must end before the database changes
-static int settle_derive(uvaia_gpu_ctx *c)
+int sync_scan_streams(uvaia_gpu_ctx *c) { for (hipStream_t st : c->scan_streams) if (st) HIPCHK(c, hipStreamSynchronize(st)); return 0; }
+int sync_derive_streams(uvaia_gpu_ctx *c) { for (hipStream_t st : c->derive_streams) if (st) HIPCHK(c, hipStreamSynchronize(st)); return 0; }
+
+template <class T> int regrow(uvaia_gpu_ctx *c, T *&p, size_t n) { if (p) hipFree(p); p = nullptr; HIPCHK(c, hipMalloc(&p, n * sizeof(T))); return 0; }
+
+// room in a counter buffer for `need` pairs of a slice of ppad columns: never less than a pool's, and never less than it held before
+// (buffer 0 is the push path's too); the streams that may still use the arrays are waited for before they go
+int slice_reserve(uvaia_gpu_ctx *c, SliceBuf &b, size_t need, size_t ppad)
 {
-  if (c->derive_pending) { for (int i_ = 0; i_ < 3; i_++) if (c->derive_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->derive_streams[i_])); c->derive_pending = 0; }
+  need = std::max(need, b.cap);
+  if (need <= b.cap && b.tmin) return 0;
+  if (int rc = sync_scan_streams(c)) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t cap = std::max(need, (size_t)c->nq_pad * c->pool_pad), refs = std::max(cap / (size_t)c->nq_pad, ppad) + 64;
+  if (cap > b.cap || !b.cnt) { if (int rc = regrow(c, b.cnt, cap)) return rc; }
+  if (int rc = regrow(c, b.tmin, cap / 64)) return rc;
+  if (c->use_ext) {
+    if (int rc = regrow(c, b.ext, cap)) return rc;
+    if (int rc = regrow(c, b.tb8, cap / 64)) return rc;
+    if (int rc = regrow(c, b.rtp, refs)) return rc;
+  }
+  if (int rc = regrow(c, b.rt, refs)) return rc;
+  b.cap = cap;
   return 0;
 }
 
-// stage + pack n_ref rows (either scattered pointers or one pitched block) into `tiles` starting at slot0
-int pack_rows(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t rows_pitch, const int *non_n, int n_ref,
-              uint4 *tiles, int *nonn_dev, int *amb_dev, int *tot_dev, long long slot0)
+// a rebuild of the derived planes still in flight (uvaia_gpu_db_rederive) must end before the database changes
+static int settle_derive(uvaia_gpu_ctx *c)
+{
+  if (c->derive_pending) { if (int rc = sync_derive_streams(c)) return rc; c->derive_pending = 0; }
+  return 0;
+}
+
+// stage + pack n_ref rows (either scattered pointers or one pitched block) into the store starting at slot0
+int pack_rows(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t rows_pitch, const int *non_n, int n_ref, const TileStore &s, long long slot0)
 {
   // two staging buffers: while chunk k crosses PCIe and is packed, the host threads copy chunk k + 1 into the other pinned buffer
   // (the hand-over of raw characters, 30 KB per reference, is what bounds the streaming entry points, not the kernels)
@@ -380,14 +445,14 @@ int pack_rows(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t
     HIPCHK(c, hipMemcpyAsync(ds, hs, (size_t)m * c->pitch, hipMemcpyHostToDevice, c->stream));
     const long long s0 = slot0 + done, t0 = s0 / 64, t1 = (s0 + m - 1) / 64;
     const int nblk = (int)(t1 - t0 + 1);
-    int *nn_out = non_n ? nullptr : nonn_dev;
-    if (c->acgt) hipLaunchKernelGGL((pack_refs_kernel<3>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, tiles, t0, nn_out, (int *)nullptr, tot_dev, c->d_err);
-    else         hipLaunchKernelGGL((pack_refs_kernel<4>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, tiles, t0, nn_out, amb_dev, tot_dev, c->d_err);
+    int *nn_out = non_n ? nullptr : s.nonn;
+    if (c->acgt) hipLaunchKernelGGL((pack_refs_kernel<3>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, s.planes, t0, nn_out, (int *)nullptr, s.tot, c->d_err);
+    else         hipLaunchKernelGGL((pack_refs_kernel<4>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, s.planes, t0, nn_out, s.amb, s.tot, c->d_err);
     HIPCHK(c, hipGetLastError());
-    if (non_n) HIPCHK(c, hipMemcpyAsync(nonn_dev + s0, non_n + done, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (non_n) HIPCHK(c, hipMemcpyAsync(s.nonn + s0, non_n + done, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(c->stage_free[k], c->stream)); c->stage_busy[k] = true;
   }
-  { int rc = derive_rows(c, tiles, slot0, n_ref); if (rc) return rc; }
+  { int rc = derive_rows(c, s, slot0, n_ref); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));     // scans may start on another stream: the packed and derived planes must be complete
   int bad = 0;
   HIPCHK(c, hipMemcpy(&bad, c->d_err, sizeof(int), hipMemcpyDeviceToHost));

@@ -2,11 +2,6 @@
 
 extern "C" {
 
-
-int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf);
-int uvaia_gpu_slice_replay(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, int stripe_start);
-size_t uvaia_gpu_state_range_bytes(const uvaia_gpu_ctx *c, int q0, int q1);
-
 const char *uvaia_gpu_last_error(const uvaia_gpu_ctx *ctx) { return ctx ? ctx->err.c_str() : g_open_error.c_str(); }
 
 void uvaia_gpu_close(uvaia_gpu_ctx *c)
@@ -15,19 +10,17 @@ void uvaia_gpu_close(uvaia_gpu_ctx *c)
   if (c->stream) hipStreamSynchronize(c->stream);
   for (auto &e : c->evts) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
-  void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_batch_grp, c->d_db_grp, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_batch_ev, c->d_batch_poly, c->d_db_ev, c->d_db_poly, c->d_batch_tote, c->d_db_tote,
-                 c->d_batch_tot, c->d_db_tot, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga, c->d_qp2, c->d_amb_q, c->d_batch_amb, c->d_db_amb, c->d_cnt2, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_batch, c->d_batch_nonn,
-                 c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_db, c->d_db_nonn};
+  void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga,
+                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err};
   for (void *p : dev) if (p) hipFree(p);
+  store_free(c->batch); store_free(c->db);
+  for (SliceBuf &b : c->slice) slice_free(b);
   if (c->h_stage) hipHostFree(c->h_stage);
   for (int i = 0; i < 2; i++) if (c->stage_free[i]) hipEventDestroy(c->stage_free[i]);
   for (int i = 0; i < 16; i++) if (c->order_ev[i]) hipEventDestroy(c->order_ev[i]);
   for (int i = 0; i < 4; i++) if (c->ball_ev[i]) hipEventDestroy(c->ball_ev[i]);
   for (int i = 0; i < 64; i++) for (int j = 0; j < 2; j++) if (c->ipc_opened[i][j]) hipIpcCloseMemHandle(c->ipc_opened[i][j]);
   for (int i = 0; i < 8; i++) for (int j = 0; j < 3; j++) if (c->mark_ev[i][j]) hipEventDestroy(c->mark_ev[i][j]);
-  for (int i = 0; i < NBUF; i++) { if (c->d_cntb[i]) hipFree(c->d_cntb[i]); if (c->d_tmin[i]) hipFree(c->d_tmin[i]); if (c->d_rtb[i]) hipFree(c->d_rtb[i]); if (c->d_extb[i]) hipFree(c->d_extb[i]); if (c->d_rtpb[i]) hipFree(c->d_rtpb[i]); if (c->d_tb8[i]) hipFree(c->d_tb8[i]); }
-  for (int i = 0; i < NBUF; i++) { if (c->scan_done[i]) hipEventDestroy(c->scan_done[i]); if (c->replay_done[i]) hipEventDestroy(c->replay_done[i]); if (c->scan_started[i]) hipEventDestroy(c->scan_started[i]); if (c->d_progress[i]) hipFree(c->d_progress[i]); }
-  if (c->d_pipe_err) hipFree(c->d_pipe_err);
   for (int i_ = 0; i_ < 3; i_++) if (c->derive_streams[i_]) { hipStreamSynchronize(c->derive_streams[i_]); hipStreamDestroy(c->derive_streams[i_]); }
   for (auto &d : c->derive_chunks) hipEventDestroy(d.done);
   for (int i = 0; i < 4; i++) if (c->derive_fence[i]) hipEventDestroy(c->derive_fence[i]);
@@ -144,7 +137,7 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
       // between the scan (lowest) and the replay (highest): its blocks take the slots scan blocks free, ahead of the next scan blocks
       for (int i = 0; i < 3; i++) OPENCHK(hipStreamCreateWithPriority(&c->derive_streams[i], hipStreamNonBlocking, (prio_least + prio_greatest) / 2));
     }
-    for (int i = 0; i < NBUF; i++) { OPENCHK(hipEventCreateWithFlags(&c->scan_done[i], hipEventDisableTiming)); OPENCHK(hipEventCreateWithFlags(&c->replay_done[i], hipEventDisableTiming)); }
+    for (SliceBuf &b : c->slice) { OPENCHK(hipEventCreateWithFlags(&b.scan_done, hipEventDisableTiming)); OPENCHK(hipEventCreateWithFlags(&b.replay_done, hipEventDisableTiming)); }
     c->derive_stream = c->derive_streams[0];
   }
   uint8_t code_tab[256]; fill_code_table(code_tab);
@@ -196,24 +189,23 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   // ---- batch buffers
   // (the buffers of a streamed batch -- packed tiles, their derived planes, side rows: 25 KB per reference of max_pool -- are allocated
   // by the first call that streams sequences in: ensure_batch_buffers)
-  if (!c->fullscan) { OPENCHK(hipMalloc(&c->d_cnt2, (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t))); c->slice_cap[0] = (size_t)c->nq_pad * c->pool_pad; }
+  SliceBuf &b0 = c->slice[0];      // (the push path works in it: sized for a pool)
+  if (!c->fullscan) { OPENCHK(hipMalloc(&b0.cnt, (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t))); b0.cap = (size_t)c->nq_pad * c->pool_pad; }
   if (c->use_ext) {
-    OPENCHK(hipMalloc(&c->d_extb[0], (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t)));
-    OPENCHK(hipMalloc(&c->d_tb8[0], (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(uint4)));
-    OPENCHK(hipMalloc(&c->d_rtpb[0], c->pool_pad * sizeof(uint32_t)));
-    OPENCHK(hipMemset(c->d_rtpb[0], 0, c->pool_pad * sizeof(uint32_t)));
+    OPENCHK(hipMalloc(&b0.ext, (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t)));
+    OPENCHK(hipMalloc(&b0.tb8, (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(uint4)));
+    OPENCHK(hipMalloc(&b0.rtp, c->pool_pad * sizeof(uint32_t)));
+    OPENCHK(hipMemset(b0.rtp, 0, c->pool_pad * sizeof(uint32_t)));
     const size_t l3 = replay3_lds_bytes(c);
     if (l3 > 160 * 1024) { uvaia_gpu_close(c); return fail(nullptr, UVAIA_GPU_EINVAL, "nbest=%d does not fit the LDS of the replay next to its staging buffers", heap_size); }
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<true, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<false, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<true, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<false, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay3_kernel<false, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l3));
+    // (every instantiation launch_replay can launch with more than the default dynamic LDS: here and below)
+#define BIGLDS(K, N) OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(N)))
+    BIGLDS((replay3_kernel<true, 32>), l3); BIGLDS((replay3_kernel<false, 32>), l3); BIGLDS((replay3_kernel<true, 16>), l3);
+    BIGLDS((replay3_kernel<false, 16>), l3); BIGLDS((replay3_kernel<true, 8>), l3); BIGLDS((replay3_kernel<false, 8>), l3);
   }
-  OPENCHK(hipMalloc(&c->d_tmin[0], (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(int2)));
-  OPENCHK(hipMalloc(&c->d_rtb[0], c->pool_pad * sizeof(int4)));
-  OPENCHK(hipMemset(c->d_rtb[0], 0, c->pool_pad * sizeof(int4)));
+  OPENCHK(hipMalloc(&b0.tmin, (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(int2)));
+  OPENCHK(hipMalloc(&b0.rt, c->pool_pad * sizeof(int4)));
+  OPENCHK(hipMemset(b0.rt, 0, c->pool_pad * sizeof(int4)));
   OPENCHK(hipMalloc(&c->d_stats, 16 * sizeof(unsigned long long)));
   OPENCHK(hipMemset(c->d_stats, 0, 16 * sizeof(unsigned long long)));
   OPENCHK(hipMalloc(&c->d_rt, c->pool_pad * sizeof(int4)));
@@ -224,17 +216,12 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   OPENCHK(hipMemset(c->d_entered, 0, c->pool_pad));
   const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int) + 128;      // heap + the listed-words bitmap of replay2_kernel
   if (lds > 64 * 1024) {
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay2_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay2_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay2_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay2_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#define BIGHEAP(A, B, PF_) OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&replay2_kernel<A, B, PF_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
-    BIGHEAP(true, true, 1); BIGHEAP(true, false, 1); BIGHEAP(false, true, 1); BIGHEAP(false, false, 1);
-    BIGHEAP(true, true, 2); BIGHEAP(true, false, 2); BIGHEAP(false, true, 2); BIGHEAP(false, false, 2);
+    BIGLDS(replay_kernel<true>, lds); BIGLDS(replay_kernel<false>, lds);
+#define BIGHEAP(PF_) BIGLDS((replay2_kernel<true, true, PF_>), lds); BIGLDS((replay2_kernel<true, false, PF_>), lds); BIGLDS((replay2_kernel<false, true, PF_>), lds); BIGLDS((replay2_kernel<false, false, PF_>), lds)
+    BIGHEAP(1); BIGHEAP(2); BIGHEAP(3);
 #undef BIGHEAP
   }
+#undef BIGLDS
 #undef OPENCHK
   int rc = uvaia_gpu_reset(c);
   if (rc) { g_open_error = c->err; uvaia_gpu_close(c); return rc; }
@@ -268,7 +255,7 @@ int uvaia_gpu_reset(uvaia_gpu_ctx *c)
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(c->d_snap, &c->nchar, sizeof(int), hipMemcpyHostToDevice, c->stream));   // cq->max_incompatible = n_sites (src/nearest.c:375)
   if (c->d_entered && c->db_n) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
-  for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
+  if (int rc = sync_scan_streams(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -7,26 +7,13 @@ int uvaia_gpu_db_reserve(uvaia_gpu_ctx *c, size_t cap)
   if (!c) return UVAIA_GPU_EINVAL;
   if (cap <= c->db_cap) return 0;
   if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "reserve the database before appending to it");
-  if (c->d_db) { hipFree(c->d_db); hipFree(c->d_db_nonn); hipFree(c->d_db_amb); hipFree(c->d_db_tot); hipFree(c->d_db_ev); hipFree(c->d_db_poly); hipFree(c->d_db_tote); hipFree(c->d_db_grp); c->d_db_grp = nullptr;
-                 c->d_db = nullptr; c->d_db_nonn = nullptr; c->d_db_amb = nullptr; c->d_db_tot = nullptr; c->d_db_ev = c->d_db_poly = nullptr; c->d_db_tote = nullptr; }
-  const size_t tiles = (cap + 63) / 64 + 1, tile_u4 = (size_t)c->W4 * c->P * 64;
+  const size_t tiles = (cap + 63) / 64 + 1;
   // reference shards: everything that is kept per reference -- packed planes, side rows, counts, derived planes -- for the owned pieces
   // only (+ one tile: a piece may end inside the capacity's last tile)
   const size_t dtiles = derived_tiles(c, tiles) + (c->shard_world > 1 ? 1 : 0);
-  HIPCHK(c, hipMalloc(&c->d_db, dtiles * tile_u4 * sizeof(uint4)));
-  HIPCHK(c, hipMemset(c->d_db, 0, dtiles * tile_u4 * sizeof(uint4)));
-  HIPCHK(c, hipMalloc(&c->d_db_nonn, dtiles * 64 * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_db_nonn, 0, dtiles * 64 * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_db_ev, dtiles * (size_t)c->W4 * 2 * 64 * sizeof(uint4)));
-  HIPCHK(c, hipMalloc(&c->d_db_grp, dtiles * (size_t)c->W4 * 64 * sizeof(uint32_t)));
-  HIPCHK(c, hipMalloc(&c->d_db_poly, dtiles * (size_t)std::max(c->NP4 + c->NR4, 1) * 3 * 64 * sizeof(uint4)));
-  HIPCHK(c, hipMalloc(&c->d_db_tote, dtiles * 64 * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_db_tot, dtiles * 64 * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_db_tot, 0, dtiles * 64 * sizeof(int)));
-  HIPCHK(c, hipMalloc(&c->d_db_amb, dtiles * 64 * AMB_ROW * sizeof(int)));
-  HIPCHK(c, hipMemset(c->d_db_amb, 0, dtiles * 64 * AMB_ROW * sizeof(int)));
+  if (int rc = store_alloc(c, c->db, dtiles)) return rc;
   c->db_local_tiles = dtiles;
-  c->peer_db[c->shard_rank] = c->d_db; c->peer_amb[c->shard_rank] = c->d_db_amb;
+  c->peer_db[c->shard_rank] = c->db.planes; c->peer_amb[c->shard_rank] = c->db.amb;
   c->db_cap = tiles * 64 - 64;
   if (c->entered_cap < tiles * 64) {
     hipFree(c->d_entered); c->d_entered = nullptr;
@@ -53,8 +40,7 @@ static int db_append_common(uvaia_gpu_ctx *c, const char *const *seq, const char
     const long long pe = c->shard_world == 1 ? s1 : std::min(s1, (a / (c->shard_pt * 64) + 1) * c->shard_pt * 64);
     if (owns_tile(c, a / 64)) {
       const long long off = a - s0, local = dtile_of(c, a / 64) * 64 + a % 64;
-      int rc = pack_rows(c, seq ? seq + off : nullptr, rows ? rows + (size_t)off * pitch : nullptr, pitch, non_n ? non_n + off : nullptr, (int)(pe - a),
-                         c->d_db, c->d_db_nonn, c->d_db_amb, c->d_db_tot, local);
+      int rc = pack_rows(c, seq ? seq + off : nullptr, rows ? rows + (size_t)off * pitch : nullptr, pitch, non_n ? non_n + off : nullptr, (int)(pe - a), c->db, local);
       if (rc) return rc;
     }
     a = pe;
@@ -88,15 +74,15 @@ size_t uvaia_gpu_db_size(const uvaia_gpu_ctx *c) { return c ? c->db_n : 0; }
 int uvaia_gpu_db_clear(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (!c->d_db || !c->db_n) { c->db_n = 0; return 0; }
+  if (!c->db.planes || !c->db_n) { c->db_n = 0; return 0; }
   { int rc = settle_derive(c); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
+  if (int rc = sync_scan_streams(c)) return rc;
   const size_t tiles = c->shard_world == 1 ? (c->db_n + 63) / 64 : c->db_local_tiles;       // lanes past the last reference of a tile must read as zero planes
-  HIPCHK(c, hipMemsetAsync(c->d_db, 0, tiles * (size_t)c->W4 * c->P * 64 * sizeof(uint4), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_db_nonn, 0, tiles * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_db_tot, 0, tiles * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->d_db_amb, 0, tiles * 64 * AMB_ROW * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->db.planes, 0, tiles * (size_t)c->W4 * c->P * 64 * sizeof(uint4), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->db.nonn, 0, tiles * 64 * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->db.tot, 0, tiles * 64 * sizeof(int), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->db.amb, 0, tiles * 64 * AMB_ROW * sizeof(int), c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->db_n = 0;
   return 0;
@@ -114,9 +100,9 @@ int uvaia_gpu_db_export(uvaia_gpu_ctx *c, size_t first_tile, size_t n_tiles, voi
   if (!n_tiles) return 0;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t tb = uvaia_gpu_db_tile_bytes(c);
-  HIPCHK(c, hipMemcpy(planes, reinterpret_cast<const char *>(c->d_db) + first_tile * tb, n_tiles * tb, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(non_n, c->d_db_nonn + first_tile * 64, n_tiles * 64 * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(side_rows, c->d_db_amb + first_tile * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(planes, reinterpret_cast<const char *>(c->db.planes) + first_tile * tb, n_tiles * tb, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(non_n, c->db.nonn + first_tile * 64, n_tiles * 64 * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(side_rows, c->db.amb + first_tile * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -139,10 +125,10 @@ int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *
     const size_t n_tiles = (size_t)nt, off = (size_t)(gt - t0g);
     const char *pl = reinterpret_cast<const char *>(planes) + off * tb;
     if (!c->acgt) {     // same form as the resident planes: straight into place, then the totals
-      HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->d_db) + (size_t)t0 * tb, pl, n_tiles * tb, hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL((import_tiles_kernel<4>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->d_db + (size_t)t0 * c->W4 * 4 * 64, c->W4, (uint4 *)nullptr, t0, c->d_db_tot);
+      HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->db.planes) + (size_t)t0 * tb, pl, n_tiles * tb, hipMemcpyHostToDevice, c->stream));
+      hipLaunchKernelGGL((import_tiles_kernel<4>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->db.planes + (size_t)t0 * c->W4 * 4 * 64, c->W4, (uint4 *)nullptr, t0, c->db.tot);
       HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(c->d_db_amb + (size_t)t0 * 64 * AMB_ROW, side_rows + off * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->db.amb + (size_t)t0 * 64 * AMB_ROW, side_rows + off * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->stream));
     } else {            // re-code through a staging buffer, a few tiles at a time
       const size_t chunk = 64;
       uint4 *d_tmp = nullptr;
@@ -150,17 +136,17 @@ int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *
       for (size_t a = 0; a < n_tiles; a += chunk) {
         const size_t m = std::min(chunk, n_tiles - a);
         hipError_t e = hipMemcpyAsync(d_tmp, pl + a * tb, m * tb, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) { hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)m), dim3(256), 0, c->stream, d_tmp, c->W4, c->d_db, t0 + (long long)a, c->d_db_tot); e = hipGetLastError(); }
+        if (e == hipSuccess) { hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)m), dim3(256), 0, c->stream, d_tmp, c->W4, c->db.planes, t0 + (long long)a, c->db.tot); e = hipGetLastError(); }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) { hipFree(d_tmp); return fail(c, UVAIA_GPU_EHIP, "import of packed tiles: %s", hipGetErrorString(e)); }
       }
       hipFree(d_tmp);
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_db_nonn + (size_t)t0 * 64, non_n + off * 64, n_tiles * 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->d_db_amb + (size_t)t0 * 64 * AMB_ROW,
-                       c->d_db_nonn + (size_t)t0 * 64, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
+    HIPCHK(c, hipMemcpyAsync(c->db.nonn + (size_t)t0 * 64, non_n + off * 64, n_tiles * 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb + (size_t)t0 * 64 * AMB_ROW,
+                       c->db.nonn + (size_t)t0 * 64, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
     HIPCHK(c, hipGetLastError());
-    return derive_rows(c, c->d_db, t0 * 64, (int)(n_tiles * 64));
+    return derive_rows(c, c->db, t0 * 64, (int)(n_tiles * 64));
   });
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -239,7 +225,7 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
   // Issued on its own stream in the chunks the search will scan, one event each: the first slice's scan starts as soon as its
   // chunk is done and the rest is rebuilt next to it (the rebuild is bound by HBM, the scan by instruction issue).
   if (!c) return UVAIA_GPU_EINVAL;
-  if (!c->d_db || !c->db_n || c->fullscan || c->scan_variant != 2) return 0;
+  if (!c->db.planes || !c->db_n || c->fullscan || c->scan_variant != 2) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   {   // searches still in flight read the planes: the rebuild queues behind them
     hipStream_t busy[4] = {c->stream, c->scan_streams[0], c->scan_streams[1], c->scan_streams[2]};
@@ -272,7 +258,7 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
       c->derive_chunks.push_back(d);
     }
     hipStream_t ds = c->derive_streams[k % (size_t)n_derive_streams];
-    int rc = for_owned_tiles(c, t0, t1, [&](long long, long long lt, long long nt) -> int { return derive_rows(c, c->d_db, lt * 64, (int)(nt * 64), ds, true); });
+    int rc = for_owned_tiles(c, t0, t1, [&](long long, long long lt, long long nt) -> int { return derive_rows(c, c->db, lt * 64, (int)(nt * 64), ds, true); });
     if (rc) return rc;
     c->derive_chunks[k].t0 = t0; c->derive_chunks[k].t1 = t1;
     HIPCHK(c, hipEventRecord(c->derive_chunks[k].done, ds));
@@ -339,7 +325,7 @@ static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs_in,
       int rc = uvaia_gpu_slice_scan(c, subs[issued].first, subs[issued].n, (int)(issued % NBUF));
       if (rc) return rc;
       issued++;
-      if (serial_) for (int i_ = 0; i_ < 3; i_++) hipStreamSynchronize(c->scan_streams[i_]);
+      if (serial_) (void)sync_scan_streams(c);
     }
     int take = subs[i].pool_start ? 1 : 0;
     if (take && snapshot >= 0) { HIPCHK(c, hipMemcpyAsync(c->d_snap, &snapshot, sizeof(int), hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); take = 0; }
@@ -370,7 +356,7 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
       head = 128;
       const bool fs = c->fullscan, prof = c->profile;
       c->fullscan = true; c->profile = false;               // (not one of the scan launches the statistics are about)
-      const int rc = run_batch(c, c->d_db, c->d_db_nonn, c->d_db_amb, 0, 2, 0, (int)head, (long long)ordinal0, c->d_entered, 128);
+      const int rc = run_batch(c, c->db, 0, 2, 0, (int)head, (long long)ordinal0, 128);
       c->fullscan = fs; c->profile = prof;
       if (rc) return rc;
     }
@@ -382,7 +368,7 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
     const long long tf = (long long)(a / 64);
     const int n_tiles = (int)((b + 63) / 64 - a / 64);
     const int rb = (int)(a - (size_t)tf * 64), re = (int)(b - (size_t)tf * 64);
-    int rc = run_batch(c, c->d_db, c->d_db_nonn + tf * 64, c->d_db_amb + tf * 64 * AMB_ROW, tf, n_tiles, rb, re, ordinal0 + (long long)a, c->d_entered + tf * 64);
+    int rc = run_batch(c, c->db, tf, n_tiles, rb, re, ordinal0 + (long long)a);
     if (rc) return rc;
   }
   if (entered) {
@@ -405,9 +391,9 @@ int uvaia_gpu_search_resident_pool(uvaia_gpu_ctx *c, size_t first, size_t n, int
 int uvaia_gpu_sync(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  for (int i_ = 0; i_ < 3; i_++) if (c->derive_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->derive_streams[i_]));
+  if (int rc = sync_derive_streams(c)) return rc;
   c->derive_pending = 0;
-  for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
+  if (int rc = sync_scan_streams(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream));
   { int rc = pipe_check(c); if (rc) return rc; }
@@ -417,20 +403,21 @@ int uvaia_gpu_sync(uvaia_gpu_ctx *c)
 int uvaia_gpu_last_batch_scores(uvaia_gpu_ctx *c, int *out, int n_ref)
 {
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  if (n_ref != c->last_n || !c->last_nonn) return fail(c, UVAIA_GPU_ESTATE, "last batch held %d references, not %d", c->last_n, n_ref);
+  if (n_ref != c->last.n || !c->last.store) return fail(c, UVAIA_GPU_ESTATE, "last batch held %d references, not %d", c->last.n, n_ref);
+  const int *nonn = c->last.store->nonn + c->last.tile_first * 64;
   int *d_out = nullptr;
   const size_t bytes = (size_t)n_ref * c->nq * 6 * sizeof(int);
   if (!c->fullscan) {   // the production path keeps two counters per pair: recount the batch with the four-counter kernel
-    int rc = ensure_cnt4(c, (size_t)c->nq_pad * c->last_ppad); if (rc) return rc;
+    int rc = ensure_cnt4(c, (size_t)c->nq_pad * c->last.ppad); if (rc) return rc;
     const bool prof = c->profile; c->profile = false;
-    rc = launch_scan(c, c->last_tiles, c->last_tile_first, c->last_ntiles, c->d_qp, c->nq, c->d_cnt, c->last_ppad, 0.0);
+    rc = launch_scan(c, *c->last.store, c->last.tile_first, c->last.n_tiles, c->d_qp, c->nq, c->d_cnt, c->last.ppad, 0.0);
     c->profile = prof;
     if (rc) return rc;
   }
   HIPCHK(c, hipMalloc(&d_out, bytes));
   dim3 grid((n_ref + 255) / 256, c->nq);
-  if (c->acgt) hipLaunchKernelGGL((batch_scores_kernel<true>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last_ppad, c->last_rt, c->last_nonn, c->last_rbegin, n_ref, c->nq, d_out);
-  else         hipLaunchKernelGGL((batch_scores_kernel<false>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last_ppad, c->last_rt, c->last_nonn, c->last_rbegin, n_ref, c->nq, d_out);
+  if (c->acgt) hipLaunchKernelGGL((batch_scores_kernel<true>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
+  else         hipLaunchKernelGGL((batch_scores_kernel<false>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -526,7 +513,7 @@ int uvaia_gpu_state_import_range(uvaia_gpu_ctx *c, const void *src, int q0, int 
 int uvaia_gpu_state_export(uvaia_gpu_ctx *c, void *dst) { return c ? uvaia_gpu_state_export_range(c, dst, 0, c->nq) : UVAIA_GPU_EINVAL; }
 int uvaia_gpu_state_import(uvaia_gpu_ctx *c, const void *src) { return c ? uvaia_gpu_state_import_range(c, src, 0, c->nq) : UVAIA_GPU_EINVAL; }
 
-// counts of database references [first, first+n) into counter buffer `buf` (0/1), asynchronously on the scan stream
+// counts of database references [first, first+n) into counter buffer `buf` (0 .. NBUF-1), asynchronously on a scan stream
 int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
 {
   if (!c || buf < 0 || buf >= NBUF) return UVAIA_GPU_EINVAL;
@@ -535,66 +522,42 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
   if (first + n > c->db_n) return fail(c, UVAIA_GPU_EINVAL, "slice [%zu,+%zu) outside the database", first, n);
   // a slice is at most a pool when the batch snapshot can matter (n_idx_c > 0); otherwise pools have no effect and slices are free
   if (n > c->max_pool && c->n_idx_c > 0) return fail(c, UVAIA_GPU_EINVAL, "slice of %zu references above max_pool %zu", n, c->max_pool);
-  {
-    const size_t ppad_ = ((first + n + 63) / 64 - first / 64) * 64;
-    // the scans write whole query tiles up to the last active one: super-tiles of 64 queries (scan3_kernel), tiles of 16 otherwise
-    const size_t qtile = c->scan_variant == 2 ? 64 : 16;
-    const size_t rows = std::min<size_t>((size_t)c->nq_pad, ((size_t)c->act_q1 + qtile - 1) / qtile * qtile);
-    const size_t need = std::max(rows * ppad_, buf == 0 ? c->slice_cap[0] : (size_t)0);
-    if (need > c->slice_cap[buf] || !c->d_tmin[buf]) {
-      for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const size_t cap = std::max(need, (size_t)c->nq_pad * c->pool_pad);
-      uint32_t *&cb = buf ? c->d_cntb[buf] : c->d_cnt2;
-      if (cap > c->slice_cap[buf] || !cb) { if (cb) hipFree(cb); cb = nullptr; HIPCHK(c, hipMalloc(&cb, cap * sizeof(uint32_t))); }
-      if (c->d_tmin[buf]) hipFree(c->d_tmin[buf]);
-      c->d_tmin[buf] = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_tmin[buf], (cap / 64) * sizeof(int2)));
-      if (c->use_ext) {
-        if (c->d_extb[buf]) hipFree(c->d_extb[buf]);
-        c->d_extb[buf] = nullptr; HIPCHK(c, hipMalloc(&c->d_extb[buf], cap * sizeof(uint32_t)));
-        if (c->d_tb8[buf]) hipFree(c->d_tb8[buf]);
-        c->d_tb8[buf] = nullptr; HIPCHK(c, hipMalloc(&c->d_tb8[buf], (cap / 64) * sizeof(uint4)));
-        if (c->d_rtpb[buf]) hipFree(c->d_rtpb[buf]);
-        c->d_rtpb[buf] = nullptr; HIPCHK(c, hipMalloc(&c->d_rtpb[buf], (std::max(cap / (size_t)c->nq_pad, ppad_) + 64) * sizeof(uint32_t)));
-      }
-      if (c->d_rtb[buf]) hipFree(c->d_rtb[buf]);
-      c->d_rtb[buf] = nullptr;
-      HIPCHK(c, hipMalloc(&c->d_rtb[buf], (std::max(cap / (size_t)c->nq_pad, ppad_) + 64) * sizeof(int4)));
-      c->slice_cap[buf] = cap;
-    }
-  }
+  SliceBuf &b = c->slice[buf];
+  const size_t ppad_ = ((first + n + 63) / 64 - first / 64) * 64;
+  // the scans write whole query tiles up to the last active one: super-tiles of 64 queries (scan3_kernel), tiles of 16 otherwise
+  const size_t qtile = c->scan_variant == 2 ? 64 : 16;
+  const size_t rows = std::min<size_t>((size_t)c->nq_pad, ((size_t)c->act_q1 + qtile - 1) / qtile * qtile);
+  if (int rc = slice_reserve(c, b, rows * ppad_, ppad_)) return rc;
   hipStream_t ss = c->scan_streams[c->scan_nstreams > 1 ? (c->scan_rr++ % c->scan_nstreams) : 0];
-  if (c->replay_recorded[buf]) HIPCHK(c, hipStreamWaitEvent(ss, c->replay_done[buf], 0));   // the buffer's previous reader
+  if (b.replay_recorded) HIPCHK(c, hipStreamWaitEvent(ss, b.replay_done, 0));   // the buffer's previous reader
   for (size_t k = 0; k < c->derive_pending; k++) {                                          // planes being rebuilt (uvaia_gpu_db_rederive)
     const auto &d = c->derive_chunks[k];
     if (d.t0 < (long long)((first + n + 63) / 64) && d.t1 > (long long)(first / 64)) HIPCHK(c, hipStreamWaitEvent(ss, d.done, 0));
   }
-  const long long tf = (long long)(first / 64);
-  const int n_tiles = n ? (int)((first + n + 63) / 64 - first / 64) : 0;
-  c->slice_tf[buf] = tf; c->slice_tiles[buf] = n_tiles;
-  c->slice_rb[buf] = (int)(first - (size_t)tf * 64); c->slice_re[buf] = c->slice_rb[buf] + (int)n;
-  c->slice_scanned[buf] = true; c->slice_cons_done[buf] = false;
+  b.tf = (long long)(first / 64);
+  b.tiles = n ? (int)((first + n + 63) / 64 - first / 64) : 0;
+  b.rb = (int)(first - (size_t)b.tf * 64); b.re = b.rb + (int)n;
+  b.scanned = true; b.cons_done = false;
   // pipelined (run_subslices, column-compressed scan): zeroed progress counters, one per stripe of tiles; the replay may start once they are zero
   unsigned *progress = nullptr;
-  c->slice_piped[buf] = false;
-  if (c->pipeline_now && c->scan_variant == 2 && n_tiles > 0) {
-    const size_t stripes = (size_t)(n_tiles + SCAN_STRIPE_TILES - 1) / SCAN_STRIPE_TILES;
-    if (stripes > c->progress_cap[buf]) {
-      if (c->d_progress[buf]) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream)); hipFree(c->d_progress[buf]); c->d_progress[buf] = nullptr; }
-      HIPCHK(c, hipMalloc(&c->d_progress[buf], (stripes + 64) * sizeof(unsigned))); c->progress_cap[buf] = stripes + 64;
+  b.piped = false;
+  if (c->pipeline_now && c->scan_variant == 2 && b.tiles > 0) {
+    const size_t stripes = (size_t)(b.tiles + SCAN_STRIPE_TILES - 1) / SCAN_STRIPE_TILES;
+    if (stripes > b.progress_cap) {
+      if (b.progress) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream)); hipFree(b.progress); b.progress = nullptr; }
+      HIPCHK(c, hipMalloc(&b.progress, (stripes + 64) * sizeof(unsigned))); b.progress_cap = stripes + 64;
     }
-    if (!c->scan_started[buf]) HIPCHK(c, hipEventCreateWithFlags(&c->scan_started[buf], hipEventDisableTiming));
+    if (!b.scan_started) HIPCHK(c, hipEventCreateWithFlags(&b.scan_started, hipEventDisableTiming));
     if (!c->d_pipe_err) { HIPCHK(c, hipMalloc(&c->d_pipe_err, sizeof(int))); HIPCHK(c, hipMemset(c->d_pipe_err, 0, sizeof(int))); }
-    progress = c->d_progress[buf];
+    progress = b.progress;
     HIPCHK(c, hipMemsetAsync(progress, 0, stripes * sizeof(unsigned), ss));
-    HIPCHK(c, hipEventRecord(c->scan_started[buf], ss));
-    c->slice_piped[buf] = true; c->pipe_used = true;
+    HIPCHK(c, hipEventRecord(b.scan_started, ss));
+    b.piped = true; c->pipe_used = true;
   }
   const double bytes = (double)n * (double)c->W4 * 16.0 * c->P + (double)c->nq * (double)c->W4 * 16.0 * c->P;
-  int rc = launch_scan2(c, c->d_db, c->d_db_tot + tf * 64, tf, n_tiles, buf ? c->d_cntb[buf] : c->d_cnt2, n_tiles * 64, bytes, ss, c->d_tmin[buf], c->slice_rb[buf], c->slice_re[buf], c->d_rtb[buf], c->use_ext ? c->d_extb[buf] : nullptr, c->d_rtpb[buf], c->d_tb8[buf], progress);
+  int rc = launch_scan2(c, c->db, b.tf, b.tiles, b.cnt, b.tiles * 64, bytes, ss, b.tmin, b.rb, b.re, b.rt, c->use_ext ? b.ext : nullptr, b.rtp, b.tb8, progress);
   if (rc) return rc;
-  HIPCHK(c, hipEventRecord(c->scan_done[buf], ss));
+  HIPCHK(c, hipEventRecord(b.scan_done, ss));
   return 0;
 }
 
@@ -604,47 +567,32 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
 int uvaia_gpu_slice_replay_range(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, int q0, int q1, int take_snapshot)
 {
   if (!c || buf < 0 || buf >= NBUF) return UVAIA_GPU_EINVAL;
-  if (!c->slice_scanned[buf]) return fail(c, UVAIA_GPU_ESTATE, "slice_replay without slice_scan");
+  SliceBuf &b = c->slice[buf];
+  if (!b.scanned) return fail(c, UVAIA_GPU_ESTATE, "slice_replay without slice_scan");
   if (q0 < 0 || q1 > c->nq || q1 < q0) return fail(c, UVAIA_GPU_EINVAL, "bad query range [%d,%d)", q0, q1);
-  const int n_tiles = c->slice_tiles[buf], rb = c->slice_rb[buf], re = c->slice_re[buf];
-  const long long tf = c->slice_tf[buf];
-  if (take_snapshot) { hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T + c->act_q0, c->act_q1 - c->act_q0, c->d_snap); c->slice_cons_done[buf] = false; }
-  if (re <= rb || q1 == q0) return 0;
-  const bool piped = c->slice_piped[buf];
-  HIPCHK(c, hipStreamWaitEvent(c->stream, piped ? c->scan_started[buf] : c->scan_done[buf], 0));
-  const unsigned *progress = piped ? c->d_progress[buf] : nullptr;
-  const unsigned blocks_per_group = (unsigned)((c->act_q1 + 63) / 64 - c->act_q0 / 64);      // the scan's super-tiles of 64 queries
-  const int ppad = n_tiles * 64;
-  const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int);
-  const int lq_words = (c->replay_lq && !c->acgt && lds + (size_t)c->W4 * 4 * 6 * 4 + 128 <= 64 * 1024) ? c->W4 * 4 * 6 : 0;
-  const uint32_t *cnt = buf ? c->d_cntb[buf] : c->d_cnt2;
-  const int *nonn = c->d_db_nonn + tf * 64, *amb = c->d_db_amb + tf * 64 * AMB_ROW;
-  uint8_t *ent = c->d_entered + tf * 64;
-#define REPLAY2P(A, B, PF_) hipLaunchKernelGGL((replay2_kernel<A, B, PF_>), dim3(q1 - q0), dim3(64), lds + (size_t)lq_words * 4 + 128, c->stream, cnt, ppad, c->d_rtb[buf], c->d_cp, nonn, amb, rb, re, (long long)ordinal0, \
-                                  c->d_heap, c->d_n, c->d_T, c->d_snap, ent, c->k, c->d_db, tf, c->W4, c->d_qp, c->d_amb_q, c->d_stats, q0, (c->scan_variant == 2 || c->scan_variant == 0) ? c->d_tmin[buf] : (const int2 *)nullptr, \
-                                  (c->scan_variant == 2 && c->shard_world == 1) ? c->d_qpl : (const uint32_t *)nullptr, lq_words, c->replay_prio, c->d_db_poly, c->NP4 + c->NR4, c->NP4, c->NR4, c->d_qrare, progress, blocks_per_group, c->scan_R, c->d_pipe_err)
+  if (take_snapshot) { hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T + c->act_q0, c->act_q1 - c->act_q0, c->d_snap); b.cons_done = false; }
+  if (b.re <= b.rb || q1 == q0) return 0;
+  HIPCHK(c, hipStreamWaitEvent(c->stream, b.piped ? b.scan_started : b.scan_done, 0));
+  const int ppad = b.tiles * 64;
+  // (packed-plane scan, default mode: the scan left every counter of every pair -- the replay without a round trip per admission)
+  const uint32_t *ext = c->use_ext ? b.ext : nullptr;
+  // (the replay's own compute units: the kernel runs on the masked stream, spliced into c->stream's order by two events)
+  hipStream_t rs = (c->rep_stream && ext) ? c->rep_stream : c->stream;
+  if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[0], c->stream)); HIPCHK(c, hipStreamWaitEvent(rs, c->rep_ev[0], 0)); }
   // Candidates of a tile whose on-demand counters are requested ahead.  The bookkeeping of the request slots costs more than the
   // latency it hides (measured on one box: config[1] 3.69 / 3.54 / 3.60 ms per step with 3 / 2 / 1, 4 queries x 1 M references
   // 4.37 / 4.03 / 3.89; with 6 or 8 over 7 ms): two for large query sets, one -- request, then use -- for a handful of queries.
   const int pf = (q1 - q0) <= 64 ? 1 : 2;
-#define REPLAY2(A, B) { if (pf == 1) REPLAY2P(A, B, 1); else REPLAY2P(A, B, 2); }
-  // (packed-plane scan, default mode: the scan left every counter of every pair -- the replay without a round trip per admission)
-  // (the replay's own compute units: the kernel runs on the masked stream, spliced into c->stream's order by two events)
-  hipStream_t rs = (c->rep_stream && c->use_ext && c->d_extb[buf]) ? c->rep_stream : c->stream;
-  if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[0], c->stream)); HIPCHK(c, hipStreamWaitEvent(rs, c->rep_ev[0], 0)); }
-#define REPLAY3(B) REPLAY3_HALF(B, dim3(q1 - q0), dim3(64), replay3_lds_bytes(c), rs, cnt, c->d_extb[buf], ppad, c->d_rtb[buf], c->d_rtpb[buf], c->d_cp, nonn, amb, rb, re, (long long)ordinal0, \
-                                  c->d_heap, c->d_n, c->d_T, c->d_snap, ent, c->k, c->d_db, tf, c->W4, c->d_qp, c->d_amb_q, c->d_stats, q0, c->d_tb8[buf], c->replay_prio)
-  if (c->use_ext && c->d_extb[buf]) { if (c->n_idx_c > 0) REPLAY3(true); else REPLAY3(false); }
-  else if (c->acgt) { if (c->n_idx_c > 0) REPLAY2(true, true) else REPLAY2(true, false) }
-  else              { if (c->n_idx_c > 0) REPLAY2(false, true) else REPLAY2(false, false) }
-#undef REPLAY3
-#undef REPLAY2P
-#undef REPLAY2
-  HIPCHK(c, hipGetLastError());
+  const unsigned blocks_per_group = (unsigned)((c->act_q1 + 63) / 64 - c->act_q0 / 64);      // the scan's super-tiles of 64 queries
+  int rc = launch_replay(c, {rs, q0, q1, b.cnt, ext, ppad, b.rt, b.rtp, b.tmin, b.tb8,
+                             c->db.planes, b.tf, c->db.nonn + b.tf * 64, c->db.amb + b.tf * 64 * AMB_ROW, c->d_entered + b.tf * 64, b.rb, b.re, (long long)ordinal0,
+                             (c->scan_variant == 2 && c->shard_world == 1) ? c->d_qpl : nullptr, c->db.poly, c->NR4, c->d_qrare, pf,
+                             b.piped ? b.progress : nullptr, blocks_per_group, c->scan_R, c->d_pipe_err});
+  if (rc) return rc;
   if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[1], rs)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->rep_ev[1], 0)); }
-  HIPCHK(c, hipEventRecord(c->replay_done[buf], c->stream));
-  c->replay_recorded[buf] = true;
-  c->last_tiles = c->d_db; c->last_nonn = nonn; c->last_n = re - rb; c->last_rbegin = rb; c->last_ppad = ppad; c->last_ntiles = n_tiles; c->last_tile_first = tf; c->last_rt = c->d_rtb[buf];
+  HIPCHK(c, hipEventRecord(b.replay_done, c->stream));
+  b.replay_recorded = true;
+  c->last = {&c->db, b.tf, b.tiles, b.re - b.rb, b.rb, ppad, b.rt};
   return 0;
 }
 

@@ -13,7 +13,7 @@ int uvaia_gpu_db_set_shard(uvaia_gpu_ctx *c, int rank, int world, size_t piece_r
   if (world < 1 || rank < 0 || rank >= world) return fail(c, UVAIA_GPU_EINVAL, "rank %d of %d", rank, world);
   if (world > 64) return fail(c, UVAIA_GPU_EINVAL, "reference shards: at most 64 ranks, all on one node (a rank reads the others' packed planes in place: peer or hipIpc mappings); got %d", world);
   if (world > 1 && (piece_refs < 64 || piece_refs % 64 || piece_refs > c->max_pool)) return fail(c, UVAIA_GPU_EINVAL, "a piece holds a whole number of tiles of 64 references, at most max_pool = %zu (got %zu)", c->max_pool, piece_refs);
-  if (c->d_db || c->db_n) return fail(c, UVAIA_GPU_ESTATE, "the reference shard is set before the database is reserved");
+  if (c->db.planes || c->db_n) return fail(c, UVAIA_GPU_ESTATE, "the reference shard is set before the database is reserved");
   if (world > 1 && c->fullscan) return fail(c, UVAIA_GPU_ESTATE, "reference shards need the two-counter scans (alignments up to 49 000 columns)");
   c->shard_rank = rank; c->shard_world = world; c->shard_pt = world > 1 ? (long long)(piece_refs / 64) : 0;
   return 0;
@@ -48,20 +48,19 @@ int uvaia_gpu_shard_scan(uvaia_gpu_ctx *c, size_t first, size_t n, void *cnt, vo
   }
   const int rb = (int)(first - (size_t)tf * 64);
   const double bytes = (double)n * (double)c->W4 * 16.0 * c->P + (double)c->nq * (double)c->W4 * 16.0 * c->P;
-  int rc = launch_scan2(c, c->d_db, c->d_db_tot + ltf * 64, ltf, n_tiles, (uint32_t *)cnt, n_tiles * 64, bytes, ss, (int2 *)tmin, rb, rb + (int)n, c->d_rtb[0]);
+  int rc = launch_scan2(c, c->db, ltf, n_tiles, (uint32_t *)cnt, n_tiles * 64, bytes, ss, (int2 *)tmin, rb, rb + (int)n, c->slice[0].rt);
   if (rc) return rc;
   // what travels with the counters: the references' valid sites and their consensus pre-score
   const size_t cols = (size_t)n_tiles * 64;
-  HIPCHK(c, hipMemcpyAsync(aux, c->d_db_nonn + ltf * 64, cols * sizeof(int), hipMemcpyDeviceToDevice, ss));
-  if (c->n_idx_c > 0) HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(aux) + cols * sizeof(int), c->d_rtb[0], cols * sizeof(int4), hipMemcpyDeviceToDevice, ss));
+  HIPCHK(c, hipMemcpyAsync(aux, c->db.nonn + ltf * 64, cols * sizeof(int), hipMemcpyDeviceToDevice, ss));
+  if (c->n_idx_c > 0) HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(aux) + cols * sizeof(int), c->slice[0].rt, cols * sizeof(int4), hipMemcpyDeviceToDevice, ss));
   return 0;
 }
 
 int uvaia_gpu_scan_wait(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  for (int i_ = 0; i_ < 3; i_++) if (c->scan_streams[i_]) HIPCHK(c, hipStreamSynchronize(c->scan_streams[i_]));
-  return 0;
+  return sync_scan_streams(c);
 }
 
 // waits for the replays issued so far (their counter buffers may then be overwritten); scans keep running
@@ -126,16 +125,16 @@ int uvaia_gpu_shard_set_peer(uvaia_gpu_ctx *c, int rank, const void *planes, con
   c->peer_db[rank] = (const uint4 *)planes; c->peer_amb[rank] = (const int *)side_rows;
   return 0;
 }
-const void *uvaia_gpu_shard_planes(const uvaia_gpu_ctx *c) { return c ? c->d_db : nullptr; }
-const void *uvaia_gpu_shard_side_rows(const uvaia_gpu_ctx *c) { return c ? c->d_db_amb : nullptr; }
+const void *uvaia_gpu_shard_planes(const uvaia_gpu_ctx *c) { return c ? c->db.planes : nullptr; }
+const void *uvaia_gpu_shard_side_rows(const uvaia_gpu_ctx *c) { return c ? c->db.amb : nullptr; }
 int uvaia_gpu_shard_ipc_handle_bytes(void) { return 2 * (int)sizeof(hipIpcMemHandle_t); }
 int uvaia_gpu_shard_ipc_handles(uvaia_gpu_ctx *c, void *out)
 { // inter-process handles of this context's packed planes and side rows (after uvaia_gpu_db_reserve)
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  if (!c->d_db || !c->d_db_amb) return fail(c, UVAIA_GPU_ESTATE, "reserve the database first");
+  if (!c->db.planes || !c->db.amb) return fail(c, UVAIA_GPU_ESTATE, "reserve the database first");
   hipIpcMemHandle_t h[2];
-  HIPCHK(c, hipIpcGetMemHandle(&h[0], c->d_db));
-  HIPCHK(c, hipIpcGetMemHandle(&h[1], c->d_db_amb));
+  HIPCHK(c, hipIpcGetMemHandle(&h[0], c->db.planes));
+  HIPCHK(c, hipIpcGetMemHandle(&h[1], c->db.amb));
   memcpy(out, h, sizeof h);
   return 0;
 }
@@ -182,25 +181,17 @@ int uvaia_gpu_shard_replay(uvaia_gpu_ctx *c, const void *cnt, const void *tmin, 
   if (!c->peer_db[owner] || (!c->acgt && !c->peer_amb[owner])) return fail(c, UVAIA_GPU_ESTATE, "the arrays of rank %d are not known to this context (uvaia_gpu_shard_set_peer / uvaia_gpu_shard_ipc_open)", owner);
   const int rb = (int)(first - (size_t)tf * 64), re = rb + (int)n;
   const long long ltf = dtile_of(c, tf);            // the piece's first tile in its owner's numbering
-  const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int);
-  const int lq_words = (c->replay_lq && !c->acgt && lds + (size_t)c->W4 * 4 * 6 * 4 + 128 <= 64 * 1024) ? c->W4 * 4 * 6 : 0;
   // the kernel indexes rows by query number: shift the bases so that row q0 is the buffer's first row
   const uint32_t *cntp = (const uint32_t *)cnt - (ptrdiff_t)q0 * ppad;
   const int2 *tminp = (const int2 *)tmin - (ptrdiff_t)q0 * (ppad / 64);
   const int *nonn = (const int *)aux;
   const int4 *rt = c->n_idx_c > 0 ? (const int4 *)(reinterpret_cast<const char *>(aux) + (size_t)ppad * sizeof(int)) : c->d_rt;
-  const uint4 *pdb = c->peer_db[owner];
   const int *amb = c->peer_amb[owner] ? c->peer_amb[owner] + ltf * 64 * AMB_ROW : nullptr;
-  uint8_t *ent = c->d_entered + tf * 64;
-  // --acgt: dist_unique of the pairs that reach a heap is counted from the packed planes (the scan's per-pair count stays on the scanning rank)
-#define REPLAY2(A, B) hipLaunchKernelGGL((replay2_kernel<A, B>), dim3(q1 - q0), dim3(64), lds + (size_t)lq_words * 4 + 128, c->stream, cntp, ppad, rt, c->d_cp, nonn, amb, rb, re, (long long)ordinal0, \
-                                  c->d_heap, c->d_n, c->d_T, c->d_snap, ent, c->k, pdb, ltf, c->W4, c->d_qp, c->d_amb_q, c->d_stats, q0, tminp, (const uint32_t *)nullptr, lq_words, c->replay_prio, \
-                                  (const uint4 *)nullptr, c->NP4 + c->NR4, c->NP4, 0, (const uint32_t *)nullptr)
-  if (c->acgt) { if (c->n_idx_c > 0) REPLAY2(true, true); else REPLAY2(true, false); }
-  else         { if (c->n_idx_c > 0) REPLAY2(false, true); else REPLAY2(false, false); }
-#undef REPLAY2
-  HIPCHK(c, hipGetLastError());
-  return 0;
+  // the owner's packed planes and side rows; no derived planes of another rank: the on-demand counters come from the packed ones
+  // (--acgt: dist_unique of the pairs that reach a heap is counted from them too, the scan's per-pair count stays on the scanning rank)
+  return launch_replay(c, {c->stream, q0, q1, cntp, nullptr, ppad, rt, nullptr, tminp, nullptr,
+                           c->peer_db[owner], ltf, nonn, amb, c->d_entered + tf * 64, rb, re, (long long)ordinal0,
+                           nullptr, nullptr, 0, nullptr, 3, nullptr, 0, 2, nullptr});
 }
 
 // ---- a group of contexts in ONE process (the C command line's --devices): the reference-shard protocol above with peer copies as

@@ -75,6 +75,34 @@ thread_local std::string g_open_error;
 
 struct ScanEvt { hipEvent_t a, b; double bytes; };
 
+// A set of reference tiles and what belongs to them: the buffers of a streamed batch and the resident database
+struct TileStore {
+  uint4 *planes = nullptr;       // packed tiles (allocated last: its presence says all of them are there)
+  int *nonn = nullptr;           // per reference: non-N sites
+  int *amb = nullptr;            // [AMB_ROW] per reference: side rows, the ambiguity-word lists of the references (as d_amb_q for the queries)
+  int *tot = nullptr;            // per reference: valid sites (default) / ACGT sites (--acgt), counted by pack_refs_kernel
+  // planes derived for the query set (column-compressed scan)
+  uint4 *ev = nullptr, *poly = nullptr;
+  uint32_t *grp = nullptr;       // [tile][W4][64]  popc(E) | popc(V) << 16 of each word group (for queries that are all-N there)
+  int *tote = nullptr;
+};
+
+// One counter buffer of the resident search: what the scan of a slice leaves for its replay, and the events between the two
+struct SliceBuf {
+  uint32_t *cnt = nullptr;       // [rows][ppad] two-counter scan output, one dword per pair: first | second << 16 (buffer 0: allocated at open for a pool, [nq_pad][pool_pad]; the others on first use)
+  int2 *tmin = nullptr;          // per (query, tile of 64 references): {smallest mismatch count, largest ACGT-match count}
+  uint32_t *ext = nullptr;       // packed-plane scan, default mode: per pair the other two counters (scan2_extras); sized like cnt
+  uint32_t *rtp = nullptr;       // ... and per reference the consensus pre-score packed into one dword (query sets with constant-and-complete columns)
+  uint4 *tb8 = nullptr;          // ... and per (query, tile of 64) the eight-entry bounds replay3_kernel walks (tile_bounds8)
+  int4 *rt = nullptr;            // per reference of a slice: untruncated consensus pre-score (query sets with constant-and-complete columns)
+  size_t cap = 0;                // pairs the buffer holds (grown when a slice needs more: slices may exceed a pool, see plan_subslices)
+  int tiles = 0, rb = 0, re = 0; long long tf = 0;     // the slice scanned into it: tiles, first and end reference relative to its first tile, that tile
+  bool scanned = false, cons_done = false, piped = false;
+  unsigned *progress = nullptr; size_t progress_cap = 0;   // pipelined search: the scan's progress counters, one per stripe
+  hipEvent_t scan_done = nullptr, scan_started = nullptr, replay_done = nullptr;
+  bool replay_recorded = false;
+};
+
 }  // namespace
 
 struct uvaia_gpu_ctx {
@@ -86,7 +114,6 @@ struct uvaia_gpu_ctx {
   int scan_nstreams_forced = 0;           // tuning.scan_streams
   int first_slice_pct = 70;               // a pool's first slice is this share of an equal one (tuning.scan_streams = 100 + p sets p; 199 = equal slices)
   hipStream_t scan_stream = nullptr;      // ring mode: scans of later slices run here while the replay chain waits
-  hipEvent_t scan_done[NBUF] = {}, replay_done[NBUF] = {};
   // uvaia_gpu_db_rederive: chunks of tiles rebuilt on their own stream; a scan waits for the chunks its slice touches
   struct DeriveChunk { long long t0, t1; hipEvent_t done; };
   hipStream_t derive_stream = nullptr;
@@ -95,23 +122,12 @@ struct uvaia_gpu_ctx {
   std::vector<DeriveChunk> derive_chunks;
   hipEvent_t derive_fence[4] = {};
   size_t derive_pending = 0;          // chunks of the last rederive a scan may still have to wait for
-  bool replay_recorded[NBUF] = {}, slice_scanned[NBUF] = {}, slice_cons_done[NBUF] = {};
   // pipelined search (column-compressed scan): the replay of a slice runs next to its scan and follows its progress counters
   // (off unless tuning.pipeline = 2: measured slower at config[1])
-  bool pipeline = false, pipeline_now = false, slice_piped[NBUF] = {}, pipe_used = false;
-  unsigned *d_progress[NBUF] = {}; size_t progress_cap[NBUF] = {};
-  hipEvent_t scan_started[NBUF] = {};
+  bool pipeline = false, pipeline_now = false, pipe_used = false;
   int *d_pipe_err = nullptr;
-  size_t slice_cap[NBUF] = {};              // pairs each counter buffer holds (grown when a slice needs more: slices may exceed a pool, see plan_subslices)
-  uint32_t *d_cntb[NBUF] = {};            // counter buffers 1..NBUF-1 (buffer 0 is d_cnt2), allocated on first use
-  int2 *d_tmin[NBUF] = {};                // per (query, tile of 64 references): {smallest mismatch count, largest ACGT-match count}, one per counter buffer
-  uint32_t *d_extb[NBUF] = {};            // packed-plane scan, default mode: per pair the other two counters (scan2_extras), one per counter buffer; sized like it
-  uint32_t *d_rtpb[NBUF] = {};            // ... and per reference the consensus pre-score packed into one dword (query sets with constant-and-complete columns)
-  uint4 *d_tb8[NBUF] = {};                // ... and per (query, tile of 64) the eight-entry bounds replay3_kernel walks (tile_bounds8)
+  SliceBuf slice[NBUF];                   // the counter buffers; the push path (run_batch) works in slice[0]
   bool use_ext = false;                   // the scan leaves the extras and replay3_kernel runs (default mode: packed-plane scan, or the column-compressed one up to 128 queries)
-  int4 *d_rtb[NBUF] = {};                 // per reference of a slice: untruncated consensus pre-score (query sets with constant-and-complete columns), one per counter buffer
-  int slice_tiles[NBUF] = {}, slice_rb[NBUF] = {}, slice_re[NBUF] = {};
-  long long slice_tf[NBUF] = {};
   size_t subslice = 25088;                // resident search: pools are cut into slices of about this size (exact: see search_resident).  (32 768 until round 4: at config[1]
                                           // four slices of 25 024 references instead of three of 33 334 cost 9 % more scan time -- a launch carries about 70 us of ramp and
                                           // tail -- and still end 4 % sooner: the first replay starts earlier, the last one is shorter)
@@ -149,14 +165,8 @@ struct uvaia_gpu_ctx {
   hipStream_t rep_stream = nullptr; hipEvent_t rep_ev[2] = {};   // ... the stream masked to them, and the events that splice its kernels into `stream`'s order
   int scan_R = 2;                // reference tiles per wave of scan3_kernel (the item stream is built for it)
   int scan_NW = 8;               // waves per block of scan3_kernel = shares a super-tile's records are cut into
-  uint4 *d_batch_ev = nullptr, *d_batch_poly = nullptr, *d_db_ev = nullptr, *d_db_poly = nullptr;
-  uint32_t *d_batch_grp = nullptr, *d_db_grp = nullptr;   // [tile][W4][64]  popc(E) | popc(V) << 16 of each word group (for queries that are all-N there)
-  int *d_batch_tote = nullptr, *d_db_tote = nullptr;
   int *d_amb_q = nullptr;        // [nq][AMB_STRIDE] ambiguity-word lists of the queries
   struct { const void *p; size_t n; } qtab[10] = {};   // the query-side tables as uvaia_gpu_export_query_table numbers them (device pointer, bytes)
-  int *d_batch_amb = nullptr, *d_db_amb = nullptr;   // same for the references of the batch buffer / database
-  int *d_batch_tot = nullptr, *d_db_tot = nullptr;   // per reference: valid sites (default) / ACGT sites (--acgt), counted by pack_refs_kernel
-  uint32_t *d_cnt2 = nullptr;    // [nq_pad][pool_pad] two-counter scan output, one dword per pair: first | second << 16 
   unsigned long long *d_stats = nullptr;             // admissions, on-demand evaluations, dense fallbacks, tiles opened (replay3_kernel)
   hipEvent_t order_ev[16] = {}; unsigned order_rr = 0;   // uvaia_gpu_wait_stream: ordering against a caller-owned stream
   hipEvent_t mark_ev[8][3] = {}; bool mark_set[8][3] = {}; // uvaia_gpu_mark
@@ -177,8 +187,7 @@ struct uvaia_gpu_ctx {
   // heaps / state
   int *d_heap = nullptr, *d_n = nullptr, *d_T = nullptr, *d_snap = nullptr, *d_err = nullptr;
   // batch buffers
-  uint4 *d_batch = nullptr;      // packed tiles of the current batch
-  int *d_batch_nonn = nullptr;
+  TileStore batch;               // the current batch (ensure_batch_buffers)
   int4 *d_cnt = nullptr;         // [nq_pad][pool_pad]
   int4 *d_rt = nullptr, *d_tr = nullptr;   // [pool_pad]
   uint8_t *d_entered = nullptr;  // [pool_pad] (push) or [db_cap] (resident)
@@ -188,13 +197,10 @@ struct uvaia_gpu_ctx {
   hipEvent_t stage_free[2] = {}; bool stage_busy[2] = {};
   size_t pitch = 0;
   // resident database
-  uint4 *d_db = nullptr;
-  int *d_db_nonn = nullptr;
+  TileStore db;
   size_t db_cap = 0, db_n = 0, db_local_tiles = 0;   // (db_n counts the stream; a context of a reference shard keeps db_local_tiles tiles of it)
   // last batch (introspection)
-  const uint4 *last_tiles = nullptr; const int *last_nonn = nullptr; int last_n = 0, last_rbegin = 0, last_ppad = 0, last_ntiles = 0;
-  long long last_tile_first = 0;
-  const int4 *last_rt = nullptr;
+  struct { const TileStore *store = nullptr; long long tile_first = 0; int n_tiles = 0, n = 0, rbegin = 0, ppad = 0; const int4 *rt = nullptr; } last;
   // stats
   std::vector<ScanEvt> evts;
   std::vector<hipEvent_t> ev_pool;      // timing events of earlier launches, reused (creating and destroying a pair per launch was 50-100 us of host time per step)
