@@ -179,6 +179,22 @@ int uvaia_gpu_ball (uvaia_gpu_ctx *ctx, const char *const *seq, int n_ref, int r
  * distance to the queries' consensus reaches the radius costs one pass over its packed planes, the queries are looked at only
  * for the references the reference's own loop would look at them for (twice the consensus distance >= radius). */
 int uvaia_gpu_ball_resident (uvaia_gpu_ctx *ctx, size_t first, size_t n, int radius, int *mindist);
+/* the same for a batch whose text is not in memory (replaces the loop of src/ball.c:248-259 for it): n_ref <= max_pool references
+ * handed in as ceil(n_ref/64) whole tiles of the packed interchange form below (what uvaia_gpu_db_export writes and a packed database
+ * file holds, uvaia_gpu_db_tile_bytes() per tile; lanes past n_ref in the last tile are ignored whatever they hold).  mindist[] as in
+ * uvaia_gpu_ball.  Works in default-mode and --acgt contexts (the latter re-code the planes while importing).  The radius search reads
+ * nothing of a reference but its planes, so no valid-site counts and no side rows are taken; nothing is derived for the
+ * nearest-neighbour scans and the resident database is not touched.  Refused like uvaia_gpu_ball: a batch above max_pool, a context
+ * with a restricted query range.  The four-plane tiles stay on the device until the next call replaces them (an --acgt context keeps
+ * a coding of its own, from which the text cannot be rebuilt): */
+int uvaia_gpu_ball_packed (uvaia_gpu_ctx *ctx, const void *planes, int n_ref, int radius, int *mindist);
+/* ... and this writes the upper-case text of references index[0..n) of that batch (positions within the batch; any order, repeats
+ * allowed) to host memory rows + k * pitch, pitch >= nchar: per site the IUPAC character of the set of bases the planes hold, 'N' for
+ * the empty and for the full set.  Invalid characters other than 'N' ('-', '?', 'X', 'O', '.') are not in the planes: the caller puts
+ * them back from its own record of them (uvdb_apply_exceptions for a packed database file).  Only nchar bytes of a row carry text, the
+ * others up to pitch are unspecified afterwards; rows whose pitch is nchar rounded up to 16 come back in one plain copy (pinned memory
+ * is the caller's choice).  An index outside the last batch, or a call with no batch, is an error return and leaves the context usable. */
+int uvaia_gpu_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
 unsigned long long uvaia_gpu_ball_asked (uvaia_gpu_ctx *ctx, int reset);    /* references sent on to the queries since the last reset */
 /* device time in ms since the last reset of the three kernels of the radius search: [0] the consensus pass, [1] the gather of the asked
    references' columns (with the read-back of their number), [2] the pair scan on the gathered tiles */

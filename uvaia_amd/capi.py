@@ -14,7 +14,7 @@ NSCORE = 6
 SYMBOLS = [
     "uvaia_gpu_open", "uvaia_gpu_open_tuned", "uvaia_gpu_close", "uvaia_gpu_last_error", "uvaia_gpu_push", "uvaia_gpu_drain",
     "uvaia_gpu_heap_slots", "uvaia_gpu_n_query", "uvaia_gpu_reset", "uvaia_gpu_db_reserve", "uvaia_gpu_db_append",
-    "uvaia_gpu_db_append_block", "uvaia_gpu_db_size", "uvaia_gpu_search_resident", "uvaia_gpu_sync", "uvaia_gpu_ball", "uvaia_gpu_ball_resident", "uvaia_gpu_ball_asked", "uvaia_gpu_ball_kernel_ms", "uvaia_gpu_export_query_table", "uvaia_gpu_agree_on_polymorphic", "uvaia_gpu_query_columns",
+    "uvaia_gpu_db_append_block", "uvaia_gpu_db_size", "uvaia_gpu_search_resident", "uvaia_gpu_sync", "uvaia_gpu_ball", "uvaia_gpu_ball_resident", "uvaia_gpu_ball_packed", "uvaia_gpu_unpack_rows", "uvaia_gpu_ball_asked", "uvaia_gpu_ball_kernel_ms", "uvaia_gpu_export_query_table", "uvaia_gpu_agree_on_polymorphic", "uvaia_gpu_query_columns",
     "uvaia_gpu_last_batch_scores", "uvaia_gpu_scan_stats", "uvaia_gpu_replay_stats", "uvaia_gpu_replay_tiles_opened", "uvaia_gpu_replay_timing",
     "uvaia_gpu_state_bytes", "uvaia_gpu_state_export", "uvaia_gpu_state_import", "uvaia_gpu_slice_scan", "uvaia_gpu_slice_replay",
     "uvaia_gpu_entered_flags", "uvaia_gpu_state_range_bytes", "uvaia_gpu_state_export_range", "uvaia_gpu_state_import_range",
@@ -111,6 +111,8 @@ def load_library():
         "uvaia_gpu_sync": (C.c_int, [vp]),
         "uvaia_gpu_ball": (C.c_int, [vp, pp, C.c_int, C.c_int, pi]),
         "uvaia_gpu_ball_resident": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_int, pi]),
+        "uvaia_gpu_ball_packed": (C.c_int, [vp, C.c_void_p, C.c_int, C.c_int, pi]),
+        "uvaia_gpu_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_ball_asked": (C.c_ulonglong, [vp, C.c_int]),
         "uvaia_gpu_ball_kernel_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_export_query_table": (C.c_int, [vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -485,6 +487,24 @@ class Engine:
         md = np.zeros(n, dtype=np.int32) if want else None
         self._chk(self.L.uvaia_gpu_ball_resident(self.ctx, int(first), int(n), int(radius), md.ctypes.data_as(C.POINTER(C.c_int)) if want else None))
         return md
+
+    def ball_packed(self, planes, n_ref, radius):
+        """Radius search over ceil(n_ref / 64) tiles of the packed interchange form (uint8 [n_tiles, tile_bytes], as db_export gives them)."""
+        planes = np.ascontiguousarray(planes, dtype=np.uint8)
+        tb = self.L.uvaia_gpu_db_tile_bytes(self.ctx)
+        if planes.size < (int(n_ref) + 63) // 64 * tb:
+            raise ValueError("%d references need %d bytes of tiles, got %d" % (n_ref, (int(n_ref) + 63) // 64 * tb, planes.size))
+        md = np.zeros(int(n_ref), dtype=np.int32)
+        self._chk(self.L.uvaia_gpu_ball_packed(self.ctx, planes.ctypes.data, int(n_ref), int(radius), md.ctypes.data_as(C.POINTER(C.c_int))))
+        return md
+
+    def unpack_rows(self, index):
+        """Upper-case text of references index[] of the last ball_packed batch, as a list of bytes (exception runs not applied)."""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        pitch = (self.nchar + 15) // 16 * 16
+        rows = np.zeros((max(len(idx), 1), pitch), dtype=np.uint8)
+        self._chk(self.L.uvaia_gpu_unpack_rows(self.ctx, idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
+        return [rows[k, :self.nchar].tobytes() for k in range(len(idx))]
 
     def ball_asked(self, reset=False):
         return int(self.L.uvaia_gpu_ball_asked(self.ctx, int(reset)))

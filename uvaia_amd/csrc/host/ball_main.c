@@ -7,22 +7,148 @@
 #include <libgen.h>
 #include <omp.h>
 
+#include <pthread.h>
+
 #include "cli_common.h"
 #include "gpu_glue.h"
 #include "prepare.h"
+#include "uvdb.h"
+
+#define PACKED_CHUNK 65536    /* references per round trip of the packed path without -p (1 024 tiles) */
+
+/* ---- the packed path: the per-batch loop of src/ball.c:248-259 for a database whose text is not in memory.  Chunks of whole tiles
+ * go from the mapping to the engine as they are; the text of the kept references comes back from the device.  Chunk c belongs to
+ * member c mod n (one context and one host thread per member); records are written in chunk order. */
+typedef struct {
+  uvdb_reader db;
+  const char *file;
+  uvaia_gpu_ctx **gpu;
+  int n_members, dist, non_n_ref, nchar;
+  uint64_t chunk, n_chunks;
+  file_compress_t out;
+  pthread_mutex_t lock;
+  pthread_cond_t turn;
+  uint64_t next_chunk;                  /* the chunk whose records are written next */
+  int n_output, n_invalid;
+  double t_search, t_unpack, t_write;   /* summed over the members */
+} packed_run;
+
+static void
+packed_member (packed_run *run, int m)
+{
+  const uint64_t n_ref = run->db->h.n_ref;
+  const size_t pitch = ((size_t) run->nchar + 16) / 16 * 16;       /* room for the NUL; the engine's own row pitch unless nchar is a multiple of 16 */
+  int *mindist = (int *) biomcmc_malloc ((size_t) run->chunk * sizeof (int)), *keep = (int *) biomcmc_malloc ((size_t) run->chunk * sizeof (int));
+  char *rows = NULL;
+  size_t rows_cap = 0;
+  for (uint64_t c = (uint64_t) m; c < run->n_chunks; c += (uint64_t) run->n_members) {
+    const uint64_t first = c * run->chunk, cnt = (n_ref - first < run->chunk) ? n_ref - first : run->chunk;
+    double t0 = omp_get_wtime ();
+    if (uvaia_gpu_ball_packed (run->gpu[m], uvdb_tile_planes (run->db, first / 64), (int) cnt, run->dist + 1, mindist)) biomcmc_error ("%s", uvaia_gpu_last_error (run->gpu[m]));
+    double t1 = omp_get_wtime ();
+    int n_keep = 0, invalid = 0;
+    for (uint64_t i = 0; i < cnt; i++) {
+      if (run->db->non_n[first + i] < run->non_n_ref) invalid++;
+      else if (mindist[i] <= run->dist) keep[n_keep++] = (int) i;
+    }
+    if ((size_t) n_keep > rows_cap) {
+      free (rows);
+      rows_cap = (size_t) n_keep;
+      rows = (char *) biomcmc_malloc (rows_cap * pitch);
+    }
+    if (uvaia_gpu_unpack_rows (run->gpu[m], keep, n_keep, rows, pitch)) biomcmc_error ("%s", uvaia_gpu_last_error (run->gpu[m]));
+    for (int k = 0; k < n_keep; k++) {
+      rows[(size_t) k * pitch + (size_t) run->nchar] = '\0';
+      uvdb_apply_exceptions (run->db, first + (uint64_t) keep[k], rows + (size_t) k * pitch);
+    }
+    double t2 = omp_get_wtime ();
+    pthread_mutex_lock (&run->lock);
+    while (run->next_chunk != c) pthread_cond_wait (&run->turn, &run->lock);
+    pthread_mutex_unlock (&run->lock);
+    double t3 = omp_get_wtime ();        /* it is this chunk's turn: nobody else writes */
+    for (int k = 0; k < n_keep; k++) write_fasta_record (run->out, uvdb_name (run->db, first + (uint64_t) keep[k]), rows + (size_t) k * pitch);
+    double t4 = omp_get_wtime ();
+    pthread_mutex_lock (&run->lock);
+    run->n_output += n_keep; run->n_invalid += invalid;
+    run->t_search += t1 - t0; run->t_unpack += t2 - t1; run->t_write += t4 - t3;
+    run->next_chunk = c + 1;
+    pthread_cond_broadcast (&run->turn);
+    pthread_mutex_unlock (&run->lock);
+  }
+  free (rows); free (mindist); free (keep);
+}
+
+typedef struct { packed_run *run; int member; pthread_t id; } packed_thread;
+
+static void *
+packed_thread_main (void *arg)
+{
+  packed_thread *t = (packed_thread *) arg;
+  packed_member (t->run, t->member);
+  return NULL;
+}
+
+static void
+search_packed (const char *packed, query_t query, int dist, double ambig_r, int pool, const int *devices, int n_devices, file_compress_t outstream, int64_t *time0)
+{
+  char msg[512];
+  packed_run run;
+  memset (&run, 0, sizeof run);
+  run.db = uvdb_open (packed, msg, sizeof msg);
+  if (!run.db) biomcmc_error ("%s", msg);
+  const struct uvdb_header *h = &run.db->h;
+  if ((int) h->nchar != query->aln->nchar) biomcmc_error ("packed database %s has %u sites but query sequences have %d sites; all sequences must be aligned", packed, h->nchar, query->aln->nchar);
+  if (!uvdb_radius_filter_is_exact ((int) h->nchar, ambig_r, h->ref_ambiguity))
+    biomcmc_error ("packed database %s was filtered with -A %g (at least %d valid sites), this search with -A %g keeps references from %d valid sites: some are not in the file; pack with a larger -A or use -r",
+                   packed, h->ref_ambiguity, (int) (h->nchar * (1. - h->ref_ambiguity)), ambig_r, (int) (h->nchar * ambig_r));
+  fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) h->n_ref, packed, biomcmc_update_elapsed_time (time0));
+  /* chunks of whole tiles: -p rounded down to a multiple of 64, never more than the database */
+  uint64_t chunk = pool > 0 ? (uint64_t) (pool / 64) * 64 : PACKED_CHUNK;
+  if (chunk > h->n_tiles * 64) chunk = h->n_tiles * 64;
+  if (chunk < 64) chunk = 64;
+  run.file = packed; run.chunk = chunk; run.n_chunks = (h->n_ref + chunk - 1) / chunk;
+  run.n_members = n_devices; run.dist = query->dist; run.nchar = query->aln->nchar; run.out = outstream;
+  run.non_n_ref = (int) (query->aln->nchar * ambig_r);                /* src/ball.c:201 */
+  run.gpu = (uvaia_gpu_ctx **) biomcmc_malloc ((size_t) n_devices * sizeof (uvaia_gpu_ctx *));
+  fprintf (stderr, "Searching in chunks of %d sequences on %d device context%s; radius distance is %d (refs more distant than this are excluded)\n", (int) chunk, n_devices, n_devices > 1 ? "s" : "", dist);
+  for (int m = 0; m < n_devices; m++) {
+    run.gpu[m] = NULL;
+    if (uvaia_gpu_open_query (&run.gpu[m], query, 2, devices[m], (size_t) chunk)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));
+    if (h->side_row_ints != (uint32_t) uvaia_gpu_db_side_row_ints () || h->tile_bytes != uvaia_gpu_db_tile_bytes (run.gpu[m])) biomcmc_error ("packed database %s does not match this engine's tile layout", packed);
+  }
+  pthread_mutex_init (&run.lock, NULL);
+  pthread_cond_init (&run.turn, NULL);
+  packed_thread *th = (packed_thread *) biomcmc_malloc ((size_t) n_devices * sizeof (packed_thread));
+  for (int m = 0; m < n_devices; m++) { th[m].run = &run; th[m].member = m; }
+  for (int m = 1; m < n_devices; m++) if (pthread_create (&th[m].id, NULL, packed_thread_main, &th[m])) biomcmc_error ("cannot start the host thread of device context %d", m);
+  packed_member (&run, 0);
+  for (int m = 1; m < n_devices; m++) pthread_join (th[m].id, NULL);
+  free (th);
+  pthread_cond_destroy (&run.turn);
+  pthread_mutex_destroy (&run.lock);
+  fprintf (stderr, "Finished searching packed database %s in %.3lf secs; Total of %d sequences read, %d sequences within radius (kept), %d too ambiguous (excluded)\n",
+           packed, biomcmc_update_elapsed_time (time0), (int) h->n_ref, run.n_output, run.n_invalid);
+  fprintf (stderr, "Time in seconds, summed over the device contexts: %.3lf search (with the copy of the tiles), %.3lf unpack, %.3lf write\n", run.t_search, run.t_unpack, run.t_write);
+  fprintf (stderr, "Saved %d sequences to file %s\n", run.n_output, outstream->filename);
+  for (int m = 0; m < n_devices; m++) uvaia_gpu_close (run.gpu[m]);
+  free (run.gpu);
+  uvdb_close_reader (run.db);
+}
 
 int
 main (int argc, char **argv)
 {
   int help = 0, version = 0, acgt = 0, keep_resolved = 0, dist = 1, trim = 0, pool = 0, device = -1, n_ref = 0, errors = 0, ch;
+  int devices[64], n_devices = 0;
   double ambig_q = 0.5, ambig_r = 0.5;
-  const char *out = NULL, *qfile = NULL;
+  const char *out = NULL, *qfile = NULL, *packed = NULL;
   const char **ref = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *));
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"acgt", no_argument, 0, 1000}, {"keep_resolved", no_argument, 0, 'k'},
     {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1001}, {"query_ambiguity", required_argument, 0, 'a'},
     {"ref_ambiguity", required_argument, 0, 'A'}, {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'},
-    {"nthreads", required_argument, 0, 't'}, {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {0, 0, 0, 0}};
+    {"nthreads", required_argument, 0, 't'}, {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002},
+    {"packed", required_argument, 0, 1003}, {"devices", required_argument, 0, 1004}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvkd:a:A:p:r:t:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -37,14 +163,21 @@ main (int argc, char **argv)
     case 't': break;                                  /* host threads do not matter here */
     case 'o': out = optarg; break;
     case 1002: device = atoi (optarg); break;
+    case 1003: packed = optarg; break;
+    case 1004: n_devices = uvaia_parse_device_list (optarg, devices, 64); if (!n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); errors++; } break;
     default: errors++;
   }
   if (optind < argc) qfile = argv[optind++];
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
-  if (help || errors || !qfile || !n_ref) {
+  if (n_devices && !packed && !help) { fprintf (stderr, "--devices goes with --packed; the text path takes --device\n"); errors++; }
+  if (help || errors || !qfile || (!n_ref && !packed) || (n_ref && packed)) {
     printf ("%s \nSearch reference alignment for sequences within a distance radius of the query sequences (experimental).\n\n", UVAIA_PACKAGE_STRING);
     printf (" %s [-hvk] [--acgt] [-d <int>] [--trim=<int>] [-A <double>] [-a <double>] [-p <int>] -r <ref.fa(.gz,.xz)>... <seqs.fa(.gz,.xz)> [-o <without suffix>]\n",
             basename (argv[0]));
+    printf (" %s [same options] --packed=<db.uvdb> [--devices=<list>] <seqs.fa(.gz,.xz)>\n\n", basename (argv[0]));
+    printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): searched tile by tile as it is, no text parsing;\n");
+    printf ("                                   -A must not be below one minus the -A it was packed with (both 0.5 by default); -p is rounded down to a multiple of 64\n");
+    printf ("  --devices=<list>                 with --packed: one GPU context per listed device (e.g. 0-3 or 0,0), chunks are dealt out among them\n");
     return help ? EXIT_SUCCESS : EXIT_FAILURE;
   }
   if (ambig_q < 0.001) ambig_q = 0.001;
@@ -54,17 +187,27 @@ main (int argc, char **argv)
   int n_clust = omp_get_max_threads ();
   if (pool >= n_clust) n_clust = pool;                /* src/ball.c:161-166 */
   fprintf (stderr, "Experimental program: %s package: %s\n", basename (argv[0]), UVAIA_PACKAGE_STRING);
-  fprintf (stderr, "Creating a queue of %d sequences; radius distance is %d (refs more distant than this are excluded)\n", n_clust, dist);
+  if (!packed) fprintf (stderr, "Creating a queue of %d sequences; radius distance is %d (refs more distant than this are excluded)\n", n_clust, dist);
 
   size_t outlength = 0;
   char *outfilename = outfile_from_prefix (out ? out : "ball_uvaia", &outlength);
   int64_t time0[2];
   biomcmc_get_time (time0);
   alignment aln = read_fasta_alignment_from_file (qfile, 0xf);
-  uvaia_set_prepare_device (device);
+  uvaia_set_prepare_device (n_devices ? devices[0] : device);
   query_t query = uvaia_prepare_query (aln, trim, dist, acgt, ambig_q, keep_resolved, 1);
   fprintf (stderr, "Query database now composed of %d valid references, after removing redundant (%s resolved) sequences.\n", query->aln->ntax, keep_resolved ? "less" : "more");
   if (query->aln->ntax < 1) biomcmc_error ("No valid reference sequences found. Please check file %s.", qfile);
+
+  if (packed) {
+    file_compress_t packed_out = biomcmc_open_compress (outfilename, "w");
+    if (!n_devices) { n_devices = 1; devices[0] = device; }
+    search_packed (packed, query, dist, ambig_r, pool, devices, n_devices, packed_out, time0);
+    biomcmc_close_compress (packed_out);
+    del_query_structure (query);
+    free (ref); free (outfilename);
+    return EXIT_SUCCESS;
+  }
 
   uvaia_gpu_ctx *gpu = NULL;
   if (uvaia_gpu_open_query (&gpu, query, 2, device, (size_t) n_clust)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));

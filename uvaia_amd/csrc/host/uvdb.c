@@ -279,11 +279,25 @@ uvdb_unpack_reference (uvdb_reader r, uint64_t i, char *out)
     out[s] = code[a | (c << 1) | (g << 2) | (t << 3)];
   }
   out[nchar] = '\0';
+  uvdb_apply_exceptions (r, i, out);
+}
+
+void
+uvdb_apply_exceptions (uvdb_reader r, uint64_t i, char *row)
+{
+  const uint32_t nchar = r->h.nchar;
+  if (i >= r->h.n_ref) return;
   for (uint64_t e = r->exc_idx[i]; e < r->exc_idx[i + 1]; e++) {
     const uint32_t pos = r->exc[e].pos, len = r->exc[e].len_char >> 8;
     const char ch = (char) (r->exc[e].len_char & 0xFFu);
-    for (uint32_t s = pos; s < pos + len && s < nchar; s++) out[s] = ch;
+    for (uint32_t s = pos; s < nchar && s - pos < len; s++) row[s] = ch;
   }
+}
+
+int
+uvdb_radius_filter_is_exact (int nchar, double ball_ambiguity, double pack_ambiguity)
+{
+  return (int) (nchar * ball_ambiguity) >= (int) (nchar * (1. - pack_ambiguity));
 }
 
 void

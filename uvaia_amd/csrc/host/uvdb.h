@@ -64,6 +64,15 @@ const void *uvdb_tile_planes (uvdb_reader r, uint64_t tile);        /* h.tile_by
 const int32_t *uvdb_tile_side_rows (uvdb_reader r, uint64_t tile);   /* 64 * h.side_row_ints ints per tile, contiguous */
 /* exact upper-case text of reference i (nchar + 1 bytes) */
 void uvdb_unpack_reference (uvdb_reader r, uint64_t i, char *out);
+/* the second half of it: the exception runs of reference i written over a row of nchar characters decoded from its planes elsewhere
+ * (uvaia_gpu_unpack_rows, include/uvaia_gpu.h) */
+void uvdb_apply_exceptions (uvdb_reader r, uint64_t i, char *row);
+/* Can a file packed with -A pack_ambiguity answer a radius search run with -A ball_ambiguity exactly?  `uvaiaball` keeps a reference
+ * with at least (int) (nchar * A) valid sites (src/ball.c:201), `uvaiapack` stored those with at least (int) (nchar * (1 - A_pack))
+ * (src/nearest.c:263-268): the stored valid-site counts let the radius search apply its own filter, which sees every reference it
+ * would have kept if and only if its threshold is not below the one of the file.  Both values as the command lines clamp them
+ * (0.001 .. 1).  1 = exact, 0 = references may be missing. */
+int uvdb_radius_filter_is_exact (int nchar, double ball_ambiguity, double pack_ambiguity);
 void uvdb_close_reader (uvdb_reader r);
 
 #ifdef __cplusplus

@@ -126,6 +126,74 @@ int uvaia_gpu_ball_resident(uvaia_gpu_ctx *c, size_t first, size_t n, int radius
   return 0;
 }
 
+// the same for a batch handed in as whole tiles of the interchange form: searched where the copy lands (default mode) or from the batch
+// store after import_tiles_kernel<3> (--acgt), then forgotten by the search; nothing is derived, the resident database is not touched.
+// ball_range reads only the planes of its store (no side rows, no valid-site counts), so a store that holds nothing else will do.
+int uvaia_gpu_ball_packed(uvaia_gpu_ctx *c, const void *planes, int n_ref, int radius, int *mindist)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (n_ref < 0 || (n_ref > 0 && (!planes || !mindist))) return fail(c, UVAIA_GPU_EINVAL, "bad batch");
+  if ((size_t)n_ref > c->max_pool) return fail(c, UVAIA_GPU_ESTATE, "batch of %d exceeds max_pool %zu", n_ref, c->max_pool);
+  if (c->act_q0 != 0 || c->act_q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "the radius search acts on the whole query set");
+  c->pk_n = 0;                                               // the tiles of the previous call are about to be replaced
+  if (n_ref == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t tb = uvaia_gpu_db_tile_bytes(c);
+  const int n_tiles = (n_ref + 63) / 64;
+  if (!c->d_pk) HIPCHK(c, hipMalloc(&c->d_pk, (c->pool_pad / 64) * tb));
+  HIPCHK(c, hipMemcpyAsync(c->d_pk, planes, (size_t)n_tiles * tb, hipMemcpyHostToDevice, c->stream));
+  int rc;
+  if (c->acgt) {
+    rc = ensure_batch_buffers(c); if (rc) return rc;
+    hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->d_pk, c->W4, c->batch.planes, 0LL, c->batch.tot);
+    HIPCHK(c, hipGetLastError());
+    rc = ball_range(c, c->batch, 0, n_tiles, 0, n_ref, radius, mindist);
+  } else {
+    TileStore view;                                          // the four planes as they came are the store's own form
+    view.planes = c->d_pk;
+    rc = ball_range(c, view, 0, n_tiles, 0, n_ref, radius, mindist);
+  }
+  if (rc) return rc;
+  c->pk_n = n_ref;
+  return 0;
+}
+
+// text of references index[0..n) of the last uvaia_gpu_ball_packed batch, rows + k * pitch; see unpack_rows_kernel
+int uvaia_gpu_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (n < 0 || (n > 0 && (!index || !rows))) return fail(c, UVAIA_GPU_EINVAL, "bad selection");
+  if (pitch < (size_t)c->nchar) return fail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
+  if (!c->pk_n) return fail(c, UVAIA_GPU_ESTATE, "no packed batch to unpack: uvaia_gpu_ball_packed comes first");
+  for (int k = 0; k < n; k++)
+    if (index[k] < 0 || index[k] >= c->pk_n) return fail(c, UVAIA_GPU_EINVAL, "index[%d] = %d lies outside the last packed batch of %d", k, index[k], c->pk_n);
+  if (n == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t dpitch = ((size_t)c->nchar + 15) / 16 * 16;
+  const size_t chunk = std::min((size_t)n, c->pool_pad);    // a selection may repeat references: longer ones go in rounds of a pool
+  if (c->rows_cap < chunk) {
+    hipFree(c->d_rows); c->d_rows = nullptr; c->rows_cap = 0;
+    HIPCHK(c, hipMalloc(&c->d_rows, chunk * dpitch));
+    c->rows_cap = chunk;
+  }
+  if (c->row_idx_cap < chunk) {
+    hipFree(c->d_row_idx); c->d_row_idx = nullptr; c->row_idx_cap = 0;
+    HIPCHK(c, hipMalloc(&c->d_row_idx, chunk * sizeof(int)));
+    c->row_idx_cap = chunk;
+  }
+  for (size_t a = 0; a < (size_t)n; a += chunk) {
+    const size_t m = std::min(chunk, (size_t)n - a);
+    HIPCHK(c, hipMemcpyAsync(c->d_row_idx, index + a, m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, c->d_pk, c->W4, c->nchar, c->d_row_idx, c->d_rows, dpitch);
+    HIPCHK(c, hipGetLastError());
+    // one copy for all rows of the round: straight when the caller's rows have the staging pitch, strided otherwise
+    if (pitch == dpitch) HIPCHK(c, hipMemcpyAsync(rows + a * pitch, c->d_rows, m * dpitch, hipMemcpyDeviceToHost, c->stream));
+    else HIPCHK(c, hipMemcpy2DAsync(rows + a * pitch, pitch, c->d_rows, dpitch, (size_t)c->nchar, m, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
 // references the last radius searches sent on to the queries (since the last call with reset != 0)
 void uvaia_gpu_ball_kernel_ms(uvaia_gpu_ctx *c, double out[3], int reset)
 {

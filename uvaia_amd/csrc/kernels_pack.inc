@@ -150,6 +150,46 @@ __global__ void sanitise_import_kernel(int *__restrict__ side_rows /* nullable *
   if (!ok) { row[0] = AMB_CAP + 1; for (int k = 0; k < AMB_CAP; k++) row[1 + k] = 0; }
 }
 
+// The opposite of pack_refs_kernel<4>: the upper-case text of selected references out of tiles of the interchange form (four IUPAC
+// planes).  One block per selected reference (index[] = positions in the batch, any order, repeats allowed: every row is independent),
+// one thread per 16 sites = one half of an alignment word: eight neighbouring threads read the same 16-byte piece of each plane (one
+// request), a wave reads eight pieces 4 KiB apart per plane and writes 1 KiB of contiguous text.  Per site the character is
+// code[A | C << 1 | G << 2 | T << 3]; the empty set reads 'N' here, the sparse exception runs ('-', '?', 'X', 'O', '.') are the host's.
+// Four sites at a time: the four bits of a plane are spread to the low bits of four bytes by one multiply, the sixteen-entry table
+// is two v_perm_b32 (entries 0-7, 8-15) and a byte-wise select on bit 3.  Sites at and beyond nchar are not written.
+static __device__ __forceinline__ uint32_t iupac_text4(uint32_t a, uint32_t c, uint32_t g, uint32_t t)
+{ // a, c, g, t: four plane bits each (bit i = site i); returns the four characters, site 0 in the low byte
+  constexpr uint32_t SPREAD = 0x00204081u, LOW = 0x01010101u;                    // bit i -> bit 8 i (the partial products do not overlap)
+  const uint32_t set = ((a * SPREAD) & LOW) | (((c * SPREAD) & LOW) << 1) | (((g * SPREAD) & LOW) << 2) | (((t * SPREAD) & LOW) << 3);
+  const uint32_t sel = set & 0x07070707u, high = ((set >> 3) & LOW) * 0xFFu;
+  const uint32_t lo = __builtin_amdgcn_perm(0x56535247u /* G R S V */, 0x4D43414Eu /* N A C M */, sel);
+  const uint32_t hi = __builtin_amdgcn_perm(0x4E42444Bu /* K D B N */, 0x48595754u /* T W Y H */, sel);
+  return (lo & ~high) | (hi & high);
+}
+
+__global__ __launch_bounds__(256) void unpack_rows_kernel(const uint4 *__restrict__ tiles, int W4, int nchar, const int *__restrict__ index,
+                                                           uint8_t *__restrict__ rows, size_t pitch /* a multiple of 16 */)
+{
+  const int r = index[blockIdx.x];
+  const uint32_t *t = reinterpret_cast<const uint32_t *>(tiles + (size_t)(r >> 6) * W4 * 4 * 64 + (r & 63));
+  uint8_t *row = rows + (size_t)blockIdx.x * pitch;
+  const int n16 = (nchar + 15) >> 4;
+  for (int k = threadIdx.x; k < n16; k += 256) {
+    const int word = k >> 1, sh = (k & 1) * 16;
+    const uint32_t *p = t + (size_t)(word >> 2) * (4 * 64 * 4) + (word & 3);      // plane A of the word; the planes of a word group are 64 uint4 apart
+    const uint32_t a = p[0] >> sh, c = p[256] >> sh, g = p[512] >> sh, tt = p[768] >> sh;
+    uint32_t out[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) out[q] = iupac_text4((a >> (4 * q)) & 15u, (c >> (4 * q)) & 15u, (g >> (4 * q)) & 15u, (tt >> (4 * q)) & 15u);
+    const int site0 = k * 16;
+    if (site0 + 16 <= nchar) *reinterpret_cast<uint4 *>(row + site0) = make_uint4(out[0], out[1], out[2], out[3]);
+    else {
+#pragma unroll
+      for (int s = 0; s < 16; s++) if (site0 + s < nchar) row[site0 + s] = (uint8_t)(out[s >> 2] >> ((s & 3) * 8));
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // device: the column walk of create_query_indices (src/fastaseq.c:732-777) over the query rows
 // ------------------------------------------------------------------------------------------------------------

@@ -184,6 +184,10 @@ struct uvaia_gpu_ctx {
   std::vector<int> idx_cols; uint32_t *d_ball_masks = nullptr; int NH4 = 0;   // their order in the gathered words: masks [W4][hot 4 | others 4], hot word groups (ensure_qgather)
   uint32_t *d_qg = nullptr;                                 // the queries on those columns (kernels_ball.inc), built by the first radius search
   unsigned long long *d_ball_key = nullptr;                 // per listed reference: first query that ends the reference's loop (query << 32 | distance)
+  // radius search over packed tiles (uvaia_gpu_ball_packed): the four IUPAC planes of the last batch stay here for uvaia_gpu_unpack_rows
+  uint4 *d_pk = nullptr; int pk_n = 0;                      // [pool_pad / 64] tiles; references of the last batch (0: none)
+  uint8_t *d_rows = nullptr; size_t rows_cap = 0;           // text of the selected references, rows of a multiple of 16 bytes
+  int *d_row_idx = nullptr; size_t row_idx_cap = 0;
   // heaps / state
   int *d_heap = nullptr, *d_n = nullptr, *d_T = nullptr, *d_snap = nullptr, *d_err = nullptr;
   // batch buffers
