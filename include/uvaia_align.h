@@ -74,6 +74,12 @@ int  uvaia_align_load_block (uvaia_aligner *a, const char *bytes, const int64_t 
 int  uvaia_align_run (uvaia_aligner *a);
 int  uvaia_align_sync (uvaia_aligner *a);
 int  uvaia_align_fetch (uvaia_aligner *a, char *aln, int *score);
+/* Instead of the fetch (the copy of uvaia_amd/csrc/uvaia_align.hip:819 and everything a caller then does to the text to bring it back to a
+ * GPU): where the rows of the last completed run lie in device memory -- *n rows of ref_len characters, *pitch = ref_len + 1 bytes apart,
+ * on HIP device *device (any of the four may be NULL).  They stay valid from the end of the run (uvaia_align_run returns when its kernels
+ * are done; uvaia_align_sync otherwise) until the next load or close, and go to the engine as they are (include/uvaia_gpu.h, "rows that
+ * are already in device memory").  UVAIA_ALIGN_ESTATE before a run has completed. */
+int  uvaia_align_device_rows (uvaia_aligner *a, const void **d_rows, size_t *pitch, int *n, int *device);
 
 /* work of the last run: M-wavefront cells computed, wavefront bytes written + read by the recurrences (13 + 20 per cell),
  * kernel passes (queries that find the workspace's pool empty are run again in a less crowded pass), kernel time in ms */

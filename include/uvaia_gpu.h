@@ -348,6 +348,35 @@ int    uvaia_gpu_db_side_row_ints (void);
 int    uvaia_gpu_db_export (uvaia_gpu_ctx *ctx, size_t first_tile, size_t n_tiles, void *planes, int *non_n, int *side_rows);
 int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const int *non_n, const int *side_rows, int n_ref);
 
+/* ---- rows that are already in device memory (what the aligner leaves behind, include/uvaia_align.h; a tensor of the caller): into the
+ * resident database and a packed database file without a round trip of their text.  A block is n rows of nchar bytes, `pitch` bytes apart
+ * (pitch >= nchar; neither the pitch nor the first row need any alignment).  Every d_rows below must be memory of the context's device: the
+ * runtime is asked, and a pointer of another device, a host pointer or rows that end beyond their allocation are refused with
+ * UVAIA_GPU_EINVAL before anything reads them.  Plain contexts only (no reference shards).
+ *
+ * rows_census: replaces, for such a block, quick_count_sequence_non_N (uvaia_amd/csrc/host/seq_query.c:105-115, the call of pack_main.c:86)
+ *   and the counting half of the exception pass of uvdb_add_reference (host/uvdb.c:79-94).  non_n[i] = valid sites of row i, n_exc[i] = the
+ *   exception records its text gives (maximal stretches of one of - ? X O . , cut every 0xFFFFFF sites).  One kernel, one copy back.  A
+ *   byte uvaia_gpu_db_append refuses fails the call with UVAIA_GPU_EALPHABET (the counts are filled in all the same).
+ * db_append_device: replaces the staging of uvaia_gpu_db_append (the copy of every row into pinned memory and over the bus): appends rows
+ *   row_index[0 .. n_sel) of the block (NULL: rows 0 .. n_sel - 1), in that order; non_n[k] belongs to the k-th appended row (NULL = count on
+ *   the device).  Planes, valid-site counts, side rows and totals are what uvaia_gpu_db_append leaves for the same rows, in default-mode
+ *   and --acgt contexts, from any database size on.  Returns when the rows have been read.
+ * rows_exceptions: replaces the record-writing half of the exception pass (host/uvdb.c:79-94).  offsets: n_sel + 1 increasing record
+ *   positions, offsets[k + 1] - offsets[k] = n_exc of the k-th selected row; exc_out: host array of (uint32 pos, uint32 len << 8 | char)
+ *   records, row k's at exc_out + offsets[k], by position.  One kernel, one copy back; offsets that do not fit the rows fail with
+ *   UVAIA_GPU_EINVAL and write nothing outside their ranges.
+ * db_drop_tiles: removes the first n_tiles tiles of the resident database; what follows them moves to the front (a caller that exports whole
+ *   tiles as they fill keeps the unfinished one resident and goes on appending to it). */
+int uvaia_gpu_rows_census (uvaia_gpu_ctx *ctx, const void *d_rows, size_t pitch, int n, int *non_n, int *n_exc);
+int uvaia_gpu_db_append_device (uvaia_gpu_ctx *ctx, const void *d_rows, size_t pitch, const int *row_index, int n_sel, const int *non_n);
+int uvaia_gpu_rows_exceptions (uvaia_gpu_ctx *ctx, const void *d_rows, size_t pitch, const int *row_index, int n_sel, const uint64_t *offsets, void *exc_out);
+int uvaia_gpu_db_drop_tiles (uvaia_gpu_ctx *ctx, size_t n_tiles);
+/* device time in ms since the last reset of [0] the census, [1] the gathers of db_append_device, [2] the exception fill */
+void uvaia_gpu_rows_kernel_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
+/* diagnostics: the length exception runs are cut at (0 = the file format's 0xFFFFFF), so that tests reach the cut with short rows */
+int uvaia_gpu_rows_set_run_cut (uvaia_gpu_ctx *ctx, unsigned cut);
+
 /* bytes the pair scan reads per reference (the default scan reads planes derived from the packed record for this query set) */
 size_t uvaia_gpu_scan_bytes_per_ref (const uvaia_gpu_ctx *ctx);
 /* the pair scan of this context: 2 = column-compressed scan over planes derived for the query set (default above 32 queries),

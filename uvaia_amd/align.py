@@ -9,6 +9,7 @@ from . import capi
 SYMBOLS = [
     "uvaia_align_default_options", "uvaia_align_open", "uvaia_align_close", "uvaia_align_last_error", "uvaia_align_batch",
     "uvaia_align_load", "uvaia_align_load_block", "uvaia_align_run", "uvaia_align_sync", "uvaia_align_fetch", "uvaia_align_stats",
+    "uvaia_align_device_rows",
 ]
 
 
@@ -45,6 +46,7 @@ def _lib():
         L.uvaia_align_sync.argtypes = [vp]
         L.uvaia_align_fetch.argtypes = [vp, C.c_void_p, pi]
         L.uvaia_align_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_double), pi, C.POINTER(C.c_double)]
+        L.uvaia_align_device_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), pi, pi]
         _ready = True
     return L
 
@@ -102,6 +104,13 @@ class Aligner:
         score = np.zeros(self.n, dtype=np.int32)
         self._chk(self.L.uvaia_align_fetch(self.ptr, rows.ctypes.data, score.ctypes.data_as(C.POINTER(C.c_int))))
         return score, rows[:, :self.ref_len]
+
+    def device_rows(self):
+        """(device pointer, pitch, n, device) of the rows of the last completed run: they stay where the kernel left them, valid until the
+        next load or close, and go to capi.Engine.rows_census / db_append_device / rows_exceptions as they are"""
+        ptr, pitch, n, dev = C.c_void_p(), C.c_size_t(0), C.c_int(0), C.c_int(0)
+        self._chk(self.L.uvaia_align_device_rows(self.ptr, C.byref(ptr), C.byref(pitch), C.byref(n), C.byref(dev)))
+        return ptr.value or 0, pitch.value, n.value, dev.value
 
     def align(self, seqs):
         """(scores [n], aligned rows [n, ref_len]) through uvaia_align_batch, the reference-shaped call"""

@@ -28,6 +28,7 @@ SYMBOLS = [
     "uvaia_gpu_group_open", "uvaia_gpu_group_close", "uvaia_gpu_group_last_error", "uvaia_gpu_group_size", "uvaia_gpu_group_member", "uvaia_gpu_group_query_shard",
     "uvaia_gpu_group_db_reserve", "uvaia_gpu_group_db_append", "uvaia_gpu_group_db_append_packed", "uvaia_gpu_group_db_clear", "uvaia_gpu_group_db_rederive",
     "uvaia_gpu_group_db_size", "uvaia_gpu_group_reset", "uvaia_gpu_group_search_resident", "uvaia_gpu_group_push", "uvaia_gpu_group_drain", "uvaia_gpu_group_sync",
+    "uvaia_gpu_rows_census", "uvaia_gpu_db_append_device", "uvaia_gpu_rows_exceptions", "uvaia_gpu_db_drop_tiles", "uvaia_gpu_rows_kernel_ms", "uvaia_gpu_rows_set_run_cut",
 ]
 
 
@@ -179,6 +180,12 @@ def load_library():
         "uvaia_gpu_group_push": (C.c_int, [vp, pp, pi, C.c_int, C.c_int64, C.POINTER(C.c_uint8)]),
         "uvaia_gpu_group_drain": (C.c_int, [vp, pi, pi, pi, C.POINTER(C.c_int64)]),
         "uvaia_gpu_group_sync": (C.c_int, [vp]),
+        "uvaia_gpu_rows_census": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_int, pi, pi]),
+        "uvaia_gpu_db_append_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, pi, C.c_int, pi]),
+        "uvaia_gpu_rows_exceptions": (C.c_int, [vp, C.c_void_p, C.c_size_t, pi, C.c_int, C.POINTER(C.c_uint64), C.c_void_p]),
+        "uvaia_gpu_db_drop_tiles": (C.c_int, [vp, C.c_size_t]),
+        "uvaia_gpu_rows_kernel_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_rows_set_run_cut": (C.c_int, [vp, C.c_uint]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -298,6 +305,57 @@ class Engine:
 
     def db_size(self):
         return self.L.uvaia_gpu_db_size(self.ctx)
+
+    @staticmethod
+    def _device_block(rows, pitch=None, n=None):
+        """(pointer, pitch, rows, keep-alive) of a block of rows in device memory: a CUDA/HIP torch.uint8 tensor [n, pitch] whose rows are
+        contiguous (any row stride: a view of a wider tensor works), or a raw device pointer with its pitch (and n where it is needed)"""
+        if hasattr(rows, "data_ptr"):
+            import torch
+            if rows.dtype != torch.uint8 or rows.dim() != 2 or not rows.is_cuda or (rows.shape[0] > 0 and rows.shape[1] > 1 and rows.stride(1) != 1):
+                raise GpuError(-1, "rows must be a 2-d torch.uint8 tensor in device memory with contiguous rows")
+            torch.cuda.current_stream(rows.device).synchronize()          # the engine reads them on a stream of its own
+            return rows.data_ptr(), (rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), rows.shape[0], rows
+        if pitch is None:
+            raise GpuError(-1, "a raw device pointer needs its pitch")
+        return int(rows), int(pitch), n, None
+
+    def rows_census(self, rows, pitch=None, n=None):
+        """(non_n [n], n_exc [n]) of a block of rows in device memory: valid sites and exception records of every row"""
+        ptr, pitch, n, _keep = self._device_block(rows, pitch, n)
+        non_n, n_exc = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        self._chk(self.L.uvaia_gpu_rows_census(self.ctx, ptr, pitch, n, non_n.ctypes.data_as(C.POINTER(C.c_int)), n_exc.ctypes.data_as(C.POINTER(C.c_int))))
+        return non_n, n_exc
+
+    def db_append_device(self, rows, row_index=None, non_n=None, pitch=None, n=None):
+        """appends rows row_index (None: all n) of a block in device memory to the resident database, without a copy of their text"""
+        ptr, pitch, n, _keep = self._device_block(rows, pitch, n)
+        _k1, ri = _int_ptr(row_index)
+        _k2, nn = _int_ptr(non_n)
+        self._chk(self.L.uvaia_gpu_db_append_device(self.ctx, ptr, pitch, ri, n if row_index is None else len(row_index), nn))
+
+    def rows_exceptions(self, rows, n_exc, row_index=None, pitch=None, n=None):
+        """(offsets uint64 [n_sel + 1], records uint32 [total, 2] = (pos, len << 8 | char)) of the selected rows; n_exc: their record counts
+        as rows_census gave them (one per selected row)"""
+        ptr, pitch, n, _keep = self._device_block(rows, pitch, n)
+        n_sel = n if row_index is None else len(row_index)
+        off = np.zeros(n_sel + 1, dtype=np.uint64)
+        off[1:] = np.cumsum(np.asarray(n_exc, dtype=np.uint64))
+        out = np.zeros((int(off[-1]), 2), dtype=np.uint32)
+        _k1, ri = _int_ptr(row_index)
+        self._chk(self.L.uvaia_gpu_rows_exceptions(self.ctx, ptr, pitch, ri, n_sel, off.ctypes.data_as(C.POINTER(C.c_uint64)), out.ctypes.data))
+        return off, out
+
+    def db_drop_tiles(self, n_tiles):
+        self._chk(self.L.uvaia_gpu_db_drop_tiles(self.ctx, int(n_tiles)))
+
+    def rows_kernel_ms(self, reset=False):
+        out = (C.c_double * 3)()
+        self.L.uvaia_gpu_rows_kernel_ms(self.ctx, out, int(reset))
+        return {"census": out[0], "gather": out[1], "exceptions": out[2]}
+
+    def rows_set_run_cut(self, cut):
+        self._chk(self.L.uvaia_gpu_rows_set_run_cut(self.ctx, int(cut)))
 
     def set_active_queries(self, q0, q1):
         self._chk(self.L.uvaia_gpu_set_active_queries(self.ctx, int(q0), int(q1)))

@@ -2,6 +2,10 @@
  * align_main.c -- `uvaialign`: aligns query sequences against one reference sequence and writes them on the reference's
  * columns.  Same options, filters, messages and output as the reference's src/align.c; the per-pool loop over align_query
  * (src/align.c:224-233,357-390) runs on the GPU through include/uvaia_align.h.
+ *
+ * --packed (no counterpart in the reference): the aligned rows go from the aligner's device memory straight into a packed database
+ * (uvdb.h), the file `uvaiapack` would write from the text output: census, -A filter, packing and exception runs happen on the rows where
+ * they lie (include/uvaia_gpu.h, "rows that are already in device memory").  Own code.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -12,20 +16,128 @@
 #include "cli_common.h"
 #include "fastaseq.h"
 #include "gpu_glue.h"
+#include "uvdb.h"
 #include "../../../include/uvaia_align.h"
+#include "../../../include/uvaia_gpu.h"
+
+#define PACK_BATCH 4096      /* kept rows per engine round trip (a multiple of 64), as in pack_main.c */
+
+/* The head of a packed database in the making.  A tile holds 64 consecutive kept rows of the whole stream, pools end anywhere: the resident
+ * database of the engine is the carry.  Rows are appended to it as they come, whole tiles are exported and dropped, the unfinished tile
+ * stays resident for the next pool (or the flush at the end), so that the file does not depend on the pool size. */
+struct packer {
+  uvaia_gpu_ctx *gpu;
+  uvdb_writer w;
+  int nchar, non_n_ref;
+  void *planes; int *tile_nonn, *side;                 /* export buffers: PACK_BATCH / 64 + 1 tiles */
+  int *non_n, *n_exc, *keep, *keep_nn; size_t pool_cap;
+  uint64_t *off; uvdb_exc *exc; size_t exc_cap;
+  long kept, dropped;
+  double align_ms, rows_ms[3];                         /* device time: the aligner's kernels; census, gathers, exception fill */
+  char err[640];
+};
+
+static int
+packer_open (struct packer *p, const char *path, int nchar, double ambig_r, int device, int pool)
+{
+  memset (p, 0, sizeof *p);
+  p->nchar = nchar;
+  p->non_n_ref = (int) (nchar * (1. - ambig_r));       /* src/nearest.c:263-268, as pack_main.c */
+  char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);   /* the engine needs some query to exist: a plain ACGT string */
+  for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
+  dummy[nchar] = '\0';
+  const char *one[1] = {dummy};
+  uvaia_gpu_query q;
+  memset (&q, 0, sizeof q);
+  q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
+  const int rc = uvaia_gpu_open (&p->gpu, &q, 1, device, PACK_BATCH);
+  free (dummy);
+  if (rc) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (NULL)); return -1; }
+  if (uvaia_gpu_db_reserve (p->gpu, PACK_BATCH + 64)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
+  const size_t tb = uvaia_gpu_db_tile_bytes (p->gpu), nt = PACK_BATCH / 64 + 1;
+  p->planes = biomcmc_malloc (nt * tb);
+  p->tile_nonn = (int *) biomcmc_malloc (nt * 64 * sizeof (int));
+  p->side = (int *) biomcmc_malloc (nt * 64 * (size_t) uvaia_gpu_db_side_row_ints () * sizeof (int));
+  p->pool_cap = (size_t) pool;
+  p->non_n = (int *) biomcmc_malloc (p->pool_cap * sizeof (int)); p->n_exc = (int *) biomcmc_malloc (p->pool_cap * sizeof (int));
+  p->keep = (int *) biomcmc_malloc (p->pool_cap * sizeof (int)); p->keep_nn = (int *) biomcmc_malloc (p->pool_cap * sizeof (int));
+  p->off = (uint64_t *) biomcmc_malloc ((PACK_BATCH + 1) * sizeof (uint64_t));
+  p->w = uvdb_create (path, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r);
+  if (!p->w) { snprintf (p->err, sizeof p->err, "cannot create %s", path); return -1; }
+  return 0;
+}
+
+/* whole tiles (all = 0) or everything that is resident (all = 1: the flush) from the engine to the file */
+static int
+packer_write_tiles (struct packer *p, int all)
+{
+  const size_t have = uvaia_gpu_db_size (p->gpu), nt = all ? (have + 63) / 64 : have / 64;
+  if (!nt) return 0;
+  if (uvaia_gpu_db_export (p->gpu, 0, nt, p->planes, p->tile_nonn, p->side) || uvaia_gpu_db_drop_tiles (p->gpu, nt)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
+  if (uvdb_add_tiles (p->w, nt, p->planes, p->tile_nonn, p->side)) { snprintf (p->err, sizeof p->err, "cannot write the packed database"); return -1; }
+  return 0;
+}
+
+/* one pool: the rows of the aligner's last run, where they lie */
+static int
+packer_add_pool (struct packer *p, uvaia_aligner *al, char **name, int fill)
+{
+  const void *d_rows = NULL; size_t pitch = 0; int n = 0;
+  if (uvaia_align_device_rows (al, &d_rows, &pitch, &n, NULL)) { snprintf (p->err, sizeof p->err, "%s", uvaia_align_last_error (al)); return -1; }
+  if (n != fill || (size_t) n > p->pool_cap) { snprintf (p->err, sizeof p->err, "the aligner holds %d rows, the pool %d", n, fill); return -1; }
+  if (uvaia_gpu_rows_census (p->gpu, d_rows, pitch, n, p->non_n, p->n_exc)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
+  int nk = 0;
+  for (int i = 0; i < n; i++) {                        /* the -A filter (pack_main.c:86-87) on a few KB of counts */
+    if (p->non_n[i] < p->non_n_ref) { p->dropped++; continue; }
+    p->keep[nk] = i; p->keep_nn[nk++] = p->non_n[i];
+  }
+  for (int a = 0; a < nk; a += PACK_BATCH) {
+    const int m = nk - a < PACK_BATCH ? nk - a : PACK_BATCH;
+    p->off[0] = 0;
+    for (int k = 0; k < m; k++) p->off[k + 1] = p->off[k] + (uint64_t) p->n_exc[p->keep[a + k]];
+    if (p->off[m] + 1 > p->exc_cap) {
+      p->exc_cap = (size_t) (p->off[m] + 1) * 2;
+      p->exc = (uvdb_exc *) biomcmc_realloc (p->exc, p->exc_cap * sizeof (uvdb_exc));
+    }
+    if (uvaia_gpu_rows_exceptions (p->gpu, d_rows, pitch, p->keep + a, m, p->off, p->exc) ||
+        uvaia_gpu_db_append_device (p->gpu, d_rows, pitch, p->keep + a, m, p->keep_nn + a)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
+    for (int k = 0; k < m; k++)                          /* (names only of rows the engine holds: the flush of packer_close stays consistent) */
+      if (uvdb_add_reference_runs (p->w, name[p->keep[a + k]], p->exc + p->off[k], (size_t) (p->off[k + 1] - p->off[k]))) { snprintf (p->err, sizeof p->err, "out of memory while indexing %s", name[p->keep[a + k]]); return -1; }
+    p->kept += m;
+    if (packer_write_tiles (p, 0)) return -1;
+  }
+  return 0;
+}
+
+/* the unfinished tile, the index sections, the engine; 0 when the file is complete */
+static int
+packer_close (struct packer *p)
+{
+  int bad = 0;
+  if (p->w) {
+    bad = p->gpu ? packer_write_tiles (p, 1) : 0;
+    if (uvdb_close (p->w) && !bad) { snprintf (p->err, sizeof p->err, "problem writing the packed database"); bad = -1; }
+    p->w = NULL;
+  }
+  if (p->gpu) { uvaia_gpu_rows_kernel_ms (p->gpu, p->rows_ms, 0); uvaia_gpu_close (p->gpu); }
+  p->gpu = NULL;
+  free (p->planes); free (p->tile_nonn); free (p->side); free (p->non_n); free (p->n_exc); free (p->keep); free (p->keep_nn); free (p->off); free (p->exc);
+  return bad;
+}
 
 int
 main (int argc, char **argv)
 {
   int help = 0, version = 0, to_screen = 0, pool = 256 * omp_get_max_threads (), device = 0, errors = 0, n_fasta = 0, ch;   /* src/align.c:59-63 */
   int devices[64], n_devices = 0;
-  double ambig = 0.5;
-  const char *out = NULL, *ref_file = NULL;
+  double ambig = 0.5, ambig_r = 0.5;
+  const char *out = NULL, *ref_file = NULL, *packed = NULL;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"stdout", no_argument, 0, 1000}, {"ambiguity", required_argument, 0, 'a'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002}, {0, 0, 0, 0}};
-  while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:", longopts, NULL)) != -1) switch (ch) {
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002},
+    {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {0, 0, 0, 0}};
+  while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
     case 1000: to_screen = 1; break;
@@ -36,6 +148,8 @@ main (int argc, char **argv)
     case 'o': out = optarg; break;
     case 1001: device = atoi (optarg); break;
     case 1002: n_devices = uvaia_parse_device_list (optarg, devices, 64); if (!n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); exit (EXIT_FAILURE); } break;
+    case 1003: packed = optarg; break;
+    case 'A': ambig_r = atof (optarg); break;
     default: errors++;
   }
   const char **fasta = (const char **) argv + optind;
@@ -43,7 +157,7 @@ main (int argc, char **argv)
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
   if (help || errors || !ref_file || n_fasta < 1 || pool < 1) {
     printf ("%s \nAlign query sequences against a reference\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb>] [-A <double>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  --stdout                         print alignment to stdout (to redirect/pipe) instead of compress to file; much faster but may generate a big output\n");
     printf ("  -p, --pool=<int>                 How many query sequences are read in batch, to be aligned in parallel (defaults to 256 per thread)\n");
@@ -54,6 +168,9 @@ main (int argc, char **argv)
     printf ("  <seqs.fa|seqs.fa.xz>             sequences to align in fasta format, possibly compressed with gz, xz, bz2 (can be multiple files)\n");
     printf ("  --device=<int>                   GPU to use (default 0)\n");
     printf ("  --devices=<list>                 several GPUs, e.g. 0-7 or 0,2,3: every pool of queries is cut among them (same rows as one GPU)\n");
+    printf ("  --packed=<out.uvdb>              write the aligned sequences straight into a packed database, the file `uvaiapack` makes of the text output;\n");
+    printf ("                                   the text itself is then written only if -o or --stdout is given as well (one GPU only)\n");
+    printf ("  -A, --ref_ambiguity=<double>     with --packed: maximum allowed ambiguity for an ALIGNED sequence to be kept in the database (default=0.5), as in `uvaiapack`\n");
     if (help) {
       printf ("Based on the wavefront algorithm (WFA, https://github.com/smarco/WFA), computed on the GPU.\n");
       printf ("Since the sequences are assumed to be similar, sequences too short or too big w.r.t. the reference are rejected.\n\n");
@@ -65,6 +182,13 @@ main (int argc, char **argv)
   }
   if (ambig < 0.001) ambig = 0.001;                   /* src/align.c:132-133 */
   if (ambig > 1.) ambig = 1.;
+  if (ambig_r < 0.001) ambig_r = 0.001;               /* pack_main.c:46-47 */
+  if (ambig_r > 1.) ambig_r = 1.;
+  if (packed && n_devices > 1) {   /* the rows of a pool would lie on several cards and a tile takes 64 consecutive ones: not built */
+    fprintf (stderr, "--packed writes the database from the rows on ONE GPU: give --device, or a --devices list of one device (%d were listed)\n", n_devices);
+    return EXIT_FAILURE;
+  }
+  const bool write_text = !packed || out || to_screen;
   int64_t time0[2], time1[2];
   biomcmc_get_time (time0);
   fprintf (stderr, "program: %s package: %s\n", basename (argv[0]), UVAIA_PACKAGE_STRING);
@@ -72,7 +196,7 @@ main (int argc, char **argv)
   size_t outlength = 0;
   char *outfilename = NULL;
   if (to_screen) fprintf (stderr, "Sequences will be shown uncompressed in screen (to redirect to file or pipe into another software).\n");
-  else {
+  else if (write_text) {
     char randname[32];
     if (!out) { sprintf (randname, "uvaia.%" PRIx64, (uint64_t) time0[1] & 0xffffff); out = randname; }     /* src/align.c:155-159 */
     outfilename = outfile_from_prefix (out, &outlength);
@@ -94,11 +218,16 @@ main (int argc, char **argv)
   if (n_devices > 1) fprintf (stderr, "Batches of %d sequences will be read and aligned on %d GPUs.\n", pool, n_devices);
   else fprintf (stderr, "Batches of %d sequences will be read and aligned on GPU %d.\n", pool, devices[0]);
 
-  file_compress_t outstream = to_screen ? NULL : biomcmc_open_compress (outfilename, "w");
+  struct packer pk;
+  if (packed) {
+    if (packer_open (&pk, packed, (int) aln_length, ambig_r, devices[0], pool)) biomcmc_error ("%s", pk.err);
+    fprintf (stderr, "Aligned sequences with at least %d valid sites will be packed into %s.\n", pk.non_n_ref, packed);
+  }
+  file_compress_t outstream = (to_screen || !write_text) ? NULL : biomcmc_open_compress (outfilename, "w");
   char **seq = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *)), **name = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *));
   int *len = (int *) biomcmc_malloc ((size_t) pool * sizeof (int));
-  char *aln = (char *) biomcmc_malloc ((size_t) pool * (aln_length + 1));
-  int count = 0, n_output = 0;
+  char *aln = write_text ? (char *) biomcmc_malloc ((size_t) pool * (aln_length + 1)) : NULL;
+  int count = 0, n_output = 0, n_pool = 0;
   const int print_interval = 5000;
   double result[3];
 
@@ -135,25 +264,43 @@ main (int argc, char **argv)
       }
       if (fill) {
         int failed = -1;
+        n_pool++;
+        if (packed) {   /* one GPU: the steps of uvaia_align_batch, the copy of the text only if somebody reads it */
+          double ms = 0.;
+          if (uvaia_align_load (gpu[0], (const char *const *) seq, len, fill) || uvaia_align_run (gpu[0]) || (write_text && uvaia_align_fetch (gpu[0], aln, NULL))) failed = 0;
+          else if (!uvaia_align_stats (gpu[0], NULL, NULL, NULL, &ms)) pk.align_ms += ms;
+        } else {
 #pragma omp parallel for num_threads(n_devices) schedule(static, 1)
-        for (int d = 0; d < n_devices; d++) {
-          const int a = (int) ((long long) fill * d / n_devices), b = (int) ((long long) fill * (d + 1) / n_devices);
-          if (b > a && uvaia_align_batch (gpu[d], (const char *const *) seq + a, len + a, b - a, aln + (size_t) a * (aln_length + 1), NULL)) {
+          for (int d = 0; d < n_devices; d++) {
+            const int a = (int) ((long long) fill * d / n_devices), b = (int) ((long long) fill * (d + 1) / n_devices);
+            if (b > a && uvaia_align_batch (gpu[d], (const char *const *) seq + a, len + a, b - a, aln + (size_t) a * (aln_length + 1), NULL)) {
 #pragma omp critical
-            failed = d;
+              failed = d;
+            }
           }
         }
         if (failed >= 0) {   /* what was aligned so far stays a complete file: close the stream before giving up */
           const int a = (int) ((long long) fill * failed / n_devices), b = (int) ((long long) fill * (failed + 1) / n_devices);
-          if (!to_screen) biomcmc_close_compress (outstream);
+          if (outstream) biomcmc_close_compress (outstream);
+          if (packed) packer_close (&pk);
           biomcmc_error ("%s (counted from sequence %s, the first of the %d handed to device %d; %d sequences were written before)",
                          uvaia_align_last_error (gpu[failed]), name[a], b - a, failed, n_output);
         }
+        if (packed && packer_add_pool (&pk, gpu[0], name, fill)) {   /* both files stay complete: close them before giving up */
+          char msg[640];
+          snprintf (msg, sizeof msg, "%s", pk.err);
+          if (outstream) biomcmc_close_compress (outstream);
+          const long kept = pk.kept;
+          packer_close (&pk);
+          biomcmc_error ("packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", n_pool, fill, name[0], msg, kept);
+        }
         for (int c = 0; c < fill; c++) {
-          const char *row = aln + (size_t) c * (aln_length + 1);
           n_output++;
-          if (to_screen) printf (">%s\n%s\n", name[c], row);
-          else write_fasta_record (outstream, name[c], row);
+          if (write_text) {
+            const char *row = aln + (size_t) c * (aln_length + 1);
+            if (to_screen) printf (">%s\n%s\n", name[c], row);
+            else write_fasta_record (outstream, name[c], row);
+          }
           free (seq[c]); free (name[c]);
         }
       }
@@ -166,7 +313,14 @@ main (int argc, char **argv)
     fprintf (stderr, "Finished reading file %s. In total %d sequences have been read.\n", fasta[j], count);
     fflush (stderr);
   }
+  if (packed) {
+    const long kept = pk.kept, dropped = pk.dropped;
+    if (packer_close (&pk)) biomcmc_error ("%s", pk.err);
+    fprintf (stderr, "Packed %ld of %d aligned sequences (%zu sites) into %s; %ld too ambiguous.\n", kept, n_output, aln_length, packed, dropped);
+    fprintf (stderr, "Device time: alignment %.3lf ms; census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n", pk.align_ms, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
+  }
   if (to_screen) fprintf (stderr, "Output %d aligned sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
+  else if (!write_text) fprintf (stderr, "Aligned %d sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
   else {
     biomcmc_close_compress (outstream);
     fprintf (stderr, "Saved %d sequences to file %s\nTotal elapsed time: %.3lf secs\n", n_output, outfilename, biomcmc_update_elapsed_time (time0));

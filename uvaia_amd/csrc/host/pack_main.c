@@ -24,6 +24,7 @@ usage (const char *prog)
   printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` must use the same value\n");
   printf ("  -o, --output=<file>              packed database to write\n");
   printf ("  --device=<int>                   GPU to use (default: current device)\n");
+  printf ("Sequences that still have to be aligned: `uvaialign --packed <out.uvdb>` writes the same file straight from the aligner, without the text in between.\n");
 }
 
 int

@@ -19,6 +19,7 @@ struct uvdb_writer_struct {
   FILE *side_tmp;                      /* side rows go through a temporary file: 256 B per reference */
   uint64_t *name_idx; size_t idx_cap; char *names; size_t names_len, names_cap;
   uint64_t *exc_idx; uvdb_exc *exc; size_t exc_len, exc_cap;
+  uvdb_exc *runs_tmp; size_t runs_cap;   /* the runs of one reference on their way from its text to the section (uvdb_add_reference) */
 };
 
 static uint64_t align64 (uint64_t x) { return (x + 63u) & ~(uint64_t) 63u; }
@@ -54,7 +55,7 @@ uvdb_create (const char *filename, int nchar, size_t tile_bytes, int side_row_in
 }
 
 int
-uvdb_add_reference (uvdb_writer w, const char *name, const char *seq)
+uvdb_add_reference_runs (uvdb_writer w, const char *name, const uvdb_exc *runs, size_t n_runs)
 {
   const uint64_t i = w->h.n_ref;
   if (i + 2 > w->idx_cap) {
@@ -72,30 +73,47 @@ uvdb_add_reference (uvdb_writer w, const char *name, const char *seq)
     if (!w->names) return -1;
     w->names_cap = ncap;
   }
+  if (w->exc_len + n_runs > w->exc_cap) {
+    size_t ncap = w->exc_cap ? w->exc_cap * 2 : (1u << 16);
+    while (ncap < w->exc_len + n_runs) ncap *= 2;
+    w->exc = (uvdb_exc *) realloc (w->exc, ncap * sizeof (uvdb_exc));
+    if (!w->exc) return -1;
+    w->exc_cap = ncap;
+  }
   w->name_idx[i] = w->names_len;
   memcpy (w->names + w->names_len, name, nl);
   w->names_len += nl;
   w->exc_idx[i] = w->exc_len;
+  if (n_runs) memcpy (w->exc + w->exc_len, runs, n_runs * sizeof (uvdb_exc));
+  w->exc_len += n_runs;
+  w->h.n_ref++;
+  w->name_idx[w->h.n_ref] = w->names_len;
+  w->exc_idx[w->h.n_ref] = w->exc_len;
+  return 0;
+}
+
+int
+uvdb_add_reference (uvdb_writer w, const char *name, const char *seq)
+{ /* the runs of the text, then the above */
+  uvdb_exc *runs = w->runs_tmp;
+  size_t n_runs = 0;
   for (uint32_t s = 0; s < w->h.nchar; ) {           /* runs of invalid characters other than N */
     const char ch = seq[s];
     if (ch == '-' || ch == '?' || ch == 'X' || ch == 'O' || ch == '.') {
       uint32_t e = s + 1;
       while (e < w->h.nchar && seq[e] == ch && e - s < 0xFFFFFFu) e++;
-      if (w->exc_len + 1 > w->exc_cap) {
-        size_t ncap = w->exc_cap ? w->exc_cap * 2 : (1u << 16);
-        w->exc = (uvdb_exc *) realloc (w->exc, ncap * sizeof (uvdb_exc));
-        if (!w->exc) return -1;
-        w->exc_cap = ncap;
+      if (n_runs + 1 > w->runs_cap) {
+        size_t ncap = w->runs_cap ? w->runs_cap * 2 : 1024;
+        runs = (uvdb_exc *) realloc (w->runs_tmp, ncap * sizeof (uvdb_exc));
+        if (!runs) return -1;
+        w->runs_tmp = runs; w->runs_cap = ncap;
       }
-      w->exc[w->exc_len].pos = s; w->exc[w->exc_len].len_char = ((e - s) << 8) | (uint32_t) (unsigned char) ch;
-      w->exc_len++;
+      runs[n_runs].pos = s; runs[n_runs].len_char = ((e - s) << 8) | (uint32_t) (unsigned char) ch;
+      n_runs++;
       s = e;
     } else s++;
   }
-  w->h.n_ref++;
-  w->name_idx[w->h.n_ref] = w->names_len;
-  w->exc_idx[w->h.n_ref] = w->exc_len;
-  return 0;
+  return uvdb_add_reference_runs (w, name, runs, n_runs);
 }
 
 int
@@ -158,7 +176,7 @@ uvdb_close (uvdb_writer w)
   bad |= fseek (w->f, 0, SEEK_SET) != 0 || fwrite (h, sizeof *h, 1, w->f) != 1;
   bad |= fclose (w->f) != 0;
   fclose (w->side_tmp);
-  free (w->non_n); free (w->name_idx); free (w->names); free (w->exc_idx); free (w->exc);
+  free (w->non_n); free (w->name_idx); free (w->names); free (w->exc_idx); free (w->exc); free (w->runs_tmp);
   free (w);
   return bad ? -1 : 0;
 }

@@ -46,6 +46,10 @@ typedef struct uvdb_writer_struct *uvdb_writer;
 uvdb_writer uvdb_create (const char *filename, int nchar, size_t tile_bytes, int side_row_ints, double ref_ambiguity);
 /* text of the next reference: recorded for the name table and the exception runs (the planes come from the engine) */
 int uvdb_add_reference (uvdb_writer w, const char *name, const char *seq);
+/* the same for a reference whose text is not on the host: its exception runs as records (pos, len << 8 | char), by position, as the rule
+ * above gives them (a maximal stretch of one of - ? X O . , cut at 0xFFFFFF sites); uvdb_add_reference computes them from the text and
+ * calls this.  The engine computes them from rows in device memory (uvaia_gpu_rows_census + uvaia_gpu_rows_exceptions). */
+int uvdb_add_reference_runs (uvdb_writer w, const char *name, const uvdb_exc *runs, size_t n_runs);
 /* the next n_tiles tiles in the engine's export form */
 int uvdb_add_tiles (uvdb_writer w, size_t n_tiles, const void *planes, const int *non_n, const int *side_rows);
 int uvdb_close (uvdb_writer w);       /* 0 on success */

@@ -10,8 +10,9 @@ void uvaia_gpu_close(uvaia_gpu_ctx *c)
   if (c->stream) hipStreamSynchronize(c->stream);
   for (auto &e : c->evts) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
+  for (hipEvent_t e : c->rows_evs) hipEventDestroy(e);
   void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga,
-                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err, c->d_pk, c->d_rows, c->d_row_idx};
+                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc};
   for (void *p : dev) if (p) hipFree(p);
   store_free(c->batch); store_free(c->db);
   for (SliceBuf &b : c->slice) slice_free(b);

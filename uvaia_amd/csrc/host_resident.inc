@@ -23,6 +23,18 @@ int uvaia_gpu_db_reserve(uvaia_gpu_ctx *c, size_t cap)
   return 0;
 }
 
+// side rows of slots slot0 .. slot0 + n_ref - 1 of the resident database in their fixed form (side_rows_canonical_kernel: what an export, and
+// with it a packed database file, holds must not depend on the timing of pack_refs_kernel's waves); returns when it is done
+static int db_canonical_side_rows(uvaia_gpu_ctx *c, long long slot0, int n_ref)
+{
+  if (c->acgt || n_ref <= 0 || !c->db.amb) return 0;
+  const long long t0 = slot0 / 64, t1 = (slot0 + n_ref - 1) / 64;
+  hipLaunchKernelGGL(side_rows_canonical_kernel, dim3((unsigned)(t1 - t0 + 1)), dim3(64), 0, c->stream, c->db.planes, c->W4, t0, slot0, n_ref, c->db.amb);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 static int db_append_common(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t pitch, const int *non_n, int n_ref)
 {
   if (!c) return UVAIA_GPU_EINVAL;
@@ -41,6 +53,8 @@ static int db_append_common(uvaia_gpu_ctx *c, const char *const *seq, const char
     if (owns_tile(c, a / 64)) {
       const long long off = a - s0, local = dtile_of(c, a / 64) * 64 + a % 64;
       int rc = pack_rows(c, seq ? seq + off : nullptr, rows ? rows + (size_t)off * pitch : nullptr, pitch, non_n ? non_n + off : nullptr, (int)(pe - a), c->db, local);
+      if (rc) return rc;
+      rc = db_canonical_side_rows(c, local, (int)(pe - a));
       if (rc) return rc;
     }
     a = pe;

@@ -822,6 +822,17 @@ int uvaia_align_fetch(uvaia_aligner *a, char *aln, int *score)
   return 0;
 }
 
+int uvaia_align_device_rows(uvaia_aligner *a, const void **d_rows, size_t *pitch, int *n, int *device)
+{
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  if (!a->ran) return afail(a, UVAIA_ALIGN_ESTATE, "no completed run whose rows could be handed out");
+  if (d_rows) *d_rows = a->n ? a->d_aln : nullptr;
+  if (pitch) *pitch = (size_t)a->plen + 1;
+  if (n) *n = a->n;
+  if (device) *device = a->device;
+  return 0;
+}
+
 int uvaia_align_batch(uvaia_aligner *a, const char *const *seq, const int *seq_len, int n, char *aln, int *score)
 {
   int rc = uvaia_align_load(a, seq, seq_len, n); if (rc) return rc;

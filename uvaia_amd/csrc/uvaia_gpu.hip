@@ -188,6 +188,12 @@ struct uvaia_gpu_ctx {
   uint4 *d_pk = nullptr; int pk_n = 0;                      // [pool_pad / 64] tiles; references of the last batch (0: none)
   uint8_t *d_rows = nullptr; size_t rows_cap = 0;           // text of the selected references, rows of a multiple of 16 bytes
   int *d_row_idx = nullptr; size_t row_idx_cap = 0;
+  // rows handed in by device pointer (host_rows.inc): the selection, per row {valid sites, exception records} + flag, record offsets, records
+  int *d_rsel = nullptr, *d_rcnt = nullptr; unsigned long long *d_roff = nullptr; uint2 *d_rexc = nullptr;
+  size_t rsel_cap = 0, rcnt_cap = 0, roff_cap = 0, rexc_cap = 0;
+  std::vector<int> rows_host; std::vector<uint2> rexc_host;
+  uint32_t run_cut = 0xFFFFFFu;                             // longest exception run of a record (uvaia_gpu_rows_set_run_cut)
+  std::vector<hipEvent_t> rows_evs; double rows_ms[3] = {0., 0., 0.};   // per-kernel time of census, gather, exception fill
   // heaps / state
   int *d_heap = nullptr, *d_n = nullptr, *d_T = nullptr, *d_snap = nullptr, *d_err = nullptr;
   // batch buffers
@@ -263,6 +269,7 @@ void fill_code_table(uint8_t *t)
 }  // namespace
 
 #include "kernels_pack.inc"
+#include "kernels_rows.inc"
 #include "kernels_consensus.inc"
 #include "kernels_scan_history.inc"
 #include "kernels_scan3.inc"
@@ -279,5 +286,6 @@ void fill_code_table(uint8_t *t)
 #include "host_open.inc"
 #include "host_batch.inc"
 #include "host_resident.inc"
+#include "host_rows.inc"
 #include "host_shards.inc"
 #include "host_ball.inc"
