@@ -59,6 +59,29 @@ const char *uvaia_clust_last_error (const uvaia_clust_ctx *c);
  * the call with UVAIA_GPU_EALPHABET and leaves the context unusable (UVAIA_GPU_ESTATE afterwards). */
 int  uvaia_clust_push (uvaia_clust_ctx *c, int n, const char *const *seq, const int *queue);
 
+/* The same for n sequences whose text is not on the host: ceil(n / 64) whole tiles of the packed interchange form (include/uvaia_gpu.h:
+ * [word group][plane A,C,G,T][lane] 16-byte words, ((nchar + 31) / 32 + 3) / 4 * 4096 bytes per tile, the formula of
+ * uvaia_gpu_db_tile_bytes; lanes past n in the last tile are ignored whatever they hold) and their exception runs, as a packed database
+ * file holds both (uvaia_amd/csrc/host/uvdb.h).  The records of sequence i are exc[exc_offsets[i] .. exc_offsets[i + 1]) (n + 1 offsets, so
+ * a file's exc_idx + first sequence and its exc array can be handed in as they are; exc_offsets NULL = no records), each (uint32 pos,
+ * uint32 len << 8 | char).  The device rebuilds the exact upper-case text of every row -- per site the IUPAC character of the set the planes
+ * hold, 'N' for the empty and the full set, then the runs written over it -- before any distance is taken: the planes alone cannot tell
+ * N - ? X O . apart, and item 1 above counts '-' against 'N' as a difference.  Push ordinals, queues and errors are those of
+ * uvaia_clust_push, both kinds of push may be mixed in one context and the result does not depend on how the sequences are cut into
+ * pushes.  A record with a character other than - ? X O . , with pos + len > nchar, or that starts before the end of the row's previous
+ * record fails the call with UVAIA_GPU_EINVAL before anything is copied: nothing is pushed and the context stays usable. */
+int  uvaia_clust_push_packed (uvaia_clust_ctx *c, int n, const void *planes, const uint64_t *exc_offsets, const void *exc, const int *queue);
+
+/* The upper-case text of pushed sequences, before or after finish: row k of `rows` (pitch >= nchar bytes apart, nchar bytes written, no
+ * NUL) = the sequence with push ordinal ordinal[k]; any order, repeats allowed.  Gathered on the device, one copy back per call: the caller
+ * bounds its memory by the n of a call (the medoids of <prefix>.aln.xz are fetched in batches). */
+int  uvaia_clust_rows (uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch);
+
+/* The row store where it lies: sequence o is the nchar bytes at *d_rows + o * *pitch in the memory of the context's device, upper-case
+ * (uvaia_gpu_rows_census, uvaia_gpu_db_append_device and uvaia_gpu_rows_exceptions of include/uvaia_gpu.h read medoid rows in place,
+ * row_index = push ordinals).  Valid until the next push or close. */
+int  uvaia_clust_device_rows (uvaia_clust_ctx *c, const void **d_rows, size_t *pitch);
+
 /* The merge tree and the final order.  No push after it. */
 int  uvaia_clust_finish (uvaia_clust_ctx *c);
 
@@ -72,6 +95,9 @@ int  uvaia_clust_result (uvaia_clust_ctx *c, int *n_clusters, int64_t *medoid, i
 /* Kernel milliseconds of each phase so far: prep (distance to the reference), queue (phase 2), merge (the tree), and the
  * number of sequences pushed. */
 int  uvaia_clust_stats (uvaia_clust_ctx *c, double *prep_ms, double *queue_ms, double *merge_ms, int64_t *pushed);
+
+/* Kernel milliseconds of the packed pushes so far: decoding the tiles to rows, writing the exception runs over them. */
+int  uvaia_clust_unpack_ms (uvaia_clust_ctx *c, double *decode_ms, double *overlay_ms);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@ from . import capi
 # every symbol include/uvaia_cluster.h declares (tests check the library exports all of them)
 SYMBOLS = [
     "uvaia_clust_open", "uvaia_clust_close", "uvaia_clust_last_error", "uvaia_clust_push", "uvaia_clust_finish", "uvaia_clust_result",
-    "uvaia_clust_stats",
+    "uvaia_clust_stats", "uvaia_clust_push_packed", "uvaia_clust_rows", "uvaia_clust_device_rows", "uvaia_clust_unpack_ms",
 ]
 
 
@@ -35,6 +35,10 @@ def _lib():
         L.uvaia_clust_finish.argtypes = [vp]
         L.uvaia_clust_result.argtypes = [vp, pi, pl, pl, pl, pi]
         L.uvaia_clust_stats.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), pl]
+        L.uvaia_clust_push_packed.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_uint64), vp, pi]
+        L.uvaia_clust_rows.argtypes = [vp, pl, C.c_int, vp, C.c_size_t]
+        L.uvaia_clust_device_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.uvaia_clust_unpack_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _ready = True
     return L
 
@@ -62,6 +66,7 @@ class Clusterer:
         if rc:
             raise ClusterError(rc, (self.L.uvaia_clust_last_error(None) or b"").decode())
         self.pushed = 0
+        self.nchar = len(reference)
 
     def _chk(self, rc):
         if rc:
@@ -88,6 +93,40 @@ class Clusterer:
         self._chk(self.L.uvaia_clust_push(self.ptr, n, arr, q.ctypes.data_as(C.POINTER(C.c_int))))
         self.pushed += n
 
+    def push_packed(self, planes, n, exc_offsets, exc, queues):
+        """n sequences as ceil(n / 64) whole tiles of the packed interchange form (planes: uint8 array) with their exception runs:
+        exc_offsets (n + 1 record positions into exc, or None for no records) and exc (uint32 [records, 2]: pos, len << 8 | char)"""
+        if not n:
+            return
+        planes = np.ascontiguousarray(planes, dtype=np.uint8).reshape(-1)
+        tile = ((self.nchar + 31) // 32 + 3) // 4 * 4096
+        if planes.size < (n + 63) // 64 * tile:
+            raise ValueError("%d sequences need %d tiles of %d bytes" % (n, (n + 63) // 64, tile))
+        q = np.ascontiguousarray(queues, dtype=np.int32)
+        if len(q) != n:
+            raise ValueError("one queue per sequence")
+        off = rec = None
+        if exc_offsets is not None:
+            off = np.ascontiguousarray(exc_offsets, dtype=np.uint64)
+            rec = np.ascontiguousarray(exc, dtype=np.uint32).reshape(-1, 2)
+            if len(off) != n + 1 or (n and int(off[-1]) > len(rec)):
+                raise ValueError("exc_offsets: n + 1 record positions inside exc")
+        self._chk(self.L.uvaia_clust_push_packed(self.ptr, n, planes.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_uint64)) if off is not None else None,
+                                                 rec.ctypes.data if rec is not None and len(rec) else None, q.ctypes.data_as(C.POINTER(C.c_int))))
+        self.pushed += n
+
+    def rows(self, ordinals):
+        """upper-case text of pushed sequences (push ordinals, any order, repeats allowed) as a list of bytes"""
+        o = np.ascontiguousarray(ordinals, dtype=np.int64)
+        buf = np.zeros((max(len(o), 1), self.nchar), dtype=np.uint8)
+        self._chk(self.L.uvaia_clust_rows(self.ptr, o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), buf.ctypes.data, self.nchar))
+        return [buf[k].tobytes() for k in range(len(o))]
+
+    def unpack_ms(self):
+        a, b = C.c_double(0), C.c_double(0)
+        self._chk(self.L.uvaia_clust_unpack_ms(self.ptr, C.byref(a), C.byref(b)))
+        return {"decode_ms": a.value, "overlay_ms": b.value}
+
     def finish(self):
         self._chk(self.L.uvaia_clust_finish(self.ptr))
 
@@ -108,6 +147,23 @@ class Clusterer:
         a, b, c, n = C.c_double(0), C.c_double(0), C.c_double(0), C.c_int64(0)
         self._chk(self.L.uvaia_clust_stats(self.ptr, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return {"prep_ms": a.value, "queue_ms": b.value, "merge_ms": c.value, "pushed": n.value}
+
+
+def exception_runs(seqs, cut=0xFFFFFF):
+    """(exc_offsets uint64 [n + 1], exc uint32 [records, 2]) of these texts, by the rule of a packed database file: a maximal stretch
+    of one of - ? X O . is a record (pos, len << 8 | char), cut every `cut` sites"""
+    off, rec = [0], []
+    for s in seqs:
+        a = np.frombuffer(s, dtype=np.uint8)
+        hit = np.isin(a, np.frombuffer(b"-?XO.", dtype=np.uint8))
+        if hit.any():
+            start = np.flatnonzero(hit & np.concatenate(([True], (a[1:] != a[:-1]) | ~hit[:-1])))
+            end = np.flatnonzero(hit & np.concatenate(((a[1:] != a[:-1]) | ~hit[1:], [True]))) + 1
+            for b, e in zip(start.tolist(), end.tolist()):
+                for p in range(b, e, cut):
+                    rec.append((p, (min(cut, e - p) << 8) | int(a[b])))
+        off.append(len(rec))
+    return np.array(off, dtype=np.uint64), np.array(rec, dtype=np.uint32).reshape(-1, 2)
 
 
 def queues_round_robin(file_sizes, n_queues):

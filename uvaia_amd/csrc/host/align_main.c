@@ -17,112 +17,18 @@
 #include "fastaseq.h"
 #include "gpu_glue.h"
 #include "uvdb.h"
+#include "uvdb_packer.h"
 #include "../../../include/uvaia_align.h"
 #include "../../../include/uvaia_gpu.h"
 
-#define PACK_BATCH 4096      /* kept rows per engine round trip (a multiple of 64), as in pack_main.c */
-
-/* The head of a packed database in the making.  A tile holds 64 consecutive kept rows of the whole stream, pools end anywhere: the resident
- * database of the engine is the carry.  Rows are appended to it as they come, whole tiles are exported and dropped, the unfinished tile
- * stays resident for the next pool (or the flush at the end), so that the file does not depend on the pool size. */
-struct packer {
-  uvaia_gpu_ctx *gpu;
-  uvdb_writer w;
-  int nchar, non_n_ref;
-  void *planes; int *tile_nonn, *side;                 /* export buffers: PACK_BATCH / 64 + 1 tiles */
-  int *non_n, *n_exc, *keep, *keep_nn; size_t pool_cap;
-  uint64_t *off; uvdb_exc *exc; size_t exc_cap;
-  long kept, dropped;
-  double align_ms, rows_ms[3];                         /* device time: the aligner's kernels; census, gathers, exception fill */
-  char err[640];
-};
-
+/* one pool into the packed database in the making: the rows of the aligner's last run, where they lie */
 static int
-packer_open (struct packer *p, const char *path, int nchar, double ambig_r, int device, int pool)
-{
-  memset (p, 0, sizeof *p);
-  p->nchar = nchar;
-  p->non_n_ref = (int) (nchar * (1. - ambig_r));       /* src/nearest.c:263-268, as pack_main.c */
-  char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);   /* the engine needs some query to exist: a plain ACGT string */
-  for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
-  dummy[nchar] = '\0';
-  const char *one[1] = {dummy};
-  uvaia_gpu_query q;
-  memset (&q, 0, sizeof q);
-  q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
-  const int rc = uvaia_gpu_open (&p->gpu, &q, 1, device, PACK_BATCH);
-  free (dummy);
-  if (rc) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (NULL)); return -1; }
-  if (uvaia_gpu_db_reserve (p->gpu, PACK_BATCH + 64)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
-  const size_t tb = uvaia_gpu_db_tile_bytes (p->gpu), nt = PACK_BATCH / 64 + 1;
-  p->planes = biomcmc_malloc (nt * tb);
-  p->tile_nonn = (int *) biomcmc_malloc (nt * 64 * sizeof (int));
-  p->side = (int *) biomcmc_malloc (nt * 64 * (size_t) uvaia_gpu_db_side_row_ints () * sizeof (int));
-  p->pool_cap = (size_t) pool;
-  p->non_n = (int *) biomcmc_malloc (p->pool_cap * sizeof (int)); p->n_exc = (int *) biomcmc_malloc (p->pool_cap * sizeof (int));
-  p->keep = (int *) biomcmc_malloc (p->pool_cap * sizeof (int)); p->keep_nn = (int *) biomcmc_malloc (p->pool_cap * sizeof (int));
-  p->off = (uint64_t *) biomcmc_malloc ((PACK_BATCH + 1) * sizeof (uint64_t));
-  p->w = uvdb_create (path, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r);
-  if (!p->w) { snprintf (p->err, sizeof p->err, "cannot create %s", path); return -1; }
-  return 0;
-}
-
-/* whole tiles (all = 0) or everything that is resident (all = 1: the flush) from the engine to the file */
-static int
-packer_write_tiles (struct packer *p, int all)
-{
-  const size_t have = uvaia_gpu_db_size (p->gpu), nt = all ? (have + 63) / 64 : have / 64;
-  if (!nt) return 0;
-  if (uvaia_gpu_db_export (p->gpu, 0, nt, p->planes, p->tile_nonn, p->side) || uvaia_gpu_db_drop_tiles (p->gpu, nt)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
-  if (uvdb_add_tiles (p->w, nt, p->planes, p->tile_nonn, p->side)) { snprintf (p->err, sizeof p->err, "cannot write the packed database"); return -1; }
-  return 0;
-}
-
-/* one pool: the rows of the aligner's last run, where they lie */
-static int
-packer_add_pool (struct packer *p, uvaia_aligner *al, char **name, int fill)
+packer_add_pool (struct uvdb_packer *p, uvaia_aligner *al, char **name, int fill)
 {
   const void *d_rows = NULL; size_t pitch = 0; int n = 0;
   if (uvaia_align_device_rows (al, &d_rows, &pitch, &n, NULL)) { snprintf (p->err, sizeof p->err, "%s", uvaia_align_last_error (al)); return -1; }
-  if (n != fill || (size_t) n > p->pool_cap) { snprintf (p->err, sizeof p->err, "the aligner holds %d rows, the pool %d", n, fill); return -1; }
-  if (uvaia_gpu_rows_census (p->gpu, d_rows, pitch, n, p->non_n, p->n_exc)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
-  int nk = 0;
-  for (int i = 0; i < n; i++) {                        /* the -A filter (pack_main.c:86-87) on a few KB of counts */
-    if (p->non_n[i] < p->non_n_ref) { p->dropped++; continue; }
-    p->keep[nk] = i; p->keep_nn[nk++] = p->non_n[i];
-  }
-  for (int a = 0; a < nk; a += PACK_BATCH) {
-    const int m = nk - a < PACK_BATCH ? nk - a : PACK_BATCH;
-    p->off[0] = 0;
-    for (int k = 0; k < m; k++) p->off[k + 1] = p->off[k] + (uint64_t) p->n_exc[p->keep[a + k]];
-    if (p->off[m] + 1 > p->exc_cap) {
-      p->exc_cap = (size_t) (p->off[m] + 1) * 2;
-      p->exc = (uvdb_exc *) biomcmc_realloc (p->exc, p->exc_cap * sizeof (uvdb_exc));
-    }
-    if (uvaia_gpu_rows_exceptions (p->gpu, d_rows, pitch, p->keep + a, m, p->off, p->exc) ||
-        uvaia_gpu_db_append_device (p->gpu, d_rows, pitch, p->keep + a, m, p->keep_nn + a)) { snprintf (p->err, sizeof p->err, "%s", uvaia_gpu_last_error (p->gpu)); return -1; }
-    for (int k = 0; k < m; k++)                          /* (names only of rows the engine holds: the flush of packer_close stays consistent) */
-      if (uvdb_add_reference_runs (p->w, name[p->keep[a + k]], p->exc + p->off[k], (size_t) (p->off[k + 1] - p->off[k]))) { snprintf (p->err, sizeof p->err, "out of memory while indexing %s", name[p->keep[a + k]]); return -1; }
-    p->kept += m;
-    if (packer_write_tiles (p, 0)) return -1;
-  }
-  return 0;
-}
-
-/* the unfinished tile, the index sections, the engine; 0 when the file is complete */
-static int
-packer_close (struct packer *p)
-{
-  int bad = 0;
-  if (p->w) {
-    bad = p->gpu ? packer_write_tiles (p, 1) : 0;
-    if (uvdb_close (p->w) && !bad) { snprintf (p->err, sizeof p->err, "problem writing the packed database"); bad = -1; }
-    p->w = NULL;
-  }
-  if (p->gpu) { uvaia_gpu_rows_kernel_ms (p->gpu, p->rows_ms, 0); uvaia_gpu_close (p->gpu); }
-  p->gpu = NULL;
-  free (p->planes); free (p->tile_nonn); free (p->side); free (p->non_n); free (p->n_exc); free (p->keep); free (p->keep_nn); free (p->off); free (p->exc);
-  return bad;
+  if (n != fill) { snprintf (p->err, sizeof p->err, "the aligner holds %d rows, the pool %d", n, fill); return -1; }
+  return uvdb_packer_add_block (p, d_rows, pitch, n, name);
 }
 
 int
@@ -218,9 +124,10 @@ main (int argc, char **argv)
   if (n_devices > 1) fprintf (stderr, "Batches of %d sequences will be read and aligned on %d GPUs.\n", pool, n_devices);
   else fprintf (stderr, "Batches of %d sequences will be read and aligned on GPU %d.\n", pool, devices[0]);
 
-  struct packer pk;
+  struct uvdb_packer pk;
+  double align_ms = 0.;
   if (packed) {
-    if (packer_open (&pk, packed, (int) aln_length, ambig_r, devices[0], pool)) biomcmc_error ("%s", pk.err);
+    if (uvdb_packer_open (&pk, packed, (int) aln_length, ambig_r, devices[0], pool)) biomcmc_error ("%s", pk.err);
     fprintf (stderr, "Aligned sequences with at least %d valid sites will be packed into %s.\n", pk.non_n_ref, packed);
   }
   file_compress_t outstream = (to_screen || !write_text) ? NULL : biomcmc_open_compress (outfilename, "w");
@@ -268,7 +175,7 @@ main (int argc, char **argv)
         if (packed) {   /* one GPU: the steps of uvaia_align_batch, the copy of the text only if somebody reads it */
           double ms = 0.;
           if (uvaia_align_load (gpu[0], (const char *const *) seq, len, fill) || uvaia_align_run (gpu[0]) || (write_text && uvaia_align_fetch (gpu[0], aln, NULL))) failed = 0;
-          else if (!uvaia_align_stats (gpu[0], NULL, NULL, NULL, &ms)) pk.align_ms += ms;
+          else if (!uvaia_align_stats (gpu[0], NULL, NULL, NULL, &ms)) align_ms += ms;
         } else {
 #pragma omp parallel for num_threads(n_devices) schedule(static, 1)
           for (int d = 0; d < n_devices; d++) {
@@ -282,7 +189,7 @@ main (int argc, char **argv)
         if (failed >= 0) {   /* what was aligned so far stays a complete file: close the stream before giving up */
           const int a = (int) ((long long) fill * failed / n_devices), b = (int) ((long long) fill * (failed + 1) / n_devices);
           if (outstream) biomcmc_close_compress (outstream);
-          if (packed) packer_close (&pk);
+          if (packed) uvdb_packer_close (&pk);
           biomcmc_error ("%s (counted from sequence %s, the first of the %d handed to device %d; %d sequences were written before)",
                          uvaia_align_last_error (gpu[failed]), name[a], b - a, failed, n_output);
         }
@@ -291,7 +198,7 @@ main (int argc, char **argv)
           snprintf (msg, sizeof msg, "%s", pk.err);
           if (outstream) biomcmc_close_compress (outstream);
           const long kept = pk.kept;
-          packer_close (&pk);
+          uvdb_packer_close (&pk);
           biomcmc_error ("packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", n_pool, fill, name[0], msg, kept);
         }
         for (int c = 0; c < fill; c++) {
@@ -315,9 +222,9 @@ main (int argc, char **argv)
   }
   if (packed) {
     const long kept = pk.kept, dropped = pk.dropped;
-    if (packer_close (&pk)) biomcmc_error ("%s", pk.err);
+    if (uvdb_packer_close (&pk)) biomcmc_error ("%s", pk.err);
     fprintf (stderr, "Packed %ld of %d aligned sequences (%zu sites) into %s; %ld too ambiguous.\n", kept, n_output, aln_length, packed, dropped);
-    fprintf (stderr, "Device time: alignment %.3lf ms; census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n", pk.align_ms, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
+    fprintf (stderr, "Device time: alignment %.3lf ms; census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n", align_ms, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
   }
   if (to_screen) fprintf (stderr, "Output %d aligned sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
   else if (!write_text) fprintf (stderr, "Aligned %d sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));

@@ -3,6 +3,11 @@
  * files as the reference's src/cluster.c; phase 2 and the merge tree run on the GPU through include/uvaia_cluster.h, whose header
  * states what is computed.  The partial saves of src/cluster.c:197-199,228-229 (their timing decides them) are not made: only the
  * final <prefix>.csv.xz and <prefix>.aln.xz are written.
+ *
+ * --packed and --packed-out (no counterpart in the reference): the sequences come from a packed database (uvdb.h) whose tiles and
+ * exception runs go to the device as they lie in the file's mapping, and the medoids leave as a packed database written from the rows in
+ * device memory (uvdb_packer.h), the file `uvaiapack` makes of <prefix>.aln.xz.  No sequence text is held on the host on that path: the
+ * medoids of <prefix>.aln.xz are fetched from the device in batches.  Own code.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -11,10 +16,39 @@
 
 #include "cli_common.h"
 #include "fastaseq.h"
+#include "uvdb.h"
+#include "uvdb_packer.h"
 #include "../../../include/uvaia_cluster.h"
 
 /* read_reference_sequence (src/cluster.c:260-277): the first record of the file, filled by up to nseqs - 1 more while Ns remain
    (accumulate_reference_sequence, src/fastaseq.c:488-512), remaining Ns replaced by A (src/fastaseq.c:514-520) */
+/* one more record s into the reference in the making (*ref NULL: the first); returns the sites that are still N */
+static int
+accumulate_reference (char **ref, const char *s, int len)
+{
+  int count = 0;
+  if (!*ref) {
+    *ref = (char *) biomcmc_malloc ((size_t) len + 1);
+    for (int k = 0; k < len; k++) {
+      (*ref)[k] = s[k];
+      if (s[k] != 'A' && s[k] != 'C' && s[k] != 'G' && s[k] != 'T') { (*ref)[k] = 'N'; count++; }
+    }
+    (*ref)[len] = '\0';
+  } else for (int k = 0; k < len; k++) if ((*ref)[k] == 'N') {
+    if (s[k] == 'A' || s[k] == 'C' || s[k] == 'G' || s[k] == 'T') (*ref)[k] = s[k];
+    else count++;
+  }
+  return count;
+}
+
+static void
+finish_reference (char *ref, int len)
+{
+  int count = 0;
+  for (int k = 0; k < len; k++) if (ref[k] == 'N') { ref[k] = 'A'; count++; }
+  if (count) fprintf (stderr, "Reference still had %d Ns or indels which were replaced arbitrarily (it only makes program a bit slower).", count);
+}
+
 static char *
 read_reference (const char *filename, int nseqs, int *nchar)
 {
@@ -25,26 +59,31 @@ read_reference (const char *filename, int nseqs, int *nchar)
   for (int i = 0; i < nseqs && count && readfasta_next (rfas) > 0; i++) {
     if (len < 0) len = (int) rfas->seqlength;
     else if (len != (int) rfas->seqlength) biomcmc_error ("Unaligned sequences: first seq has %d sites but %s has %lu sites\n", len, rfas->name, (unsigned long) rfas->seqlength);
-    const char *s = rfas->seq;
-    count = 0;
-    if (!ref) {
-      ref = (char *) biomcmc_malloc ((size_t) len + 1);
-      for (int k = 0; k < len; k++) {
-        ref[k] = s[k];
-        if (s[k] != 'A' && s[k] != 'C' && s[k] != 'G' && s[k] != 'T') { ref[k] = 'N'; count++; }
-      }
-      ref[len] = '\0';
-    } else for (int k = 0; k < len; k++) if (ref[k] == 'N') {
-      if (s[k] == 'A' || s[k] == 'C' || s[k] == 'G' || s[k] == 'T') ref[k] = s[k];
-      else count++;
-    }
+    count = accumulate_reference (&ref, rfas->seq, len);
   }
   del_readfasta (rfas);
   if (!ref) biomcmc_error ("No sequence found in %s to build a reference from", filename);
-  count = 0;
-  for (int k = 0; k < len; k++) if (ref[k] == 'N') { ref[k] = 'A'; count++; }
-  if (count) fprintf (stderr, "Reference still had %d Ns or indels which were replaced arbitrarily (it only makes program a bit slower).", count);
+  finish_reference (ref, len);
   *nchar = len;
+  return ref;
+}
+
+/* the same rule over the records of a packed database: their exact text, one at a time, from uvdb_unpack_reference */
+static char *
+read_reference_packed (uvdb_reader db, const char *filename, int nseqs)
+{
+  char *ref = NULL;
+  int count = 0xff;
+  const int len = (int) db->h.nchar;
+  char *text = (char *) biomcmc_malloc ((size_t) len + 1);
+  fprintf (stderr, "Generating a reference from up to %d sequences in %s\n", nseqs, filename);
+  for (uint64_t i = 0; i < (uint64_t) nseqs && count && i < db->h.n_ref; i++) {
+    uvdb_unpack_reference (db, i, text);
+    count = accumulate_reference (&ref, text, len);
+  }
+  free (text);
+  if (!ref) biomcmc_error ("No sequence found in %s to build a reference from", filename);
+  finish_reference (ref, len);
   return ref;
 }
 
@@ -75,16 +114,67 @@ push_batch (gpu_state *g, str_vec *seqs, int64_t from, int *queue, int n)
   if (uvaia_clust_push (g->ctx, n, (const char *const *) seqs->v + from, queue)) biomcmc_error ("%s", uvaia_clust_last_error (g->ctx));
 }
 
+#define PACKED_CHUNK 4096    /* sequences of a packed database per push: whole tiles (a multiple of 64); a tuning value, the result does not depend on it */
+#define ROWS_BATCH 256       /* medoids fetched from the device per round trip for <prefix>.aln.xz */
+
+/* --packed-out: the medoids in their final order into a packed database, from the rows in the clusterer's device memory */
+static void
+write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, int64_t count, const int64_t *medoid, int n_out,
+                  const char *(*name_of) (void *, int64_t), void *name_arg)
+{
+  const void *d_rows = NULL; size_t pitch = 0;
+  if (uvaia_clust_device_rows (ctx, &d_rows, &pitch)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
+  struct uvdb_packer pk;
+  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH)) biomcmc_error ("%s", pk.err);
+  /* the census takes consecutive rows: the whole store in blocks, the counts of the medoids are kept */
+  int *slot = (int *) biomcmc_malloc ((size_t) (count + 1) * sizeof (int));
+  int *m_nn = (int *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int)), *m_exc = (int *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int));
+  for (int64_t i = 0; i < count; i++) slot[i] = -1;
+  for (int c = 0; c < n_out; c++) slot[medoid[c]] = c;
+  int *nn = (int *) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (int)), *ne = (int *) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (int)), *row = (int *) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (int));
+  char **name = (char **) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (char *));
+  for (int64_t a = 0; a < count && n_out; a += UVDB_PACK_BATCH) {
+    const int m = (int) (count - a < UVDB_PACK_BATCH ? count - a : UVDB_PACK_BATCH);
+    if (uvaia_gpu_rows_census (pk.gpu, (const char *) d_rows + (size_t) a * pitch, pitch, m, nn, ne)) {
+      char msg[640];
+      snprintf (msg, sizeof msg, "%s", uvaia_gpu_last_error (pk.gpu));
+      uvdb_packer_close (&pk);
+      biomcmc_error ("%s: %s", path, msg);
+    }
+    for (int k = 0; k < m; k++) if (slot[a + k] >= 0) { m_nn[slot[a + k]] = nn[k]; m_exc[slot[a + k]] = ne[k]; }
+  }
+  for (int a = 0; a < n_out; a += UVDB_PACK_BATCH) {
+    const int m = n_out - a < UVDB_PACK_BATCH ? n_out - a : UVDB_PACK_BATCH;
+    for (int k = 0; k < m; k++) { row[k] = (int) medoid[a + k]; name[k] = (char *) name_of (name_arg, medoid[a + k]); }
+    if (uvdb_packer_add_rows (&pk, d_rows, pitch, row, m_nn + a, m_exc + a, name, m)) {
+      char msg[640];
+      snprintf (msg, sizeof msg, "%s", pk.err);
+      uvdb_packer_close (&pk);
+      biomcmc_error ("%s: %s", path, msg);
+    }
+  }
+  const long kept = pk.kept, dropped = pk.dropped;
+  if (uvdb_packer_close (&pk)) biomcmc_error ("%s", pk.err);
+  fprintf (stderr, "Packed %ld of %d medoids (%d sites) into %s; %ld too ambiguous. Device time: census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n",
+           kept, n_out, nchar, path, dropped, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
+  free (slot); free (m_nn); free (m_exc); free (nn); free (ne); free (row); free (name);
+}
+
+static const char *name_from_vec (void *v, int64_t i) { return ((str_vec *) v)->v[i]; }
+static const char *name_from_db (void *v, int64_t i) { return uvdb_name ((uvdb_reader) v, (uint64_t) i); }
+
 int
 main (int argc, char **argv)
 {
   int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, ch;   /* src/cluster.c:57-64 */
-  const char *out = "cluster_uvaia", *ref_file = NULL;
+  double ambig_r = -1.;
+  const char *out = "cluster_uvaia", *ref_file = NULL, *packed = NULL, *packed_out = NULL;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
     {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {0, 0, 0, 0}};
-  while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:", longopts, NULL)) != -1) switch (ch) {
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"packed", required_argument, 0, 1002},
+    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {0, 0, 0, 0}};
+  while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
     case 'd': dist = atoi (optarg); break;
@@ -94,14 +184,21 @@ main (int argc, char **argv)
     case 'r': if (ref_file) errors++; ref_file = optarg; break;
     case 'o': out = optarg; break;
     case 1001: device = atoi (optarg); break;
+    case 1002: if (packed) errors++; packed = optarg; break;
+    case 1003: if (packed_out) errors++; packed_out = optarg; break;
+    case 'A': ambig_r = atof (optarg); if (ambig_r < 0.) ambig_r = 0.; break;
     default: errors++;
   }
   const char **fasta = (const char **) argv + optind;
   const int n_fasta = argc - optind;
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
-  if (help || errors || n_fasta < 1 || n_fasta > 1024) {
+  if (!help && !errors && packed && n_fasta > 0) {
+    fprintf (stderr, "--packed %s takes the place of the alignment files: give one or the other, not both (%s was given as well)\n", packed, fasta[0]);
+    errors++;
+  }
+  if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024) {
     printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... [-o <without suffix>]\n\n", basename (argv[0]));
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb>\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
     printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
@@ -111,6 +208,11 @@ main (int argc, char **argv)
     printf ("  <seqs.fa(.gz,.xz)>               alignments to merge\n");
     printf ("  -o, --output=<without suffix>    prefix of xzipped output alignment and cluster table files\n");
     printf ("  --device=<int>                   GPU to use (default 0)\n");
+    printf ("  --packed=<in.uvdb>               cluster the sequences of a packed database (`uvaiapack`, `uvaialign --packed`) instead of alignment files:\n");
+    printf ("                                   its tiles are decoded on the GPU, no text is parsed or held; same output files as from the same sequences as text\n");
+    printf ("  --packed-out=<out.uvdb>          also write the medoids as a packed database, the file `uvaiapack` makes of <prefix>.aln.xz (with either kind of input)\n");
+    printf ("  -A, --ref_ambiguity=<double>     with --packed-out: maximum allowed ambiguity for a medoid to be kept in that database, as in `uvaiapack`\n");
+    printf ("                                   (default: the value recorded in the --packed database, 0.5 for alignment files)\n");
     if (help) {
       printf ("One-pass clustering similar to canopy clustering with single, tight distance, computed on the GPU.\n");
       printf ("A pool of independent clustering queues is created, such that each sequence is compared to only one of them at first.\n\n");
@@ -125,37 +227,68 @@ main (int argc, char **argv)
   int64_t time0[2];
   biomcmc_get_time (time0);
 
+  uvdb_reader db = NULL;
+  if (packed) {   /* a damaged file is refused here, before any GPU work */
+    char msg[512] = "";
+    db = uvdb_open (packed, msg, sizeof msg);
+    if (!db) biomcmc_error ("%s", msg);
+    if (db->h.nchar > 0x3fffffff) biomcmc_error ("%s: sequences of %u sites are too long", packed, db->h.nchar);
+  }
+  if (ambig_r < 0.) ambig_r = db ? db->h.ref_ambiguity : 0.5;
+  if (ambig_r < 0.001) ambig_r = 0.001;                                    /* pack_main.c:46-47 */
+  if (ambig_r > 1.) ambig_r = 1.;
+
   int nchar = 0;
-  char *refseq = ref_file ? read_reference (ref_file, 1, &nchar) : read_reference (fasta[0], 1024, &nchar);
+  char *refseq = NULL;
+  if (ref_file) refseq = read_reference (ref_file, 1, &nchar);
+  else if (db) { refseq = read_reference_packed (db, packed, 1024); nchar = (int) db->h.nchar; }
+  else refseq = read_reference (fasta[0], 1024, &nchar);
+  if (db && (uint32_t) nchar != db->h.nchar)
+    biomcmc_error ("%s cannot work with unaligned sequences; the sequences of %s have %u sites while reference has %d.", UVAIA_PACKAGE_STRING, packed, db->h.nchar, nchar);
   if (trim < 0) trim = 0;                                                  /* new_cqueue, src/cluster.c:287-289 */
   if (trim > nchar / 2.1) trim = (int) (nchar / 2.1);
   if (dist > nchar / 10) dist = nchar / 10;
   fprintf (stderr, "Creating a pool of %d cluster queues; maximum distance is %d, and %d SNP locations are kept\n", n_clust, dist, snps);
   gpu_state g = {device, nchar, dist, trim, snps, n_clust, refseq, NULL};
 
-  /* read every file, sequence k of a file to queue k mod Q (src/cluster.c:164-181); push in batches of 4 Q */
   str_vec names = {0}, seqs = {0};
-  const int batch = 4 * n_clust;
-  int *queue = (int *) biomcmc_malloc ((size_t) batch * sizeof (int));
   int64_t count = 0;
-  for (int j = 0; j < n_fasta; j++) {
-    readfasta_t rfas = new_readfasta (fasta[j]);
-    int64_t k = 0, from = seqs.n;
-    int fill = 0;
-    while (readfasta_next (rfas) >= 0) {
-      if ((int64_t) rfas->seqlength != nchar)
-        biomcmc_error ("%s cannot work with unaligned sequences; sequence %s has %lu sites while reference has %d.", UVAIA_PACKAGE_STRING, rfas->name ? rfas->name : "(unnamed)", (unsigned long) rfas->seqlength, nchar);
-      for (int i = 0; i < nchar; i++) if ((unsigned char) rfas->seq[i] >= 0x80)   /* they index the reference's site tables out of range */
-        biomcmc_error ("sequence %s holds byte 0x%02x at site %d: only bytes 1-127 are defined", rfas->name ? rfas->name : "(unnamed)", (unsigned char) rfas->seq[i], i + 1);
-      str_vec_push (&seqs, rfas->seq); rfas->seq = NULL; rfas->seqlength = 0;
-      str_vec_push (&names, rfas->name); rfas->name = NULL;
-      queue[fill++] = (int) (k++ % n_clust);
-      count++;
-      if (fill == batch) { push_batch (&g, &seqs, from, queue, fill); from += fill; fill = 0; }
+  if (db) {
+    /* sequence k of the database to queue k mod Q; chunks of whole tiles go to the device from the file's mapping as they are */
+    int *queue = (int *) biomcmc_malloc (PACKED_CHUNK * sizeof (int));
+    open_context (&g);
+    for (uint64_t first = 0; first < db->h.n_ref; first += PACKED_CHUNK) {
+      const int n = (int) (db->h.n_ref - first < PACKED_CHUNK ? db->h.n_ref - first : PACKED_CHUNK);
+      for (int i = 0; i < n; i++) queue[i] = (int) ((first + (uint64_t) i) % (uint64_t) n_clust);
+      if (uvaia_clust_push_packed (g.ctx, n, uvdb_tile_planes (db, first / 64), db->exc_idx + first, db->exc, queue)) biomcmc_error ("%s: %s", packed, uvaia_clust_last_error (g.ctx));
+      count += n;
     }
-    push_batch (&g, &seqs, from, queue, fill);
-    del_readfasta (rfas);
-    fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", fasta[j], biomcmc_update_elapsed_time (time0), (long) count);
+    free (queue);
+    fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", packed, biomcmc_update_elapsed_time (time0), (long) count);
+  } else {
+    /* read every file, sequence k of a file to queue k mod Q (src/cluster.c:164-181); push in batches of 4 Q */
+    const int batch = 4 * n_clust;
+    int *queue = (int *) biomcmc_malloc ((size_t) batch * sizeof (int));
+    for (int j = 0; j < n_fasta; j++) {
+      readfasta_t rfas = new_readfasta (fasta[j]);
+      int64_t k = 0, from = seqs.n;
+      int fill = 0;
+      while (readfasta_next (rfas) >= 0) {
+        if ((int64_t) rfas->seqlength != nchar)
+          biomcmc_error ("%s cannot work with unaligned sequences; sequence %s has %lu sites while reference has %d.", UVAIA_PACKAGE_STRING, rfas->name ? rfas->name : "(unnamed)", (unsigned long) rfas->seqlength, nchar);
+        for (int i = 0; i < nchar; i++) if ((unsigned char) rfas->seq[i] >= 0x80)   /* they index the reference's site tables out of range */
+          biomcmc_error ("sequence %s holds byte 0x%02x at site %d: only bytes 1-127 are defined", rfas->name ? rfas->name : "(unnamed)", (unsigned char) rfas->seq[i], i + 1);
+        str_vec_push (&seqs, rfas->seq); rfas->seq = NULL; rfas->seqlength = 0;
+        str_vec_push (&names, rfas->name); rfas->name = NULL;
+        queue[fill++] = (int) (k++ % n_clust);
+        count++;
+        if (fill == batch) { push_batch (&g, &seqs, from, queue, fill); from += fill; fill = 0; }
+      }
+      push_batch (&g, &seqs, from, queue, fill);
+      del_readfasta (rfas);
+      fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", fasta[j], biomcmc_update_elapsed_time (time0), (long) count);
+    }
+    free (queue);
   }
   open_context (&g);
   free (refseq);
@@ -166,9 +299,11 @@ main (int argc, char **argv)
   int64_t *medoid = (int64_t *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int64_t)), *offsets = (int64_t *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int64_t));
   int64_t *members = (int64_t *) biomcmc_malloc ((size_t) (count - n_out + 1) * sizeof (int64_t));
   if (uvaia_clust_result (ctx, &n_out, medoid, offsets, members, NULL)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
-  double prep_ms = 0, queue_ms = 0, merge_ms = 0;
+  double prep_ms = 0, queue_ms = 0, merge_ms = 0, decode_ms = 0, overlay_ms = 0;
   uvaia_clust_stats (ctx, &prep_ms, &queue_ms, &merge_ms, NULL);
-  uvaia_clust_close (ctx);
+  uvaia_clust_unpack_ms (ctx, &decode_ms, &overlay_ms);
+  const char *(*name_of) (void *, int64_t) = db ? name_from_db : name_from_vec;
+  void *name_arg = db ? (void *) db : (void *) &names;
 
   /* save_neighbours_to_xz_file and save_cluster_to_xz_file (src/fastaseq.c:293-392) for the final order */
   size_t outlength = 0;
@@ -177,10 +312,12 @@ main (int argc, char **argv)
   file_compress_t csv = biomcmc_open_compress (outfilename, "w");
   int bad = 0;
   for (int c = 0; c < n_out; c++) {
-    bad += biomcmc_write_compress (csv, names.v[medoid[c]]) != (int) strlen (names.v[medoid[c]]);
+    const char *nm = name_of (name_arg, medoid[c]);
+    bad += biomcmc_write_compress (csv, nm) != (int) strlen (nm);
     for (int64_t m = offsets[c]; m < offsets[c + 1]; m++) {
+      nm = name_of (name_arg, members[m]);
       bad += biomcmc_write_compress (csv, ",") != 1;
-      bad += biomcmc_write_compress (csv, names.v[members[m]]) != (int) strlen (names.v[members[m]]);
+      bad += biomcmc_write_compress (csv, nm) != (int) strlen (nm);
     }
     bad += biomcmc_write_compress (csv, "\n") != 1;
   }
@@ -188,12 +325,26 @@ main (int argc, char **argv)
   if (bad) fprintf (stderr, "File %s may not be correctly compressed, %d error%s occurred.\n", outfilename, bad, bad > 1 ? "s" : "");
   strcpy (outfilename + outlength, ".aln.xz");
   file_compress_t aln = biomcmc_open_compress (outfilename, "w");
-  for (int c = 0; c < n_out; c++) write_fasta_record (aln, names.v[medoid[c]], seqs.v[medoid[c]]);
+  if (db) {   /* the text of the medoids exists on the device only: a bounded batch of it at a time */
+    const size_t pitch = (size_t) nchar + 1;
+    char *text = (char *) biomcmc_malloc (ROWS_BATCH * pitch);
+    memset (text, 0, ROWS_BATCH * pitch);
+    for (int a = 0; a < n_out; a += ROWS_BATCH) {
+      const int m = n_out - a < ROWS_BATCH ? n_out - a : ROWS_BATCH;
+      if (uvaia_clust_rows (ctx, medoid + a, m, text, pitch)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
+      for (int k = 0; k < m; k++) write_fasta_record (aln, name_of (name_arg, medoid[a + k]), text + (size_t) k * pitch);
+    }
+    free (text);
+  } else for (int c = 0; c < n_out; c++) write_fasta_record (aln, names.v[medoid[c]], seqs.v[medoid[c]]);
   biomcmc_close_compress (aln);
-  fprintf (stderr, "%d clusters from %ld sequences; GPU kernels: prep %.3lf ms, queues %.3lf ms, merge %.3lf ms\n", n_out, (long) count, prep_ms, queue_ms, merge_ms);
+  if (packed_out) write_packed_out (packed_out, ctx, device, nchar, ambig_r, count, medoid, n_out, name_of, name_arg);
+  uvaia_clust_close (ctx);
+  fprintf (stderr, "%d clusters from %ld sequences; GPU kernels: prep %.3lf ms, queues %.3lf ms, merge %.3lf ms, decode %.3lf ms, overlay %.3lf ms\n", n_out, (long) count,
+           prep_ms, queue_ms, merge_ms, decode_ms, overlay_ms);
   fprintf (stderr, "Finished sorting clusters and saving files in %lf secs\n", biomcmc_update_elapsed_time (time0));
 
   for (int64_t i = 0; i < seqs.n; i++) { free (seqs.v[i]); free (names.v[i]); }
-  free (seqs.v); free (names.v); free (queue); free (medoid); free (offsets); free (members); free (outfilename);
+  free (seqs.v); free (names.v); free (medoid); free (offsets); free (members); free (outfilename);
+  if (db) uvdb_close_reader (db);
   return EXIT_SUCCESS;
 }

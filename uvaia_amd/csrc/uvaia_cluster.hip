@@ -16,6 +16,11 @@
 //   * merge: one launch per round of the tree, one wave per (pair, absorbed cluster): the host gives each its window of the
 //     absorbing list (binary search on the sorted stored distances), the wave compares in order and stops at the first match.
 //     The host does the stable sorts and splices the member lists.
+//   * packed pushes (uvaia_clust_push_packed): the rows come as whole tiles of the packed interchange form and are rebuilt on the device.
+//     unpack: lane = reference, one 1 KiB wave load per plane and word group, sets decoded to characters in registers (iupac_decode.h), a
+//     transpose through an XOR-swizzled LDS image so that every row's 128 characters of a word group leave as eight 16-byte stores.
+//     overlay: the exception runs ('-', '?', 'X', 'O', '.': the planes hold them all as the empty set) are written over the decoded rows,
+//     one wave per run, the lanes spread over its length.  Prep and queue then run on these rows as on rows that came as text.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +33,7 @@
 #include <vector>
 
 #include "../../include/uvaia_cluster.h"
+#include "iupac_decode.h"
 
 namespace {
 
@@ -36,6 +42,9 @@ constexpr int QW = QTPB / 64;
 constexpr int LDS_ST = 14336;           // stored distances of a queue's first medoids kept in LDS (56 KB)
 constexpr int PTPB = 256;               // prep and merge: one wave per row / item
 constexpr int UNROLL = 4;               // 16-B loads in flight per lane in a comparison: 4 KB per wave per round trip
+constexpr int UTPB = 256;               // unpack: four waves, each with a transpose image of its own (4 x 8 KiB of LDS)
+constexpr int UGROUPS = 16;             // unpack: word groups per work unit (a 29 903-site alignment is 15 units per tile)
+constexpr int OTPB = 256;               // overlay: one block per row, one wave per run
 
 __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
 __device__ __forceinline__ uint32_t expand4(uint32_t b) { return ((b & 1u) << 7) | ((b & 2u) << 14) | ((b & 4u) << 21) | ((b & 8u) << 28); }
@@ -247,6 +256,91 @@ __global__ __launch_bounds__(PTPB) void clust_merge_kernel(const uint8_t *__rest
   if ((threadIdx.x & 63) == 0) target[w] = t;
 }
 
+// Byte offset of the 16-byte piece k (0..7) of row r (0..63) in a wave's transpose image: 64 rows of 128 B, piece index XORed with r & 7.
+// Writes are lane = row, one piece index per instruction: ds_write_b128 is served in groups of 8 consecutive lanes over 32 banks (128 B), and
+// the XOR sends those 8 rows to the 8 different 16-byte slots.  Reads are lane = (row 8 i + lane / 8, piece lane % 8): ds_read_b128 is served
+// in four groups of 16 lanes over 64 banks (256 B = two rows); each group holds four rows, two even and two odd, with pieces {0-3} of one and
+// {4-7} of the other of each parity, which the XOR permutes inside their halves: 16 different slots.  Every access stays 16-byte aligned.
+__device__ __forceinline__ int unpack_image_offset(int r, int k) { return r * 128 + ((k ^ (r & 7)) << 4); }
+
+// Whole tiles of the packed interchange form ([word group][plane A,C,G,T][lane] 16-byte words) -> rows of text.  Block = (tile, UGROUPS word
+// groups of it), wave v of it takes the word groups g0 + v, g0 + v + 4, ...  Lane r loads the four plane words of reference r of the tile (1 KiB
+// per wave load), decodes its 128 sites to characters and writes them to the wave's LDS image; the wave then stores 8 rows x 128 B per
+// instruction.  rows points at the row of lane 0 of tile 0; lanes at and past n_ref are not written; sites in [nchar, pitch) are written as
+// zero bytes (pitch is a multiple of 64: a piece starts below it or not at all).
+__global__ __launch_bounds__(UTPB) void clust_unpack_tiles_kernel(const uint4 *__restrict__ tiles, int W4, int nchar, int n_ref, uint8_t *__restrict__ rows, size_t pitch,
+                                                                  int units_per_tile)
+{
+  __shared__ uint4 image[UTPB / 64][64 * 8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int tile = blockIdx.x / units_per_tile, g0 = (blockIdx.x % units_per_tile) * UGROUPS, g1 = min(W4, g0 + UGROUPS);
+  const uint4 *t = tiles + (size_t)tile * W4 * 4 * 64 + lane;
+  uint8_t *im = reinterpret_cast<uint8_t *>(image[wave]);
+  uint8_t *out = rows + (size_t)tile * 64 * pitch;
+  const int live = min(64, n_ref - tile * 64);
+  for (int base = g0; base < g1; base += UTPB / 64) {
+    const int w4 = base + wave;
+    if (w4 < g1) {
+      const uint4 *p = t + (size_t)w4 * 4 * 64;
+      const uint4 pa = p[0], pc = p[64], pg = p[128], pt = p[192];
+      const uint32_t A[4] = {pa.x, pa.y, pa.z, pa.w}, C[4] = {pc.x, pc.y, pc.z, pc.w}, G[4] = {pg.x, pg.y, pg.z, pg.w}, T[4] = {pt.x, pt.y, pt.z, pt.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        uint32_t o[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) o[q] = iupac_text4((A[j] >> (4 * q)) & 15u, (C[j] >> (4 * q)) & 15u, (G[j] >> (4 * q)) & 15u, (T[j] >> (4 * q)) & 15u);
+        *reinterpret_cast<uint4 *>(im + unpack_image_offset(lane, 2 * j)) = make_uint4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<uint4 *>(im + unpack_image_offset(lane, 2 * j + 1)) = make_uint4(o[4], o[5], o[6], o[7]);
+      }
+    }
+    __syncthreads();
+    const int k = lane & 7, site0 = w4 * 128 + k * 16;
+    if (w4 < g1 && site0 < (int)pitch) {
+      const int keep = nchar - site0;                  // characters of this piece inside the alignment
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+        const int r = i * 8 + (lane >> 3);
+        if (r >= live) continue;
+        uint4 v = *reinterpret_cast<const uint4 *>(im + unpack_image_offset(r, k));
+        if (keep < 16) {
+          uint32_t *vv = &v.x;
+#pragma unroll
+          for (int m = 0; m < 4; m++) { const int kb = min(max(keep - 4 * m, 0), 4); vv[m] &= kb == 4 ? 0xffffffffu : ((1u << (8 * kb)) - 1u); }
+        }
+        *reinterpret_cast<uint4 *>(out + (size_t)r * pitch + site0) = v;
+      }
+    }
+    __syncthreads();     // the image is rewritten by the next round
+  }
+}
+
+// The exception runs of a push over its decoded rows.  Block i = row i of the push (rows points at it); its records are rec[off[i] .. off[i + 1]),
+// (pos, len << 8 | char), checked by the host: inside the row, in increasing position, not overlapping.  One wave per record, the lanes spread
+// over its length in aligned 4-byte words; the words a run covers partly are written byte by byte, so neighbouring runs never touch each other.
+__global__ __launch_bounds__(OTPB) void clust_overlay_runs_kernel(uint8_t *__restrict__ rows, size_t pitch, const uint32_t *__restrict__ off, const uint2 *__restrict__ rec)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint8_t *row = rows + (size_t)blockIdx.x * pitch;
+  for (uint32_t e = off[blockIdx.x] + wave, e1 = off[blockIdx.x + 1]; e < e1; e += OTPB / 64) {
+    const uint2 x = rec[e];
+    const uint32_t pos = x.x, len = x.y >> 8, ch = x.y & 0xffu, end = pos + len;
+    if (!len) continue;
+    for (uint32_t w = (pos >> 2) + lane, w1 = (end - 1) >> 2; w <= w1; w += 64) {
+      const uint32_t s = 4 * w;
+      if (s >= pos && s + 4 <= end) *reinterpret_cast<uint32_t *>(row + s) = ch * 0x01010101u;
+      else for (uint32_t b = s; b < s + 4; b++) if (b >= pos && b < end) row[b] = (uint8_t)ch;
+    }
+  }
+}
+
+// uvaia_clust_rows: row k of dst = row ord[k] of the store (whole pitch, 16 bytes per thread)
+__global__ __launch_bounds__(256) void clust_gather_rows_kernel(const uint8_t *__restrict__ rows, size_t pitch, const int *__restrict__ ord, uint8_t *__restrict__ dst)
+{
+  const uint4 *s = reinterpret_cast<const uint4 *>(rows + (size_t)ord[blockIdx.x] * pitch);
+  uint4 *d = reinterpret_cast<uint4 *>(dst + (size_t)blockIdx.x * pitch);
+  for (int k = threadIdx.x; k < (int)(pitch / 16); k += 256) d[k] = s[k];
+}
+
 thread_local std::string g_open_error;
 
 }  // namespace
@@ -259,13 +353,17 @@ struct uvaia_clust_ctx {
   uint8_t *d_ref = nullptr, *d_rows = nullptr;
   int *d_dist = nullptr, *d_p = nullptr, *d_join = nullptr, *d_bad = nullptr;
   int *d_qoff = nullptr, *d_qlist = nullptr, *d_mcount = nullptr, *d_mord = nullptr, *d_mst = nullptr;
-  size_t rows_cap = 0, qlist_cap = 0;
+  uint8_t *d_tiles = nullptr, *d_gather = nullptr;      // packed pushes: the tiles of a push; uvaia_clust_rows: the gathered rows
+  uint32_t *d_xoff = nullptr; uint2 *d_xrec = nullptr;  // packed pushes: record offsets per row of the push, and the records
+  int *d_gord = nullptr;
+  size_t rows_cap = 0, qlist_cap = 0, tiles_cap = 0, xoff_cap = 0, xrec_cap = 0, gather_cap = 0, gord_cap = 0;
   int m_cap = 0;
   long long pushed = 0;
   std::vector<long long> per_queue;        // rows pushed to each queue so far (bounds its medoid count)
   std::vector<int> queue_of;               // queue of every pushed row
   std::vector<uint8_t> h_rows;
-  double prep_ms = 0, queue_ms = 0, merge_ms = 0;
+  std::vector<uint32_t> h_xoff;
+  double prep_ms = 0, queue_ms = 0, merge_ms = 0, decode_ms = 0, overlay_ms = 0;
   bool finished = false, broken = false;
   // after finish: clusters in the final order
   std::vector<long long> r_medoid, r_offsets, r_members;
@@ -331,6 +429,92 @@ int ensure_medoids(uvaia_clust_ctx *c, long long need)
   return 0;
 }
 
+struct uvdb_like_exc { uint32_t pos, len_char; };   // an exception record as a packed database file holds it (host/uvdb.h)
+
+// a device scratch array of at least `want` bytes; its contents are not kept
+int ensure_bytes(uvaia_clust_ctx *c, void **ptr, size_t *cap, size_t want)
+{
+  if (want <= *cap) return 0;
+  CCHK(c, hipStreamSynchronize(c->stream));
+  if (*ptr) hipFree(*ptr);
+  *ptr = nullptr; *cap = 0;
+  CCHK(c, hipMalloc(ptr, want));
+  *cap = want;
+  return 0;
+}
+
+// what both kinds of push check first
+int push_check(uvaia_clust_ctx *c, int n, bool have_data, const int *queue)
+{
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "push after finish");
+  if (n < 0 || (n && (!have_data || !queue))) return cfail(c, UVAIA_GPU_EINVAL, "bad push arguments");
+  if (c->pushed + n > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences", INT_MAX / 2);
+  for (int i = 0; i < n; i++)
+    if (queue[i] < 0 || queue[i] >= c->n_queues) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: queue %d out of range [0, %d)", i, queue[i], c->n_queues);
+  return 0;
+}
+
+// per-queue lists of the push's ordinals (first .. first + n), in push order, and room for the medoids they may found
+int push_lists(uvaia_clust_ctx *c, long long first, int n, const int *queue)
+{
+  const int big = INT_MAX;
+  CCHK(c, hipMemcpyAsync(c->d_bad, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  std::vector<int> qoff((size_t)c->n_queues + 1, 0), qlist((size_t)n);
+  for (int i = 0; i < n; i++) qoff[(size_t)queue[i] + 1]++;
+  for (int q = 0; q < c->n_queues; q++) qoff[(size_t)q + 1] += qoff[(size_t)q];
+  { std::vector<int> fill(qoff.begin(), qoff.end() - 1); for (int i = 0; i < n; i++) qlist[(size_t)fill[(size_t)queue[i]]++] = (int)(first + i); }
+  long long busiest = 0;
+  for (int i = 0; i < n; i++) busiest = std::max(busiest, ++c->per_queue[(size_t)queue[i]]);
+  c->queue_of.insert(c->queue_of.end(), queue, queue + n);
+  if (int rc = ensure_medoids(c, busiest)) return rc;
+  if ((size_t)n > c->qlist_cap) {
+    hipFree(c->d_qlist); c->d_qlist = nullptr; c->qlist_cap = 0;
+    CCHK(c, hipMalloc(&c->d_qlist, (size_t)n * sizeof(int)));
+    c->qlist_cap = (size_t)n;
+  }
+  CCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  CCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));            // qoff and qlist leave scope
+  return 0;
+}
+
+// prep and phase 2 for the rows first .. first + n of the store; seq (nullable): their text on the host, for the message about a bad byte
+int push_kernels(uvaia_clust_ctx *c, long long first, int n, const char *const *seq)
+{
+  const int big = INT_MAX;
+  float ms = 0;
+  CCHK(c, hipEventRecord(c->ev_a, c->stream));
+  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, first, n, c->d_ref,
+                     c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipEventRecord(c->ev_b, c->stream));
+  CCHK(c, hipEventSynchronize(c->ev_b));
+  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  c->prep_ms += ms;
+  int bad = big;
+  CCHK(c, hipMemcpy(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad != big) {
+    c->broken = true;
+    for (int k = 0; seq && k < c->nchar; k++) {
+      const unsigned char b = (unsigned char)seq[bad][k];
+      if (b == 0 || b >= 0x80) return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds byte 0x%02x at site %d: only bytes 1-127 are defined", first + bad, b, k);
+    }
+    return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds a byte 0 or >= 0x80", first + bad);
+  }
+
+  CCHK(c, hipEventRecord(c->ev_a, c->stream));
+  hipLaunchKernelGGL(clust_queue_kernel, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar, c->trim, c->dist, c->n_score,
+                     c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipEventRecord(c->ev_b, c->stream));
+  CCHK(c, hipEventSynchronize(c->ev_b));
+  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  c->queue_ms += ms;
+  c->pushed += n;
+  return 0;
+}
+
 struct Clust {
   int ord;                          // push ordinal of the medoid
   int stored;                       // score[0] as the reference leaves it
@@ -361,6 +545,7 @@ void uvaia_clust_close(uvaia_clust_ctx *c)
   if (c->stream) hipStreamSynchronize(c->stream);
   hipFree(c->d_ref); hipFree(c->d_rows); hipFree(c->d_dist); hipFree(c->d_p); hipFree(c->d_join); hipFree(c->d_bad);
   hipFree(c->d_qoff); hipFree(c->d_qlist); hipFree(c->d_mcount); hipFree(c->d_mord); hipFree(c->d_mst);
+  hipFree(c->d_tiles); hipFree(c->d_gather); hipFree(c->d_xoff); hipFree(c->d_xrec); hipFree(c->d_gord);
   if (c->ev_a) hipEventDestroy(c->ev_a);
   if (c->ev_b) hipEventDestroy(c->ev_b);
   if (c->stream) hipStreamDestroy(c->stream);
@@ -408,15 +593,9 @@ int uvaia_clust_open(uvaia_clust_ctx **out, int device, const char *reference, i
 int uvaia_clust_push(uvaia_clust_ctx *c, int n, const char *const *seq, const int *queue)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
-  if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "push after finish");
-  if (n < 0 || (n && (!seq || !queue))) return cfail(c, UVAIA_GPU_EINVAL, "bad push arguments");
+  if (int rc = push_check(c, n, seq != nullptr, queue)) return rc;
   if (!n) return 0;
-  if (c->pushed + n > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences", INT_MAX / 2);
-  for (int i = 0; i < n; i++) {
-    if (queue[i] < 0 || queue[i] >= c->n_queues) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: queue %d out of range [0, %d)", i, queue[i], c->n_queues);
-    if (!seq[i]) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push is null", i);
-  }
+  for (int i = 0; i < n; i++) if (!seq[i]) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push is null", i);
   hipSetDevice(c->device);
   int rc;
   if ((rc = ensure_rows(c, (size_t)c->pushed + n))) return rc;
@@ -425,54 +604,106 @@ int uvaia_clust_push(uvaia_clust_ctx *c, int n, const char *const *seq, const in
   c->h_rows.assign((size_t)n * c->pitch, 0);
   for (int i = 0; i < n; i++) memcpy(c->h_rows.data() + (size_t)i * c->pitch, seq[i], (size_t)c->nchar);
   CCHK(c, hipMemcpyAsync(c->d_rows + (size_t)first * c->pitch, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
-  const int big = INT_MAX;
-  CCHK(c, hipMemcpyAsync(c->d_bad, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  // per-queue lists of this push's ordinals, in push order
-  std::vector<int> qoff((size_t)c->n_queues + 1, 0), qlist((size_t)n);
-  for (int i = 0; i < n; i++) qoff[(size_t)queue[i] + 1]++;
-  for (int q = 0; q < c->n_queues; q++) qoff[(size_t)q + 1] += qoff[(size_t)q];
-  { std::vector<int> fill(qoff.begin(), qoff.end() - 1); for (int i = 0; i < n; i++) qlist[(size_t)fill[(size_t)queue[i]]++] = (int)(first + i); }
-  long long busiest = 0;
-  for (int i = 0; i < n; i++) busiest = std::max(busiest, ++c->per_queue[(size_t)queue[i]]);
-  c->queue_of.insert(c->queue_of.end(), queue, queue + n);
-  if ((rc = ensure_medoids(c, busiest))) return rc;
-  if ((size_t)n > c->qlist_cap) {
-    hipFree(c->d_qlist); c->d_qlist = nullptr; c->qlist_cap = 0;
-    CCHK(c, hipMalloc(&c->d_qlist, (size_t)n * sizeof(int)));
-    c->qlist_cap = (size_t)n;
-  }
-  CCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  CCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if ((rc = push_lists(c, first, n, queue))) return rc;
+  return push_kernels(c, first, n, seq);
+}
 
+int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const uint64_t *exc_offsets, const void *exc, const int *queue)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (int rc = push_check(c, n, planes != nullptr, queue)) return rc;
+  if (!n) return 0;
+  // the exception records, from the caller's arrays (a file mapping) as they are about to be copied: nothing of a bad record reaches the device
+  const uvdb_like_exc *rec = reinterpret_cast<const uvdb_like_exc *>(exc);
+  const uint64_t x0 = exc_offsets ? exc_offsets[0] : 0, x1 = exc_offsets ? exc_offsets[n] : 0;
+  if (exc_offsets) {
+    for (int i = 0; i < n; i++) if (exc_offsets[i + 1] < exc_offsets[i]) return cfail(c, UVAIA_GPU_EINVAL, "exc_offsets[%d] decreases", i + 1);
+    if (x1 - x0 > (uint64_t)INT_MAX) return cfail(c, UVAIA_GPU_EINVAL, "%llu exception records in one push", (unsigned long long)(x1 - x0));
+    if (x1 > x0 && !rec) return cfail(c, UVAIA_GPU_EINVAL, "null exception records");
+    for (int i = 0; i < n; i++) {
+      uint64_t at = 0;                                 // end of the row's previous run
+      for (uint64_t e = exc_offsets[i]; e < exc_offsets[i + 1]; e++) {
+        const uint64_t pos = rec[e].pos, len = rec[e].len_char >> 8;
+        const unsigned ch = rec[e].len_char & 0xffu;
+        if (ch != '-' && ch != '?' && ch != 'X' && ch != 'O' && ch != '.')
+          return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: exception record %llu holds character 0x%02x (only - ? X O . are exceptions)", i, (unsigned long long)(e - exc_offsets[i]), ch);
+        if (pos + len > (uint64_t)c->nchar)
+          return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: exception run of %llu sites at site %llu ends beyond the %d sites of a row", i, (unsigned long long)len, (unsigned long long)pos, c->nchar);
+        if (pos < at) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push: exception runs overlap or are out of order at site %llu", i, (unsigned long long)pos);
+        at = pos + len;
+      }
+    }
+  }
+  hipSetDevice(c->device);
+  int rc;
+  if ((rc = ensure_rows(c, (size_t)c->pushed + n))) return rc;
+  const long long first = c->pushed;
+  const int W4 = ((c->nchar + 31) / 32 + 3) / 4, n_tiles = (n + 63) / 64;
+  const size_t tile_bytes = (size_t)W4 * 4 * 64 * 16, n_rec = (size_t)(x1 - x0);
+  if ((rc = ensure_bytes(c, (void **)&c->d_tiles, &c->tiles_cap, (size_t)n_tiles * tile_bytes))) return rc;
+  if ((rc = ensure_bytes(c, (void **)&c->d_xoff, &c->xoff_cap, ((size_t)n + 1) * sizeof(uint32_t)))) return rc;
+  if (n_rec && (rc = ensure_bytes(c, (void **)&c->d_xrec, &c->xrec_cap, n_rec * sizeof(uint2)))) return rc;
+  CCHK(c, hipMemcpyAsync(c->d_tiles, planes, (size_t)n_tiles * tile_bytes, hipMemcpyHostToDevice, c->stream));
+  if (n_rec) {
+    c->h_xoff.resize((size_t)n + 1);
+    for (int i = 0; i <= n; i++) c->h_xoff[(size_t)i] = (uint32_t)(exc_offsets[i] - x0);
+    CCHK(c, hipMemcpyAsync(c->d_xoff, c->h_xoff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    CCHK(c, hipMemcpyAsync(c->d_xrec, rec + x0, n_rec * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+  }
+  uint8_t *dst = c->d_rows + (size_t)first * c->pitch;
+  const int units = (W4 + UGROUPS - 1) / UGROUPS;
   float ms = 0;
   CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, first, n, c->d_ref,
-                     c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
+  hipLaunchKernelGGL(clust_unpack_tiles_kernel, dim3((unsigned)(n_tiles * units)), dim3(UTPB), 0, c->stream, reinterpret_cast<const uint4 *>(c->d_tiles), W4, c->nchar, n, dst,
+                     c->pitch, units);
   CCHK(c, hipGetLastError());
   CCHK(c, hipEventRecord(c->ev_b, c->stream));
   CCHK(c, hipEventSynchronize(c->ev_b));
   CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->prep_ms += ms;
-  int bad = big;
-  CCHK(c, hipMemcpy(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost));
-  if (bad != big) {
-    c->broken = true;
-    for (int k = 0; k < c->nchar; k++) {
-      const unsigned char b = (unsigned char)seq[bad][k];
-      if (b == 0 || b >= 0x80) return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds byte 0x%02x at site %d: only bytes 1-127 are defined", first + bad, b, k);
-    }
-    return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds a byte 0 or >= 0x80", first + bad);
+  c->decode_ms += ms;
+  if (n_rec) {
+    CCHK(c, hipEventRecord(c->ev_a, c->stream));
+    hipLaunchKernelGGL(clust_overlay_runs_kernel, dim3((unsigned)n), dim3(OTPB), 0, c->stream, dst, c->pitch, c->d_xoff, c->d_xrec);
+    CCHK(c, hipGetLastError());
+    CCHK(c, hipEventRecord(c->ev_b, c->stream));
+    CCHK(c, hipEventSynchronize(c->ev_b));
+    CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+    c->overlay_ms += ms;
   }
+  if ((rc = push_lists(c, first, n, queue))) return rc;
+  return push_kernels(c, first, n, nullptr);
+}
 
-  CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_queue_kernel, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar, c->trim, c->dist, c->n_score,
-                     c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+int uvaia_clust_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (n < 0 || (n && (!ordinal || !rows))) return cfail(c, UVAIA_GPU_EINVAL, "bad arguments");
+  if (n && pitch < (size_t)c->nchar) return cfail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
+  if (!n) return 0;
+  std::vector<int> ord((size_t)n);
+  for (int k = 0; k < n; k++) {
+    if (ordinal[k] < 0 || ordinal[k] >= c->pushed) return cfail(c, UVAIA_GPU_EINVAL, "ordinal[%d] = %lld: %lld sequences were pushed", k, (long long)ordinal[k], c->pushed);
+    ord[(size_t)k] = (int)ordinal[k];
+  }
+  hipSetDevice(c->device);
+  int rc;
+  if ((rc = ensure_bytes(c, (void **)&c->d_gord, &c->gord_cap, (size_t)n * sizeof(int)))) return rc;
+  if ((rc = ensure_bytes(c, (void **)&c->d_gather, &c->gather_cap, (size_t)n * c->pitch))) return rc;
+  CCHK(c, hipMemcpyAsync(c->d_gord, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(clust_gather_rows_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, c->d_rows, c->pitch, c->d_gord, c->d_gather);
   CCHK(c, hipGetLastError());
-  CCHK(c, hipEventRecord(c->ev_b, c->stream));
-  CCHK(c, hipEventSynchronize(c->ev_b));
-  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->queue_ms += ms;
-  c->pushed += n;
+  CCHK(c, hipMemcpy2DAsync(rows, pitch, c->d_gather, c->pitch, (size_t)c->nchar, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int uvaia_clust_device_rows(uvaia_clust_ctx *c, const void **d_rows, size_t *pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (d_rows) *d_rows = c->d_rows;
+  if (pitch) *pitch = c->pitch;
   return 0;
 }
 
@@ -622,6 +853,14 @@ int uvaia_clust_stats(uvaia_clust_ctx *c, double *prep_ms, double *queue_ms, dou
   if (queue_ms) *queue_ms = c->queue_ms;
   if (merge_ms) *merge_ms = c->merge_ms;
   if (pushed) *pushed = c->pushed;
+  return 0;
+}
+
+int uvaia_clust_unpack_ms(uvaia_clust_ctx *c, double *decode_ms, double *overlay_ms)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (decode_ms) *decode_ms = c->decode_ms;
+  if (overlay_ms) *overlay_ms = c->overlay_ms;
   return 0;
 }
 

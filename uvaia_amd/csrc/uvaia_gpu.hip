@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/uvaia_gpu.h"
+#include "iupac_decode.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // small helpers
