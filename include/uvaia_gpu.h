@@ -348,6 +348,37 @@ int    uvaia_gpu_db_side_row_ints (void);
 int    uvaia_gpu_db_export (uvaia_gpu_ctx *ctx, size_t first_tile, size_t n_tiles, void *planes, int *non_n, int *side_rows);
 int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const int *non_n, const int *side_rows, int n_ref);
 
+/* ---- windowed search: a packed database larger than device memory (`uvaia --packed --window`).  Replaces, like the resident search, the
+ * read/filter/fill loop of src/nearest.c:251-286 and the batch loop :288-306 -- for a file of which only a window of references is
+ * resident at a time.  The machine is a serial walk over the stream whose state (heaps, tolerances) stays in the context, so the caller
+ * walks the windows in stream order:
+ *     stage_reserve (tiles of the largest span);  stage_packed (slot 0, first span)
+ *     per window w:  load_staged (slot w % 2, sel, n);  search_resident (pool, ordinal0 = stream position of the window's first reference,
+ *                    NULL);  stage_packed (slot (w + 1) % 2, next span);  sync;  entered_flags;  db_unpack_rows of those that entered
+ * with windows that are a multiple of the pool (and of 64), so that the pools -- where the snapshot of the tolerances is retaken,
+ * src/nearest.c:290-291 -- are the ones a search of the whole stream cuts.  Plain contexts only: a context of a reference shard gets
+ * UVAIA_GPU_ESTATE, as from the other resident entries.
+ *   stage_reserve  room for n_tiles whole tiles (planes, valid-site counts, side rows) in each of the two staging slots
+ *   stage_packed   asynchronous copy of n_tiles whole file tiles (the arrays of uvaia_gpu_db_append_packed) into slot 0 or 1, on a copy
+ *                  stream of the context's own: the bytes of the next window cross the bus while the current one is searched.  The
+ *                  host arrays must stay as they are until the slot has been loaded.
+ *   load_staged    waits for the slot's copy, empties the resident database (as uvaia_gpu_db_clear) and fills it with references
+ *                  sel[0 .. n_ref) of the slot, in that order: sel[k] is a position within the slot (0 .. 64 * n_tiles - 1), NULL = positions
+ *                  0 .. n_ref - 1.  Totals, the checks on side rows and counts and the planes derived for the query set are made as
+ *                  uvaia_gpu_db_append_packed makes them.  A bad sel entry is refused with UVAIA_GPU_EINVAL before anything is
+ *                  launched and leaves the database as it was.  Afterwards uvaia_gpu_db_size() is n_ref; heaps and tolerances are
+ *                  not touched.  Returns when the window is complete.
+ *   db_unpack_rows the contract of uvaia_gpu_unpack_rows for positions of the window loaded last, in default-mode and --acgt contexts
+ *                  (the latter keep a four-plane image of the window for it).
+ *   window_ms      device time in ms since the last reset of [0] the selection, [1] totals, checks and derived planes after it, [2] the decode
+ *   free_bytes     free memory of the context's device as the runtime reports it (0: the runtime could not tell) */
+int uvaia_gpu_db_stage_reserve (uvaia_gpu_ctx *ctx, size_t n_tiles);
+int uvaia_gpu_db_stage_packed (uvaia_gpu_ctx *ctx, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles);
+int uvaia_gpu_db_load_staged (uvaia_gpu_ctx *ctx, int slot, const int *sel, int n_ref);
+int uvaia_gpu_db_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
+void uvaia_gpu_window_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
+size_t uvaia_gpu_free_bytes (uvaia_gpu_ctx *ctx);
+
 /* ---- rows that are already in device memory (what the aligner leaves behind, include/uvaia_align.h; a tensor of the caller): into the
  * resident database and a packed database file without a round trip of their text.  A block is n rows of nchar bytes, `pitch` bytes apart
  * (pitch >= nchar; neither the pitch nor the first row need any alignment).  Every d_rows below must be memory of the context's device: the

@@ -29,6 +29,7 @@ SYMBOLS = [
     "uvaia_gpu_group_db_reserve", "uvaia_gpu_group_db_append", "uvaia_gpu_group_db_append_packed", "uvaia_gpu_group_db_clear", "uvaia_gpu_group_db_rederive",
     "uvaia_gpu_group_db_size", "uvaia_gpu_group_reset", "uvaia_gpu_group_search_resident", "uvaia_gpu_group_push", "uvaia_gpu_group_drain", "uvaia_gpu_group_sync",
     "uvaia_gpu_rows_census", "uvaia_gpu_db_append_device", "uvaia_gpu_rows_exceptions", "uvaia_gpu_db_drop_tiles", "uvaia_gpu_rows_kernel_ms", "uvaia_gpu_rows_set_run_cut",
+    "uvaia_gpu_db_stage_reserve", "uvaia_gpu_db_stage_packed", "uvaia_gpu_db_load_staged", "uvaia_gpu_db_unpack_rows", "uvaia_gpu_window_ms", "uvaia_gpu_free_bytes",
 ]
 
 
@@ -186,6 +187,12 @@ def load_library():
         "uvaia_gpu_db_drop_tiles": (C.c_int, [vp, C.c_size_t]),
         "uvaia_gpu_rows_kernel_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_rows_set_run_cut": (C.c_int, [vp, C.c_uint]),
+        "uvaia_gpu_db_stage_reserve": (C.c_int, [vp, C.c_size_t]),
+        "uvaia_gpu_db_stage_packed": (C.c_int, [vp, C.c_int, C.c_void_p, pi, pi, C.c_int]),
+        "uvaia_gpu_db_load_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
+        "uvaia_gpu_db_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
+        "uvaia_gpu_window_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -563,6 +570,46 @@ class Engine:
         rows = np.zeros((max(len(idx), 1), pitch), dtype=np.uint8)
         self._chk(self.L.uvaia_gpu_unpack_rows(self.ctx, idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
         return [rows[k, :self.nchar].tobytes() for k in range(len(idx))]
+
+    # ---- windowed search over a packed database (see include/uvaia_gpu.h)
+    def db_stage_reserve(self, n_tiles):
+        self._chk(self.L.uvaia_gpu_db_stage_reserve(self.ctx, int(n_tiles)))
+
+    def db_stage_packed(self, slot, planes, non_n, side_rows, n_tiles):
+        """asynchronous copy of n_tiles whole tiles into staging slot 0 or 1; the arrays are kept alive until the slot is staged again"""
+        planes = np.ascontiguousarray(planes, dtype=np.uint8)
+        non_n = np.ascontiguousarray(non_n, dtype=np.int32)
+        side_rows = np.ascontiguousarray(side_rows, dtype=np.int32)
+        tb = self.L.uvaia_gpu_db_tile_bytes(self.ctx)
+        if planes.size < int(n_tiles) * tb or non_n.size < int(n_tiles) * 64 or side_rows.size < int(n_tiles) * 64 * self.L.uvaia_gpu_db_side_row_ints():
+            raise ValueError("arrays shorter than %d tiles" % n_tiles)
+        if not hasattr(self, "_staged"):
+            self._staged = {}
+        self._staged[int(slot)] = (planes, non_n, side_rows)
+        self._chk(self.L.uvaia_gpu_db_stage_packed(self.ctx, int(slot), planes.ctypes.data, non_n.ctypes.data_as(C.POINTER(C.c_int)),
+                                                   side_rows.ctypes.data_as(C.POINTER(C.c_int)), int(n_tiles)))
+
+    def db_load_staged(self, slot, sel, n_ref):
+        """the resident database becomes references sel[0 .. n_ref) of the slot (None: the first n_ref)"""
+        _k, sp = _int_ptr(sel)
+        self._chk(self.L.uvaia_gpu_db_load_staged(self.ctx, int(slot), sp, int(n_ref)))
+
+    def db_unpack_rows(self, index, pitch=None):
+        """Upper-case text of references index[] of the window loaded last, as a list of bytes (exception runs not applied)."""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        pitch = (self.nchar + 15) // 16 * 16 if pitch is None else int(pitch)
+        rows = np.zeros((max(len(idx), 1), pitch), dtype=np.uint8)
+        self._chk(self.L.uvaia_gpu_db_unpack_rows(self.ctx, idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
+        return [rows[k, :self.nchar].tobytes() for k in range(len(idx))]
+
+    def window_ms(self, reset=False):
+        """Device ms since the last reset of (selection, totals + checks + derived planes after it, decode)."""
+        out = (C.c_double * 3)()
+        self.L.uvaia_gpu_window_ms(self.ctx, out, int(reset))
+        return tuple(out)
+
+    def free_bytes(self):
+        return int(self.L.uvaia_gpu_free_bytes(self.ctx))
 
     def ball_asked(self, reset=False):
         return int(self.L.uvaia_gpu_ball_asked(self.ctx, int(reset)))

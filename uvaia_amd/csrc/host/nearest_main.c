@@ -7,14 +7,17 @@
 #include <getopt.h>
 #include <libgen.h>
 #include <omp.h>
+#include <time.h>
 
 #include "cli_common.h"
 #include "gpu_glue.h"
 #include "prepare.h"
 #include "uvdb.h"
+#include "uvdb_window.h"
 
 typedef struct {
   int help, version, acgt, keep_resolved, exclude_self, nbest, trim, pool, threads, threads_given, device, devices[64], n_devices;
+  long long window; int window_given, window_report;
   double ambig_q, ambig_r;
   const char *out, *query, *packed;
   const char **ref; int n_ref;
@@ -39,6 +42,8 @@ usage (const char *prog, int long_help)
   printf ("  -p, --pool=<int>                 Pool size, i.e. how many reference seqs are sent to the GPU per batch (defaults to 64 per host thread; larger is faster)\n");
   printf ("  -r, --reference=<ref.fa(.gz,.xz)> aligned reference sequences (can be several files)\n");
   printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): loaded as it is, no text parsing\n");
+  printf ("  --window=<refs>                  with --packed: keep only this many references on the GPU at a time (rounded up to whole pools and tiles\n                                   of 64), for a database larger than GPU memory; chosen automatically when the database does not fit\n");
+  printf ("  --window-report                  with --packed: one line on stderr with the GPU's free memory before and after and the time of the window steps\n");
   printf ("  <seqs.fa(.gz,.xz)>               aligned query sequences\n");
   printf ("  -t, --nthreads=<int>             suggested number of host threads (only sets the default pool size here)\n");
   printf ("  -o, --output=<without suffix>    prefix of xzipped output alignment and table with nearest neighbour sequences\n");
@@ -67,7 +72,8 @@ parse_options (int argc, char **argv)
     {"keep_resolved", no_argument, 0, 'k'}, {"exclude_self", no_argument, 0, 'x'}, {"nbest", required_argument, 0, 'n'},
     {"trim", required_argument, 0, 1001}, {"query_ambiguity", required_argument, 0, 'a'}, {"ref_ambiguity", required_argument, 0, 'A'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"packed", required_argument, 0, 1003}, {"devices", required_argument, 0, 1004}, {0, 0, 0, 0}};
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"packed", required_argument, 0, 1003}, {"devices", required_argument, 0, 1004},
+    {"window", required_argument, 0, 1005}, {"window-report", no_argument, 0, 1006}, {0, 0, 0, 0}};
   int ch, errors = 0;
   while ((ch = getopt_long (argc, argv, "hvkxn:a:A:p:r:t:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': o.help = 1; break;
@@ -86,6 +92,8 @@ parse_options (int argc, char **argv)
     case 1002: o.device = atoi (optarg); break;
     case 1004: o.n_devices = uvaia_parse_device_list (optarg, o.devices, 64); if (!o.n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); exit (EXIT_FAILURE); } break;
     case 1003: o.packed = optarg; break;
+    case 1005: o.window = atoll (optarg); o.window_given = 1; break;
+    case 1006: o.window_report = 1; break;
     default: errors++;
   }
   if (optind < argc) o.query = argv[optind++];
@@ -97,7 +105,87 @@ parse_options (int argc, char **argv)
     usage (basename (argv[0]), 0);
     exit (EXIT_FAILURE);
   }
+  /* --window: refused here, before anything touches a GPU */
+  if (o.window_given && !o.packed) { fprintf (stderr, "--window needs --packed: only a packed database is searched a window at a time\n"); exit (EXIT_FAILURE); }
+  if (o.window_given && o.window < 1) { fprintf (stderr, "--window: expected a positive number of references\n"); exit (EXIT_FAILURE); }
+  if (o.window_given && o.n_devices > 1) { fprintf (stderr, "--window works on one GPU: give --device, not a --devices list of several\n"); exit (EXIT_FAILURE); }
   return o;
+}
+
+static double
+wall_ms (void)
+{
+  struct timespec ts;
+  clock_gettime (CLOCK_MONOTONIC, &ts);
+  return (double) ts.tv_sec * 1e3 + (double) ts.tv_nsec * 1e-6;
+}
+
+/* The windowed search over a packed database (include/uvaia_gpu.h, "windowed search"): stands where the resident search replaces the
+ * loops of src/nearest.c:251-306, for a file of which `window` references are on the GPU at a time.  The next window's tiles are handed to
+ * the copy stream while the current one is searched; what entered a heap is decoded on the GPU.  Host memory: one window of flags and of
+ * selection entries and 256 rows of text, whatever the size of the file.  Returns the number of sequences written. */
+static int
+search_windowed (uvaia_gpu_ctx *gpu, uvdb_reader db, const uint64_t *keep, uint64_t n, uint64_t window, uint64_t n_windows, size_t pool, int nchar,
+                 file_compress_t outstream, name_table *names, double upload_ms[3])
+{
+  enum { ROUND = 256 };
+  const uint64_t wmax = window < n ? window : n;
+  const size_t pitch = ((size_t) nchar + 15) / 16 * 16;
+  uint64_t max_tiles = 1;
+  for (uint64_t w = 0; w < n_windows; w++) {
+    uint64_t t0, nt;
+    const uint64_t a = w * window, b = (a + window < n) ? a + window : n;
+    if (uvdb_window_span (keep, a, b, &t0, &nt, NULL)) biomcmc_error ("--window: the window at reference %llu spans more file tiles than the engine counts", (unsigned long long) a);
+    if (nt > max_tiles) max_tiles = nt;
+  }
+  if (uvaia_gpu_db_reserve (gpu, (size_t) (wmax ? wmax : 1)) || uvaia_gpu_db_stage_reserve (gpu, (size_t) max_tiles)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  int *sel = keep ? (int *) biomcmc_malloc ((size_t) (wmax ? wmax : 1) * sizeof (int)) : NULL, index[ROUND], n_output = 0;
+  uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (wmax ? wmax : 1));
+  char *rows = (char *) biomcmc_malloc (ROUND * pitch + 1);
+  uint64_t t0 = 0, nt = 0;
+  upload_ms[0] = upload_ms[1] = upload_ms[2] = 0.;
+#define STAGE(w_) do { const uint64_t a_ = (w_) * window, b_ = (a_ + window < n) ? a_ + window : n; \
+    uvdb_window_span (keep, a_, b_, &t0, &nt, NULL); \
+    if (uvaia_gpu_db_stage_packed (gpu, (int) ((w_) & 1), uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) nt)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu)); } while (0)
+  double t = wall_ms ();
+  if (n_windows) STAGE ((uint64_t) 0);
+  upload_ms[0] = upload_ms[1] = wall_ms () - t;           /* the first window's upload has nothing to hide behind */
+  for (uint64_t w = 0; w < n_windows; w++) {
+    const uint64_t a = w * window, b = (a + window < n) ? a + window : n;
+    if (keep) uvdb_window_span (keep, a, b, &t0, &nt, sel);
+    if (uvaia_gpu_db_load_staged (gpu, (int) (w & 1), sel, (int) (b - a))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    if (uvaia_gpu_search_resident (gpu, pool, (int64_t) a, NULL)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    if (w + 1 < n_windows) {                              /* the search runs: the next window's tiles cross the bus next to it */
+      t = wall_ms ();
+      STAGE (w + 1);
+      const double up = wall_ms () - t;
+      t = wall_ms ();
+      if (uvaia_gpu_sync (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+      upload_ms[0] += up;
+      if (wall_ms () - t < 0.01 * up) upload_ms[1] += up;   /* the search had ended before the upload: counted as not hidden at all */
+    } else if (uvaia_gpu_sync (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    if (uvaia_gpu_entered_flags (gpu, ent, 0)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    for (uint64_t k = 0; k < b - a;) {                    /* dump every sequence that entered some heap, in stream order */
+      int m = 0;
+      for (; k < b - a && m < ROUND; k++) if (ent[k]) index[m++] = (int) k;
+      if (!m) break;
+      if (uvaia_gpu_db_unpack_rows (gpu, index, m, rows, pitch)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+      for (int j = 0; j < m; j++) {
+        const uint64_t i = a + (uint64_t) index[j], r = keep ? keep[i] : i;
+        char *row = rows + (size_t) j * pitch, after = row[nchar];
+        uvdb_apply_exceptions (db, r, row);
+        row[nchar] = '\0';
+        write_fasta_record (outstream, uvdb_name (db, r), row);
+        row[nchar] = after;
+        name_table_set (names, (int64_t) i, uvdb_name (db, r));
+        n_output++;
+      }
+    }
+  }
+#undef STAGE
+  upload_ms[2] = upload_ms[0] > 0. ? 1. - upload_ms[1] / upload_ms[0] : 0.;
+  free (rows); free (ent); free (sel);
+  return n_output;
 }
 
 static void
@@ -205,46 +293,75 @@ main (int argc, char **argv)
       for (uint64_t i = 0; i < n_all; i++) { if (lookup_hashtable (query->aln->taxlabel_hash, (char *) uvdb_name (db, i)) > -1) same_name++; else keep[n++] = i; }
       if (n == n_all) { free (keep); keep = NULL; }
     }
-    if (uvaia_gpu_group_db_reserve (grp, (size_t) (n ? n : 1))) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-    if (!keep) {
-      for (uint64_t t = 0; t < db->h.n_tiles; t += chunk_tiles) {
-        const uint64_t nt = (db->h.n_tiles - t < chunk_tiles) ? db->h.n_tiles - t : chunk_tiles;
-        const uint64_t first = t * 64, cnt = (first + nt * 64 > n) ? n - first : nt * 64;
-        if (uvaia_gpu_group_db_append_packed (grp, uvdb_tile_planes (db, t), db->non_n + first, uvdb_tile_side_rows (db, t), (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+    /* a window at a time (--window, or a database that does not fit the GPU's free memory), or resident as a whole */
+    uint64_t window = 0, n_windows = 0;
+    size_t mem_before = uvaia_gpu_free_bytes (gpu);
+    if (o.window_given) {
+      if (uvdb_window_plan (n, (uint64_t) o.pool, (uint64_t) o.window, &window, &n_windows)) biomcmc_error ("--window %lld with a pool of %d: the window is beyond what the engine counts", o.window, o.pool);
+    } else if (o.n_devices == 1 && mem_before) {
+      /* per resident reference: packed planes, the planes derived for the query set (with the valid-site plane the appends write), side
+         row, counts and flag; an --acgt context also keeps the four-plane image of a window */
+      const uint64_t bpr = uvaia_gpu_packed_bytes_per_ref (gpu) + uvaia_gpu_derived_bytes_per_ref (gpu) + uvaia_gpu_db_tile_bytes (gpu) / 256
+                         + (uint64_t) uvaia_gpu_db_side_row_ints () * 4 + 20 + (o.acgt ? uvaia_gpu_db_tile_bytes (gpu) / 64 : 0);
+      const int64_t w = uvdb_window_choose (n, (uint64_t) o.pool, bpr, (uint64_t) mem_before);
+      if (w < 0) biomcmc_error ("packed database %s: not even one window of %d references (%llu bytes each, and two staging slots) fits the %zu free bytes of the GPU; try a smaller --pool", o.packed, o.pool, (unsigned long long) bpr, mem_before);
+      if (w > 0 && uvdb_window_plan (n, (uint64_t) o.pool, (uint64_t) w, &window, &n_windows)) biomcmc_error ("packed database %s: no window plan for %lld references", o.packed, (long long) w);
+      if (w > 0) fprintf (stderr, "The packed database does not fit the free memory of the GPU: searching it in %llu windows of %llu sequences.\n", (unsigned long long) n_windows, (unsigned long long) window);
+    }
+    if (window) {
+      double upload_ms[3], part_ms[3] = {0., 0., 0.};
+      count = (int) n_all;
+      fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, o.packed, biomcmc_update_elapsed_time (time0));
+      n_output = search_windowed (gpu, db, keep, n, window, n_windows, (size_t) o.pool, query->aln->nchar, outstream, &names, upload_ms);
+      if (o.window_report) {
+        uvaia_gpu_window_ms (gpu, part_ms, 0);
+        fprintf (stderr, "window report: {\"window\": %llu, \"n_windows\": %llu, \"free_before\": %zu, \"free_after\": %zu, \"select_ms\": %.3f, \"derive_ms\": %.3f, \"decode_ms\": %.3f, \"upload_ms\": %.3f, \"upload_hidden_share\": %.3f}\n",
+                 (unsigned long long) window, (unsigned long long) n_windows, mem_before, uvaia_gpu_free_bytes (gpu), part_ms[0], part_ms[1], part_ms[2], upload_ms[0], upload_ms[2]);
       }
     } else {
-      const size_t tb = (size_t) db->h.tile_bytes, row = (size_t) db->h.side_row_ints, pieces = tb / (64 * 16);   /* 16-byte pieces per lane */
-      unsigned char *planes = (unsigned char *) biomcmc_malloc (chunk_tiles * tb);
-      int32_t *nn = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * sizeof (int32_t)), *side = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * row * sizeof (int32_t));
-      for (uint64_t s0 = 0; s0 < n; s0 += chunk_tiles * 64) {
-        const uint64_t cnt = (n - s0 < chunk_tiles * 64) ? n - s0 : chunk_tiles * 64;
-        memset (planes, 0, chunk_tiles * tb); memset (nn, 0, chunk_tiles * 64 * sizeof (int32_t)); memset (side, 0, chunk_tiles * 64 * row * sizeof (int32_t));
-#pragma omp parallel for schedule(static)
-        for (uint64_t k = 0; k < cnt; k++) {
-          const uint64_t r = keep[s0 + k];
-          const unsigned char *src = (const unsigned char *) uvdb_tile_planes (db, r / 64) + (r % 64) * 16;
-          unsigned char *dst = planes + (k / 64) * tb + (k % 64) * 16;
-          for (size_t p = 0; p < pieces; p++) memcpy (dst + p * 1024, src + p * 1024, 16);
-          nn[k] = db->non_n[r];
-          memcpy (side + k * row, uvdb_tile_side_rows (db, r / 64) + (r % 64) * row, row * sizeof (int32_t));
+      if (uvaia_gpu_group_db_reserve (grp, (size_t) (n ? n : 1))) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+      if (!keep) {
+        for (uint64_t t = 0; t < db->h.n_tiles; t += chunk_tiles) {
+          const uint64_t nt = (db->h.n_tiles - t < chunk_tiles) ? db->h.n_tiles - t : chunk_tiles;
+          const uint64_t first = t * 64, cnt = (first + nt * 64 > n) ? n - first : nt * 64;
+          if (uvaia_gpu_group_db_append_packed (grp, uvdb_tile_planes (db, t), db->non_n + first, uvdb_tile_side_rows (db, t), (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
         }
-        if (uvaia_gpu_group_db_append_packed (grp, planes, nn, side, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+      } else {
+        const size_t tb = (size_t) db->h.tile_bytes, row = (size_t) db->h.side_row_ints, pieces = tb / (64 * 16);   /* 16-byte pieces per lane */
+        unsigned char *planes = (unsigned char *) biomcmc_malloc (chunk_tiles * tb);
+        int32_t *nn = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * sizeof (int32_t)), *side = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * row * sizeof (int32_t));
+        for (uint64_t s0 = 0; s0 < n; s0 += chunk_tiles * 64) {
+          const uint64_t cnt = (n - s0 < chunk_tiles * 64) ? n - s0 : chunk_tiles * 64;
+          memset (planes, 0, chunk_tiles * tb); memset (nn, 0, chunk_tiles * 64 * sizeof (int32_t)); memset (side, 0, chunk_tiles * 64 * row * sizeof (int32_t));
+#pragma omp parallel for schedule(static)
+          for (uint64_t k = 0; k < cnt; k++) {
+            const uint64_t r = keep[s0 + k];
+            const unsigned char *src = (const unsigned char *) uvdb_tile_planes (db, r / 64) + (r % 64) * 16;
+            unsigned char *dst = planes + (k / 64) * tb + (k % 64) * 16;
+            for (size_t p = 0; p < pieces; p++) memcpy (dst + p * 1024, src + p * 1024, 16);
+            nn[k] = db->non_n[r];
+            memcpy (side + k * row, uvdb_tile_side_rows (db, r / 64) + (r % 64) * row, row * sizeof (int32_t));
+          }
+          if (uvaia_gpu_group_db_append_packed (grp, planes, nn, side, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+        }
+        free (planes); free (nn); free (side);
       }
-      free (planes); free (nn); free (side);
+      count = (int) n_all;
+      fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, o.packed, biomcmc_update_elapsed_time (time0));
+      uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1));
+      if (n && uvaia_gpu_group_search_resident (grp, (size_t) o.pool, 0, ent)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+      char *text = (char *) biomcmc_malloc ((size_t) query->aln->nchar + 1);
+      for (uint64_t i = 0; i < n; i++) if (ent[i]) {     /* dump every sequence that entered some heap, in stream order */
+        const uint64_t r = keep ? keep[i] : i;
+        n_output++;
+        uvdb_unpack_reference (db, r, text);
+        write_fasta_record (outstream, uvdb_name (db, r), text);
+        name_table_set (&names, (int64_t) i, uvdb_name (db, r));
+      }
+      free (text); free (ent);
+      if (o.window_report) fprintf (stderr, "window report: {\"window\": 0, \"n_windows\": 0, \"free_before\": %zu, \"free_after\": %zu}\n", mem_before, uvaia_gpu_free_bytes (gpu));
     }
-    count = (int) n_all;
-    fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, o.packed, biomcmc_update_elapsed_time (time0));
-    uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1));
-    if (n && uvaia_gpu_group_search_resident (grp, (size_t) o.pool, 0, ent)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-    char *text = (char *) biomcmc_malloc ((size_t) query->aln->nchar + 1);
-    for (uint64_t i = 0; i < n; i++) if (ent[i]) {     /* dump every sequence that entered some heap, in stream order */
-      const uint64_t r = keep ? keep[i] : i;
-      n_output++;
-      uvdb_unpack_reference (db, r, text);
-      write_fasta_record (outstream, uvdb_name (db, r), text);
-      name_table_set (&names, (int64_t) i, uvdb_name (db, r));
-    }
-    free (text); free (ent); free (keep);
+    free (keep);
     fprintf (stderr, "Total of %d sequences searched; %d saved sequences include closest neighbours and intermediate. %.3lf secs elapsed. \n", count, n_output, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
     uvdb_close_reader (db);

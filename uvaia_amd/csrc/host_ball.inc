@@ -158,15 +158,17 @@ int uvaia_gpu_ball_packed(uvaia_gpu_ctx *c, const void *planes, int n_ref, int r
   return 0;
 }
 
-// text of references index[0..n) of the last uvaia_gpu_ball_packed batch, rows + k * pitch; see unpack_rows_kernel
-int uvaia_gpu_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
+// text of references index[0..n) of `count` references held as four-plane tiles at `tiles`, rows + k * pitch; see unpack_rows_kernel.
+// what / first: how the two entries name the tiles in their error texts.  ev (nullable): two events that bracket every kernel launch
+// of the call, the elapsed time of each pair is added to *ms.
+static int unpack_rows_from(uvaia_gpu_ctx *c, const uint4 *tiles, int count, const char *what, const char *first, const int *index, int n, char *rows, size_t pitch,
+                            hipEvent_t *ev = nullptr, double *ms = nullptr)
 {
-  if (!c) return UVAIA_GPU_EINVAL;
   if (n < 0 || (n > 0 && (!index || !rows))) return fail(c, UVAIA_GPU_EINVAL, "bad selection");
   if (pitch < (size_t)c->nchar) return fail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
-  if (!c->pk_n) return fail(c, UVAIA_GPU_ESTATE, "no packed batch to unpack: uvaia_gpu_ball_packed comes first");
+  if (!count) return fail(c, UVAIA_GPU_ESTATE, "no %s to unpack: %s comes first", what, first);
   for (int k = 0; k < n; k++)
-    if (index[k] < 0 || index[k] >= c->pk_n) return fail(c, UVAIA_GPU_EINVAL, "index[%d] = %d lies outside the last packed batch of %d", k, index[k], c->pk_n);
+    if (index[k] < 0 || index[k] >= count) return fail(c, UVAIA_GPU_EINVAL, "index[%d] = %d lies outside the last %s of %d", k, index[k], what, count);
   if (n == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t dpitch = ((size_t)c->nchar + 15) / 16 * 16;
@@ -184,14 +186,24 @@ int uvaia_gpu_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows,
   for (size_t a = 0; a < (size_t)n; a += chunk) {
     const size_t m = std::min(chunk, (size_t)n - a);
     HIPCHK(c, hipMemcpyAsync(c->d_row_idx, index + a, m * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, c->d_pk, c->W4, c->nchar, c->d_row_idx, c->d_rows, dpitch);
+    if (ev) HIPCHK(c, hipEventRecord(ev[0], c->stream));
+    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)m), dim3(256), 0, c->stream, tiles, c->W4, c->nchar, c->d_row_idx, c->d_rows, dpitch);
     HIPCHK(c, hipGetLastError());
+    if (ev) HIPCHK(c, hipEventRecord(ev[1], c->stream));
     // one copy for all rows of the round: straight when the caller's rows have the staging pitch, strided otherwise
     if (pitch == dpitch) HIPCHK(c, hipMemcpyAsync(rows + a * pitch, c->d_rows, m * dpitch, hipMemcpyDeviceToHost, c->stream));
     else HIPCHK(c, hipMemcpy2DAsync(rows + a * pitch, pitch, c->d_rows, dpitch, (size_t)c->nchar, m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ev && ms) { float t = 0.f; if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) *ms += t; }
   }
   return 0;
+}
+
+// text of references index[0..n) of the last uvaia_gpu_ball_packed batch
+int uvaia_gpu_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  return unpack_rows_from(c, c->d_pk, c->pk_n, "packed batch", "uvaia_gpu_ball_packed", index, n, rows, pitch);
 }
 
 // references the last radius searches sent on to the queries (since the last call with reset != 0)

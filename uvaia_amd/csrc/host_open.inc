@@ -12,7 +12,7 @@ void uvaia_gpu_close(uvaia_gpu_ctx *c)
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
   for (hipEvent_t e : c->rows_evs) hipEventDestroy(e);
   void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga,
-                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc};
+                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc, c->d_wsel, c->d_win4};
   for (void *p : dev) if (p) hipFree(p);
   store_free(c->batch); store_free(c->db);
   for (SliceBuf &b : c->slice) slice_free(b);
@@ -20,6 +20,9 @@ void uvaia_gpu_close(uvaia_gpu_ctx *c)
   for (int i = 0; i < 2; i++) if (c->stage_free[i]) hipEventDestroy(c->stage_free[i]);
   for (int i = 0; i < 16; i++) if (c->order_ev[i]) hipEventDestroy(c->order_ev[i]);
   for (int i = 0; i < 4; i++) if (c->ball_ev[i]) hipEventDestroy(c->ball_ev[i]);
+  if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
+  for (auto &sl : c->wstage) { for (void *p : {(void *)sl.planes, (void *)sl.nonn, (void *)sl.side}) if (p) hipFree(p); for (hipEvent_t e : {sl.copied, sl.read}) if (e) hipEventDestroy(e); }
+  for (int i = 0; i < 5; i++) if (c->win_ev[i]) hipEventDestroy(c->win_ev[i]);
   for (int i = 0; i < 64; i++) for (int j = 0; j < 2; j++) if (c->ipc_opened[i][j]) hipIpcCloseMemHandle(c->ipc_opened[i][j]);
   for (int i = 0; i < 8; i++) for (int j = 0; j < 3; j++) if (c->mark_ev[i][j]) hipEventDestroy(c->mark_ev[i][j]);
   for (int i_ = 0; i_ < 3; i_++) if (c->derive_streams[i_]) { hipStreamSynchronize(c->derive_streams[i_]); hipStreamDestroy(c->derive_streams[i_]); }

@@ -1,0 +1,136 @@
+// host_window.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): the windowed search over a packed database that does
+// not fit device memory: two staging slots of whole file tiles filled by a copy stream, the load of a selection of their lanes into the
+// resident store (select_tiles_kernel), the text of a loaded window.  The search itself is uvaia_gpu_search_resident, window after window:
+// its state (heaps, tolerances) lives in the context and ordinal0 gives the stream position.
+
+extern "C" {
+
+static_assert(AMB_ROW == 64, "select_tiles_kernel moves a side row with one wave");
+
+size_t uvaia_gpu_free_bytes(uvaia_gpu_ctx *c)
+{
+  if (!c || hipSetDevice(c->device) != hipSuccess) return 0;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  return free_b;
+}
+
+int uvaia_gpu_db_stage_reserve(uvaia_gpu_ctx *c, size_t n_tiles)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (n_tiles < 1 || n_tiles > (size_t)(0x7FFFFFFF / 64)) return fail(c, UVAIA_GPU_EINVAL, "staging capacity of %zu tiles", n_tiles);
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+  for (auto &sl : c->wstage) {
+    if (!sl.copied) HIPCHK(c, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
+    if (!sl.read) HIPCHK(c, hipEventCreateWithFlags(&sl.read, hipEventDisableTiming));
+  }
+  if (n_tiles <= c->wstage_tiles) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->copy_stream));          // nothing may still use the slots that go
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->wstage_tiles = 0;
+  const size_t tb = uvaia_gpu_db_tile_bytes(c);
+  for (auto &sl : c->wstage) {
+    for (void *p : {(void *)sl.planes, (void *)sl.nonn, (void *)sl.side}) if (p) hipFree(p);
+    sl.planes = nullptr; sl.nonn = nullptr; sl.side = nullptr; sl.n_tiles = 0; sl.read_recorded = false;
+    HIPCHK(c, hipMalloc(&sl.nonn, n_tiles * 64 * sizeof(int)));
+    HIPCHK(c, hipMalloc(&sl.side, n_tiles * 64 * AMB_ROW * sizeof(int)));
+    HIPCHK(c, hipMalloc(&sl.planes, n_tiles * tb));
+  }
+  c->wstage_tiles = n_tiles;
+  return 0;
+}
+
+int uvaia_gpu_db_stage_packed(uvaia_gpu_ctx *c, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  if (n_tiles < 0 || (n_tiles > 0 && (!planes || !non_n || (!c->acgt && !side_rows)))) return fail(c, UVAIA_GPU_EINVAL, "NULL packed arrays");
+  if ((size_t)n_tiles > c->wstage_tiles) return fail(c, UVAIA_GPU_ESTATE, "%d tiles exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, c->wstage_tiles);
+  HIPCHK(c, hipSetDevice(c->device));
+  auto &sl = c->wstage[slot];
+  sl.n_tiles = 0;
+  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
+  if (n_tiles) {
+    const size_t tb = uvaia_gpu_db_tile_bytes(c), nt = (size_t)n_tiles;
+    HIPCHK(c, hipMemcpyAsync(sl.planes, planes, nt * tb, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipMemcpyAsync(sl.nonn, non_n, nt * 64 * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
+    if (!c->acgt) HIPCHK(c, hipMemcpyAsync(sl.side, side_rows, nt * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
+  }
+  HIPCHK(c, hipEventRecord(sl.copied, c->copy_stream));
+  sl.n_tiles = n_tiles;
+  return 0;
+}
+
+int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
+  auto &sl = c->wstage[slot];
+  const long long staged = (long long)sl.n_tiles * 64;
+  if (n_ref > 0 && !sl.n_tiles) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
+  if (!sel && n_ref > staged) return fail(c, UVAIA_GPU_EINVAL, "%d references asked of the %lld staged in slot %d", n_ref, staged, slot);
+  if (sel) for (int k = 0; k < n_ref; k++)
+    if (sel[k] < 0 || sel[k] >= staged) return fail(c, UVAIA_GPU_EINVAL, "sel[%d] = %d lies outside the %lld references staged in slot %d", k, sel[k], staged, slot);
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = uvaia_gpu_db_clear(c); if (rc) return rc; }
+  c->win_n = 0;
+  if (n_ref == 0) return 0;
+  if ((size_t)n_ref > c->db_cap) { int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc; }
+  const size_t n_tiles = ((size_t)n_ref + 63) / 64, tile_u4 = (size_t)c->W4 * 4 * 64;
+  if (c->acgt && c->win4_tiles < n_tiles) {       // the four-plane image of a window: as many tiles as the resident store holds
+    const size_t cap = std::max(n_tiles, c->db_cap / 64 + 1);
+    hipFree(c->d_win4); c->d_win4 = nullptr; c->win4_tiles = 0;
+    HIPCHK(c, hipMalloc(&c->d_win4, cap * tile_u4 * sizeof(uint4)));
+    c->win4_tiles = cap;
+  }
+  if (sel) {
+    if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
+    HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
+  uint4 *four = c->acgt ? c->d_win4 : c->db.planes;
+  HIPCHK(c, hipEventRecord(c->win_ev[0], c->stream));
+  hipLaunchKernelGGL(select_tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, sl.planes, sl.nonn, c->acgt ? (const int *)nullptr : sl.side, sel ? c->d_wsel : (const int *)nullptr, n_ref, c->W4,
+                     four, c->db.nonn, c->acgt ? (int *)nullptr : c->db.amb);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->win_ev[1], c->stream));
+  HIPCHK(c, hipEventRecord(sl.read, c->stream)); sl.read_recorded = true;
+  // from here on as uvaia_gpu_db_append_packed: re-coding (--acgt) and totals, the checks on what came from outside, the derived planes
+  if (c->acgt) hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->d_win4, c->W4, c->db.planes, 0LL, c->db.tot);
+  else         hipLaunchKernelGGL((import_tiles_kernel<4>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->db.planes, c->W4, (uint4 *)nullptr, 0LL, c->db.tot);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb, c->db.nonn, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
+  HIPCHK(c, hipGetLastError());
+  { int rc = derive_rows(c, c->db, 0, (int)(n_tiles * 64)); if (rc) return rc; }
+  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
+  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  c->db_n = (size_t)n_ref;
+  c->win_n = n_ref;
+  return 0;
+}
+
+// text of references index[0..n) of the window loaded last (positions within the window)
+int uvaia_gpu_db_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  const int count = (c->win_n && (size_t)c->win_n == c->db_n) ? c->win_n : 0;     // (the database changed since the load: the window is gone)
+  for (int i = 3; i < 5; i++) if (!c->win_ev[i]) HIPCHK(c, hipEventCreate(&c->win_ev[i]));
+  return unpack_rows_from(c, c->acgt ? c->d_win4 : c->db.planes, count, "loaded window", "uvaia_gpu_db_load_staged", index, n, rows, pitch, c->win_ev + 3, &c->win_ms[2]);
+}
+
+void uvaia_gpu_window_ms(uvaia_gpu_ctx *c, double out[3], int reset)
+{
+  if (!c) return;
+  for (int i = 0; i < 3; i++) { out[i] = c->win_ms[i]; if (reset) c->win_ms[i] = 0.; }
+}
+
+}  // extern "C"

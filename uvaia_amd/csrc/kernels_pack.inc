@@ -150,6 +150,36 @@ __global__ void sanitise_import_kernel(int *__restrict__ side_rows /* nullable *
   if (!ok) { row[0] = AMB_CAP + 1; for (int k = 0; k < AMB_CAP; k++) row[1 + k] = 0; }
 }
 
+// Windowed search (host_window.inc): tiles of the interchange form that were staged as the file holds them -> tiles of the same form that
+// hold the selected references only, in order.  Destination slot k = tile k / 64, lane k % 64 receives every 16-byte piece of staged slot
+// sel[k] (sel == NULL: slot k), its valid-site count and its side row; lanes at and past n_ref are written as zero planes, zero count and
+// zero side row, so a destination tile is complete whatever it held before.  One block per destination tile, lane = destination reference:
+// a wave moves one plane of one word group per load, and with few exclusions consecutive lanes read consecutive 16-byte words of the same
+// staged tile (the holes shift the run by a lane, a run that crosses a tile boundary continues in the next tile).  Side rows: one wave per
+// reference, lane = int of the row, the reference's staged slot handed round by a shuffle.  sel[] was checked by the host against the
+// staged tiles; nothing here depends on what the staged bytes hold.
+__global__ __launch_bounds__(256) void select_tiles_kernel(const uint4 *__restrict__ src, const int *__restrict__ src_nonn, const int *__restrict__ src_side /* nullable */,
+                                                            const int *__restrict__ sel /* nullable */, int n_ref, int W4,
+                                                            uint4 *__restrict__ dst, int *__restrict__ dst_nonn, int *__restrict__ dst_side /* nullable, with src_side */)
+{
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long k = (long long)blockIdx.x * 64 + lane;
+  const bool active = k < n_ref;
+  const int s = active ? (sel ? sel[k] : (int)k) : 0;
+  const uint4 *t = src + (size_t)(s >> 6) * W4 * 4 * 64 + (s & 63);
+  uint4 *o = dst + (size_t)blockIdx.x * W4 * 4 * 64 + lane;
+  const int rows = W4 * 4;                             // (word group, plane) rows of 64 lanes
+  for (int r = wv; r < rows; r += 4) o[(size_t)r * 64] = active ? ld_stream(t + (size_t)r * 64) : make_uint4(0u, 0u, 0u, 0u);
+  if (wv == 0) dst_nonn[k] = active ? src_nonn[s] : 0;
+  if (dst_side) {
+    for (int i = wv; i < 64; i += 4) {
+      const int si = __shfl(s, i);
+      const long long ki = (long long)blockIdx.x * 64 + i;
+      dst_side[(size_t)ki * AMB_ROW + lane] = ki < n_ref ? src_side[(size_t)si * AMB_ROW + lane] : 0;
+    }
+  }
+}
+
 // The opposite of pack_refs_kernel<4>: the upper-case text of selected references out of tiles of the interchange form (four IUPAC
 // planes).  One block per selected reference (index[] = positions in the batch, any order, repeats allowed: every row is independent),
 // one thread per 16 sites = one half of an alignment word: eight neighbouring threads read the same 16-byte piece of each plane (one

@@ -195,6 +195,14 @@ struct uvaia_gpu_ctx {
   std::vector<int> rows_host; std::vector<uint2> rexc_host;
   uint32_t run_cut = 0xFFFFFFu;                             // longest exception run of a record (uvaia_gpu_rows_set_run_cut)
   std::vector<hipEvent_t> rows_evs; double rows_ms[3] = {0., 0., 0.};   // per-kernel time of census, gather, exception fill
+  // windowed search over a packed database larger than device memory (host_window.inc): two staging slots of whole file tiles filled by a copy
+  // stream of their own, and (--acgt) the four-plane image of the window loaded last, which the text is decoded from
+  struct StageSlot { uint4 *planes = nullptr; int *nonn = nullptr, *side = nullptr; int n_tiles = 0; hipEvent_t copied = nullptr, read = nullptr; bool read_recorded = false; };
+  StageSlot wstage[2]; size_t wstage_tiles = 0;
+  hipStream_t copy_stream = nullptr;
+  int *d_wsel = nullptr; size_t wsel_cap = 0;
+  uint4 *d_win4 = nullptr; size_t win4_tiles = 0; int win_n = 0;      // win_n: references of the window loaded last (0: none)
+  hipEvent_t win_ev[5] = {}; double win_ms[3] = {0., 0., 0.};          // device time of selection, import + derive, decode
   // heaps / state
   int *d_heap = nullptr, *d_n = nullptr, *d_T = nullptr, *d_snap = nullptr, *d_err = nullptr;
   // batch buffers
@@ -290,3 +298,4 @@ void fill_code_table(uint8_t *t)
 #include "host_rows.inc"
 #include "host_shards.inc"
 #include "host_ball.inc"
+#include "host_window.inc"
