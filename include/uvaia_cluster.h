@@ -54,6 +54,18 @@ int  uvaia_clust_open (uvaia_clust_ctx **out, int device, const char *reference,
 void uvaia_clust_close (uvaia_clust_ctx *c);
 const char *uvaia_clust_last_error (const uvaia_clust_ctx *c);
 
+/* The second residency mode, "keep medoids": call it after uvaia_clust_open and before the first push (UVAIA_GPU_ESTATE once a sequence was
+ * pushed).  By default every pushed row stays in device memory as text, nchar rounded up to 64 bytes each, in one array that grows by
+ * doubling (the old and the new array exist together while it grows).  After phase 2 has placed a sequence its text is read again only if
+ * it founded a cluster (item 2: the medoid is the first member), so in this mode only those rows are kept: the rows of a push land in a
+ * staging buffer of that push's size, and its founders are copied into slabs of slab_rows rows each, which are added one at a time and never
+ * moved.  Device memory for row text is then bounded by (clusters founded in phase 2, rounded up to whole slabs) + (the largest push), and
+ * no longer by the number of sequences; 16 bytes + 4 n_score bytes per pushed sequence (its scores, join and slot) still stay.
+ * slab_rows: 0 = the default (65 536 rows, a design choice that has not been measured), else a power of two >= 1, or UVAIA_GPU_EINVAL.
+ * Clusters, member lists and scores are those of the default mode for the same pushes; push, push_packed, finish, result and stats keep
+ * their contracts.  What changes: uvaia_clust_rows answers for founders only, uvaia_clust_device_rows has no store to hand out. */
+int  uvaia_clust_keep_medoids (uvaia_clust_ctx *c, int slab_rows);
+
 /* Phase 2 for n sequences of nchar bytes each (seq[i]); queue[i] in [0, n_queues) is the queue sequence i goes to.  Within a
  * queue the order is push order.  Sequences are numbered by push ordinal from 0 across all calls.  A byte 0 or >= 0x80 fails
  * the call with UVAIA_GPU_EALPHABET and leaves the context unusable (UVAIA_GPU_ESTATE afterwards). */
@@ -74,13 +86,28 @@ int  uvaia_clust_push_packed (uvaia_clust_ctx *c, int n, const void *planes, con
 
 /* The upper-case text of pushed sequences, before or after finish: row k of `rows` (pitch >= nchar bytes apart, nchar bytes written, no
  * NUL) = the sequence with push ordinal ordinal[k]; any order, repeats allowed.  Gathered on the device, one copy back per call: the caller
- * bounds its memory by the n of a call (the medoids of <prefix>.aln.xz are fetched in batches). */
+ * bounds its memory by the n of a call (the medoids of <prefix>.aln.xz are fetched in batches).
+ * Keep medoids: every ordinal must be a sequence that founded a cluster in phase 2 -- the medoids of the result, and the founders the merge
+ * tree absorbed into another cluster since; the bytes are those of the default mode.  Any other ordinal fails the call with
+ * UVAIA_GPU_EINVAL before anything is copied, and the context stays usable. */
 int  uvaia_clust_rows (uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch);
 
 /* The row store where it lies: sequence o is the nchar bytes at *d_rows + o * *pitch in the memory of the context's device, upper-case
  * (uvaia_gpu_rows_census, uvaia_gpu_db_append_device and uvaia_gpu_rows_exceptions of include/uvaia_gpu.h read medoid rows in place,
- * row_index = push ordinals).  Valid until the next push or close. */
+ * row_index = push ordinals).  Valid until the next push or close.  Keep medoids: UVAIA_GPU_ESTATE, there is no such array; use
+ * uvaia_clust_gather_device. */
 int  uvaia_clust_device_rows (uvaia_clust_ctx *c, const void **d_rows, size_t *pitch);
+
+/* Rows in device memory, in either mode: the rows of ordinal[0 .. n) (the ordinals uvaia_clust_rows accepts; any order, repeats allowed)
+ * gathered into the context's gather buffer, row k = the nchar bytes at *d_rows + k * *pitch, upper-case, so that uvaia_gpu_rows_census,
+ * uvaia_gpu_db_append_device and uvaia_gpu_rows_exceptions read them with row_index = 0 .. n - 1.  Valid until the next call on the context
+ * (uvaia_clust_rows uses the same buffer).  n = 0: *d_rows NULL.  The caller bounds the buffer by the n of a call. */
+int  uvaia_clust_gather_device (uvaia_clust_ctx *c, const int64_t *ordinal, int n, const void **d_rows, size_t *pitch);
+
+/* Device memory (each pointer nullable): *row_bytes = bytes held for row text now -- the row store, or the slabs and the staging buffer --
+ * *peak_row_bytes = the most they have been at once (the default mode's store holds old + new capacity while it grows), *free_bytes = the
+ * free memory of the context's device as the runtime reports it. */
+int  uvaia_clust_memory (uvaia_clust_ctx *c, size_t *row_bytes, size_t *peak_row_bytes, size_t *free_bytes);
 
 /* The merge tree and the final order.  No push after it. */
 int  uvaia_clust_finish (uvaia_clust_ctx *c);

@@ -9,6 +9,7 @@ from . import capi
 SYMBOLS = [
     "uvaia_clust_open", "uvaia_clust_close", "uvaia_clust_last_error", "uvaia_clust_push", "uvaia_clust_finish", "uvaia_clust_result",
     "uvaia_clust_stats", "uvaia_clust_push_packed", "uvaia_clust_rows", "uvaia_clust_device_rows", "uvaia_clust_unpack_ms",
+    "uvaia_clust_keep_medoids", "uvaia_clust_gather_device", "uvaia_clust_memory",
 ]
 
 
@@ -39,6 +40,9 @@ def _lib():
         L.uvaia_clust_rows.argtypes = [vp, pl, C.c_int, vp, C.c_size_t]
         L.uvaia_clust_device_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.uvaia_clust_unpack_ms.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.uvaia_clust_keep_medoids.argtypes = [vp, C.c_int]
+        L.uvaia_clust_gather_device.argtypes = [vp, pl, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
+        L.uvaia_clust_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         _ready = True
     return L
 
@@ -121,6 +125,28 @@ class Clusterer:
         buf = np.zeros((max(len(o), 1), self.nchar), dtype=np.uint8)
         self._chk(self.L.uvaia_clust_rows(self.ptr, o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), buf.ctypes.data, self.nchar))
         return [buf[k].tobytes() for k in range(len(o))]
+
+    def keep_medoids(self, slab_rows=0):
+        """before the first push: keep the rows of the sequences that found a cluster only, in slabs of slab_rows rows (0: the default)"""
+        self._chk(self.L.uvaia_clust_keep_medoids(self.ptr, slab_rows))
+
+    def device_rows(self):
+        """(device address of the row store, pitch): sequence o at address + o * pitch"""
+        p, pitch = C.c_void_p(), C.c_size_t(0)
+        self._chk(self.L.uvaia_clust_device_rows(self.ptr, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def gather_device(self, ordinals):
+        """(device address, pitch) of these sequences gathered contiguously in device memory; valid until the next call on the context"""
+        o = np.ascontiguousarray(ordinals, dtype=np.int64)
+        p, pitch = C.c_void_p(), C.c_size_t(0)
+        self._chk(self.L.uvaia_clust_gather_device(self.ptr, o.ctypes.data_as(C.POINTER(C.c_int64)), len(o), C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
+
+    def memory(self):
+        a, b, f = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.L.uvaia_clust_memory(self.ptr, C.byref(a), C.byref(b), C.byref(f)))
+        return {"row_bytes": a.value, "peak_row_bytes": b.value, "free_bytes": f.value}
 
     def unpack_ms(self):
         a, b = C.c_double(0), C.c_double(0)

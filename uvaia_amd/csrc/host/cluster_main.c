@@ -8,6 +8,11 @@
  * exception runs go to the device as they lie in the file's mapping, and the medoids leave as a packed database written from the rows in
  * device memory (uvdb_packer.h), the file `uvaiapack` makes of <prefix>.aln.xz.  No sequence text is held on the host on that path: the
  * medoids of <prefix>.aln.xz are fetched from the device in batches.  Own code.
+ *
+ * --keep-medoids (no counterpart in the reference): the clusterer keeps the rows of the sequences that found a cluster only
+ * (uvaia_clust_keep_medoids), so device memory follows the number of clusters and not the number of sequences; same output files.  With
+ * --packed it is chosen without being asked for when the file's sequence count says that the row store could not grow to hold them
+ * (clust_plan.h).  Own code.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -18,6 +23,7 @@
 #include "fastaseq.h"
 #include "uvdb.h"
 #include "uvdb_packer.h"
+#include "clust_plan.h"
 #include "../../../include/uvaia_cluster.h"
 
 /* read_reference_sequence (src/cluster.c:260-277): the first record of the file, filled by up to nseqs - 1 more while Ns remain
@@ -96,7 +102,7 @@ str_vec_push (str_vec *s, char *x)
   s->v[s->n++] = x;
 }
 
-typedef struct { int device, nchar, dist, trim, snps, n_clust; char *refseq; uvaia_clust_ctx *ctx; } gpu_state;
+typedef struct { int device, nchar, dist, trim, snps, n_clust; char *refseq; uvaia_clust_ctx *ctx; int keep_medoids; } gpu_state;
 
 /* the context is opened at the first push: errors in the input found by then are reported as such, GPU or not */
 static void
@@ -104,6 +110,7 @@ open_context (gpu_state *g)
 {
   if (g->ctx) return;
   if (uvaia_clust_open (&g->ctx, g->device, g->refseq, g->nchar, g->dist, g->trim, g->snps, g->n_clust)) biomcmc_error ("%s", uvaia_clust_last_error (NULL));
+  if (g->keep_medoids && uvaia_clust_keep_medoids (g->ctx, 0)) biomcmc_error ("%s", uvaia_clust_last_error (g->ctx));
 }
 
 static void
@@ -116,6 +123,40 @@ push_batch (gpu_state *g, str_vec *seqs, int64_t from, int *queue, int n)
 
 #define PACKED_CHUNK 4096    /* sequences of a packed database per push: whole tiles (a multiple of 64); a tuning value, the result does not depend on it */
 #define ROWS_BATCH 256       /* medoids fetched from the device per round trip for <prefix>.aln.xz */
+
+static void
+packer_report (const struct uvdb_packer *pk, const char *path, int n_out, int nchar, long kept, long dropped)
+{
+  fprintf (stderr, "Packed %ld of %d medoids (%d sites) into %s; %ld too ambiguous. Device time: census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n",
+           kept, n_out, nchar, path, dropped, pk->rows_ms[0], pk->rows_ms[1], pk->rows_ms[2]);
+}
+
+/* --packed-out with --keep-medoids: there is no row store to read in place, so each batch of medoids, in the final order, is gathered into
+   consecutive rows of device memory (uvaia_clust_gather_device) and goes to the packer as a block: census, filter and append as below */
+static void
+write_packed_out_gathered (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, const int64_t *medoid, int n_out,
+                           const char *(*name_of) (void *, int64_t), void *name_arg)
+{
+  struct uvdb_packer pk;
+  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH)) biomcmc_error ("%s", pk.err);
+  char **name = (char **) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (char *));
+  for (int a = 0; a < n_out; a += UVDB_PACK_BATCH) {
+    const int m = n_out - a < UVDB_PACK_BATCH ? n_out - a : UVDB_PACK_BATCH;
+    const void *d_rows = NULL; size_t pitch = 0;
+    if (uvaia_clust_gather_device (ctx, medoid + a, m, &d_rows, &pitch)) { uvdb_packer_close (&pk); biomcmc_error ("%s", uvaia_clust_last_error (ctx)); }
+    for (int k = 0; k < m; k++) name[k] = (char *) name_of (name_arg, medoid[a + k]);
+    if (uvdb_packer_add_block (&pk, d_rows, pitch, m, name)) {
+      char msg[640];
+      snprintf (msg, sizeof msg, "%s", pk.err);
+      uvdb_packer_close (&pk);
+      biomcmc_error ("%s: %s", path, msg);
+    }
+  }
+  const long kept = pk.kept, dropped = pk.dropped;
+  if (uvdb_packer_close (&pk)) biomcmc_error ("%s", pk.err);
+  packer_report (&pk, path, n_out, nchar, kept, dropped);
+  free (name);
+}
 
 /* --packed-out: the medoids in their final order into a packed database, from the rows in the clusterer's device memory */
 static void
@@ -155,8 +196,7 @@ write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar,
   }
   const long kept = pk.kept, dropped = pk.dropped;
   if (uvdb_packer_close (&pk)) biomcmc_error ("%s", pk.err);
-  fprintf (stderr, "Packed %ld of %d medoids (%d sites) into %s; %ld too ambiguous. Device time: census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n",
-           kept, n_out, nchar, path, dropped, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
+  packer_report (&pk, path, n_out, nchar, kept, dropped);
   free (slot); free (m_nn); free (m_exc); free (nn); free (ne); free (row); free (name);
 }
 
@@ -166,14 +206,14 @@ static const char *name_from_db (void *v, int64_t i) { return uvdb_name ((uvdb_r
 int
 main (int argc, char **argv)
 {
-  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, ch;   /* src/cluster.c:57-64 */
+  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, ch;   /* src/cluster.c:57-64 */
   double ambig_r = -1.;
   const char *out = "cluster_uvaia", *ref_file = NULL, *packed = NULL, *packed_out = NULL;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
     {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"packed", required_argument, 0, 1002},
-    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {0, 0, 0, 0}};
+    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"keep-medoids", no_argument, 0, 1004}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -186,6 +226,7 @@ main (int argc, char **argv)
     case 1001: device = atoi (optarg); break;
     case 1002: if (packed) errors++; packed = optarg; break;
     case 1003: if (packed_out) errors++; packed_out = optarg; break;
+    case 1004: keep_medoids = 1; break;
     case 'A': ambig_r = atof (optarg); if (ambig_r < 0.) ambig_r = 0.; break;
     default: errors++;
   }
@@ -198,7 +239,7 @@ main (int argc, char **argv)
   }
   if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024) {
     printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb>\n\n", basename (argv[0]));
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb>\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
     printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
@@ -213,6 +254,8 @@ main (int argc, char **argv)
     printf ("  --packed-out=<out.uvdb>          also write the medoids as a packed database, the file `uvaiapack` makes of <prefix>.aln.xz (with either kind of input)\n");
     printf ("  -A, --ref_ambiguity=<double>     with --packed-out: maximum allowed ambiguity for a medoid to be kept in that database, as in `uvaiapack`\n");
     printf ("                                   (default: the value recorded in the --packed database, 0.5 for alignment files)\n");
+    printf ("  --keep-medoids                   keep only the sequences that found a cluster in GPU memory, not every sequence: memory follows the number of\n");
+    printf ("                                   clusters; same output files (with --packed: chosen by itself when the sequences would not fit otherwise)\n");
     if (help) {
       printf ("One-pass clustering similar to canopy clustering with single, tight distance, computed on the GPU.\n");
       printf ("A pool of independent clustering queues is created, such that each sequence is compared to only one of them at first.\n\n");
@@ -249,7 +292,7 @@ main (int argc, char **argv)
   if (trim > nchar / 2.1) trim = (int) (nchar / 2.1);
   if (dist > nchar / 10) dist = nchar / 10;
   fprintf (stderr, "Creating a pool of %d cluster queues; maximum distance is %d, and %d SNP locations are kept\n", n_clust, dist, snps);
-  gpu_state g = {device, nchar, dist, trim, snps, n_clust, refseq, NULL};
+  gpu_state g = {device, nchar, dist, trim, snps, n_clust, refseq, NULL, keep_medoids};
 
   str_vec names = {0}, seqs = {0};
   int64_t count = 0;
@@ -257,6 +300,19 @@ main (int argc, char **argv)
     /* sequence k of the database to queue k mod Q; chunks of whole tiles go to the device from the file's mapping as they are */
     int *queue = (int *) biomcmc_malloc (PACKED_CHUNK * sizeof (int));
     open_context (&g);
+    if (!keep_medoids) {   /* the file says how many sequences come: would the store of every row reach that count in the memory there is? */
+      size_t free_bytes = 0;
+      const uint64_t row_bytes = ((uint64_t) nchar + 63) / 64 * 64;
+      uint64_t peak = 0;
+      if (uvaia_clust_memory (g.ctx, NULL, NULL, &free_bytes)) free_bytes = 0;   /* unknown: as without the option */
+      uvclust_store_peak (db->h.n_ref, PACKED_CHUNK, row_bytes, &peak);
+      if (uvclust_choose_keep_medoids (db->h.n_ref, PACKED_CHUNK, row_bytes, (uint64_t) free_bytes) == 1) {
+        fprintf (stderr, "Keeping medoid rows only (as with --keep-medoids): the rows of the %llu sequences of %s would need %llu bytes of GPU memory while their store grows, %zu are free\n",
+                 (unsigned long long) db->h.n_ref, packed, (unsigned long long) peak, free_bytes);
+        if (uvaia_clust_keep_medoids (g.ctx, 0)) biomcmc_error ("%s", uvaia_clust_last_error (g.ctx));
+        keep_medoids = g.keep_medoids = 1;
+      }
+    }
     for (uint64_t first = 0; first < db->h.n_ref; first += PACKED_CHUNK) {
       const int n = (int) (db->h.n_ref - first < PACKED_CHUNK ? db->h.n_ref - first : PACKED_CHUNK);
       for (int i = 0; i < n; i++) queue[i] = (int) ((first + (uint64_t) i) % (uint64_t) n_clust);
@@ -302,6 +358,8 @@ main (int argc, char **argv)
   double prep_ms = 0, queue_ms = 0, merge_ms = 0, decode_ms = 0, overlay_ms = 0;
   uvaia_clust_stats (ctx, &prep_ms, &queue_ms, &merge_ms, NULL);
   uvaia_clust_unpack_ms (ctx, &decode_ms, &overlay_ms);
+  size_t peak_row_bytes = 0;
+  uvaia_clust_memory (ctx, NULL, &peak_row_bytes, NULL);
   const char *(*name_of) (void *, int64_t) = db ? name_from_db : name_from_vec;
   void *name_arg = db ? (void *) db : (void *) &names;
 
@@ -337,8 +395,10 @@ main (int argc, char **argv)
     free (text);
   } else for (int c = 0; c < n_out; c++) write_fasta_record (aln, names.v[medoid[c]], seqs.v[medoid[c]]);
   biomcmc_close_compress (aln);
-  if (packed_out) write_packed_out (packed_out, ctx, device, nchar, ambig_r, count, medoid, n_out, name_of, name_arg);
+  if (packed_out && keep_medoids) write_packed_out_gathered (packed_out, ctx, device, nchar, ambig_r, medoid, n_out, name_of, name_arg);
+  else if (packed_out) write_packed_out (packed_out, ctx, device, nchar, ambig_r, count, medoid, n_out, name_of, name_arg);
   uvaia_clust_close (ctx);
+  fprintf (stderr, "GPU memory for sequence rows: %zu bytes at the peak (%s)\n", peak_row_bytes, keep_medoids ? "medoid rows in slabs and one push" : "every row kept");
   fprintf (stderr, "%d clusters from %ld sequences; GPU kernels: prep %.3lf ms, queues %.3lf ms, merge %.3lf ms, decode %.3lf ms, overlay %.3lf ms\n", n_out, (long) count,
            prep_ms, queue_ms, merge_ms, decode_ms, overlay_ms);
   fprintf (stderr, "Finished sorting clusters and saving files in %lf secs\n", biomcmc_update_elapsed_time (time0));

@@ -21,6 +21,12 @@
 //     transpose through an XOR-swizzled LDS image so that every row's 128 characters of a word group leave as eight 16-byte stores.
 //     overlay: the exception runs ('-', '?', 'X', 'O', '.': the planes hold them all as the empty set) are written over the decoded rows,
 //     one wave per run, the lanes spread over its length.  Prep and queue then run on these rows as on rows that came as text.
+//   * keep medoids (uvaia_clust_keep_medoids): the second residency mode.  A row is read again after phase 2 has placed it only if it
+//     founded a cluster, so only founders are kept: the rows of a push land in a staging buffer, the queue kernel reads the row it places
+//     and the founders of the running push from staging and earlier founders from their slot, and after it the founders of the push get
+//     consecutive slots in push order (a block-wise prefix sum over join[] < 0) and their rows are copied to the slots.  Slots live in slabs
+//     of slab_rows rows (a power of two) behind a device table of base pointers: growth adds a slab and copies nothing.  The kernels that
+//     read rows take the addressing as a template parameter (FlatRows / SlabRows); dist[], p[] and join[] stay per push ordinal.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +51,8 @@ constexpr int UNROLL = 4;               // 16-B loads in flight per lane in a co
 constexpr int UTPB = 256;               // unpack: four waves, each with a transpose image of its own (4 x 8 KiB of LDS)
 constexpr int UGROUPS = 16;             // unpack: word groups per work unit (a 29 903-site alignment is 15 units per tile)
 constexpr int OTPB = 256;               // overlay: one block per row, one wave per run
+constexpr int KTPB = 256;               // keep medoids: rows of a push per block of the founder prefix sum
+constexpr int SLAB_ROWS = 65536;        // keep medoids: default rows per slab (1.96 GB at 29 952 B per row); a design choice, not measured
 
 __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
 __device__ __forceinline__ uint32_t expand4(uint32_t b) { return ((b & 1u) << 7) | ((b & 2u) << 14) | ((b & 4u) << 21) | ((b & 8u) << 28); }
@@ -104,6 +112,31 @@ __device__ int wave_distance(const uint8_t *__restrict__ a, const uint8_t *__res
   return total;
 }
 
+// Where the kernels below find a row.  FlatRows: every pushed row stays, row o at rows + o * pitch.
+struct FlatRows {
+  const uint8_t *__restrict__ rows; size_t pitch;
+  __device__ __forceinline__ const uint8_t *pushed(int o) const { return rows + (size_t)o * pitch; }
+  __device__ __forceinline__ const uint8_t *by_ordinal(int o) const { return pushed(o); }
+  __device__ __forceinline__ const uint8_t *medoid(int m, int, int, int) const { return pushed(m); }
+  __device__ __forceinline__ void found(int, int, int, int) const {}
+};
+
+// SlabRows (keep medoids): the rows of the running push (ordinals first ..) in staging, founders of earlier pushes in their slots.
+// m_loc (cap entries per queue, beside m_ord / m_st) says where a queue's medoid lies: its slot when >= 0, -1 - staging index for a
+// founder of the running push; slot_of[o] is the slot of founder o of an earlier push (-1 for a row that joined).
+struct SlabRows {
+  const uint8_t *stage; uint8_t *const *slab; size_t pitch; const int *slot_of; int *m_loc; long long first; int shift, mask;
+  __device__ __forceinline__ const uint8_t *kept(int slot) const { return slab[slot >> shift] + (size_t)(slot & mask) * pitch; }
+  __device__ __forceinline__ const uint8_t *pushed(int o) const { return stage + (size_t)(o - first) * pitch; }
+  __device__ __forceinline__ const uint8_t *by_ordinal(int o) const { return kept(slot_of[o]); }
+  __device__ __forceinline__ const uint8_t *medoid(int, int q, int cap, int idx) const
+  {
+    const int l = m_loc[(size_t)q * cap + idx];
+    return l >= 0 ? kept(l) : stage + (size_t)(-1 - l) * pitch;
+  }
+  __device__ __forceinline__ void found(int q, int cap, int idx, int o) const { m_loc[(size_t)q * cap + idx] = -1 - (int)(o - first); }
+};
+
 // One wave per pushed row (ordinals first .. first + n): upper-case in place, flag bytes 0 and >= 0x80 (bad_out = lowest such
 // row of the push), distance to the reference over [trim, nchar - trim) and the first n_score differing sites (relative to trim).
 __global__ __launch_bounds__(PTPB) void clust_prep_kernel(uint8_t *__restrict__ rows, size_t pitch, long long first, int n, const uint8_t *__restrict__ ref, int nchar,
@@ -156,7 +189,9 @@ __global__ __launch_bounds__(PTPB) void clust_prep_kernel(uint8_t *__restrict__ 
 
 // Phase 2 for the rows of one push: workgroup q takes the ordinals qlist[qoff[q] .. qoff[q + 1]) in order against queue q's medoids
 // (m_ord / m_st: cap slots per queue, m_count of them used).  join[o] = slot of the medoid o joined, or -1 - slot if o founded one.
-__global__ __launch_bounds__(QTPB) void clust_queue_kernel(const uint8_t *__restrict__ rows, size_t pitch, int nchar, int trim, int d, int n_score,
+// Rows says where the row being placed and a candidate's row lie (FlatRows: the code as it was before the parameter).
+template <class Rows>
+__global__ __launch_bounds__(QTPB) void clust_queue_kernel(const Rows rows, int nchar, int trim, int d, int n_score,
                                                            const int *__restrict__ dist, const int *__restrict__ p, const int *__restrict__ qoff,
                                                            const int *__restrict__ qlist, int *__restrict__ m_count, int *__restrict__ m_ord_all,
                                                            int *__restrict__ m_st_all, int cap, int *__restrict__ join)
@@ -215,7 +250,7 @@ __global__ __launch_bounds__(QTPB) void clust_queue_kernel(const uint8_t *__rest
         int minloc = 0;
         if (n_score) minloc = max(0, min(ps, p[(size_t)m * n_score]) - 1);
         const int lo = trim + minloc, hi = min(nchar, nchar - trim + minloc);
-        const int dd = wave_distance(rows + (size_t)o * pitch, rows + (size_t)m * pitch, lo, hi, d);
+        const int dd = wave_distance(rows.pushed(o), rows.medoid(m, q, cap, slot), lo, hi, d);
         if (lane == 0) hit[wave] = dd <= d;
       }
       __syncthreads();
@@ -230,6 +265,7 @@ __global__ __launch_bounds__(QTPB) void clust_queue_kernel(const uint8_t *__rest
       if (threadIdx.x == 0) {
         const int stored = compared ? d + 1 : r;
         m_ord[n] = o; m_st[n] = stored;
+        rows.found(q, cap, n, o);
         if (n < LDS_ST) st[n] = stored;
         join[o] = -1 - n;
       }
@@ -243,16 +279,17 @@ __global__ __launch_bounds__(QTPB) void clust_queue_kernel(const uint8_t *__rest
 
 // One wave per item of a merge round: item i compares row item_ord[i] with the rows list_ord[item_lo[i] .. item_hi[i]) in order over
 // the trimmed sites and writes the first position within d (or -1) to target[i].
-__global__ __launch_bounds__(PTPB) void clust_merge_kernel(const uint8_t *__restrict__ rows, size_t pitch, int nchar, int trim, int d, const int *__restrict__ item_ord,
+template <class Rows>
+__global__ __launch_bounds__(PTPB) void clust_merge_kernel(const Rows rows, int nchar, int trim, int d, const int *__restrict__ item_ord,
                                                            const int *__restrict__ item_lo, const int *__restrict__ item_hi, const int *__restrict__ list_ord,
                                                            int n_items, int *__restrict__ target)
 {
   const int w = blockIdx.x * (PTPB / 64) + (threadIdx.x >> 6);
   if (w >= n_items) return;
-  const uint8_t *a = rows + (size_t)item_ord[w] * pitch;
+  const uint8_t *a = rows.by_ordinal(item_ord[w]);
   int t = -1;
   for (int j = item_lo[w], e = item_hi[w]; j < e; j++)
-    if (wave_distance(a, rows + (size_t)list_ord[j] * pitch, trim, nchar - trim, d) <= d) { t = j; break; }
+    if (wave_distance(a, rows.by_ordinal(list_ord[j]), trim, nchar - trim, d) <= d) { t = j; break; }
   if ((threadIdx.x & 63) == 0) target[w] = t;
 }
 
@@ -334,10 +371,79 @@ __global__ __launch_bounds__(OTPB) void clust_overlay_runs_kernel(uint8_t *__res
 }
 
 // uvaia_clust_rows: row k of dst = row ord[k] of the store (whole pitch, 16 bytes per thread)
-__global__ __launch_bounds__(256) void clust_gather_rows_kernel(const uint8_t *__restrict__ rows, size_t pitch, const int *__restrict__ ord, uint8_t *__restrict__ dst)
+template <class Rows>
+__global__ __launch_bounds__(256) void clust_gather_rows_kernel(const Rows rows, const int *__restrict__ ord, uint8_t *__restrict__ dst)
 {
-  const uint4 *s = reinterpret_cast<const uint4 *>(rows + (size_t)ord[blockIdx.x] * pitch);
+  const size_t pitch = rows.pitch;
+  const uint4 *s = reinterpret_cast<const uint4 *>(rows.by_ordinal(ord[blockIdx.x]));
   uint4 *d = reinterpret_cast<uint4 *>(dst + (size_t)blockIdx.x * pitch);
+  for (int k = threadIdx.x; k < (int)(pitch / 16); k += 256) d[k] = s[k];
+}
+
+// Keep medoids, after the queue kernel of a push of n rows (ordinals first ..): the founders (join < 0) get the slots kept, kept + 1, ... in
+// push order.  Three steps, so that a push of any size works: founders per block of KTPB rows; the exclusive prefix sum of those counts by one
+// block (blk[nb] = all founders of the push, which the host reads to add slabs before the next step); then every row's slot.
+__global__ __launch_bounds__(KTPB) void clust_founder_count_kernel(const int *__restrict__ join, long long first, int n, int *__restrict__ blk)
+{
+  __shared__ int s[KTPB / 64];
+  const int i = blockIdx.x * KTPB + threadIdx.x;
+  const int cnt = __popcll(__ballot(i < n && join[first + i] < 0));
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < KTPB / 64; w++) t += s[w]; blk[blockIdx.x] = t; }
+}
+
+__global__ __launch_bounds__(KTPB) void clust_founder_offsets_kernel(int *__restrict__ blk, int nb)
+{
+  __shared__ int s[KTPB / 64];
+  __shared__ int carry;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < nb; base += KTPB) {
+    const int i = base + threadIdx.x, v = i < nb ? blk[i] : 0;
+    int incl = v;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    if (lane == 63) s[wave] = incl;
+    __syncthreads();
+    int before = carry;
+    for (int w = 0; w < wave; w++) before += s[w];
+    if (i < nb) blk[i] = before + incl - v;
+    __syncthreads();                 // every thread has read carry and s
+    if (threadIdx.x == KTPB - 1) carry = before + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) blk[nb] = carry;
+}
+
+// slot_of[o] = the slot of founder o, -1 for a row that joined; the founder's entry of its queue's m_loc (queue pq[i], list position
+// -1 - join[o]) goes from its staging index to the slot.
+__global__ __launch_bounds__(KTPB) void clust_founder_slots_kernel(const int *__restrict__ join, const int *__restrict__ pq, long long first, int n, const int *__restrict__ blk,
+                                                                   int kept, int *__restrict__ slot_of, int *__restrict__ m_loc, int cap)
+{
+  __shared__ int s[KTPB / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.x * KTPB + threadIdx.x;
+  const int j = i < n ? join[first + i] : 0;
+  const unsigned long long m = __ballot(j < 0);
+  if (lane == 0) s[wave] = __popcll(m);
+  __syncthreads();
+  int before = blk[blockIdx.x];
+  for (int w = 0; w < wave; w++) before += s[w];
+  if (i >= n) return;
+  const int slot = j < 0 ? kept + before + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+  slot_of[first + i] = slot;
+  if (j < 0) m_loc[(size_t)pq[i] * cap + (-1 - j)] = slot;
+}
+
+// block i: row i of staging to its slot if it founded a cluster (whole pitch, 16 bytes per thread)
+__global__ __launch_bounds__(256) void clust_keep_founders_kernel(const uint8_t *__restrict__ stage, size_t pitch, long long first, const int *__restrict__ slot_of,
+                                                                  uint8_t *const *__restrict__ slab, int shift, int mask)
+{
+  const int slot = slot_of[first + blockIdx.x];
+  if (slot < 0) return;
+  const uint4 *s = reinterpret_cast<const uint4 *>(stage + (size_t)blockIdx.x * pitch);
+  uint4 *d = reinterpret_cast<uint4 *>(slab[slot >> shift] + (size_t)(slot & mask) * pitch);
   for (int k = threadIdx.x; k < (int)(pitch / 16); k += 256) d[k] = s[k];
 }
 
@@ -359,6 +465,16 @@ struct uvaia_clust_ctx {
   size_t rows_cap = 0, qlist_cap = 0, tiles_cap = 0, xoff_cap = 0, xrec_cap = 0, gather_cap = 0, gord_cap = 0;
   int m_cap = 0;
   long long pushed = 0;
+  // keep medoids: the rows of the running push (d_stage), the founders in slabs (slabs / d_slabtab), and where they are
+  bool keep = false;
+  int slab_rows = 0, slab_shift = 0;
+  std::vector<uint8_t *> slabs;
+  uint8_t **d_slabtab = nullptr, *d_stage = nullptr;
+  int *d_slot = nullptr, *d_mloc = nullptr, *d_blk = nullptr, *d_pq = nullptr;   // slot per push ordinal, location per medoid entry, prefix-sum scratch, queue per row of the push
+  size_t slabtab_cap = 0, stage_cap = 0, blk_cap = 0, pq_cap = 0;
+  long long kept = 0;                      // founders so far = slots in use
+  std::vector<int> h_slot;                 // d_slot on the host: uvaia_clust_rows and uvaia_clust_gather_device check their ordinals against it
+  size_t peak_row_bytes = 0;
   std::vector<long long> per_queue;        // rows pushed to each queue so far (bounds its medoid count)
   std::vector<int> queue_of;               // queue of every pushed row
   std::vector<uint8_t> h_rows;
@@ -402,7 +518,12 @@ int ensure_rows(uvaia_clust_ctx *c, size_t need)
   const size_t cap = std::max(need, std::max<size_t>(c->rows_cap * 2, 1024));
   const size_t old = (size_t)c->pushed;
   int rc;
-  if ((rc = grow(c, (void **)&c->d_rows, old * c->pitch, cap * c->pitch))) return rc;
+  if (c->keep) {                       // the text of the rows is not kept: their slots are
+    if ((rc = grow(c, (void **)&c->d_slot, old * sizeof(int), cap * sizeof(int)))) return rc;
+  } else {
+    c->peak_row_bytes = std::max(c->peak_row_bytes, (c->rows_cap + cap) * c->pitch);     // grow() holds the old and the new array at once
+    if ((rc = grow(c, (void **)&c->d_rows, old * c->pitch, cap * c->pitch))) return rc;
+  }
   if ((rc = grow(c, (void **)&c->d_dist, old * sizeof(int), cap * sizeof(int)))) return rc;
   if ((rc = grow(c, (void **)&c->d_p, old * std::max(c->n_score, 1) * sizeof(int), cap * std::max(c->n_score, 1) * sizeof(int)))) return rc;
   if ((rc = grow(c, (void **)&c->d_join, old * sizeof(int), cap * sizeof(int)))) return rc;
@@ -416,16 +537,18 @@ int ensure_medoids(uvaia_clust_ctx *c, long long need)
   if (need <= c->m_cap) return 0;
   if (need > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences in one queue", INT_MAX / 2);
   const int cap = (int)std::max<long long>(need, std::max(2LL * c->m_cap, 256LL));
-  int *no = nullptr, *ns = nullptr;
+  int *no = nullptr, *ns = nullptr, *nl = nullptr;
   CCHK(c, hipMalloc(&no, (size_t)c->n_queues * cap * sizeof(int)));
   CCHK(c, hipMalloc(&ns, (size_t)c->n_queues * cap * sizeof(int)));
+  if (c->keep) CCHK(c, hipMalloc(&nl, (size_t)c->n_queues * cap * sizeof(int)));
   if (c->m_cap) {
+    if (c->keep) CCHK(c, hipMemcpy2DAsync(nl, (size_t)cap * sizeof(int), c->d_mloc, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
     CCHK(c, hipMemcpy2DAsync(no, (size_t)cap * sizeof(int), c->d_mord, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
     CCHK(c, hipMemcpy2DAsync(ns, (size_t)cap * sizeof(int), c->d_mst, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
   }
   CCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(c->d_mord); hipFree(c->d_mst);
-  c->d_mord = no; c->d_mst = ns; c->m_cap = cap;
+  hipFree(c->d_mord); hipFree(c->d_mst); hipFree(c->d_mloc);
+  c->d_mord = no; c->d_mst = ns; c->d_mloc = nl; c->m_cap = cap;
   return 0;
 }
 
@@ -441,6 +564,50 @@ int ensure_bytes(uvaia_clust_ctx *c, void **ptr, size_t *cap, size_t want)
   CCHK(c, hipMalloc(ptr, want));
   *cap = want;
   return 0;
+}
+
+size_t row_bytes_now(const uvaia_clust_ctx *c)
+{
+  return c->keep ? c->slabs.size() * (size_t)c->slab_rows * c->pitch + c->stage_cap : c->rows_cap * c->pitch;
+}
+
+// keep medoids: slabs for `need` slots.  A new slab is a new allocation: nothing is copied, the table of base pointers is sent again.
+int ensure_slabs(uvaia_clust_ctx *c, long long need)
+{
+  const size_t want = (size_t)((need + c->slab_rows - 1) >> c->slab_shift);
+  if (want <= c->slabs.size()) return 0;
+  while (c->slabs.size() < want) {
+    uint8_t *p = nullptr;
+    CCHK(c, hipMalloc(&p, (size_t)c->slab_rows * c->pitch));
+    c->slabs.push_back(p);
+  }
+  if (want > c->slabtab_cap) {
+    size_t cap = 0;
+    if (int rc = ensure_bytes(c, (void **)&c->d_slabtab, &cap, std::max(want, 2 * c->slabtab_cap) * sizeof(uint8_t *))) { c->slabtab_cap = 0; return rc; }
+    c->slabtab_cap = cap / sizeof(uint8_t *);
+  }
+  CCHK(c, hipMemcpyAsync(c->d_slabtab, c->slabs.data(), c->slabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));
+  c->peak_row_bytes = std::max(c->peak_row_bytes, row_bytes_now(c));
+  return 0;
+}
+
+// where the n rows of a push (ordinals first ..) are written: their place in the store, or the staging buffer
+int push_rows_dst(uvaia_clust_ctx *c, long long first, int n, uint8_t **dst)
+{
+  int rc;
+  if ((rc = ensure_rows(c, (size_t)first + n))) return rc;
+  if (c->keep) {
+    if ((rc = ensure_bytes(c, (void **)&c->d_stage, &c->stage_cap, (size_t)n * c->pitch))) return rc;
+    *dst = c->d_stage;
+  } else *dst = c->d_rows + (size_t)first * c->pitch;
+  c->peak_row_bytes = std::max(c->peak_row_bytes, row_bytes_now(c));
+  return 0;
+}
+
+SlabRows slab_rows_of(const uvaia_clust_ctx *c, long long first)
+{
+  return SlabRows{c->d_stage, c->d_slabtab, c->pitch, c->d_slot, c->d_mloc, first, c->slab_shift, c->slab_rows - 1};
 }
 
 // what both kinds of push check first
@@ -475,17 +642,53 @@ int push_lists(uvaia_clust_ctx *c, long long first, int n, const int *queue)
   }
   CCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   CCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (c->keep) {
+    if (int rc = ensure_bytes(c, (void **)&c->d_pq, &c->pq_cap, (size_t)n * sizeof(int))) return rc;
+    CCHK(c, hipMemcpyAsync(c->d_pq, queue, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
   CCHK(c, hipStreamSynchronize(c->stream));            // qoff and qlist leave scope
   return 0;
 }
 
-// prep and phase 2 for the rows first .. first + n of the store; seq (nullable): their text on the host, for the message about a bad byte
-int push_kernels(uvaia_clust_ctx *c, long long first, int n, const char *const *seq)
+// keep medoids, after the queue kernel: slots for the founders of the push, their rows from staging into the slabs
+int keep_founders(uvaia_clust_ctx *c, long long first, int n)
+{
+  const int nb = (n + KTPB - 1) / KTPB;
+  int rc, founders = 0;
+  if ((rc = ensure_bytes(c, (void **)&c->d_blk, &c->blk_cap, ((size_t)nb + 1) * sizeof(int)))) return rc;
+  hipLaunchKernelGGL(clust_founder_count_kernel, dim3((unsigned)nb), dim3(KTPB), 0, c->stream, c->d_join, first, n, c->d_blk);
+  CCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(clust_founder_offsets_kernel, dim3(1), dim3(KTPB), 0, c->stream, c->d_blk, nb);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipMemcpyAsync(&founders, c->d_blk + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));
+  if (founders < 0 || founders > n) { c->broken = true; return cfail(c, UVAIA_GPU_EHIP, "push of %d sequences: %d founders counted", n, founders); }
+  if ((rc = ensure_slabs(c, c->kept + founders))) return rc;          // before anything is written to a slot
+  hipLaunchKernelGGL(clust_founder_slots_kernel, dim3((unsigned)nb), dim3(KTPB), 0, c->stream, c->d_join, c->d_pq, first, n, c->d_blk, (int)c->kept, c->d_slot,
+                     c->d_mloc, c->m_cap);
+  CCHK(c, hipGetLastError());
+  if (founders) {
+    hipLaunchKernelGGL(clust_keep_founders_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, c->d_stage, c->pitch, first, c->d_slot, c->d_slabtab, c->slab_shift,
+                       c->slab_rows - 1);
+    CCHK(c, hipGetLastError());
+  }
+  c->h_slot.resize((size_t)first + n);
+  CCHK(c, hipMemcpyAsync(c->h_slot.data() + first, c->d_slot + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  CCHK(c, hipStreamSynchronize(c->stream));
+  c->kept += founders;
+  return 0;
+}
+
+// prep and phase 2 for the rows first .. first + n, which lie at rows (their place in the store, or staging); seq (nullable): their text on
+// the host, for the message about a bad byte
+int push_kernels(uvaia_clust_ctx *c, uint8_t *rows, long long first, int n, const char *const *seq)
 {
   const int big = INT_MAX;
   float ms = 0;
+  // prep addresses row o at base + o * pitch: for staging the base is the address its row `first` would have, and only rows first .. are touched
+  uint8_t *prep_base = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(rows) - (uintptr_t)((size_t)first * c->pitch));
   CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, first, n, c->d_ref,
+  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, prep_base, c->pitch, first, n, c->d_ref,
                      c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
   CCHK(c, hipGetLastError());
   CCHK(c, hipEventRecord(c->ev_b, c->stream));
@@ -504,14 +707,43 @@ int push_kernels(uvaia_clust_ctx *c, long long first, int n, const char *const *
   }
 
   CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_queue_kernel, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar, c->trim, c->dist, c->n_score,
-                     c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+  if (c->keep)
+    hipLaunchKernelGGL(clust_queue_kernel<SlabRows>, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, slab_rows_of(c, first), c->nchar, c->trim, c->dist,
+                       c->n_score, c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+  else
+    hipLaunchKernelGGL(clust_queue_kernel<FlatRows>, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->nchar, c->trim, c->dist,
+                       c->n_score, c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
   CCHK(c, hipGetLastError());
   CCHK(c, hipEventRecord(c->ev_b, c->stream));
   CCHK(c, hipEventSynchronize(c->ev_b));
   CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
   c->queue_ms += ms;
+  if (c->keep) if (int rc = keep_founders(c, first, n)) return rc;
   c->pushed += n;
+  return 0;
+}
+
+// rows ordinal[0 .. n) into the gather buffer, row k at d_gather + k * pitch.  Keep medoids: every ordinal must have founded a cluster.
+int gather_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n)
+{
+  std::vector<int> ord((size_t)n);
+  for (int k = 0; k < n; k++) {
+    if (ordinal[k] < 0 || ordinal[k] >= c->pushed) return cfail(c, UVAIA_GPU_EINVAL, "ordinal[%d] = %lld: %lld sequences were pushed", k, (long long)ordinal[k], c->pushed);
+    if (c->keep && c->h_slot[(size_t)ordinal[k]] < 0)
+      return cfail(c, UVAIA_GPU_EINVAL, "ordinal[%d] = %lld joined a cluster: this context keeps the rows of the sequences that founded one only", k, (long long)ordinal[k]);
+    ord[(size_t)k] = (int)ordinal[k];
+  }
+  hipSetDevice(c->device);
+  int rc;
+  if ((rc = ensure_bytes(c, (void **)&c->d_gord, &c->gord_cap, (size_t)n * sizeof(int)))) return rc;
+  if ((rc = ensure_bytes(c, (void **)&c->d_gather, &c->gather_cap, (size_t)n * c->pitch))) return rc;
+  CCHK(c, hipMemcpyAsync(c->d_gord, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (c->keep)
+    hipLaunchKernelGGL(clust_gather_rows_kernel<SlabRows>, dim3((unsigned)n), dim3(256), 0, c->stream, slab_rows_of(c, c->pushed), c->d_gord, c->d_gather);
+  else
+    hipLaunchKernelGGL(clust_gather_rows_kernel<FlatRows>, dim3((unsigned)n), dim3(256), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->d_gord, c->d_gather);
+  CCHK(c, hipGetLastError());
+  CCHK(c, hipStreamSynchronize(c->stream));        // ord leaves scope
   return 0;
 }
 
@@ -546,6 +778,8 @@ void uvaia_clust_close(uvaia_clust_ctx *c)
   hipFree(c->d_ref); hipFree(c->d_rows); hipFree(c->d_dist); hipFree(c->d_p); hipFree(c->d_join); hipFree(c->d_bad);
   hipFree(c->d_qoff); hipFree(c->d_qlist); hipFree(c->d_mcount); hipFree(c->d_mord); hipFree(c->d_mst);
   hipFree(c->d_tiles); hipFree(c->d_gather); hipFree(c->d_xoff); hipFree(c->d_xrec); hipFree(c->d_gord);
+  hipFree(c->d_slabtab); hipFree(c->d_stage); hipFree(c->d_slot); hipFree(c->d_mloc); hipFree(c->d_blk); hipFree(c->d_pq);
+  for (uint8_t *p : c->slabs) hipFree(p);
   if (c->ev_a) hipEventDestroy(c->ev_a);
   if (c->ev_b) hipEventDestroy(c->ev_b);
   if (c->stream) hipStreamDestroy(c->stream);
@@ -598,14 +832,15 @@ int uvaia_clust_push(uvaia_clust_ctx *c, int n, const char *const *seq, const in
   for (int i = 0; i < n; i++) if (!seq[i]) return cfail(c, UVAIA_GPU_EINVAL, "sequence %d of the push is null", i);
   hipSetDevice(c->device);
   int rc;
-  if ((rc = ensure_rows(c, (size_t)c->pushed + n))) return rc;
   const long long first = c->pushed;
+  uint8_t *dst = nullptr;
+  if ((rc = push_rows_dst(c, first, n, &dst))) return rc;
   // rows, padded with zero bytes to the pitch
   c->h_rows.assign((size_t)n * c->pitch, 0);
   for (int i = 0; i < n; i++) memcpy(c->h_rows.data() + (size_t)i * c->pitch, seq[i], (size_t)c->nchar);
-  CCHK(c, hipMemcpyAsync(c->d_rows + (size_t)first * c->pitch, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
+  CCHK(c, hipMemcpyAsync(dst, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
   if ((rc = push_lists(c, first, n, queue))) return rc;
-  return push_kernels(c, first, n, seq);
+  return push_kernels(c, dst, first, n, seq);
 }
 
 int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const uint64_t *exc_offsets, const void *exc, const int *queue)
@@ -636,8 +871,9 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
   }
   hipSetDevice(c->device);
   int rc;
-  if ((rc = ensure_rows(c, (size_t)c->pushed + n))) return rc;
   const long long first = c->pushed;
+  uint8_t *dst = nullptr;
+  if ((rc = push_rows_dst(c, first, n, &dst))) return rc;
   const int W4 = ((c->nchar + 31) / 32 + 3) / 4, n_tiles = (n + 63) / 64;
   const size_t tile_bytes = (size_t)W4 * 4 * 64 * 16, n_rec = (size_t)(x1 - x0);
   if ((rc = ensure_bytes(c, (void **)&c->d_tiles, &c->tiles_cap, (size_t)n_tiles * tile_bytes))) return rc;
@@ -650,7 +886,6 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
     CCHK(c, hipMemcpyAsync(c->d_xoff, c->h_xoff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     CCHK(c, hipMemcpyAsync(c->d_xrec, rec + x0, n_rec * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
   }
-  uint8_t *dst = c->d_rows + (size_t)first * c->pitch;
   const int units = (W4 + UGROUPS - 1) / UGROUPS;
   float ms = 0;
   CCHK(c, hipEventRecord(c->ev_a, c->stream));
@@ -671,7 +906,7 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
     c->overlay_ms += ms;
   }
   if ((rc = push_lists(c, first, n, queue))) return rc;
-  return push_kernels(c, first, n, nullptr);
+  return push_kernels(c, dst, first, n, nullptr);
 }
 
 int uvaia_clust_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch)
@@ -681,20 +916,23 @@ int uvaia_clust_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *ro
   if (n < 0 || (n && (!ordinal || !rows))) return cfail(c, UVAIA_GPU_EINVAL, "bad arguments");
   if (n && pitch < (size_t)c->nchar) return cfail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
   if (!n) return 0;
-  std::vector<int> ord((size_t)n);
-  for (int k = 0; k < n; k++) {
-    if (ordinal[k] < 0 || ordinal[k] >= c->pushed) return cfail(c, UVAIA_GPU_EINVAL, "ordinal[%d] = %lld: %lld sequences were pushed", k, (long long)ordinal[k], c->pushed);
-    ord[(size_t)k] = (int)ordinal[k];
-  }
-  hipSetDevice(c->device);
-  int rc;
-  if ((rc = ensure_bytes(c, (void **)&c->d_gord, &c->gord_cap, (size_t)n * sizeof(int)))) return rc;
-  if ((rc = ensure_bytes(c, (void **)&c->d_gather, &c->gather_cap, (size_t)n * c->pitch))) return rc;
-  CCHK(c, hipMemcpyAsync(c->d_gord, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(clust_gather_rows_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, c->d_rows, c->pitch, c->d_gord, c->d_gather);
-  CCHK(c, hipGetLastError());
+  if (int rc = gather_rows(c, ordinal, n)) return rc;
   CCHK(c, hipMemcpy2DAsync(rows, pitch, c->d_gather, c->pitch, (size_t)c->nchar, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   CCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int uvaia_clust_gather_device(uvaia_clust_ctx *c, const int64_t *ordinal, int n, const void **d_rows, size_t *pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (n < 0 || (n && !ordinal)) return cfail(c, UVAIA_GPU_EINVAL, "bad arguments");
+  if (n) {
+    if (int rc = gather_rows(c, ordinal, n)) return rc;
+    CCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (d_rows) *d_rows = n ? c->d_gather : nullptr;
+  if (pitch) *pitch = c->pitch;
   return 0;
 }
 
@@ -702,8 +940,36 @@ int uvaia_clust_device_rows(uvaia_clust_ctx *c, const void **d_rows, size_t *pit
 {
   if (!c) return UVAIA_GPU_EINVAL;
   if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (c->keep) return cfail(c, UVAIA_GPU_ESTATE, "this context keeps medoid rows only, in slabs: there is no row store to hand out; uvaia_clust_gather_device gives the rows of medoids");
   if (d_rows) *d_rows = c->d_rows;
   if (pitch) *pitch = c->pitch;
+  return 0;
+}
+
+int uvaia_clust_keep_medoids(uvaia_clust_ctx *c, int slab_rows)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (c->pushed || c->finished) return cfail(c, UVAIA_GPU_ESTATE, "uvaia_clust_keep_medoids after a push: the mode is chosen before the first one");
+  if (slab_rows < 0 || (slab_rows & (slab_rows - 1))) return cfail(c, UVAIA_GPU_EINVAL, "slab_rows %d is not a power of two", slab_rows);
+  c->keep = true;
+  c->slab_rows = slab_rows ? slab_rows : SLAB_ROWS;
+  c->slab_shift = 0;
+  while ((1 << c->slab_shift) < c->slab_rows) c->slab_shift++;
+  return 0;
+}
+
+int uvaia_clust_memory(uvaia_clust_ctx *c, size_t *row_bytes, size_t *peak_row_bytes, size_t *free_bytes)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (row_bytes) *row_bytes = row_bytes_now(c);
+  if (peak_row_bytes) *peak_row_bytes = std::max(c->peak_row_bytes, row_bytes_now(c));
+  if (free_bytes) {
+    size_t fr = 0, total = 0;
+    hipSetDevice(c->device);
+    if (hipMemGetInfo(&fr, &total) != hipSuccess) return cfail(c, UVAIA_GPU_EHIP, "cannot query the free memory of device %d", c->device);
+    *free_bytes = fr;
+  }
   return 0;
 }
 
@@ -785,8 +1051,13 @@ int uvaia_clust_finish(uvaia_clust_ctx *c)
       up(d_item_ord, item_ord); up(d_item_lo, item_lo); up(d_item_hi, item_hi); up(d_list, list);
       if (e == hipSuccess) e = hipEventRecord(c->ev_a, c->stream);
       if (e == hipSuccess) {
-        hipLaunchKernelGGL(clust_merge_kernel, dim3((unsigned)((n_items + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, c->d_rows, c->pitch, c->nchar,
-                           c->trim, c->dist, d_item_ord, d_item_lo, d_item_hi, d_list, n_items, d_target);
+        const dim3 grid((unsigned)((n_items + PTPB / 64 - 1) / (PTPB / 64)));
+        if (c->keep)
+          hipLaunchKernelGGL(clust_merge_kernel<SlabRows>, grid, dim3(PTPB), 0, c->stream, slab_rows_of(c, c->pushed), c->nchar, c->trim, c->dist, d_item_ord, d_item_lo,
+                             d_item_hi, d_list, n_items, d_target);
+        else
+          hipLaunchKernelGGL(clust_merge_kernel<FlatRows>, grid, dim3(PTPB), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->nchar, c->trim, c->dist, d_item_ord, d_item_lo,
+                             d_item_hi, d_list, n_items, d_target);
         e = hipGetLastError();
       }
       if (e == hipSuccess) e = hipEventRecord(c->ev_b, c->stream);
