@@ -370,11 +370,27 @@ int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const
  *                  not touched.  Returns when the window is complete.
  *   db_unpack_rows the contract of uvaia_gpu_unpack_rows for positions of the window loaded last, in default-mode and --acgt contexts
  *                  (the latter keep a four-plane image of the window for it).
+ *   stage_packed_at  stage_packed for a piece of a slot: the n_tiles tiles land at tile `tile_offset` of the slot, so that spans of several
+ *                  files sit one after another in one slot and sel indexes the slot.  A piece at tile 0 starts the slot afresh (its tile
+ *                  count becomes n_tiles); a later piece leaves the count at the largest end reached.  A piece that ends beyond the
+ *                  reserved capacity is refused with UVAIA_GPU_ESTATE.  Tiles of the slot no piece has filled hold whatever they held.
+ *   append_staged  waits for the slot's copy and appends references sel[0 .. n_ref) of it (NULL: positions 0 .. n_ref - 1) BEHIND the
+ *                  uvaia_gpu_db_size() references already resident, whatever that size is modulo 64: reference db_size + k goes to tile
+ *                  (db_size + k) / 64, lane (db_size + k) % 64 with its plane words, valid-site count and side row.  The database is not
+ *                  cleared and the resident lanes of the first tile are not written; lanes past the new end of the last tile are zero
+ *                  (what uvaia_gpu_db_export promises).  Re-coding (--acgt), totals, the checks on side rows and counts and the derived
+ *                  planes are made for the rows added, as uvaia_gpu_db_append_packed makes them; db_unpack_rows then decodes positions of
+ *                  the whole resident database (--acgt: as long as all of it came through load_staged / append_staged since it was last
+ *                  empty; db_clear, the other appends and db_drop_tiles end the image, and db_unpack_rows then answers UVAIA_GPU_ESTATE).  Refusals as
+ *                  load_staged, before anything is launched; capacity as uvaia_gpu_db_append_packed (reserve before the first append).
+ *                  Several packed files load as one stream this way, and a merge is stage -> append_staged -> export.
  *   window_ms      device time in ms since the last reset of [0] the selection, [1] totals, checks and derived planes after it, [2] the decode
  *   free_bytes     free memory of the context's device as the runtime reports it (0: the runtime could not tell) */
 int uvaia_gpu_db_stage_reserve (uvaia_gpu_ctx *ctx, size_t n_tiles);
 int uvaia_gpu_db_stage_packed (uvaia_gpu_ctx *ctx, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles);
 int uvaia_gpu_db_load_staged (uvaia_gpu_ctx *ctx, int slot, const int *sel, int n_ref);
+int uvaia_gpu_db_stage_packed_at (uvaia_gpu_ctx *ctx, int slot, size_t tile_offset, const void *planes, const int *non_n, const int *side_rows, int n_tiles);
+int uvaia_gpu_db_append_staged (uvaia_gpu_ctx *ctx, int slot, const int *sel, int n_ref);
 int uvaia_gpu_db_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
 void uvaia_gpu_window_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 size_t uvaia_gpu_free_bytes (uvaia_gpu_ctx *ctx);

@@ -30,6 +30,7 @@ SYMBOLS = [
     "uvaia_gpu_group_db_size", "uvaia_gpu_group_reset", "uvaia_gpu_group_search_resident", "uvaia_gpu_group_push", "uvaia_gpu_group_drain", "uvaia_gpu_group_sync",
     "uvaia_gpu_rows_census", "uvaia_gpu_db_append_device", "uvaia_gpu_rows_exceptions", "uvaia_gpu_db_drop_tiles", "uvaia_gpu_rows_kernel_ms", "uvaia_gpu_rows_set_run_cut",
     "uvaia_gpu_db_stage_reserve", "uvaia_gpu_db_stage_packed", "uvaia_gpu_db_load_staged", "uvaia_gpu_db_unpack_rows", "uvaia_gpu_window_ms", "uvaia_gpu_free_bytes",
+    "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged",
 ]
 
 
@@ -190,6 +191,8 @@ def load_library():
         "uvaia_gpu_db_stage_reserve": (C.c_int, [vp, C.c_size_t]),
         "uvaia_gpu_db_stage_packed": (C.c_int, [vp, C.c_int, C.c_void_p, pi, pi, C.c_int]),
         "uvaia_gpu_db_load_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
+        "uvaia_gpu_db_stage_packed_at": (C.c_int, [vp, C.c_int, C.c_size_t, C.c_void_p, pi, pi, C.c_int]),
+        "uvaia_gpu_db_append_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
         "uvaia_gpu_db_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_window_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
@@ -593,6 +596,27 @@ class Engine:
         """the resident database becomes references sel[0 .. n_ref) of the slot (None: the first n_ref)"""
         _k, sp = _int_ptr(sel)
         self._chk(self.L.uvaia_gpu_db_load_staged(self.ctx, int(slot), sp, int(n_ref)))
+
+    def db_stage_packed_at(self, slot, tile_offset, planes, non_n, side_rows, n_tiles):
+        """db_stage_packed for a piece of a slot: the tiles land at tile_offset (a piece at 0 starts the slot afresh)"""
+        planes = np.ascontiguousarray(planes, dtype=np.uint8)
+        non_n = np.ascontiguousarray(non_n, dtype=np.int32)
+        side_rows = np.ascontiguousarray(side_rows, dtype=np.int32)
+        tb = self.L.uvaia_gpu_db_tile_bytes(self.ctx)
+        if planes.size < int(n_tiles) * tb or non_n.size < int(n_tiles) * 64 or side_rows.size < int(n_tiles) * 64 * self.L.uvaia_gpu_db_side_row_ints():
+            raise ValueError("arrays shorter than %d tiles" % n_tiles)
+        if not hasattr(self, "_staged_at"):
+            self._staged_at = {}
+        if int(tile_offset) == 0:
+            self._staged_at[int(slot)] = []
+        self._staged_at.setdefault(int(slot), []).append((planes, non_n, side_rows))
+        self._chk(self.L.uvaia_gpu_db_stage_packed_at(self.ctx, int(slot), int(tile_offset), planes.ctypes.data, non_n.ctypes.data_as(C.POINTER(C.c_int)),
+                                                      side_rows.ctypes.data_as(C.POINTER(C.c_int)), int(n_tiles)))
+
+    def db_append_staged(self, slot, sel, n_ref):
+        """references sel[0 .. n_ref) of the slot (None: the first n_ref) go behind the resident ones, at any database size"""
+        _k, sp = _int_ptr(sel)
+        self._chk(self.L.uvaia_gpu_db_append_staged(self.ctx, int(slot), sp, int(n_ref)))
 
     def db_unpack_rows(self, index, pitch=None):
         """Upper-case text of references index[] of the window loaded last, as a list of bytes (exception runs not applied)."""

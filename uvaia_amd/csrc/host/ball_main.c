@@ -13,15 +13,19 @@
 #include "gpu_glue.h"
 #include "prepare.h"
 #include "uvdb.h"
+#include "uvdb_set.h"
 
 #define PACKED_CHUNK 65536    /* references per round trip of the packed path without -p (1 024 tiles) */
 
 /* ---- the packed path: the per-batch loop of src/ball.c:248-259 for a database whose text is not in memory.  Chunks of whole tiles
  * go from the mapping to the engine as they are; the text of the kept references comes back from the device.  Chunk c belongs to
- * member c mod n (one context and one host thread per member); records are written in chunk order. */
+ * member c mod n (one context and one host thread per member); records are written in chunk order.  Several files (a repeated --packed)
+ * are searched one after the other: the chunks of the first, then those of the second, and so on -- a chunk never spans two files, and
+ * uvaia_gpu_ball_packed ignores the lanes past a file's last reference. */
+typedef struct { int file; uint64_t first, cnt; } packed_chunk;
 typedef struct {
-  uvdb_reader db;
-  const char *file;
+  uvdb_reader *dbs; int n_files;
+  packed_chunk *chunks;
   uvaia_gpu_ctx **gpu;
   int n_members, dist, non_n_ref, nchar;
   uint64_t chunk, n_chunks;
@@ -36,19 +40,19 @@ typedef struct {
 static void
 packed_member (packed_run *run, int m)
 {
-  const uint64_t n_ref = run->db->h.n_ref;
   const size_t pitch = ((size_t) run->nchar + 16) / 16 * 16;       /* room for the NUL; the engine's own row pitch unless nchar is a multiple of 16 */
   int *mindist = (int *) biomcmc_malloc ((size_t) run->chunk * sizeof (int)), *keep = (int *) biomcmc_malloc ((size_t) run->chunk * sizeof (int));
   char *rows = NULL;
   size_t rows_cap = 0;
   for (uint64_t c = (uint64_t) m; c < run->n_chunks; c += (uint64_t) run->n_members) {
-    const uint64_t first = c * run->chunk, cnt = (n_ref - first < run->chunk) ? n_ref - first : run->chunk;
+    const uint64_t first = run->chunks[c].first, cnt = run->chunks[c].cnt;
+    uvdb_reader db = run->dbs[run->chunks[c].file];
     double t0 = omp_get_wtime ();
-    if (uvaia_gpu_ball_packed (run->gpu[m], uvdb_tile_planes (run->db, first / 64), (int) cnt, run->dist + 1, mindist)) biomcmc_error ("%s", uvaia_gpu_last_error (run->gpu[m]));
+    if (uvaia_gpu_ball_packed (run->gpu[m], uvdb_tile_planes (db, first / 64), (int) cnt, run->dist + 1, mindist)) biomcmc_error ("%s", uvaia_gpu_last_error (run->gpu[m]));
     double t1 = omp_get_wtime ();
     int n_keep = 0, invalid = 0;
     for (uint64_t i = 0; i < cnt; i++) {
-      if (run->db->non_n[first + i] < run->non_n_ref) invalid++;
+      if (db->non_n[first + i] < run->non_n_ref) invalid++;
       else if (mindist[i] <= run->dist) keep[n_keep++] = (int) i;
     }
     if ((size_t) n_keep > rows_cap) {
@@ -59,14 +63,14 @@ packed_member (packed_run *run, int m)
     if (uvaia_gpu_unpack_rows (run->gpu[m], keep, n_keep, rows, pitch)) biomcmc_error ("%s", uvaia_gpu_last_error (run->gpu[m]));
     for (int k = 0; k < n_keep; k++) {
       rows[(size_t) k * pitch + (size_t) run->nchar] = '\0';
-      uvdb_apply_exceptions (run->db, first + (uint64_t) keep[k], rows + (size_t) k * pitch);
+      uvdb_apply_exceptions (db, first + (uint64_t) keep[k], rows + (size_t) k * pitch);
     }
     double t2 = omp_get_wtime ();
     pthread_mutex_lock (&run->lock);
     while (run->next_chunk != c) pthread_cond_wait (&run->turn, &run->lock);
     pthread_mutex_unlock (&run->lock);
     double t3 = omp_get_wtime ();        /* it is this chunk's turn: nobody else writes */
-    for (int k = 0; k < n_keep; k++) write_fasta_record (run->out, uvdb_name (run->db, first + (uint64_t) keep[k]), rows + (size_t) k * pitch);
+    for (int k = 0; k < n_keep; k++) write_fasta_record (run->out, uvdb_name (db, first + (uint64_t) keep[k]), rows + (size_t) k * pitch);
     double t4 = omp_get_wtime ();
     pthread_mutex_lock (&run->lock);
     run->n_output += n_keep; run->n_invalid += invalid;
@@ -89,24 +93,41 @@ packed_thread_main (void *arg)
 }
 
 static void
-search_packed (const char *packed, query_t query, int dist, double ambig_r, int pool, const int *devices, int n_devices, file_compress_t outstream, int64_t *time0)
+search_packed (const char *const *files, int n_files, query_t query, int dist, double ambig_r, int pool, const int *devices, int n_devices, file_compress_t outstream, int64_t *time0)
 {
-  char msg[512];
+  char msg[1024];
   packed_run run;
   memset (&run, 0, sizeof run);
-  run.db = uvdb_open (packed, msg, sizeof msg);
-  if (!run.db) biomcmc_error ("%s", msg);
-  const struct uvdb_header *h = &run.db->h;
+  /* the set checks that the files agree on the alignment length and the tile layout; the filter of the radius search is judged file by file */
+  uvdb_set set = uvdb_set_open (files, n_files, UVDB_SET_ANY_AMBIGUITY, msg, sizeof msg);
+  if (!set) biomcmc_error ("%s", msg);
+  const char *packed = files[0];
+  const struct uvdb_header *h = &set->db[0]->h;
   if ((int) h->nchar != query->aln->nchar) biomcmc_error ("packed database %s has %u sites but query sequences have %d sites; all sequences must be aligned", packed, h->nchar, query->aln->nchar);
-  if (!uvdb_radius_filter_is_exact ((int) h->nchar, ambig_r, h->ref_ambiguity))
-    biomcmc_error ("packed database %s was filtered with -A %g (at least %d valid sites), this search with -A %g keeps references from %d valid sites: some are not in the file; pack with a larger -A or use -r",
-                   packed, h->ref_ambiguity, (int) (h->nchar * (1. - h->ref_ambiguity)), ambig_r, (int) (h->nchar * ambig_r));
-  fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) h->n_ref, packed, biomcmc_update_elapsed_time (time0));
-  /* chunks of whole tiles: -p rounded down to a multiple of 64, never more than the database */
+  uint64_t max_tiles = 0;
+  for (int f = 0; f < n_files; f++) {
+    const struct uvdb_header *hf = &set->db[f]->h;
+    if (!uvdb_radius_filter_is_exact ((int) hf->nchar, ambig_r, hf->ref_ambiguity))
+      biomcmc_error ("packed database %s was filtered with -A %g (at least %d valid sites), this search with -A %g keeps references from %d valid sites: some are not in the file; pack with a larger -A or use -r",
+                     files[f], hf->ref_ambiguity, (int) (hf->nchar * (1. - hf->ref_ambiguity)), ambig_r, (int) (hf->nchar * ambig_r));
+    if (hf->n_tiles > max_tiles) max_tiles = hf->n_tiles;
+  }
+  if (n_files == 1) fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) set->n_ref, packed, biomcmc_update_elapsed_time (time0));
+  else              fprintf (stderr, "Loaded %d packed sequences from %d files in %.3lf secs;\n", (int) set->n_ref, n_files, biomcmc_update_elapsed_time (time0));
+  /* chunks of whole tiles: -p rounded down to a multiple of 64, never more than the (largest) database */
   uint64_t chunk = pool > 0 ? (uint64_t) (pool / 64) * 64 : PACKED_CHUNK;
-  if (chunk > h->n_tiles * 64) chunk = h->n_tiles * 64;
+  if (chunk > max_tiles * 64) chunk = max_tiles * 64;
   if (chunk < 64) chunk = 64;
-  run.file = packed; run.chunk = chunk; run.n_chunks = (h->n_ref + chunk - 1) / chunk;
+  run.dbs = set->db; run.n_files = n_files; run.chunk = chunk;
+  for (int f = 0; f < n_files; f++) run.n_chunks += (set->db[f]->h.n_ref + chunk - 1) / chunk;
+  run.chunks = (packed_chunk *) biomcmc_malloc ((size_t) (run.n_chunks ? run.n_chunks : 1) * sizeof (packed_chunk));
+  {
+    uint64_t c = 0;
+    for (int f = 0; f < n_files; f++) for (uint64_t first = 0; first < set->db[f]->h.n_ref; first += chunk, c++) {
+      const uint64_t left = set->db[f]->h.n_ref - first;
+      run.chunks[c].file = f; run.chunks[c].first = first; run.chunks[c].cnt = left < chunk ? left : chunk;
+    }
+  }
   run.n_members = n_devices; run.dist = query->dist; run.nchar = query->aln->nchar; run.out = outstream;
   run.non_n_ref = (int) (query->aln->nchar * ambig_r);                /* src/ball.c:201 */
   run.gpu = (uvaia_gpu_ctx **) biomcmc_malloc ((size_t) n_devices * sizeof (uvaia_gpu_ctx *));
@@ -126,13 +147,13 @@ search_packed (const char *packed, query_t query, int dist, double ambig_r, int 
   free (th);
   pthread_cond_destroy (&run.turn);
   pthread_mutex_destroy (&run.lock);
-  fprintf (stderr, "Finished searching packed database %s in %.3lf secs; Total of %d sequences read, %d sequences within radius (kept), %d too ambiguous (excluded)\n",
-           packed, biomcmc_update_elapsed_time (time0), (int) h->n_ref, run.n_output, run.n_invalid);
+  fprintf (stderr, "Finished searching packed database %s%s in %.3lf secs; Total of %d sequences read, %d sequences within radius (kept), %d too ambiguous (excluded)\n",
+           packed, n_files > 1 ? " and the files after it" : "", biomcmc_update_elapsed_time (time0), (int) set->n_ref, run.n_output, run.n_invalid);
   fprintf (stderr, "Time in seconds, summed over the device contexts: %.3lf search (with the copy of the tiles), %.3lf unpack, %.3lf write\n", run.t_search, run.t_unpack, run.t_write);
   fprintf (stderr, "Saved %d sequences to file %s\n", run.n_output, outstream->filename);
   for (int m = 0; m < n_devices; m++) uvaia_gpu_close (run.gpu[m]);
-  free (run.gpu);
-  uvdb_close_reader (run.db);
+  free (run.gpu); free (run.chunks);
+  uvdb_set_close (set);
 }
 
 int
@@ -142,6 +163,7 @@ main (int argc, char **argv)
   int devices[64], n_devices = 0;
   double ambig_q = 0.5, ambig_r = 0.5;
   const char *out = NULL, *qfile = NULL, *packed = NULL;
+  const char **packed_files = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *)); int n_packed = 0;
   const char **ref = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *));
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"acgt", no_argument, 0, 1000}, {"keep_resolved", no_argument, 0, 'k'},
@@ -163,20 +185,22 @@ main (int argc, char **argv)
     case 't': break;                                  /* host threads do not matter here */
     case 'o': out = optarg; break;
     case 1002: device = atoi (optarg); break;
-    case 1003: packed = optarg; break;
+    case 1003: if (!packed) packed = optarg; packed_files[n_packed++] = optarg; break;
     case 1004: n_devices = uvaia_parse_device_list (optarg, devices, 64); if (!n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); errors++; } break;
     default: errors++;
   }
   if (optind < argc) qfile = argv[optind++];
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
   if (n_devices && !packed && !help) { fprintf (stderr, "--devices goes with --packed; the text path takes --device\n"); errors++; }
+  if (n_packed > UVDB_SET_MAX_FILES) { fprintf (stderr, "--packed: at most %d files\n", UVDB_SET_MAX_FILES); errors++; }
   if (help || errors || !qfile || (!n_ref && !packed) || (n_ref && packed)) {
     printf ("%s \nSearch reference alignment for sequences within a distance radius of the query sequences (experimental).\n\n", UVAIA_PACKAGE_STRING);
     printf (" %s [-hvk] [--acgt] [-d <int>] [--trim=<int>] [-A <double>] [-a <double>] [-p <int>] -r <ref.fa(.gz,.xz)>... <seqs.fa(.gz,.xz)> [-o <without suffix>]\n",
             basename (argv[0]));
-    printf (" %s [same options] --packed=<db.uvdb> [--devices=<list>] <seqs.fa(.gz,.xz)>\n\n", basename (argv[0]));
+    printf (" %s [same options] --packed=<db.uvdb> [--packed=<db.uvdb>]... [--devices=<list>] <seqs.fa(.gz,.xz)>\n\n", basename (argv[0]));
     printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): searched tile by tile as it is, no text parsing;\n");
-    printf ("                                   -A must not be below one minus the -A it was packed with (both 0.5 by default); -p is rounded down to a multiple of 64\n");
+    printf ("                                   -A must not be below one minus the -A it was packed with (both 0.5 by default); -p is rounded down to a multiple of 64;\n");
+    printf ("                                   can be several files, searched one after the other as one database\n");
     printf ("  --devices=<list>                 with --packed: one GPU context per listed device (e.g. 0-3 or 0,0), chunks are dealt out among them\n");
     return help ? EXIT_SUCCESS : EXIT_FAILURE;
   }
@@ -202,10 +226,10 @@ main (int argc, char **argv)
   if (packed) {
     file_compress_t packed_out = biomcmc_open_compress (outfilename, "w");
     if (!n_devices) { n_devices = 1; devices[0] = device; }
-    search_packed (packed, query, dist, ambig_r, pool, devices, n_devices, packed_out, time0);
+    search_packed (packed_files, n_packed, query, dist, ambig_r, pool, devices, n_devices, packed_out, time0);
     biomcmc_close_compress (packed_out);
     del_query_structure (query);
-    free (ref); free (outfilename);
+    free (ref); free (packed_files); free (outfilename);
     return EXIT_SUCCESS;
   }
 

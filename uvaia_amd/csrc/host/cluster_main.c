@@ -23,6 +23,7 @@
 #include "fastaseq.h"
 #include "uvdb.h"
 #include "uvdb_packer.h"
+#include "uvdb_set.h"
 #include "clust_plan.h"
 #include "../../../include/uvaia_cluster.h"
 
@@ -201,7 +202,7 @@ write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar,
 }
 
 static const char *name_from_vec (void *v, int64_t i) { return ((str_vec *) v)->v[i]; }
-static const char *name_from_db (void *v, int64_t i) { return uvdb_name ((uvdb_reader) v, (uint64_t) i); }
+static const char *name_from_db (void *v, int64_t i) { return uvdb_set_name ((uvdb_set) v, (uint64_t) i); }      /* i: position in the stream of all --packed files */
 
 int
 main (int argc, char **argv)
@@ -209,6 +210,7 @@ main (int argc, char **argv)
   int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, ch;   /* src/cluster.c:57-64 */
   double ambig_r = -1.;
   const char *out = "cluster_uvaia", *ref_file = NULL, *packed = NULL, *packed_out = NULL;
+  const char **packed_files = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *)); int n_packed = 0;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
     {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
@@ -224,7 +226,7 @@ main (int argc, char **argv)
     case 'r': if (ref_file) errors++; ref_file = optarg; break;
     case 'o': out = optarg; break;
     case 1001: device = atoi (optarg); break;
-    case 1002: if (packed) errors++; packed = optarg; break;
+    case 1002: if (!packed) packed = optarg; packed_files[n_packed++] = optarg; break;
     case 1003: if (packed_out) errors++; packed_out = optarg; break;
     case 1004: keep_medoids = 1; break;
     case 'A': ambig_r = atof (optarg); if (ambig_r < 0.) ambig_r = 0.; break;
@@ -237,9 +239,9 @@ main (int argc, char **argv)
     fprintf (stderr, "--packed %s takes the place of the alignment files: give one or the other, not both (%s was given as well)\n", packed, fasta[0]);
     errors++;
   }
-  if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024) {
+  if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024 || n_packed > UVDB_SET_MAX_FILES) {
     printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb>\n\n", basename (argv[0]));
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb> [--packed <in.uvdb>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
     printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
@@ -250,7 +252,8 @@ main (int argc, char **argv)
     printf ("  -o, --output=<without suffix>    prefix of xzipped output alignment and cluster table files\n");
     printf ("  --device=<int>                   GPU to use (default 0)\n");
     printf ("  --packed=<in.uvdb>               cluster the sequences of a packed database (`uvaiapack`, `uvaialign --packed`) instead of alignment files:\n");
-    printf ("                                   its tiles are decoded on the GPU, no text is parsed or held; same output files as from the same sequences as text\n");
+    printf ("                                   its tiles are decoded on the GPU, no text is parsed or held; same output files as from the same sequences as text;\n");
+    printf ("                                   can be several files, clustered in the order given like several alignment files\n");
     printf ("  --packed-out=<out.uvdb>          also write the medoids as a packed database, the file `uvaiapack` makes of <prefix>.aln.xz (with either kind of input)\n");
     printf ("  -A, --ref_ambiguity=<double>     with --packed-out: maximum allowed ambiguity for a medoid to be kept in that database, as in `uvaiapack`\n");
     printf ("                                   (default: the value recorded in the --packed database, 0.5 for alignment files)\n");
@@ -270,14 +273,16 @@ main (int argc, char **argv)
   int64_t time0[2];
   biomcmc_get_time (time0);
 
-  uvdb_reader db = NULL;
+  uvdb_reader db = NULL;          /* the first --packed file: the reference sequence comes from it, as from the first alignment file */
+  uvdb_set set = NULL;            /* all of them, one stream */
   if (packed) {   /* a damaged file is refused here, before any GPU work */
-    char msg[512] = "";
-    db = uvdb_open (packed, msg, sizeof msg);
-    if (!db) biomcmc_error ("%s", msg);
+    char msg[1024] = "";
+    set = uvdb_set_open (packed_files, n_packed, UVDB_SET_ANY_AMBIGUITY, msg, sizeof msg);      /* (the filter of the inputs does not matter to the clustering) */
+    if (!set) biomcmc_error ("%s", msg);
+    db = set->db[0];
     if (db->h.nchar > 0x3fffffff) biomcmc_error ("%s: sequences of %u sites are too long", packed, db->h.nchar);
   }
-  if (ambig_r < 0.) ambig_r = db ? db->h.ref_ambiguity : 0.5;
+  if (ambig_r < 0.) ambig_r = set ? set->ref_ambiguity : 0.5;
   if (ambig_r < 0.001) ambig_r = 0.001;                                    /* pack_main.c:46-47 */
   if (ambig_r > 1.) ambig_r = 1.;
 
@@ -305,22 +310,27 @@ main (int argc, char **argv)
       const uint64_t row_bytes = ((uint64_t) nchar + 63) / 64 * 64;
       uint64_t peak = 0;
       if (uvaia_clust_memory (g.ctx, NULL, NULL, &free_bytes)) free_bytes = 0;   /* unknown: as without the option */
-      uvclust_store_peak (db->h.n_ref, PACKED_CHUNK, row_bytes, &peak);
-      if (uvclust_choose_keep_medoids (db->h.n_ref, PACKED_CHUNK, row_bytes, (uint64_t) free_bytes) == 1) {
+      uvclust_store_peak (set->n_ref, PACKED_CHUNK, row_bytes, &peak);
+      if (uvclust_choose_keep_medoids (set->n_ref, PACKED_CHUNK, row_bytes, (uint64_t) free_bytes) == 1) {
         fprintf (stderr, "Keeping medoid rows only (as with --keep-medoids): the rows of the %llu sequences of %s would need %llu bytes of GPU memory while their store grows, %zu are free\n",
-                 (unsigned long long) db->h.n_ref, packed, (unsigned long long) peak, free_bytes);
+                 (unsigned long long) set->n_ref, n_packed > 1 ? "the --packed files" : packed, (unsigned long long) peak, free_bytes);
         if (uvaia_clust_keep_medoids (g.ctx, 0)) biomcmc_error ("%s", uvaia_clust_last_error (g.ctx));
         keep_medoids = g.keep_medoids = 1;
       }
     }
-    for (uint64_t first = 0; first < db->h.n_ref; first += PACKED_CHUNK) {
-      const int n = (int) (db->h.n_ref - first < PACKED_CHUNK ? db->h.n_ref - first : PACKED_CHUNK);
-      for (int i = 0; i < n; i++) queue[i] = (int) ((first + (uint64_t) i) % (uint64_t) n_clust);
-      if (uvaia_clust_push_packed (g.ctx, n, uvdb_tile_planes (db, first / 64), db->exc_idx + first, db->exc, queue)) biomcmc_error ("%s: %s", packed, uvaia_clust_last_error (g.ctx));
-      count += n;
+    /* file after file, sequence k of a FILE to queue k mod Q as for alignment files below; the result does not depend on how the
+       sequences are cut into pushes (include/uvaia_cluster.h) */
+    for (int f = 0; f < n_packed; f++) {
+      uvdb_reader fd = set->db[f];
+      for (uint64_t first = 0; first < fd->h.n_ref; first += PACKED_CHUNK) {
+        const int n = (int) (fd->h.n_ref - first < PACKED_CHUNK ? fd->h.n_ref - first : PACKED_CHUNK);
+        for (int i = 0; i < n; i++) queue[i] = (int) ((first + (uint64_t) i) % (uint64_t) n_clust);
+        if (uvaia_clust_push_packed (g.ctx, n, uvdb_tile_planes (fd, first / 64), fd->exc_idx + first, fd->exc, queue)) biomcmc_error ("%s: %s", packed_files[f], uvaia_clust_last_error (g.ctx));
+        count += n;
+      }
+      fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", packed_files[f], biomcmc_update_elapsed_time (time0), (long) count);
     }
     free (queue);
-    fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", packed, biomcmc_update_elapsed_time (time0), (long) count);
   } else {
     /* read every file, sequence k of a file to queue k mod Q (src/cluster.c:164-181); push in batches of 4 Q */
     const int batch = 4 * n_clust;
@@ -361,7 +371,7 @@ main (int argc, char **argv)
   size_t peak_row_bytes = 0;
   uvaia_clust_memory (ctx, NULL, &peak_row_bytes, NULL);
   const char *(*name_of) (void *, int64_t) = db ? name_from_db : name_from_vec;
-  void *name_arg = db ? (void *) db : (void *) &names;
+  void *name_arg = db ? (void *) set : (void *) &names;
 
   /* save_neighbours_to_xz_file and save_cluster_to_xz_file (src/fastaseq.c:293-392) for the final order */
   size_t outlength = 0;
@@ -405,6 +415,7 @@ main (int argc, char **argv)
 
   for (int64_t i = 0; i < seqs.n; i++) { free (seqs.v[i]); free (names.v[i]); }
   free (seqs.v); free (names.v); free (medoid); free (offsets); free (members); free (outfilename);
-  if (db) uvdb_close_reader (db);
+  uvdb_set_close (set);
+  free (packed_files);
   return EXIT_SUCCESS;
 }

@@ -3,6 +3,11 @@
  * No counterpart in the reference.  The filters of the reference's slot-filling loop that do not depend on
  * the queries are applied here once: the length check and the -A ambiguity filter (src/nearest.c:263-268).  The packing itself
  * runs on the GPU (uvaia_gpu_db_append + uvaia_gpu_db_export): the file holds exactly what the engine keeps resident.  Own code.
+ *
+ * `uvaiapack --merge`: packed databases -> one packed database, without their text: the file the same command without --merge writes from
+ * the texts the inputs were packed from, byte for byte.  The tiles of an input are staged as the file holds them and its references
+ * appended behind the resident ones on the device (uvaia_gpu_db_append_staged: an input rarely ends on a tile boundary); a tighter -A
+ * drops rows through the selection of that call.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -11,6 +16,7 @@
 #include "cli_common.h"
 #include "fastaseq.h"
 #include "uvdb.h"
+#include "uvdb_set.h"
 #include "../../../include/uvaia_gpu.h"
 
 #define PACK_BATCH 4096      /* references per engine round trip (a multiple of 64) */
@@ -20,11 +26,94 @@ usage (const char *prog)
 {
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("Packs an aligned reference FASTA into the bit-plane database the MI355X engine searches without parsing text.\n\n");
-  printf (" %s [-hv] [-A <double>] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n\n", prog);
-  printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` must use the same value\n");
+  printf (" %s [-hv] [-A <double>] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
+  printf (" %s --merge [-A <double>] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n\n", prog);
+  printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` is run with the value of its file\n");
+  printf ("  --merge                          the inputs are packed databases: joins them, in order, into the file that packing their texts together gives.\n");
+  printf ("                                   -A then defaults to the inputs' common value; a smaller one drops the rows it excludes, a larger one than\n");
+  printf ("                                   an input's is refused (that input no longer holds the rows it would keep)\n");
   printf ("  -o, --output=<file>              packed database to write\n");
   printf ("  --device=<int>                   GPU to use (default: current device)\n");
   printf ("Sequences that still have to be aligned: `uvaialign --packed <out.uvdb>` writes the same file straight from the aligner, without the text in between.\n");
+}
+
+/* `uvaiapack --merge`.  Whole tiles are exported once MERGE_BATCH references are resident and dropped from the front of the resident
+ * database (uvaia_gpu_db_drop_tiles); the partly filled last tile stays resident and the next input's references go on filling it. */
+static int
+merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r, int device)
+{
+  enum { MERGE_BATCH = PACK_BATCH, CHUNK_TILES = PACK_BATCH / 64 };
+  char msg[1024];
+  int64_t time0[2];
+  biomcmc_get_time (time0);
+  if (n_in > UVDB_SET_MAX_FILES) biomcmc_error ("--merge: at most %d packed databases", UVDB_SET_MAX_FILES);
+  uvdb_set set = uvdb_set_open ((const char *const *) in, n_in, have_ambig ? UVDB_SET_ANY_AMBIGUITY : 0, msg, sizeof msg);
+  if (!set) biomcmc_error ("%s", msg);
+  if (!have_ambig) ambig_r = set->ref_ambiguity;
+  for (int f = 0; f < n_in; f++) if (ambig_r > set->db[f]->h.ref_ambiguity)
+    biomcmc_error ("--merge: -A %g is looser than the -A %g that packed database %s was filtered with: it does not hold the rows that filter dropped", ambig_r, set->db[f]->h.ref_ambiguity, in[f]);
+  const int nchar = (int) set->nchar, non_n_ref = (int) (nchar * (1. - ambig_r));      /* the threshold of the text path below */
+
+  uvaia_gpu_ctx *gpu = NULL;
+  {
+    char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);
+    for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
+    dummy[nchar] = '\0';
+    const char *one[1] = {dummy};
+    uvaia_gpu_query q;
+    memset (&q, 0, sizeof q);
+    q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
+    if (uvaia_gpu_open (&gpu, &q, 1, device, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));
+    free (dummy);
+  }
+  const size_t tb = uvaia_gpu_db_tile_bytes (gpu), row = (size_t) uvaia_gpu_db_side_row_ints ();
+  if (set->tile_bytes != tb || set->side_row_ints != (uint32_t) row) biomcmc_error ("packed database %s does not match this engine's tile layout", in[0]);
+  /* resident: what a round leaves behind (below MERGE_BATCH) and one chunk on top of it */
+  if (uvaia_gpu_db_reserve (gpu, 2 * MERGE_BATCH) || uvaia_gpu_db_stage_reserve (gpu, CHUNK_TILES)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  void *planes = biomcmc_malloc ((size_t) (2 * CHUNK_TILES) * tb);
+  int *tile_nonn = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * sizeof (int)), *side = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * row * sizeof (int));
+  int *sel = (int *) biomcmc_malloc (MERGE_BATCH * sizeof (int));
+  uvdb_writer w = uvdb_create (out, nchar, tb, (int) row, ambig_r);
+  if (!w) biomcmc_error ("cannot create %s", out);
+  long count = 0, kept = 0;
+  int slot = 0;
+  for (int f = 0; f <= n_in; f++) {
+    uvdb_reader db = f < n_in ? set->db[f] : NULL;
+    const int filter = db && ambig_r < db->h.ref_ambiguity;      /* only then can a stored row fall below the threshold */
+    for (uint64_t t = 0; db && t < db->h.n_tiles; t += CHUNK_TILES) {
+      const uint64_t nt = db->h.n_tiles - t < CHUNK_TILES ? db->h.n_tiles - t : CHUNK_TILES;
+      const uint64_t r0 = t * 64, r1 = r0 + nt * 64 < db->h.n_ref ? r0 + nt * 64 : db->h.n_ref;
+      int m = 0;
+      for (uint64_t r = r0; r < r1; r++) {
+        count++;
+        if (filter && db->non_n[r] < non_n_ref) continue;
+        if (uvdb_add_reference_runs (w, uvdb_name (db, r), db->exc + db->exc_idx[r], (size_t) (db->exc_idx[r + 1] - db->exc_idx[r]))) biomcmc_error ("out of memory while indexing %s", uvdb_name (db, r));
+        sel[m++] = (int) (r - r0);
+      }
+      kept += m;
+      if (!m) continue;
+      if (uvaia_gpu_db_stage_packed (gpu, slot, uvdb_tile_planes (db, t), db->non_n + r0, uvdb_tile_side_rows (db, t), (int) nt) ||
+          uvaia_gpu_db_append_staged (gpu, slot, (uint64_t) m == r1 - r0 ? NULL : sel, m)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+      slot ^= 1;
+      const size_t whole = uvaia_gpu_db_size (gpu) / 64;
+      if (uvaia_gpu_db_size (gpu) >= MERGE_BATCH) {
+        if (uvaia_gpu_db_export (gpu, 0, whole, planes, tile_nonn, side) || uvaia_gpu_db_drop_tiles (gpu, whole)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+        if (uvdb_add_tiles (w, whole, planes, tile_nonn, side)) biomcmc_error ("cannot write to %s", out);
+      }
+    }
+    if (db) fprintf (stderr, "Finished merging file %s in %.3lf secs; %ld sequences so far, %ld kept.\n", in[f], biomcmc_update_elapsed_time (time0), count, kept);
+    else if (uvaia_gpu_db_size (gpu)) {                  /* the tail after the last input */
+      const size_t nt = (uvaia_gpu_db_size (gpu) + 63) / 64;
+      if (uvaia_gpu_db_export (gpu, 0, nt, planes, tile_nonn, side)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+      if (uvdb_add_tiles (w, nt, planes, tile_nonn, side)) biomcmc_error ("cannot write to %s", out);
+    }
+  }
+  if (uvdb_close (w)) biomcmc_error ("problem writing %s", out);
+  fprintf (stderr, "Merged %ld of %ld sequences (%d sites, -A %g) from %d packed databases into %s\n", kept, count, nchar, ambig_r, n_in, out);
+  uvaia_gpu_close (gpu);
+  uvdb_set_close (set);
+  free (planes); free (tile_nonn); free (side); free (sel);
+  return EXIT_SUCCESS;
 }
 
 int
@@ -32,20 +121,22 @@ main (int argc, char **argv)
 {
   double ambig_r = 0.5;
   const char *out = NULL;
-  int device = -1, ch, errors = 0;
+  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {0, 0, 0, 0}};
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
-    case 'A': ambig_r = atof (optarg); break;
+    case 'A': ambig_r = atof (optarg); have_ambig = 1; break;
     case 'o': out = optarg; break;
     case 1002: device = atoi (optarg); break;
+    case 1003: merge = 1; break;
     default: errors++;
   }
   if (errors || !out || optind >= argc) { printf ("Error when reading arguments from command line:\n"); usage (basename (argv[0])); return EXIT_FAILURE; }
   if (ambig_r < 0.001) ambig_r = 0.001;
   if (ambig_r > 1.) ambig_r = 1.;
+  if (merge) return merge_main (argc - optind, argv + optind, out, have_ambig, ambig_r, device);
   int64_t time0[2];
   biomcmc_get_time (time0);
 

@@ -128,7 +128,7 @@ uvdb_add_tiles (uvdb_writer w, size_t n_tiles, const void *planes, const int *no
     if (!w->non_n) return -1;
     w->nonn_cap = ncap;
   }
-  memcpy (w->non_n + w->tiles_written * 64, non_n, n * sizeof (int32_t));
+  if (n) memcpy (w->non_n + w->tiles_written * 64, non_n, n * sizeof (int32_t));      /* (no tiles: the array may not exist yet) */
   if (fwrite (side_rows, (size_t) w->h.side_row_ints * sizeof (int32_t), n, w->side_tmp) != n) return -1;
   w->tiles_written += n_tiles;
   return 0;

@@ -15,6 +15,8 @@
  *   exc      (uint32 pos, uint32 len<<8 | char)   runs of invalid sites whose character is not 'N' ('-', '?', 'X', 'O', '.'):
  *            with them the exact (upper-case) text of a reference is recovered from its planes, as the .aln.xz dump needs
  * References that fail the -A filter or the length check are not stored: the filter value is recorded in the header.
+ * Several files are read as one stream through uvdb_set.h (a repeated --packed); `uvaiapack --merge` joins files into the one file their
+ * texts would have been packed to, and is where a recorded -A is tightened (a filter cannot be loosened: the rows are not there).
  */
 #ifndef UVAIA_HOST_UVDB_H
 #define UVAIA_HOST_UVDB_H

@@ -60,6 +60,7 @@ static int db_append_common(uvaia_gpu_ctx *c, const char *const *seq, const char
     a = pe;
   }
   c->db_n += (size_t)n_ref;
+  c->win_n = 0;                                        // rows that did not come through the staged calls: no four-plane image covers them
   return 0;
 }
 
@@ -88,6 +89,7 @@ size_t uvaia_gpu_db_size(const uvaia_gpu_ctx *c) { return c ? c->db_n : 0; }
 int uvaia_gpu_db_clear(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
+  c->win_n = 0;                                        // the four-plane image of a loaded window goes with the rows
   if (!c->db.planes || !c->db_n) { c->db_n = 0; return 0; }
   { int rc = settle_derive(c); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -165,6 +167,7 @@ int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->db_n += (size_t)n_ref;
+  c->win_n = 0;
   return 0;
 }
 

@@ -135,6 +135,7 @@ int uvaia_gpu_db_append_device(uvaia_gpu_ctx *c, const void *d_rows, size_t pitc
     return fail(c, UVAIA_GPU_EALPHABET, "a reference sequence holds a byte outside ACGT / MRWSYKVHDB / NX-?O.");
   }
   c->db_n += (size_t)n_sel;
+  c->win_n = 0;                                        // (as the other appends that are not the staged ones)
   return 0;
 }
 
@@ -201,6 +202,7 @@ int uvaia_gpu_db_drop_tiles(uvaia_gpu_ctx *c, size_t n_tiles)
   HIPCHK(c, hipMemsetAsync(c->db.amb + rest_tiles * 64 * AMB_ROW, 0, z * 64 * AMB_ROW * sizeof(int), c->stream));
   if (c->d_entered) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, std::min(c->entered_cap, have * 64), c->stream));
   c->db_n = rest;
+  c->win_n = 0;                                        // the four-plane image of a window is not moved with the tiles
   { int rc = derive_rows(c, c->db, 0, (int)rest); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;

@@ -118,6 +118,93 @@ int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_r
   return 0;
 }
 
+int uvaia_gpu_db_stage_packed_at(uvaia_gpu_ctx *c, int slot, size_t tile_offset, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  if (n_tiles < 0 || (n_tiles > 0 && (!planes || !non_n || (!c->acgt && !side_rows)))) return fail(c, UVAIA_GPU_EINVAL, "NULL packed arrays");
+  if (tile_offset > c->wstage_tiles || (size_t)n_tiles > c->wstage_tiles - tile_offset)
+    return fail(c, UVAIA_GPU_ESTATE, "%d tiles at tile %zu exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, tile_offset, c->wstage_tiles);
+  HIPCHK(c, hipSetDevice(c->device));
+  auto &sl = c->wstage[slot];
+  const size_t before = tile_offset ? (size_t)sl.n_tiles : 0;      // a piece at tile 0 starts the slot afresh
+  sl.n_tiles = 0;
+  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
+  if (n_tiles) {
+    const size_t tb = uvaia_gpu_db_tile_bytes(c), nt = (size_t)n_tiles;
+    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(sl.planes) + tile_offset * tb, planes, nt * tb, hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipMemcpyAsync(sl.nonn + tile_offset * 64, non_n, nt * 64 * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
+    if (!c->acgt) HIPCHK(c, hipMemcpyAsync(sl.side + tile_offset * 64 * AMB_ROW, side_rows, nt * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
+  }
+  HIPCHK(c, hipEventRecord(sl.copied, c->copy_stream));        // the copy stream runs in order: this one covers the earlier pieces too
+  sl.n_tiles = (int)std::max(before, tile_offset + (size_t)n_tiles);
+  return 0;
+}
+
+int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
+  auto &sl = c->wstage[slot];
+  const long long staged = (long long)sl.n_tiles * 64;
+  if (n_ref > 0 && !sl.n_tiles) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
+  if (!sel && n_ref > staged) return fail(c, UVAIA_GPU_EINVAL, "%d references asked of the %lld staged in slot %d", n_ref, staged, slot);
+  if (sel) for (int k = 0; k < n_ref; k++)
+    if (sel[k] < 0 || sel[k] >= staged) return fail(c, UVAIA_GPU_EINVAL, "sel[%d] = %d lies outside the %lld references staged in slot %d", k, sel[k], staged, slot);
+  if (n_ref == 0) return 0;
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rc = settle_derive(c); if (rc) return rc; }
+  if (c->db_n + (size_t)n_ref > c->db_cap) {
+    if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
+    int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc;
+  }
+  const size_t n0 = c->db_n, n1 = n0 + (size_t)n_ref;
+  const long long t0 = (long long)(n0 / 64), t1 = (long long)((n1 - 1) / 64);
+  // the four-plane image the text is decoded from (uvaia_gpu_db_unpack_rows): the resident planes themselves in a default-mode context; an
+  // --acgt context keeps it next to them, and it is whole as long as every resident reference came through load_staged / append_staged
+  bool image = n1 <= 0x7FFFFFFFu && (!c->acgt || n0 == 0 || (c->win_n > 0 && (size_t)c->win_n == n0));
+  if (c->acgt && c->win4_tiles < c->db_cap / 64 + 1) {
+    if (n0) image = false;                              // (what it held goes with the old array)
+    const size_t cap = c->db_cap / 64 + 1;
+    hipFree(c->d_win4); c->d_win4 = nullptr; c->win4_tiles = 0;
+    HIPCHK(c, hipMalloc(&c->d_win4, cap * (size_t)c->W4 * 4 * 64 * sizeof(uint4)));
+    c->win4_tiles = cap;
+  }
+  if (n0 % 64) { if (int rc = sync_scan_streams(c)) return rc; }      // the derived planes of the first tile are rebuilt: no scan may still read them
+  if (sel) {
+    if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
+    HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
+  HIPCHK(c, hipEventRecord(c->win_ev[0], c->stream));
+  const unsigned nblk = (unsigned)(t1 - t0 + 1);
+  const int *d_sel = sel ? c->d_wsel : (const int *)nullptr;
+  if (c->acgt) hipLaunchKernelGGL((append_lanes_kernel<3>), dim3(nblk), dim3(256), 0, c->stream, sl.planes, sl.nonn, (const int *)nullptr, d_sel, (long long)n0, n_ref, c->W4,
+                                  c->db.planes, c->d_win4, t0, c->db.nonn, (int *)nullptr, c->db.tot);
+  else         hipLaunchKernelGGL((append_lanes_kernel<4>), dim3(nblk), dim3(256), 0, c->stream, sl.planes, sl.nonn, sl.side, d_sel, (long long)n0, n_ref, c->W4,
+                                  c->db.planes, (uint4 *)nullptr, t0, c->db.nonn, c->db.amb, c->db.tot);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->win_ev[1], c->stream));
+  HIPCHK(c, hipEventRecord(sl.read, c->stream)); sl.read_recorded = true;
+  // as uvaia_gpu_db_append_packed, for the rows added: the checks on what came from outside, the derived planes of their tiles
+  hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)(((size_t)n_ref + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb + n0 * AMB_ROW, c->db.nonn + n0,
+                     (long long)n_ref, c->W4 * 4, c->nchar);
+  HIPCHK(c, hipGetLastError());
+  { int rc = derive_rows(c, c->db, (long long)n0, n_ref); if (rc) return rc; }
+  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
+  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  c->db_n = n1;
+  c->win_n = image ? (int)n1 : 0;
+  return 0;
+}
+
 // text of references index[0..n) of the window loaded last (positions within the window)
 int uvaia_gpu_db_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
 {

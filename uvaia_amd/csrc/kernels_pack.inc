@@ -180,6 +180,74 @@ __global__ __launch_bounds__(256) void select_tiles_kernel(const uint4 *__restri
   }
 }
 
+// Append of staged lanes behind the references already resident (uvaia_gpu_db_append_staged, host_window.inc): destination slot
+// slot0 + k, k in [0, n_ref), = tile (slot0 + k) / 64, lane (slot0 + k) % 64 of the resident store receives staged slot sel[k]
+// (sel == NULL: slot k).  slot0 is any position: the first destination tile may hold resident references in the lanes below slot0 % 64,
+// and a thread of such a lane stores nothing at all -- no plane word, count, total or side row -- so they survive untouched without a
+// read-modify-write.  Lanes at and past slot0 + n_ref of the last tile are written as zero, as uvaia_gpu_db_export promises.  Selection,
+// the re-coding of an --acgt context (P == 3, as import_tiles_kernel<3>, plus the four-plane image in `four` that the text is decoded
+// from) and the totals are one pass: a wave loads the four planes of one word group, 64 lanes x 16 bytes each, and stores P of them.  With
+// few exclusions consecutive lanes read consecutive 16-byte words of one staged tile, shifted against the destination lanes by
+// (slot0 - first staged lane) % 64: a wave load is then two contiguous runs, the end of one staged tile's 1 KiB row and the start of the
+// next tile's, whose other halves the neighbouring blocks read (no lane order to mend, so no LDS transpose), and the stores are whole
+// 1 KiB rows but for the first tile's resident lanes.  One block per
+// destination tile, tile_base = slot0 / 64.  Side rows as in select_tiles_kernel: one wave per reference.  sel[] was checked by the host.
+template <int P>
+__global__ __launch_bounds__(256) void append_lanes_kernel(const uint4 *__restrict__ src, const int *__restrict__ src_nonn, const int *__restrict__ src_side /* nullable */,
+                                                            const int *__restrict__ sel /* nullable */, long long slot0, int n_ref, int W4,
+                                                            uint4 *__restrict__ dst, uint4 *__restrict__ four /* P == 3 only, nullable */, long long tile_base,
+                                                            int *__restrict__ dst_nonn, int *__restrict__ dst_side /* nullable, with src_side */, int *__restrict__ dst_tot)
+{
+  __shared__ int partial[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long long tile = tile_base + blockIdx.x;
+  const long long slot = tile * 64 + lane;
+  const long long k = slot - slot0;
+  const bool mine = k >= 0;                            // lanes below slot0 hold resident references
+  const bool active = mine && k < n_ref;
+  const int s = active ? (sel ? sel[k] : (int)k) : 0;
+  const uint4 *t = src + (size_t)(s >> 6) * W4 * 4 * 64 + (s & 63);
+  uint4 *o = dst + (size_t)tile * W4 * P * 64 + lane;
+  uint4 *f = (P == 3 && four) ? four + (size_t)tile * W4 * 4 * 64 + lane : nullptr;
+  int tot = 0;
+  if (mine) for (int w4 = wv; w4 < W4; w4 += 4) {
+    uint4 pA = make_uint4(0u, 0u, 0u, 0u), pC = pA, pG = pA, pT = pA;
+    if (active) { pA = ld_stream(t + (size_t)(w4 * 4 + 0) * 64); pC = ld_stream(t + (size_t)(w4 * 4 + 1) * 64); pG = ld_stream(t + (size_t)(w4 * 4 + 2) * 64); pT = ld_stream(t + (size_t)(w4 * 4 + 3) * 64); }
+    if (P == 4) {
+      o[(size_t)(w4 * 4 + 0) * 64] = pA; o[(size_t)(w4 * 4 + 1) * 64] = pC; o[(size_t)(w4 * 4 + 2) * 64] = pG; o[(size_t)(w4 * 4 + 3) * 64] = pT;
+#pragma unroll
+      for (int j = 0; j < 4; j++) tot += __popc(u4c(pA, j) | u4c(pC, j) | u4c(pG, j) | u4c(pT, j));
+    } else {
+      uint32_t L[4], H[4], I[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t a = u4c(pA, j), cc = u4c(pC, j), g = u4c(pG, j), tt = u4c(pT, j);
+        const uint32_t par = a ^ cc ^ g ^ tt, three = (a & cc & (g | tt)) | (g & tt & (a | cc));
+        I[j] = par & ~three; L[j] = (cc | tt) & I[j]; H[j] = (g | tt) & I[j];
+        tot += __popc(I[j]);
+      }
+      o[(size_t)(w4 * 3 + 0) * 64] = make_uint4(L[0], L[1], L[2], L[3]);
+      o[(size_t)(w4 * 3 + 1) * 64] = make_uint4(H[0], H[1], H[2], H[3]);
+      o[(size_t)(w4 * 3 + 2) * 64] = make_uint4(I[0], I[1], I[2], I[3]);
+      if (f) { f[(size_t)(w4 * 4 + 0) * 64] = pA; f[(size_t)(w4 * 4 + 1) * 64] = pC; f[(size_t)(w4 * 4 + 2) * 64] = pG; f[(size_t)(w4 * 4 + 3) * 64] = pT; }
+    }
+  }
+  partial[wv][lane] = tot;
+  __syncthreads();
+  if (wv == 0 && mine) {
+    dst_tot[slot] = partial[0][lane] + partial[1][lane] + partial[2][lane] + partial[3][lane];
+    dst_nonn[slot] = active ? src_nonn[s] : 0;
+  }
+  if (dst_side) {
+    for (int i = wv; i < 64; i += 4) {
+      const int si = __shfl(s, i);
+      const long long ki = tile * 64 + i - slot0;
+      if (ki < 0) continue;
+      dst_side[(size_t)(tile * 64 + i) * AMB_ROW + lane] = ki < n_ref ? src_side[(size_t)si * AMB_ROW + lane] : 0;
+    }
+  }
+}
+
 // The opposite of pack_refs_kernel<4>: the upper-case text of selected references out of tiles of the interchange form (four IUPAC
 // planes).  One block per selected reference (index[] = positions in the batch, any order, repeats allowed: every row is independent),
 // one thread per 16 sites = one half of an alignment word: eight neighbouring threads read the same 16-byte piece of each plane (one

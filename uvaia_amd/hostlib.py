@@ -198,3 +198,85 @@ class Synth:
             self.L.uvaia_synth_free(self.h)
         except Exception:
             pass
+
+
+class UvdbSetPiece(C.Structure):
+    _fields_ = [("file", C.c_int), ("first_tile", C.c_uint64), ("n_tiles", C.c_uint64), ("slot_tile", C.c_uint64)]
+
+
+class UvdbSet:
+    """Several packed databases as one stream (csrc/host/uvdb_set.h)."""
+
+    MAX_FILES = 1024
+    ANY_AMBIGUITY = 1
+
+    def __init__(self, paths, flags=0):
+        L = self.L = load_library()
+        if not getattr(L, "_uvdb_set_ready", False):
+            L.uvdb_set_open.restype = C.c_void_p
+            L.uvdb_set_open.argtypes = [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+            L.uvdb_set_close.restype = None
+            L.uvdb_set_close.argtypes = [C.c_void_p]
+            L.uvdb_set_locate.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+            L.uvdb_set_name.restype = C.c_char_p
+            L.uvdb_set_name.argtypes = [C.c_void_p, C.c_uint64]
+            L.uvdb_set_non_n.restype = C.c_int32
+            L.uvdb_set_non_n.argtypes = [C.c_void_p, C.c_uint64]
+            L.uvdb_set_unpack_reference.restype = None
+            L.uvdb_set_unpack_reference.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p]
+            L.uvdb_set_apply_exceptions.restype = None
+            L.uvdb_set_apply_exceptions.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p]
+            L.uvdb_set_runs.restype = C.c_size_t
+            L.uvdb_set_runs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+            L.uvdb_set_span.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(UvdbSetPiece), C.c_int, C.POINTER(C.c_int),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+            L._uvdb_set_ready = True
+        err = C.create_string_buffer(1024)
+        self.h = L.uvdb_set_open(_cstrs([str(p) for p in paths]), len(paths), int(flags), err, len(err))
+        if not self.h:
+            raise ValueError(err.value.decode())
+
+    def locate(self, i):
+        """(file, position within it) of stream index i; None outside the stream"""
+        f, l = C.c_int(-1), C.c_uint64(0)
+        return None if self.L.uvdb_set_locate(self.h, int(i), C.byref(f), C.byref(l)) else (f.value, l.value)
+
+    def name(self, i):
+        s = self.L.uvdb_set_name(self.h, int(i))
+        return None if s is None else s.decode()
+
+    def non_n(self, i):
+        return int(self.L.uvdb_set_non_n(self.h, int(i)))
+
+    def n_runs(self, i):
+        p = C.c_void_p()
+        return int(self.L.uvdb_set_runs(self.h, int(i), C.byref(p)))
+
+    def unpack_reference(self, i, nchar):
+        out = C.create_string_buffer(nchar + 1)
+        self.L.uvdb_set_unpack_reference(self.h, int(i), out)
+        return out.raw[:nchar]
+
+    def span(self, keep, a, b, max_pieces=1024):
+        """uvdb_set_span: (pieces [(file, first_tile, n_tiles, slot_tile)], slot_tiles, sel int32 array), or None where it returns -1"""
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint64)
+            kp = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        pieces = (UvdbSetPiece * max(max_pieces, 1))()
+        n, st = C.c_int(0), C.c_uint64(0)
+        sel = np.full(max(int(b) - int(a), 1), -1, dtype=np.int32)
+        if self.L.uvdb_set_span(self.h, kp, int(a), int(b), pieces, int(max_pieces), C.byref(n), C.byref(st), sel.ctypes.data_as(C.POINTER(C.c_int))):
+            return None
+        return [(p.file, p.first_tile, p.n_tiles, p.slot_tile) for p in pieces[:n.value]], st.value, sel[:max(int(b) - int(a), 0)]
+
+    def close(self):
+        if self.h:
+            self.L.uvdb_set_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
