@@ -270,6 +270,17 @@ const char *orc_wfa_cigar (const orc_wfa *w, int *n_ops) { *n_ops = w->ops_end -
 int64_t orc_wfa_cells (const orc_wfa *w) { return w->cells; }
 int orc_wfa_max_width (const orc_wfa *w) { return w->max_width; }
 
+int
+orc_wfa_limits (const orc_wfa *w, int score, int out[5])
+{
+  for (int j = 0; j < 5; j++) out[j] = 0;
+  if (score < 0 || score >= w->n_used) return -1;
+  const wavefront *m = w->m[score];
+  out[0] = (m ? 1 : 0) | (w->i[score] ? 2 : 0) | (w->d[score] ? 4 : 0);
+  if (m) { out[1] = m->lo_base; out[2] = m->hi_base; out[3] = m->lo; out[4] = m->hi; }
+  return 0;
+}
+
 /* ---- uvaialign ---- */
 void
 orc_align_project (const char *ops, int n_ops, const char *seq, char *aln)

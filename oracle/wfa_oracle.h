@@ -50,6 +50,9 @@ int  orc_wfa_align (orc_wfa *w, const char *pattern, int plen, const char *text,
 const char *orc_wfa_cigar (const orc_wfa *w, int *n_ops);   /* 'M','X','I','D', first operation first */
 int64_t orc_wfa_cells (const orc_wfa *w);                     /* M-wavefront cells computed by the last call */
 int  orc_wfa_max_width (const orc_wfa *w);
+/* the wavefronts of one score of the last call: out = { bit 0 M, bit 1 I, bit 2 D exists; M's allocated limits lo_base, hi_base; M's
+ * effective limits lo, hi (after the reduction; I and D share them) }.  Returns -1 (and zeros) for a score the call never reached. */
+int  orc_wfa_limits (const orc_wfa *w, int score, int out[5]);
 
 /* src/align.c:366-390 */
 void orc_align_project (const char *ops, int n_ops, const char *seq, char *aln /* >= plen + 1 bytes */);

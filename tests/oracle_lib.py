@@ -100,6 +100,10 @@ def lib():
     L.orc_wfa_cells.argtypes = [C.c_void_p]
     L.orc_wfa_max_width.restype = C.c_int
     L.orc_wfa_max_width.argtypes = [C.c_void_p]
+    L.orc_wfa_limits.restype = C.c_int
+    L.orc_wfa_limits.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.orc_align_project.restype = None
+    L.orc_align_project.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_char_p]
     L.orc_uvaialign_query.restype = C.c_int
     L.orc_uvaialign_query.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_char_p, C.POINTER(C.c_int64)]
     L.orc_uvaialign_accepts.restype = C.c_int
@@ -234,8 +238,8 @@ def search(query, refs, names, pool=64, nbest=100, ambig_r=0.5, exclude_self=Fal
 
 
 # ---- uvaialign (oracle/wfa_oracle.h) ----
-def wfa_align(pattern, text, penalties=UVAIALIGN_PENALTIES, min_wavefront_length=128, max_distance_threshold=512, max_score=1 << 30):
-    """(score, cigar bytes, M-wavefront cells, widest wavefront); min_wavefront_length <= 0: complete wavefronts."""
+def wfa_run(pattern, text, penalties, min_wavefront_length, max_distance_threshold, max_score, with_shape):
+    """one alignment: (score, cigar, cells, widest wavefront, per-score limits as wfa_shape lists them or [] without with_shape)"""
     L = lib()
     w = L.orc_wfa_new(WfaPenalties(*penalties), min_wavefront_length, max_distance_threshold)
     try:
@@ -243,9 +247,33 @@ def wfa_align(pattern, text, penalties=UVAIALIGN_PENALTIES, min_wavefront_length
         n = C.c_int(0)
         ops = L.orc_wfa_cigar(w, C.byref(n))
         cigar = C.string_at(ops, n.value) if score >= 0 else b""
-        return score, cigar, L.orc_wfa_cells(w), L.orc_wfa_max_width(w)
+        shape, out = [], (C.c_int * 5)()
+        for s in range(score + 1 if with_shape else 0):
+            if L.orc_wfa_limits(w, s, out) == 0 and out[0] & 1:
+                shape.append((s, out[1], out[2], out[3], out[4], bool(out[0] & 2), bool(out[0] & 4)))
+        return score, cigar, L.orc_wfa_cells(w), L.orc_wfa_max_width(w), shape
     finally:
         L.orc_wfa_del(w)
+
+
+def wfa_align(pattern, text, penalties=UVAIALIGN_PENALTIES, min_wavefront_length=128, max_distance_threshold=512, max_score=1 << 30):
+    """(score, cigar bytes, M-wavefront cells, widest wavefront); min_wavefront_length <= 0: complete wavefronts."""
+    return wfa_run(pattern, text, penalties, min_wavefront_length, max_distance_threshold, max_score, False)[:4]
+
+
+def wfa_shape(pattern, text, penalties=UVAIALIGN_PENALTIES, min_wavefront_length=128, max_distance_threshold=512, max_score=1 << 30):
+    """(score, cigar bytes, shape): shape lists, for every score 0 .. score that has an M wavefront, the tuple
+    (score, lo_base, hi_base, lo, hi, has_i, has_d) -- allocated limits, limits after the reduction, whether I and D exist
+    (orc_wfa_limits)."""
+    r = wfa_run(pattern, text, penalties, min_wavefront_length, max_distance_threshold, max_score, True)
+    return r[0], r[1], r[4]
+
+
+def align_project(cigar, seq):
+    """the row a CIGAR leaves on the reference's columns (src/align.c:366-390): M/X copy, I drops, D gives '-'"""
+    out = C.create_string_buffer(len(cigar) + 1)
+    lib().orc_align_project(cigar, len(cigar), seq, out)
+    return out.raw[:len(cigar) - cigar.count(b"I")]
 
 
 def gotoh_score(pattern, text, penalties=UVAIALIGN_PENALTIES):
