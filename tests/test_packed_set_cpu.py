@@ -1,6 +1,8 @@
 """Several packed databases as one stream, the host side (uvaia_amd/csrc/host/uvdb_set.h): the mapping of stream positions to files, the
-pieces and selection entries of a range of kept positions against a numpy restatement, the refusals, and the same code driven by a
-stand-alone program under the address and undefined-behaviour sanitizers.  No GPU."""
+pieces and selection entries of a range of kept positions against a numpy restatement, a set of one file against uvdb_window_span, the
+chunks that go straight from a mapping, the refusals, and the same code driven by a stand-alone program under the address and
+undefined-behaviour sanitizers.  No GPU."""
+import ctypes as C
 import os
 import subprocess
 
@@ -33,7 +35,7 @@ def _write(path, tag, n, nchar=NCHAR, ambiguity=0.5):
 
 
 # file sizes of a set: single files at the tile edges, files that end inside a tile, two whole tiles, a file that holds nothing at the end
-SETS = [(1,), (63,), (64,), (65,), (5, 7, 60), (64, 64), (130, 1, 0), (0, 3, 0, 70), (1, 1, 1, 1, 200)]
+SETS = [(1,), (63,), (64,), (65,), (5, 7, 60), (64, 64), (130, 1, 0), (0, 3, 0, 70), (1, 1, 1, 1, 200), (200,)]
 
 
 def _restate(sizes, keep, a, b):
@@ -110,6 +112,84 @@ def test_pieces_and_selection_against_the_restatement(sets, sizes):
     if total > 3:
         assert s.span(np.array([2, 1, 3], dtype=np.uint64), 0, 3) is None          # not increasing
         assert s.span(np.array([1, total], dtype=np.uint64), 0, 2) is None         # outside the stream
+    s.close()
+
+
+def _kept_lists(sizes):
+    """the kept lists of test_pieces_and_selection_against_the_restatement"""
+    total = sum(sizes)
+    first = set(np.concatenate([[0], np.cumsum(sizes)]).tolist())
+    at_edges = np.array([i for i in range(total) if i not in first and i + 1 not in first], dtype=np.uint64)
+    thirds = np.array([i for i in range(total) if i % 3 != 1], dtype=np.uint64)
+    return (None, at_edges, thirds)
+
+
+@pytest.mark.parametrize("sizes", [s for s in SETS if len(s) == 1])
+def test_a_set_of_one_file_plans_what_uvdb_window_span_plans(sets, sizes):
+    """one piece (0, first_tile, n_tiles, 0) with the tiles and the selection uvdb_window_span gives for the same keep, a, b"""
+    L = hostlib.load_library()
+    U64 = C.c_uint64
+    L.uvdb_window_span.restype = C.c_int
+    L.uvdb_window_span.argtypes = [C.POINTER(U64), U64, U64, C.POINTER(U64), C.POINTER(U64), C.POINTER(C.c_int)]
+    paths, _ = sets[1][sizes]
+    s = hostlib.UvdbSet(paths)
+    checked = 0
+    for keep in _kept_lists(sizes):
+        n = sizes[0] if keep is None else len(keep)
+        ranges = [(0, n)] + [(a, min(n, a + w)) for w in (1, 50, 64, 100) for a in range(0, n, w)]
+        ranges += [(a, b) for a in (3, 63, 66, 131) for b in (a + 1, a + 64, n) if a < b <= n]
+        for a, b in ranges:
+            if b <= a:
+                continue
+            arr = None if keep is None else keep.ctypes.data_as(C.POINTER(U64))
+            t0, nt = U64(0), U64(0)
+            sel = np.full(b - a, -1, dtype=np.int32)
+            assert L.uvdb_window_span(arr, a, b, C.byref(t0), C.byref(nt), sel.ctypes.data_as(C.POINTER(C.c_int))) == 0
+            pieces, slot, got = s.span(keep, a, b)
+            assert pieces == [(0, t0.value, nt.value, 0)] and slot == nt.value and np.array_equal(got, sel), (sizes, keep is None, a, b)
+            checked += 1
+    assert checked >= 3
+    s.close()
+
+
+def _direct(sizes, keep, a, b, n, store):
+    """what uvdb_set_direct_tiles promises, from the sizes alone: (file, first tile) of a range that is whole tiles of one file behind
+    whole tiles, None for any other"""
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    if keep is not None or b <= a or b > n or store % 64:
+        return None
+    f = int(np.searchsorted(first, a, side="right")) - 1
+    local = a - int(first[f])
+    if local % 64 or b > first[f + 1]:                       # not at lane 0 of a tile, or not in one file
+        return None
+    if (b - a) % 64 and b != n:                              # a partly filled tile anywhere but at the end of the stream
+        return None
+    return f, local // 64
+
+
+@pytest.mark.parametrize("sizes", SETS)
+def test_direct_tiles_against_the_restatement(sets, sizes):
+    paths, _ = sets[1][sizes]
+    s = hostlib.UvdbSet(paths)
+    total = sum(sizes)
+    yes = 0
+    for keep in (None, _kept_lists(sizes)[2]):
+        n = total if keep is None else len(keep)
+        for chunk in (64, 100, 128):
+            for store in (0, 64, 70):
+                for a in range(0, n, chunk):
+                    b = min(n, a + chunk)
+                    got = s.direct_tiles(keep, a, b, n, store)
+                    assert got == _direct(sizes, keep, a, b, n, store), (sizes, keep is None, chunk, store, a, b)
+                    yes += got is not None
+        assert s.direct_tiles(keep, 0, 0, n, 0) is None and s.direct_tiles(keep, 64, 64, n, 0) is None          # an empty range
+        assert s.direct_tiles(keep, 0, n + 1, n + 1, 0) is None and s.direct_tiles(keep, n, n + 64, n + 64, 0) is None      # past the stream
+    if len(sizes) == 1 or sizes[0] >= 64:                    # the first chunk into an empty store, at the least
+        assert yes > 0
+    if sizes == (200,):                                      # one file without -x: every chunk, the last partly filled one too
+        assert [s.direct_tiles(None, a, min(200, a + 64), 200, a) for a in range(0, 200, 64)] == [(0, 0), (0, 1), (0, 2), (0, 3)]
+    if sizes == (130, 1, 0):                                 # a set: the leading chunks of the first file, nothing behind the cut tile
+        assert [s.direct_tiles(None, a, min(131, a + 64), 131, a) for a in range(0, 131, 64)] == [(0, 0), (0, 1), None]
     s.close()
 
 

@@ -163,6 +163,57 @@ def test_append_staged_behind_text_rows_and_refusals():
         assert rows == [P.decode_reference(tiles[0], i, 129) for i in (0, 36, 37, 199)]
 
 
+def _whole_tiles_then_staged(eng, tiles, rows, whole):
+    """the resident load of a stream whose leading chunk goes as whole host tiles: one append_packed of rows[:whole], the tiles of the
+    pool that hold the others staged and their lanes (which are not the destination's) appended"""
+    planes, non_n, side = tiles
+    eng.db_append_packed(*_compact(tiles, rows[:whole]), whole)
+    t0, t1 = rows[whole] // 64, rows[-1] // 64 + 1
+    eng.db_stage_packed(0, planes[t0:t1], non_n[t0 * 64:t1 * 64], side[t0 * 64:t1 * 64], t1 - t0)
+    sel = [r - t0 * 64 for r in rows[whole:]]
+    assert sel[0] % 64 != 0                                  # a lane shift: destination lane 0 reads another lane of the slot
+    eng.db_append_staged(0, sel, len(sel))
+    assert eng.db_size() == len(rows)
+
+
+@pytest.mark.parametrize("whole,rest", [(128, 70), (64, 1)])
+def test_append_staged_behind_append_packed_is_one_append_packed(whole, rest):
+    qs, qn, upper, tiles = _pool(129)
+    rows = list(range(5, 5 + whole + rest))
+    with capi.Engine.from_query(O.Query(qs, qn), nbest=2, max_pool=128) as eng:
+        eng.db_reserve(N_POOL)
+        eng.db_stage_reserve(3)
+        eng.db_append_packed(*_compact(tiles, rows), len(rows))
+        want = eng.db_export()
+        eng.db_clear()
+        _whole_tiles_then_staged(eng, tiles, rows, whole)
+        got = eng.db_export()
+        for g, w, what in zip(got, want, ("planes", "non_n", "side rows")):
+            assert np.array_equal(g, w), (whole, rest, what)
+        pad = len(rows) % 64                                 # the padding lanes of the last tile read as zero
+        assert pad and not got[0].reshape(got[0].shape[0], -1, 64, 16)[-1, :, pad:, :].any() and not got[1][len(rows):].any() and not got[2][len(rows):].any()
+
+
+@pytest.mark.parametrize("whole,rest", [(128, 70), (64, 1)])
+def test_append_staged_behind_append_packed_acgt_context(whole, rest):
+    """the same two calls in an --acgt context: the heaps of a search against one append_packed load (append_packed keeps no four-plane
+    image, so there is no text of the rows to compare)"""
+    qs, qn, upper, tiles = _pool(129)
+    rows = list(range(5, 5 + whole + rest))
+    with capi.Engine.from_query(O.Query(qs, qn, acgt=True), nbest=4, max_pool=64) as eng:
+        eng.db_reserve(N_POOL)
+        eng.db_stage_reserve(3)
+        eng.db_append_packed(*_compact(tiles, rows), len(rows))
+        ent = eng.search_resident(64)
+        want = eng.drain()
+        eng.reset(); eng.db_clear()
+        _whole_tiles_then_staged(eng, tiles, rows, whole)
+        got_ent = eng.search_resident(64)
+        got = eng.drain()
+        assert all(np.array_equal(x, y) for x, y in zip(got, want)), (whole, rest)
+        assert np.array_equal(got_ent, ent) and ent.any()
+
+
 @pytest.mark.parametrize("nchar", [100, 128, 129, 1000])
 def test_append_staged_acgt_context(nchar):
     """an --acgt context re-codes while appending: the heaps of a search and the text of every row against one append_packed load"""
@@ -238,6 +289,14 @@ def test_stage_packed_at_pieces_are_one_staging():
             eng.db_load_staged(1, None, 250)
             for g, w in zip(eng.db_export(), want):
                 assert np.array_equal(g, w), k
+        sel = list(range(1, 21)) + list(range(65, 85)) + list(range(192, 255))      # stage_packed is stage_packed_at at tile 0
+        eng.db_stage_packed(0, planes[:4], non_n[:256], side[:256], 4)
+        eng.db_load_staged(0, sel, len(sel))
+        want = eng.db_export()
+        eng.db_stage_packed_at(1, 0, planes[:4], non_n[:256], side[:256], 4)
+        eng.db_load_staged(1, sel, len(sel))
+        for g, w, c in zip(eng.db_export(), want, _compact(tiles, sel)):
+            assert np.array_equal(g, w) and np.array_equal(g, c)
         for off, nt in ((4, 1), (5, 0), (2, 3), (1 << 40, 1)):      # a piece that ends beyond the reserved tiles
             with pytest.raises(capi.GpuError) as ei:
                 eng.db_stage_packed_at(1, off, planes[:nt], non_n[:nt * 64], side[:nt * 64], nt)
@@ -291,7 +350,8 @@ def cli(tmp_path_factory, bundled_db):
     return d, texts, packed, str(d / "abc.uvdb"), rnames, refs
 
 
-@pytest.mark.parametrize("extra,set_only", [([], []), (["-x"], []), (["--acgt"], []), (["-p", "64"], ["--window", "64"]), ([], ["--devices", "0,0"])])
+@pytest.mark.parametrize("extra,set_only", [([], []), (["-x"], []), (["--acgt"], []), (["-p", "64"], ["--window", "64"]), ([], ["--devices", "0,0"]),
+                                            (["-x", "-p", "64"], ["--window", "64"])])
 def test_uvaia_over_three_packed_files(cli, extra, set_only):
     d, texts, packed, joint, rnames, refs = cli
     tag = "".join(x.strip("-").replace(",", "") for x in extra + set_only)
@@ -300,13 +360,19 @@ def test_uvaia_over_three_packed_files(cli, extra, set_only):
     _run(base + ["-o", out["text"]] + [x for t in texts for x in ("-r", t)])
     _run(base + ["-o", out["joint"], "--packed", joint])
     log = _run(base + ["-o", out["set"]] + set_only + [x for p in packed for x in ("--packed", p)])
+    windowed = "--window" in set_only                        # the joint file a window at a time too: a set of one, windowed
+    if windowed:
+        out["joint_window"] = str(d / ("joint_window_" + tag))
+        _run(base + ["-o", out["joint_window"], "--packed", joint] + set_only)
     for suffix in (".csv.xz", ".aln.xz"):
         want = _xz(out["text"], suffix)
         assert len(want) > 500
         assert _xz(out["joint"], suffix) == want, suffix
         assert _xz(out["set"], suffix) == want, suffix
-    assert "Loaded %d packed sequences from 3 files" % (sum(SIZES_CLI) - (2 if extra == ["-x"] else 0)) in log
-    if extra == ["-x"]:
+        if windowed:
+            assert _xz(out["joint_window"], suffix) == want, suffix
+    assert "Loaded %d packed sequences from 3 files" % (sum(SIZES_CLI) - (2 if "-x" in extra else 0)) in log
+    if "-x" in extra:
         assert " 2 reference sequences already present" in log
 
 

@@ -80,6 +80,28 @@ check_span (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b)
   free (sel);
 }
 
+/* uvdb_set_direct_tiles by brute force: yes exactly when every reference of [a, b) lies in one file at the lane of its place in the range,
+ * the tile that is not filled ends the stream, and the store ends on a tile */
+static void
+check_direct (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uint64_t n, uint64_t store)
+{
+  int f = -7, want = keep == NULL && a < b && b <= n && n == s->n_ref && store % 64 == 0 && ((b - a) % 64 == 0 || b == n);
+  uint64_t t = 77, l0 = 0;
+  int f0 = -1;
+  for (uint64_t k = a; want && k < b; k++) {
+    int fk = -1; uint64_t l = 0;
+    CHECK (uvdb_set_locate (s, k, &fk, &l) == 0);
+    if (k == a) { f0 = fk; l0 = l; }
+    if (fk != f0 || l != l0 + (k - a) || l0 % 64) want = 0;
+  }
+  const int rc = uvdb_set_direct_tiles (s, keep, a, b, n, store, &f, &t);
+  CHECK (rc == (want ? 0 : -1));
+  if (want) {
+    CHECK (f == f0 && t == l0 / 64 && t + (b - a + 63) / 64 <= s->db[f]->h.n_tiles);
+    CHECK (uvdb_set_direct_tiles (s, keep, a, b, n, store, NULL, NULL) == 0);
+  } else CHECK (f == -7 && t == 77);      /* nothing written with a no */
+}
+
 int
 main (int argc, char **argv)
 {
@@ -125,6 +147,15 @@ main (int argc, char **argv)
   /* spans: everything, every window of 64 and of 100, and kept lists with holes at the file boundaries */
   check_span (s, NULL, 0, total);
   for (uint64_t w = 64; w <= 100; w += 36) for (uint64_t a = 0; a < total; a += w) check_span (s, NULL, a, a + w < total ? a + w : total);
+  /* chunks that go straight from a mapping: every chunk of 64, 100 and 128 into stores that end on a tile and inside one; the refusals */
+  for (uint64_t w = 64; w <= 128; w += (w == 64 ? 36 : 28)) for (uint64_t a = 0; a < total; a += w) for (uint64_t store = 0; store <= 70; store += (store ? 6 : 64))
+    check_direct (s, NULL, a, a + w < total ? a + w : total, total, store);
+  check_direct (s, NULL, 0, 64, total, 0);
+  check_direct (s, NULL, 64, 127, total, 64);          /* file 2 from its lane 0, one reference short of its tile */
+  check_direct (s, NULL, 5, 5, total, 0);
+  check_direct (s, NULL, total - 5, total, total, 0);  /* the last file, from its lane 0 to the end of the stream */
+  check_direct (s, NULL, total, total + 64, total + 64, 0);
+  check_direct (s, NULL, 0, total + 1, total + 1, 0);
   uint64_t *keep = (uint64_t *) malloc ((size_t) total * sizeof (uint64_t)), n = 0;
   CHECK (keep);
   for (i = 0; i < total; i++) {
@@ -136,6 +167,7 @@ main (int argc, char **argv)
   CHECK (n > 100 && n < total);
   check_span (s, keep, 0, n);
   for (uint64_t a = 0; a < n; a += 50) check_span (s, keep, a, a + 50 < n ? a + 50 : n);
+  for (uint64_t a = 0; a < n; a += 64) check_direct (s, keep, a, a + 64 < n ? a + 64 : n, n, 0);       /* a keep list: never */
   CHECK (uvdb_set_span (s, keep, 3, 3, NULL, 0, NULL, NULL, NULL) == -1);
   CHECK (uvdb_set_span (s, NULL, 0, total + 1, NULL, 0, NULL, NULL, NULL) == -1);
   keep[5] = keep[4];                       /* not increasing */

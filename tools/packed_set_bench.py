@@ -2,11 +2,13 @@
 """Several packed databases as one on the GPU box: one synthetic database (tools/ingest_bench.py's generator) packed as 1, 4 and 16 files of
 equal share, then for every cut the whole command `uvaia --packed f0 --packed f1 ...` (resident load of all files, search, output) and
 `uvaiapack --merge` of the files (references per second), alternating, medians over the repeats.  The cut into one file is the single-file
-command, unchanged by the set code: it is the figure to hold the others against (and, run on the parent commit with --single-only, the
-parent's figure on the same box).  Records whether every cut gives the single file's outputs and whether every merge gives its bytes.
+command: the same code as the other cuts, a set of one file, whose chunks go to the engine straight from the mapping.  It is the figure to
+hold the others against, and the one to hold against the parent commit's (its --single-only run on the same box).  With --same-names K,
+K queries are named like references spread over the database and every command gets -x: the kept stream has holes, so one file too is
+staged and selected on the device.  Records whether every cut gives the single file's outputs and whether every merge gives its bytes.
 Writes profiles/packed_set.json and prints it.
 Usage: python tools/packed_set_bench.py [--refs 100000] [--queries 1000] [--dir /tmp/packed_set_bench] [--out profiles/packed_set.json] [--single-only]
-       [--parent-single-file-s <seconds>]   (the search_median_s a --single-only run on the parent commit printed)"""
+       [--same-names K] [--parent-single-file-s <seconds>]   (the search_median_s a --single-only run on the parent commit printed)"""
 import argparse
 import json
 import lzma
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--cuts", default="1,4,16")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--single-only", action="store_true", help="only the single-file command (what a commit without the set code can run)")
+    ap.add_argument("--same-names", type=int, default=0, help="name this many queries like references spread over the database and pass -x")
     ap.add_argument("--parent-single-file-s", type=float, default=None, help="median of the single-file command on the parent commit (its --single-only run on the same box): recorded next to the cuts")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "packed_set.json"))
     a = ap.parse_args()
@@ -50,7 +53,9 @@ def main():
     with open(q_fa, "wb") as fh:
         rows, _ = gen.generate(10_000_000, a.queries)
         for i in range(rows.shape[0]):
-            fh.write(b">q_%d\n" % i + rows[i].tobytes() + b"\n")
+            name = b"ref_%d" % (i * a.refs // a.same_names) if i < a.same_names else b"q_%d" % i
+            fh.write(b">" + name + b"\n" + rows[i].tobytes() + b"\n")
+    exclude = ["-x"] if a.same_names else []
     files = {}
     for c in cuts:                                          # file k of a cut into c holds references [k * share, (k + 1) * share): no multiple of 64 unless the share is
         share, files[c] = -(-a.refs // c), []
@@ -67,7 +72,7 @@ def main():
     search, merge = {c: [] for c in cuts}, {c: [] for c in cuts}
     for rep in range(a.repeats + 1):                        # the first round warms the page cache and is not counted
         for c in cuts:
-            t = run([uv, q_fa, "-p", str(a.pool), "-n", "100", "-o", os.path.join(a.dir, "out_%d" % c)] + [x for f in files[c] for x in ("--packed", f)])
+            t = run([uv, q_fa, "-p", str(a.pool), "-n", "100", "-o", os.path.join(a.dir, "out_%d" % c)] + exclude + [x for f in files[c] for x in ("--packed", f)])
             if rep:
                 search[c].append(t)
             if not a.single_only:
@@ -76,7 +81,7 @@ def main():
                     merge[c].append(t)
     content = {c: [lzma.open(os.path.join(a.dir, "out_%d%s" % (c, s)), "rb").read() for s in (".csv.xz", ".aln.xz")] for c in cuts}
     single = open(files[1][0], "rb").read() if 1 in cuts and not a.single_only else None
-    result = {"refs": a.refs, "queries": a.queries, "pool": a.pool, "repeats": a.repeats, "cuts": {}}
+    result = {"refs": a.refs, "queries": a.queries, "pool": a.pool, "repeats": a.repeats, "same_names": a.same_names, "cuts": {}}
     for c in cuts:
         e = {"files": c, "search_median_s": round(statistics.median(search[c]), 3), "search_all_s": [round(x, 3) for x in search[c]],
              "outputs_equal_single_file": content[c] == content[cuts[0]]}
@@ -86,7 +91,8 @@ def main():
                       "merge_equals_single_file": (open(os.path.join(a.dir, "merged_%d.uvdb" % c), "rb").read() == single) if single is not None else None})
         result["cuts"][str(c)] = e
     result["note"] = ("wall clock of the whole commands (query preparation, engine start-up, xz output included), page cache warm; the cut into 1 file runs "
-                      "the single-file path, which the set code does not touch; parent_single_file_s: the same command on the parent commit, where it was run")
+                      "the same code as a set of one file (without -x its chunks go straight from the mapping, as on the parent); same_names > 0: "
+                      "that many queries named like references and -x; parent_single_file_s: the same command on the parent commit, where it was run")
     result["parent_single_file_s"] = a.parent_single_file_s
     with open(a.out, "w") as fh:
         json.dump(result, fh, indent=1)

@@ -20,7 +20,7 @@ typedef struct {
   int help, version, acgt, keep_resolved, exclude_self, nbest, trim, pool, threads, threads_given, device, devices[64], n_devices;
   long long window; int window_given, window_report;
   double ambig_q, ambig_r;
-  const char *out, *query, *packed;          /* packed: the first --packed */
+  const char *out, *query;
   const char **ref; int n_ref;
   const char **packed_files; int n_packed;
 } options;
@@ -94,7 +94,7 @@ parse_options (int argc, char **argv)
     case 'o': o.out = optarg; break;
     case 1002: o.device = atoi (optarg); break;
     case 1004: o.n_devices = uvaia_parse_device_list (optarg, o.devices, 64); if (!o.n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); exit (EXIT_FAILURE); } break;
-    case 1003: if (!o.n_packed) o.packed = optarg; o.packed_files[o.n_packed++] = optarg; break;
+    case 1003: o.packed_files[o.n_packed++] = optarg; break;
     case 1005: o.window = atoll (optarg); o.window_given = 1; break;
     case 1006: o.window_report = 1; break;
     default: errors++;
@@ -103,13 +103,13 @@ parse_options (int argc, char **argv)
   if (optind < argc) errors++;
   if (o.version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); exit (EXIT_SUCCESS); }
   if (o.help) { usage (basename (argv[0]), 1); exit (EXIT_SUCCESS); }
-  if (errors || !o.query || (!o.n_ref && !o.packed) || (o.n_ref && o.packed)) {
+  if (errors || !o.query || (!o.n_ref && !o.n_packed) || (o.n_ref && o.n_packed)) {
     printf ("Error when reading arguments from command line:\n");
     usage (basename (argv[0]), 0);
     exit (EXIT_FAILURE);
   }
   /* --window: refused here, before anything touches a GPU */
-  if (o.window_given && !o.packed) { fprintf (stderr, "--window needs --packed: only a packed database is searched a window at a time\n"); exit (EXIT_FAILURE); }
+  if (o.window_given && !o.n_packed) { fprintf (stderr, "--window needs --packed: only a packed database is searched a window at a time\n"); exit (EXIT_FAILURE); }
   if (o.window_given && o.window < 1) { fprintf (stderr, "--window: expected a positive number of references\n"); exit (EXIT_FAILURE); }
   if (o.n_packed > UVDB_SET_MAX_FILES) { fprintf (stderr, "--packed: at most %d files\n", UVDB_SET_MAX_FILES); exit (EXIT_FAILURE); }
   if (o.window_given && o.n_devices > 1) { fprintf (stderr, "--window works on one GPU: give --device, not a --devices list of several\n"); exit (EXIT_FAILURE); }
@@ -124,81 +124,15 @@ wall_ms (void)
   return (double) ts.tv_sec * 1e3 + (double) ts.tv_nsec * 1e-6;
 }
 
-/* The windowed search over a packed database (include/uvaia_gpu.h, "windowed search"): stands where the resident search replaces the
- * loops of src/nearest.c:251-306, for a file of which `window` references are on the GPU at a time.  The next window's tiles are handed to
- * the copy stream while the current one is searched; what entered a heap is decoded on the GPU.  Host memory: one window of flags and of
- * selection entries and 256 rows of text, whatever the size of the file.  Returns the number of sequences written. */
+/* ---- --packed: the files are one stream through uvdb_set.h, a single file as a set of one.  The tiles of every file are staged as the
+ * file holds them, piece after piece of a staging slot, and the kept references of the pieces go into the resident store by position (a
+ * file rarely ends on a tile boundary, -x leaves holes): appended behind what is resident (resident search), or as the next window
+ * (windowed search). */
+
+/* kept positions [a, b) into staging slot `slot`; sel (b - a entries) receives their positions within it.  Returns whether these are
+ * 0, 1, 2, ... for certain: no keep list, one piece, the first at lane 0 */
 static int
-search_windowed (uvaia_gpu_ctx *gpu, uvdb_reader db, const uint64_t *keep, uint64_t n, uint64_t window, uint64_t n_windows, size_t pool, int nchar,
-                 file_compress_t outstream, name_table *names, double upload_ms[3])
-{
-  enum { ROUND = 256 };
-  const uint64_t wmax = window < n ? window : n;
-  const size_t pitch = ((size_t) nchar + 15) / 16 * 16;
-  uint64_t max_tiles = 1;
-  for (uint64_t w = 0; w < n_windows; w++) {
-    uint64_t t0, nt;
-    const uint64_t a = w * window, b = (a + window < n) ? a + window : n;
-    if (uvdb_window_span (keep, a, b, &t0, &nt, NULL)) biomcmc_error ("--window: the window at reference %llu spans more file tiles than the engine counts", (unsigned long long) a);
-    if (nt > max_tiles) max_tiles = nt;
-  }
-  if (uvaia_gpu_db_reserve (gpu, (size_t) (wmax ? wmax : 1)) || uvaia_gpu_db_stage_reserve (gpu, (size_t) max_tiles)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-  int *sel = keep ? (int *) biomcmc_malloc ((size_t) (wmax ? wmax : 1) * sizeof (int)) : NULL, index[ROUND], n_output = 0;
-  uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (wmax ? wmax : 1));
-  char *rows = (char *) biomcmc_malloc (ROUND * pitch + 1);
-  uint64_t t0 = 0, nt = 0;
-  upload_ms[0] = upload_ms[1] = upload_ms[2] = 0.;
-#define STAGE(w_) do { const uint64_t a_ = (w_) * window, b_ = (a_ + window < n) ? a_ + window : n; \
-    uvdb_window_span (keep, a_, b_, &t0, &nt, NULL); \
-    if (uvaia_gpu_db_stage_packed (gpu, (int) ((w_) & 1), uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) nt)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu)); } while (0)
-  double t = wall_ms ();
-  if (n_windows) STAGE ((uint64_t) 0);
-  upload_ms[0] = upload_ms[1] = wall_ms () - t;           /* the first window's upload has nothing to hide behind */
-  for (uint64_t w = 0; w < n_windows; w++) {
-    const uint64_t a = w * window, b = (a + window < n) ? a + window : n;
-    if (keep) uvdb_window_span (keep, a, b, &t0, &nt, sel);
-    if (uvaia_gpu_db_load_staged (gpu, (int) (w & 1), sel, (int) (b - a))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-    if (uvaia_gpu_search_resident (gpu, pool, (int64_t) a, NULL)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-    if (w + 1 < n_windows) {                              /* the search runs: the next window's tiles cross the bus next to it */
-      t = wall_ms ();
-      STAGE (w + 1);
-      const double up = wall_ms () - t;
-      t = wall_ms ();
-      if (uvaia_gpu_sync (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-      upload_ms[0] += up;
-      if (wall_ms () - t < 0.01 * up) upload_ms[1] += up;   /* the search had ended before the upload: counted as not hidden at all */
-    } else if (uvaia_gpu_sync (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-    if (uvaia_gpu_entered_flags (gpu, ent, 0)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-    for (uint64_t k = 0; k < b - a;) {                    /* dump every sequence that entered some heap, in stream order */
-      int m = 0;
-      for (; k < b - a && m < ROUND; k++) if (ent[k]) index[m++] = (int) k;
-      if (!m) break;
-      if (uvaia_gpu_db_unpack_rows (gpu, index, m, rows, pitch)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-      for (int j = 0; j < m; j++) {
-        const uint64_t i = a + (uint64_t) index[j], r = keep ? keep[i] : i;
-        char *row = rows + (size_t) j * pitch, after = row[nchar];
-        uvdb_apply_exceptions (db, r, row);
-        row[nchar] = '\0';
-        write_fasta_record (outstream, uvdb_name (db, r), row);
-        row[nchar] = after;
-        name_table_set (names, (int64_t) i, uvdb_name (db, r));
-        n_output++;
-      }
-    }
-  }
-#undef STAGE
-  upload_ms[2] = upload_ms[0] > 0. ? 1. - upload_ms[1] / upload_ms[0] : 0.;
-  free (rows); free (ent); free (sel);
-  return n_output;
-}
-
-/* ---- several --packed files: one stream through uvdb_set.h.  The tiles of every file are staged as the file holds them, piece after piece
- * of a staging slot, and the kept references of the pieces go into the resident store by position (a file rarely ends on a tile boundary,
- * -x leaves holes): appended behind what is resident (resident search), or as the next window (windowed search). */
-
-/* kept positions [a, b) into staging slot `slot`; sel (b - a entries) receives their positions within it */
-static void
-stage_set_range (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t a, uint64_t b, int slot, uvdb_set_piece *pieces, int *sel)
+stage_range (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t a, uint64_t b, int slot, uvdb_set_piece *pieces, int *sel)
 {
   int np = 0;
   uint64_t st = 0;
@@ -209,44 +143,50 @@ stage_set_range (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_
     if (uvaia_gpu_db_stage_packed_at (gpu, slot, (size_t) pieces[p].slot_tile, uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) pieces[p].n_tiles))
       biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
   }
+  return !keep && np == 1 && sel[0] == 0;
 }
 
-/* the largest staging slot the ranges [w * step, (w + 1) * step) of n kept references need, in tiles */
+/* the largest staging slot the ranges [w * step, (w + 1) * step) of n kept references need, in tiles (0: none is staged); resident: the
+ * ranges are chunks of the resident load, of which those that go straight from the mapping need no slot */
 static uint64_t
-set_max_slot_tiles (uvdb_set set, const uint64_t *keep, uint64_t n, uint64_t step)
+max_slot_tiles (uvdb_set set, const uint64_t *keep, uint64_t n, uint64_t step, int resident)
 {
-  uint64_t max_tiles = 1;
+  uint64_t max_tiles = 0;
   for (uint64_t a = 0; a < n; a += step) {
     uint64_t st = 0;
     const uint64_t b = (a + step < n) ? a + step : n;
+    if (resident && !uvdb_set_direct_tiles (set, keep, a, b, n, a, NULL, NULL)) continue;
     if (uvdb_set_span (set, keep, a, b, NULL, 0, NULL, &st, NULL)) biomcmc_error ("--packed: the references from %llu on span more file tiles than the engine counts", (unsigned long long) a);
     if (st > max_tiles) max_tiles = st;
   }
   return max_tiles;
 }
 
-/* search_windowed over a set: the same walk, a window's span is a list of pieces */
+/* The windowed search (include/uvaia_gpu.h, "windowed search"): stands where the resident search replaces the loops of
+ * src/nearest.c:251-306, for a stream of which `window` references are on the GPU at a time.  The next window's tiles are handed to the
+ * copy stream while the current one is searched; what entered a heap is decoded on the GPU.  Host memory: one window of flags, two of
+ * selection entries and 256 rows of text, whatever the size of the files.  Returns the number of sequences written. */
 static int
-search_windowed_set (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t n, uint64_t window, uint64_t n_windows, size_t pool, int nchar,
-                     file_compress_t outstream, name_table *names, double upload_ms[3])
+search_windowed (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t n, uint64_t window, uint64_t n_windows, size_t pool, int nchar,
+                 file_compress_t outstream, name_table *names, double upload_ms[3])
 {
   enum { ROUND = 256 };
-  const uint64_t wmax = window < n ? window : n;
+  const uint64_t wmax = window < n ? window : n, slot_tiles = max_slot_tiles (set, keep, n, window, 0);
   const size_t pitch = ((size_t) nchar + 15) / 16 * 16;
-  if (uvaia_gpu_db_reserve (gpu, (size_t) (wmax ? wmax : 1)) || uvaia_gpu_db_stage_reserve (gpu, (size_t) set_max_slot_tiles (set, keep, n, window))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  if (uvaia_gpu_db_reserve (gpu, (size_t) (wmax ? wmax : 1)) || uvaia_gpu_db_stage_reserve (gpu, (size_t) (slot_tiles ? slot_tiles : 1))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
   uvdb_set_piece *pieces = (uvdb_set_piece *) biomcmc_malloc (UVDB_SET_MAX_FILES * sizeof (uvdb_set_piece));
-  int *sel[2], index[ROUND], n_output = 0;
+  int *sel[2], identity[2] = {0, 0}, index[ROUND], n_output = 0;
   for (int i = 0; i < 2; i++) sel[i] = (int *) biomcmc_malloc ((size_t) (wmax ? wmax : 1) * sizeof (int));
   uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (wmax ? wmax : 1));
   char *rows = (char *) biomcmc_malloc (ROUND * pitch + 1);
   upload_ms[0] = upload_ms[1] = upload_ms[2] = 0.;
-#define STAGE(w_) do { const uint64_t a_ = (w_) * window, b_ = (a_ + window < n) ? a_ + window : n; stage_set_range (gpu, set, keep, a_, b_, (int) ((w_) & 1), pieces, sel[(w_) & 1]); } while (0)
+#define STAGE(w_) do { const uint64_t a_ = (w_) * window, b_ = (a_ + window < n) ? a_ + window : n; identity[(w_) & 1] = stage_range (gpu, set, keep, a_, b_, (int) ((w_) & 1), pieces, sel[(w_) & 1]); } while (0)
   double t = wall_ms ();
   if (n_windows) STAGE ((uint64_t) 0);
   upload_ms[0] = upload_ms[1] = wall_ms () - t;           /* the first window's upload has nothing to hide behind */
   for (uint64_t w = 0; w < n_windows; w++) {
     const uint64_t a = w * window, b = (a + window < n) ? a + window : n;
-    if (uvaia_gpu_db_load_staged (gpu, (int) (w & 1), sel[w & 1], (int) (b - a))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    if (uvaia_gpu_db_load_staged (gpu, (int) (w & 1), identity[w & 1] ? NULL : sel[w & 1], (int) (b - a))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
     if (uvaia_gpu_search_resident (gpu, pool, (int64_t) a, NULL)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
     if (w + 1 < n_windows) {                              /* the search runs: the next window's tiles cross the bus next to it */
       t = wall_ms ();
@@ -281,18 +221,67 @@ search_windowed_set (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uin
   return n_output;
 }
 
-/* the whole of the --packed branch of main for several files; returns the number of sequences written */
+/* The n kept references into the resident store, in chunks of 16 384.  A chunk that is whole tiles of one file behind whole tiles
+ * (uvdb_set_direct_tiles: without -x, every chunk of a single file) goes straight from the mapping.  Any other is staged piece by piece
+ * and its lanes appended on the device; a group of devices takes whole host tiles, so for it the lanes are gathered here. */
+static void
+load_resident (uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, int n_devices, uvdb_set set, const uint64_t *keep, uint64_t n)
+{
+  const uint64_t chunk_tiles = 256, chunk = chunk_tiles * 64, slot_tiles = n_devices == 1 ? max_slot_tiles (set, keep, n, chunk, 1) : 0;
+  const size_t tb = (size_t) set->tile_bytes, row = (size_t) set->side_row_ints, lane_pieces = tb / (64 * 16);   /* 16-byte pieces per lane */
+  if (slot_tiles && uvaia_gpu_db_stage_reserve (gpu, (size_t) slot_tiles)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  uvdb_set_piece *pieces = (uvdb_set_piece *) biomcmc_malloc (UVDB_SET_MAX_FILES * sizeof (uvdb_set_piece));
+  int *sel = (int *) biomcmc_malloc ((size_t) chunk * sizeof (int));
+  unsigned char *planes = NULL;                      /* the host tiles of a gathered chunk: allocated with the first one */
+  int32_t *nn = NULL, *side = NULL;
+  for (uint64_t a = 0; a < n; a += chunk) {
+    const uint64_t b = (a + chunk < n) ? a + chunk : n, cnt = b - a;
+    const int slot = (int) (a / chunk & 1);
+    int f = 0; uint64_t t = 0;
+    if (!uvdb_set_direct_tiles (set, keep, a, b, n, a, &f, &t)) {
+      uvdb_reader db = set->db[f];
+      if (uvaia_gpu_group_db_append_packed (grp, uvdb_tile_planes (db, t), db->non_n + t * 64, uvdb_tile_side_rows (db, t), (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+    } else if (n_devices == 1) {
+      stage_range (gpu, set, keep, a, b, slot, pieces, sel);
+      if (uvaia_gpu_db_append_staged (gpu, slot, sel, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    } else {
+      if (!planes) {
+        planes = (unsigned char *) biomcmc_malloc (chunk_tiles * tb);
+        nn = (int32_t *) biomcmc_malloc (chunk * sizeof (int32_t)); side = (int32_t *) biomcmc_malloc (chunk * row * sizeof (int32_t));
+      }
+      memset (planes, 0, chunk_tiles * tb); memset (nn, 0, chunk * sizeof (int32_t)); memset (side, 0, chunk * row * sizeof (int32_t));
+#pragma omp parallel for schedule(static)
+      for (uint64_t k = 0; k < cnt; k++) {
+        int fk = 0; uint64_t r = 0;
+        uvdb_set_locate (set, keep ? keep[a + k] : a + k, &fk, &r);
+        uvdb_reader db = set->db[fk];
+        const unsigned char *src = (const unsigned char *) uvdb_tile_planes (db, r / 64) + (r % 64) * 16;
+        unsigned char *dst = planes + (k / 64) * tb + (k % 64) * 16;
+        for (size_t p = 0; p < lane_pieces; p++) memcpy (dst + p * 1024, src + p * 1024, 16);
+        nn[k] = db->non_n[r];
+        memcpy (side + k * row, uvdb_tile_side_rows (db, r / 64) + (r % 64) * row, row * sizeof (int32_t));
+      }
+      if (uvaia_gpu_group_db_append_packed (grp, planes, nn, side, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+    }
+  }
+  free (planes); free (nn); free (side); free (sel); free (pieces);
+}
+
+/* the search over o->packed_files: replaces the read/filter/fill loop of main (src/nearest.c:251-286); returns the number of sequences written */
 static int
-search_packed_set (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, file_compress_t outstream, name_table *names, int *count, int *same_name, int64_t *time0)
+search_packed (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, file_compress_t outstream, name_table *names, int *count, int *same_name, int64_t *time0)
 {
   char msg[1024];
+  const char *first = o->packed_files[0];
+  const int one = o->n_packed == 1, nchar = query->aln->nchar;
   uvdb_set set = uvdb_set_open (o->packed_files, o->n_packed, 0, msg, sizeof msg);
   if (!set) biomcmc_error ("%s", msg);
-  const int nchar = query->aln->nchar;
-  if ((int) set->nchar != nchar) biomcmc_error ("packed database %s has %u sites but query sequences have %d sites; all sequences must be aligned", o->packed, set->nchar, nchar);
-  if (set->ref_ambiguity != o->ambig_r) biomcmc_error ("packed databases %s ... were filtered with -A %g: search them with that value, or rewrite them with a tighter one by `uvaiapack --merge -A` (a filter cannot be undone)", o->packed, set->ref_ambiguity);
-  if (set->side_row_ints != (uint32_t) uvaia_gpu_db_side_row_ints () || set->tile_bytes != uvaia_gpu_db_tile_bytes (gpu)) biomcmc_error ("packed database %s does not match this engine's tile layout", o->packed);
-  const uint64_t n_all = set->n_ref, chunk_tiles = 256, chunk = chunk_tiles * 64;
+  if ((int) set->nchar != nchar) biomcmc_error ("packed database %s has %u sites but query sequences have %d sites; all sequences must be aligned", first, set->nchar, nchar);
+  if (set->ref_ambiguity != o->ambig_r)
+    biomcmc_error (one ? "packed database %s was filtered with -A %g: search it with that value, or rewrite it with a tighter one by `uvaiapack --merge -A` (a filter cannot be undone)"
+                       : "packed databases %s ... were filtered with -A %g: search them with that value, or rewrite them with a tighter one by `uvaiapack --merge -A` (a filter cannot be undone)", first, set->ref_ambiguity);
+  if (set->side_row_ints != (uint32_t) uvaia_gpu_db_side_row_ints () || set->tile_bytes != uvaia_gpu_db_tile_bytes (gpu)) biomcmc_error ("packed database %s does not match this engine's tile layout", first);
+  const uint64_t n_all = set->n_ref;
   int n_output = 0;
   /* -x: references named like a query leave the stream (src/nearest.c:257-262) */
   uint64_t *keep = NULL, n = n_all;
@@ -302,63 +291,41 @@ search_packed_set (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_
     for (uint64_t i = 0; i < n_all; i++) { if (lookup_hashtable (query->aln->taxlabel_hash, (char *) uvdb_set_name (set, i)) > -1) (*same_name)++; else keep[n++] = i; }
     if (n == n_all) { free (keep); keep = NULL; }
   }
+  /* a window at a time (--window, or a stream that does not fit the GPU's free memory), or resident as a whole */
   uint64_t window = 0, n_windows = 0;
   size_t mem_before = uvaia_gpu_free_bytes (gpu);
   if (o->window_given) {
     if (uvdb_window_plan (n, (uint64_t) o->pool, (uint64_t) o->window, &window, &n_windows)) biomcmc_error ("--window %lld with a pool of %d: the window is beyond what the engine counts", o->window, o->pool);
-  } else if (o->n_devices == 1 && mem_before) {      /* the automatic choice, over the summed count (the footprint as for one file) */
+  } else if (o->n_devices == 1 && mem_before) {
+    /* per resident reference: packed planes, the planes derived for the query set (with the valid-site plane the appends write), side
+       row, counts and flag; an --acgt context also keeps the four-plane image of a window */
     const uint64_t bpr = uvaia_gpu_packed_bytes_per_ref (gpu) + uvaia_gpu_derived_bytes_per_ref (gpu) + uvaia_gpu_db_tile_bytes (gpu) / 256
                        + (uint64_t) uvaia_gpu_db_side_row_ints () * 4 + 20 + (o->acgt ? uvaia_gpu_db_tile_bytes (gpu) / 64 : 0);
     const int64_t w = uvdb_window_choose (n, (uint64_t) o->pool, bpr, (uint64_t) mem_before);
-    if (w < 0) biomcmc_error ("packed databases %s ...: not even one window of %d references (%llu bytes each, and two staging slots) fits the %zu free bytes of the GPU; try a smaller --pool", o->packed, o->pool, (unsigned long long) bpr, mem_before);
-    if (w > 0 && uvdb_window_plan (n, (uint64_t) o->pool, (uint64_t) w, &window, &n_windows)) biomcmc_error ("packed databases %s ...: no window plan for %lld references", o->packed, (long long) w);
-    if (w > 0) fprintf (stderr, "The packed databases do not fit the free memory of the GPU: searching them in %llu windows of %llu sequences.\n", (unsigned long long) n_windows, (unsigned long long) window);
+    if (w < 0) biomcmc_error (one ? "packed database %s: not even one window of %d references (%llu bytes each, and two staging slots) fits the %zu free bytes of the GPU; try a smaller --pool"
+                                  : "packed databases %s ...: not even one window of %d references (%llu bytes each, and two staging slots) fits the %zu free bytes of the GPU; try a smaller --pool",
+                              first, o->pool, (unsigned long long) bpr, mem_before);
+    if (w > 0 && uvdb_window_plan (n, (uint64_t) o->pool, (uint64_t) w, &window, &n_windows))
+      biomcmc_error (one ? "packed database %s: no window plan for %lld references" : "packed databases %s ...: no window plan for %lld references", first, (long long) w);
+    if (w > 0) fprintf (stderr, one ? "The packed database does not fit the free memory of the GPU: searching it in %llu windows of %llu sequences.\n"
+                                    : "The packed databases do not fit the free memory of the GPU: searching them in %llu windows of %llu sequences.\n", (unsigned long long) n_windows, (unsigned long long) window);
   }
   *count = (int) n_all;
+  if (!window) {
+    if (uvaia_gpu_group_db_reserve (grp, (size_t) (n ? n : 1))) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+    load_resident (grp, gpu, o->n_devices, set, keep, n);
+  }
+  if (one) fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, first, biomcmc_update_elapsed_time (time0));
+  else     fprintf (stderr, "Loaded %d packed sequences from %d files in %.3lf secs;\n", (int) n, o->n_packed, biomcmc_update_elapsed_time (time0));
   if (window) {
     double upload_ms[3], part_ms[3] = {0., 0., 0.};
-    fprintf (stderr, "Loaded %d packed sequences from %d files in %.3lf secs;\n", (int) n, o->n_packed, biomcmc_update_elapsed_time (time0));
-    n_output = search_windowed_set (gpu, set, keep, n, window, n_windows, (size_t) o->pool, nchar, outstream, names, upload_ms);
+    n_output = search_windowed (gpu, set, keep, n, window, n_windows, (size_t) o->pool, nchar, outstream, names, upload_ms);
     if (o->window_report) {
       uvaia_gpu_window_ms (gpu, part_ms, 0);
       fprintf (stderr, "window report: {\"window\": %llu, \"n_windows\": %llu, \"free_before\": %zu, \"free_after\": %zu, \"select_ms\": %.3f, \"derive_ms\": %.3f, \"decode_ms\": %.3f, \"upload_ms\": %.3f, \"upload_hidden_share\": %.3f}\n",
                (unsigned long long) window, (unsigned long long) n_windows, mem_before, uvaia_gpu_free_bytes (gpu), part_ms[0], part_ms[1], part_ms[2], upload_ms[0], upload_ms[2]);
     }
   } else {
-    if (uvaia_gpu_group_db_reserve (grp, (size_t) (n ? n : 1))) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-    if (o->n_devices == 1) {     /* chunks of the kept stream: staged piece by piece, appended on the device */
-      if (n && uvaia_gpu_db_stage_reserve (gpu, (size_t) set_max_slot_tiles (set, keep, n, chunk))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-      uvdb_set_piece *pieces = (uvdb_set_piece *) biomcmc_malloc (UVDB_SET_MAX_FILES * sizeof (uvdb_set_piece));
-      int *sel = (int *) biomcmc_malloc ((size_t) chunk * sizeof (int)), slot = 0;
-      for (uint64_t a = 0; a < n; a += chunk, slot ^= 1) {
-        const uint64_t b = (a + chunk < n) ? a + chunk : n;
-        stage_set_range (gpu, set, keep, a, b, slot, pieces, sel);
-        if (uvaia_gpu_db_append_staged (gpu, slot, sel, (int) (b - a))) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-      }
-      free (sel); free (pieces);
-    } else {                     /* a group of devices takes whole host tiles: the lanes are gathered here, from the set */
-      const size_t tb = (size_t) set->tile_bytes, row = (size_t) set->side_row_ints, lane_pieces = tb / (64 * 16);   /* 16-byte pieces per lane */
-      unsigned char *planes = (unsigned char *) biomcmc_malloc (chunk_tiles * tb);
-      int32_t *nn = (int32_t *) biomcmc_malloc (chunk * sizeof (int32_t)), *side = (int32_t *) biomcmc_malloc (chunk * row * sizeof (int32_t));
-      for (uint64_t s0 = 0; s0 < n; s0 += chunk) {
-        const uint64_t cnt = (n - s0 < chunk) ? n - s0 : chunk;
-        memset (planes, 0, chunk_tiles * tb); memset (nn, 0, chunk * sizeof (int32_t)); memset (side, 0, chunk * row * sizeof (int32_t));
-#pragma omp parallel for schedule(static)
-        for (uint64_t k = 0; k < cnt; k++) {
-          int f = 0; uint64_t r = 0;
-          uvdb_set_locate (set, keep ? keep[s0 + k] : s0 + k, &f, &r);
-          uvdb_reader db = set->db[f];
-          const unsigned char *src = (const unsigned char *) uvdb_tile_planes (db, r / 64) + (r % 64) * 16;
-          unsigned char *dst = planes + (k / 64) * tb + (k % 64) * 16;
-          for (size_t p = 0; p < lane_pieces; p++) memcpy (dst + p * 1024, src + p * 1024, 16);
-          nn[k] = db->non_n[r];
-          memcpy (side + k * row, uvdb_tile_side_rows (db, r / 64) + (r % 64) * row, row * sizeof (int32_t));
-        }
-        if (uvaia_gpu_group_db_append_packed (grp, planes, nn, side, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-      }
-      free (planes); free (nn); free (side);
-    }
-    fprintf (stderr, "Loaded %d packed sequences from %d files in %.3lf secs;\n", (int) n, o->n_packed, biomcmc_update_elapsed_time (time0));
     uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1));
     if (n && uvaia_gpu_group_search_resident (grp, (size_t) o->pool, 0, ent)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
     char *text = (char *) biomcmc_malloc ((size_t) nchar + 1);
@@ -466,98 +433,10 @@ main (int argc, char **argv)
            query->n_idx + query->n_idx_c + query->n_idx_m, query->aln->nchar);
   fprintf (stderr, "\n The next step is main comparison, which may take a while\n\n");
 
-  if (o.n_packed > 1) {     /* several packed databases, one stream */
-    n_output = search_packed_set (&o, query, grp, gpu, outstream, &names, &count, &same_name, time0);
+  if (o.n_packed) {     /* packed databases, one stream */
+    n_output = search_packed (&o, query, grp, gpu, outstream, &names, &count, &same_name, time0);
     fprintf (stderr, "Total of %d sequences searched; %d saved sequences include closest neighbours and intermediate. %.3lf secs elapsed. \n", count, n_output, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
-  } else if (o.packed) {     /* resident search over a packed database: replaces the read/filter/fill loop below (src/nearest.c:251-286) */
-    char msg[512];
-    uvdb_reader db = uvdb_open (o.packed, msg, sizeof msg);
-    if (!db) biomcmc_error ("%s", msg);
-    if ((int) db->h.nchar != query->aln->nchar) biomcmc_error ("packed database %s has %u sites but query sequences have %d sites; all sequences must be aligned", o.packed, db->h.nchar, query->aln->nchar);
-    if (db->h.ref_ambiguity != o.ambig_r) biomcmc_error ("packed database %s was filtered with -A %g: search it with that value, or rewrite it with a tighter one by `uvaiapack --merge -A` (a filter cannot be undone)", o.packed, db->h.ref_ambiguity);
-    if (db->h.side_row_ints != (uint32_t) uvaia_gpu_db_side_row_ints () || db->h.tile_bytes != uvaia_gpu_db_tile_bytes (gpu)) biomcmc_error ("packed database %s does not match this engine's tile layout", o.packed);
-    const uint64_t n_all = db->h.n_ref, chunk_tiles = 256;
-    /* -x: references named like a query leave the stream (src/nearest.c:257-262); the others move up, lane by lane */
-    uint64_t *keep = NULL, n = n_all;
-    if (o.exclude_self) {
-      keep = (uint64_t *) biomcmc_malloc ((size_t) (n_all ? n_all : 1) * sizeof (uint64_t));
-      n = 0;
-      for (uint64_t i = 0; i < n_all; i++) { if (lookup_hashtable (query->aln->taxlabel_hash, (char *) uvdb_name (db, i)) > -1) same_name++; else keep[n++] = i; }
-      if (n == n_all) { free (keep); keep = NULL; }
-    }
-    /* a window at a time (--window, or a database that does not fit the GPU's free memory), or resident as a whole */
-    uint64_t window = 0, n_windows = 0;
-    size_t mem_before = uvaia_gpu_free_bytes (gpu);
-    if (o.window_given) {
-      if (uvdb_window_plan (n, (uint64_t) o.pool, (uint64_t) o.window, &window, &n_windows)) biomcmc_error ("--window %lld with a pool of %d: the window is beyond what the engine counts", o.window, o.pool);
-    } else if (o.n_devices == 1 && mem_before) {
-      /* per resident reference: packed planes, the planes derived for the query set (with the valid-site plane the appends write), side
-         row, counts and flag; an --acgt context also keeps the four-plane image of a window */
-      const uint64_t bpr = uvaia_gpu_packed_bytes_per_ref (gpu) + uvaia_gpu_derived_bytes_per_ref (gpu) + uvaia_gpu_db_tile_bytes (gpu) / 256
-                         + (uint64_t) uvaia_gpu_db_side_row_ints () * 4 + 20 + (o.acgt ? uvaia_gpu_db_tile_bytes (gpu) / 64 : 0);
-      const int64_t w = uvdb_window_choose (n, (uint64_t) o.pool, bpr, (uint64_t) mem_before);
-      if (w < 0) biomcmc_error ("packed database %s: not even one window of %d references (%llu bytes each, and two staging slots) fits the %zu free bytes of the GPU; try a smaller --pool", o.packed, o.pool, (unsigned long long) bpr, mem_before);
-      if (w > 0 && uvdb_window_plan (n, (uint64_t) o.pool, (uint64_t) w, &window, &n_windows)) biomcmc_error ("packed database %s: no window plan for %lld references", o.packed, (long long) w);
-      if (w > 0) fprintf (stderr, "The packed database does not fit the free memory of the GPU: searching it in %llu windows of %llu sequences.\n", (unsigned long long) n_windows, (unsigned long long) window);
-    }
-    if (window) {
-      double upload_ms[3], part_ms[3] = {0., 0., 0.};
-      count = (int) n_all;
-      fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, o.packed, biomcmc_update_elapsed_time (time0));
-      n_output = search_windowed (gpu, db, keep, n, window, n_windows, (size_t) o.pool, query->aln->nchar, outstream, &names, upload_ms);
-      if (o.window_report) {
-        uvaia_gpu_window_ms (gpu, part_ms, 0);
-        fprintf (stderr, "window report: {\"window\": %llu, \"n_windows\": %llu, \"free_before\": %zu, \"free_after\": %zu, \"select_ms\": %.3f, \"derive_ms\": %.3f, \"decode_ms\": %.3f, \"upload_ms\": %.3f, \"upload_hidden_share\": %.3f}\n",
-                 (unsigned long long) window, (unsigned long long) n_windows, mem_before, uvaia_gpu_free_bytes (gpu), part_ms[0], part_ms[1], part_ms[2], upload_ms[0], upload_ms[2]);
-      }
-    } else {
-      if (uvaia_gpu_group_db_reserve (grp, (size_t) (n ? n : 1))) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-      if (!keep) {
-        for (uint64_t t = 0; t < db->h.n_tiles; t += chunk_tiles) {
-          const uint64_t nt = (db->h.n_tiles - t < chunk_tiles) ? db->h.n_tiles - t : chunk_tiles;
-          const uint64_t first = t * 64, cnt = (first + nt * 64 > n) ? n - first : nt * 64;
-          if (uvaia_gpu_group_db_append_packed (grp, uvdb_tile_planes (db, t), db->non_n + first, uvdb_tile_side_rows (db, t), (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-        }
-      } else {
-        const size_t tb = (size_t) db->h.tile_bytes, row = (size_t) db->h.side_row_ints, pieces = tb / (64 * 16);   /* 16-byte pieces per lane */
-        unsigned char *planes = (unsigned char *) biomcmc_malloc (chunk_tiles * tb);
-        int32_t *nn = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * sizeof (int32_t)), *side = (int32_t *) biomcmc_malloc (chunk_tiles * 64 * row * sizeof (int32_t));
-        for (uint64_t s0 = 0; s0 < n; s0 += chunk_tiles * 64) {
-          const uint64_t cnt = (n - s0 < chunk_tiles * 64) ? n - s0 : chunk_tiles * 64;
-          memset (planes, 0, chunk_tiles * tb); memset (nn, 0, chunk_tiles * 64 * sizeof (int32_t)); memset (side, 0, chunk_tiles * 64 * row * sizeof (int32_t));
-#pragma omp parallel for schedule(static)
-          for (uint64_t k = 0; k < cnt; k++) {
-            const uint64_t r = keep[s0 + k];
-            const unsigned char *src = (const unsigned char *) uvdb_tile_planes (db, r / 64) + (r % 64) * 16;
-            unsigned char *dst = planes + (k / 64) * tb + (k % 64) * 16;
-            for (size_t p = 0; p < pieces; p++) memcpy (dst + p * 1024, src + p * 1024, 16);
-            nn[k] = db->non_n[r];
-            memcpy (side + k * row, uvdb_tile_side_rows (db, r / 64) + (r % 64) * row, row * sizeof (int32_t));
-          }
-          if (uvaia_gpu_group_db_append_packed (grp, planes, nn, side, (int) cnt)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-        }
-        free (planes); free (nn); free (side);
-      }
-      count = (int) n_all;
-      fprintf (stderr, "Loaded %d packed sequences from %s in %.3lf secs;\n", (int) n, o.packed, biomcmc_update_elapsed_time (time0));
-      uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1));
-      if (n && uvaia_gpu_group_search_resident (grp, (size_t) o.pool, 0, ent)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-      char *text = (char *) biomcmc_malloc ((size_t) query->aln->nchar + 1);
-      for (uint64_t i = 0; i < n; i++) if (ent[i]) {     /* dump every sequence that entered some heap, in stream order */
-        const uint64_t r = keep ? keep[i] : i;
-        n_output++;
-        uvdb_unpack_reference (db, r, text);
-        write_fasta_record (outstream, uvdb_name (db, r), text);
-        name_table_set (&names, (int64_t) i, uvdb_name (db, r));
-      }
-      free (text); free (ent);
-      if (o.window_report) fprintf (stderr, "window report: {\"window\": 0, \"n_windows\": 0, \"free_before\": %zu, \"free_after\": %zu}\n", mem_before, uvaia_gpu_free_bytes (gpu));
-    }
-    free (keep);
-    fprintf (stderr, "Total of %d sequences searched; %d saved sequences include closest neighbours and intermediate. %.3lf secs elapsed. \n", count, n_output, biomcmc_update_elapsed_time (time1));
-    if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
-    uvdb_close_reader (db);
   }
   for (int j = 0; j < o.n_ref; j++) {
     readfasta_t rfas = new_readfasta (o.ref[j]);

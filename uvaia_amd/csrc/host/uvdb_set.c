@@ -144,3 +144,16 @@ uvdb_set_span (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uvdb_se
   if (slot_tiles) *slot_tiles = slot;
   return 0;
 }
+
+int
+uvdb_set_direct_tiles (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uint64_t n, uint64_t store, int *file, uint64_t *first_tile)
+{
+  int f = 0;
+  uint64_t l = 0;
+  if (!s || keep || b <= a || b > n || n != s->n_ref || store % 64) return -1;
+  if (uvdb_set_locate (s, a, &f, &l) || l % 64 || b > s->first[f + 1]) return -1;
+  if ((b - a) % 64 && b != n) return -1;
+  if (file) *file = f;
+  if (first_tile) *first_tile = l / 64;
+  return 0;
+}

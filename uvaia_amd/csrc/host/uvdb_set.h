@@ -58,6 +58,14 @@ typedef struct { int file; uint64_t first_tile, n_tiles, slot_tile; } uvdb_set_p
  * slot beyond what an int counts. */
 int uvdb_set_span (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uvdb_set_piece *pieces, int max_pieces, int *n_pieces, uint64_t *slot_tiles, int *sel_out);
 
+/* Whether kept positions [a, b) of the n kept can go into a resident store of `store` references as whole tiles straight from a mapping
+ * (uvaia_gpu_db_append_packed: whole tiles behind whole tiles), without staging or gathering.  Yes (0, and *file, *first_tile: the b - a
+ * references are the first of the tiles of that file from first_tile on) when nothing is left out (keep == NULL, n = references of the
+ * stream), the range lies in one file and starts at lane 0 of one of its tiles, b - a is a multiple of 64 or b == n (the stream ends with
+ * the range, so the lanes behind it in its last tile are the file's padding), and store is a multiple of 64.  Otherwise -1, as for an
+ * empty range and for one past the stream. */
+int uvdb_set_direct_tiles (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uint64_t n, uint64_t store, int *file, uint64_t *first_tile);
+
 #ifdef __cplusplus
 }
 #endif

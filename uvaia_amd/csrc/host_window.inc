@@ -42,40 +42,45 @@ int uvaia_gpu_db_stage_reserve(uvaia_gpu_ctx *c, size_t n_tiles)
   return 0;
 }
 
-int uvaia_gpu_db_stage_packed(uvaia_gpu_ctx *c, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
-{
-  if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
-  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
-  if (n_tiles < 0 || (n_tiles > 0 && (!planes || !non_n || (!c->acgt && !side_rows)))) return fail(c, UVAIA_GPU_EINVAL, "NULL packed arrays");
-  if ((size_t)n_tiles > c->wstage_tiles) return fail(c, UVAIA_GPU_ESTATE, "%d tiles exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, c->wstage_tiles);
-  HIPCHK(c, hipSetDevice(c->device));
-  auto &sl = c->wstage[slot];
-  sl.n_tiles = 0;
-  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
-  if (n_tiles) {
-    const size_t tb = uvaia_gpu_db_tile_bytes(c), nt = (size_t)n_tiles;
-    HIPCHK(c, hipMemcpyAsync(sl.planes, planes, nt * tb, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(c, hipMemcpyAsync(sl.nonn, non_n, nt * 64 * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
-    if (!c->acgt) HIPCHK(c, hipMemcpyAsync(sl.side, side_rows, nt * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
-  }
-  HIPCHK(c, hipEventRecord(sl.copied, c->copy_stream));
-  sl.n_tiles = n_tiles;
-  return 0;
-}
-
-int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
+// what load_staged and append_staged refuse before anything is touched
+static int check_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 {
   if (!c) return UVAIA_GPU_EINVAL;
   if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
   if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
   if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
-  auto &sl = c->wstage[slot];
-  const long long staged = (long long)sl.n_tiles * 64;
-  if (n_ref > 0 && !sl.n_tiles) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
+  const long long staged = (long long)c->wstage[slot].n_tiles * 64;
+  if (n_ref > 0 && !staged) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
   if (!sel && n_ref > staged) return fail(c, UVAIA_GPU_EINVAL, "%d references asked of the %lld staged in slot %d", n_ref, staged, slot);
   if (sel) for (int k = 0; k < n_ref; k++)
     if (sel[k] < 0 || sel[k] >= staged) return fail(c, UVAIA_GPU_EINVAL, "sel[%d] = %d lies outside the %lld references staged in slot %d", k, sel[k], staged, slot);
+  return 0;
+}
+
+// sel (may be NULL) to the device, on the context's stream
+static int upload_sel(uvaia_gpu_ctx *c, const int *sel, int n_ref)
+{
+  if (!sel) return 0;
+  if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
+  HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// the end of a load: the third event, the wait, the device time of the selection and of what followed it
+static int finish_staged(uvaia_gpu_ctx *c)
+{
+  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
+  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  return 0;
+}
+
+int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
+{
+  if (int rc = check_staged(c, slot, sel, n_ref)) return rc;
+  auto &sl = c->wstage[slot];
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = uvaia_gpu_db_clear(c); if (rc) return rc; }
   c->win_n = 0;
@@ -88,10 +93,7 @@ int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_r
     HIPCHK(c, hipMalloc(&c->d_win4, cap * tile_u4 * sizeof(uint4)));
     c->win4_tiles = cap;
   }
-  if (sel) {
-    if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
-    HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
+  if (int rc = upload_sel(c, sel, n_ref)) return rc;
   for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
   HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
   uint4 *four = c->acgt ? c->d_win4 : c->db.planes;
@@ -108,11 +110,7 @@ int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_r
   hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb, c->db.nonn, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
   HIPCHK(c, hipGetLastError());
   { int rc = derive_rows(c, c->db, 0, (int)(n_tiles * 64)); if (rc) return rc; }
-  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
-  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  if (int rc = finish_staged(c)) return rc;
   c->db_n = (size_t)n_ref;
   c->win_n = n_ref;
   return 0;
@@ -142,18 +140,15 @@ int uvaia_gpu_db_stage_packed_at(uvaia_gpu_ctx *c, int slot, size_t tile_offset,
   return 0;
 }
 
+int uvaia_gpu_db_stage_packed(uvaia_gpu_ctx *c, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
+{
+  return uvaia_gpu_db_stage_packed_at(c, slot, 0, planes, non_n, side_rows, n_tiles);
+}
+
 int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 {
-  if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
-  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
-  if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
+  if (int rc = check_staged(c, slot, sel, n_ref)) return rc;
   auto &sl = c->wstage[slot];
-  const long long staged = (long long)sl.n_tiles * 64;
-  if (n_ref > 0 && !sl.n_tiles) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
-  if (!sel && n_ref > staged) return fail(c, UVAIA_GPU_EINVAL, "%d references asked of the %lld staged in slot %d", n_ref, staged, slot);
-  if (sel) for (int k = 0; k < n_ref; k++)
-    if (sel[k] < 0 || sel[k] >= staged) return fail(c, UVAIA_GPU_EINVAL, "sel[%d] = %d lies outside the %lld references staged in slot %d", k, sel[k], staged, slot);
   if (n_ref == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = settle_derive(c); if (rc) return rc; }
@@ -174,10 +169,7 @@ int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n
     c->win4_tiles = cap;
   }
   if (n0 % 64) { if (int rc = sync_scan_streams(c)) return rc; }      // the derived planes of the first tile are rebuilt: no scan may still read them
-  if (sel) {
-    if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
-    HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  }
+  if (int rc = upload_sel(c, sel, n_ref)) return rc;
   for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
   HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
   HIPCHK(c, hipEventRecord(c->win_ev[0], c->stream));
@@ -195,11 +187,7 @@ int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n
                      (long long)n_ref, c->W4 * 4, c->nchar);
   HIPCHK(c, hipGetLastError());
   { int rc = derive_rows(c, c->db, (long long)n0, n_ref); if (rc) return rc; }
-  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
-  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  if (int rc = finish_staged(c)) return rc;
   c->db_n = n1;
   c->win_n = image ? (int)n1 : 0;
   return 0;

@@ -230,6 +230,7 @@ class UvdbSet:
             L.uvdb_set_runs.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
             L.uvdb_set_span.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.POINTER(UvdbSetPiece), C.c_int, C.POINTER(C.c_int),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
+            L.uvdb_set_direct_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
             L._uvdb_set_ready = True
         err = C.create_string_buffer(1024)
         self.h = L.uvdb_set_open(_cstrs([str(p) for p in paths]), len(paths), int(flags), err, len(err))
@@ -269,6 +270,15 @@ class UvdbSet:
         if self.L.uvdb_set_span(self.h, kp, int(a), int(b), pieces, int(max_pieces), C.byref(n), C.byref(st), sel.ctypes.data_as(C.POINTER(C.c_int))):
             return None
         return [(p.file, p.first_tile, p.n_tiles, p.slot_tile) for p in pieces[:n.value]], st.value, sel[:max(int(b) - int(a), 0)]
+
+    def direct_tiles(self, keep, a, b, n, store):
+        """uvdb_set_direct_tiles: (file, first_tile), or None where it returns -1"""
+        kp = None
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint64)
+            kp = keep.ctypes.data_as(C.POINTER(C.c_uint64))
+        f, t = C.c_int(-1), C.c_uint64(0)
+        return None if self.L.uvdb_set_direct_tiles(self.h, kp, int(a), int(b), int(n), int(store), C.byref(f), C.byref(t)) else (f.value, t.value)
 
     def close(self):
         if self.h:
