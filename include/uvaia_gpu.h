@@ -78,7 +78,7 @@ typedef struct {
   int serial;                  /* 1 = no overlap between the rebuild of the derived planes, the scans and the replays (isolated kernel timings) */
   int scan_tiles_per_wave;     /* column-compressed scan: 1, 2 or 4 tiles of 64 references per wave (default 2; 4 only with 8 waves per block) */
   int scan_waves_per_block;    /* column-compressed scan: 4 or 8 waves share a super-tile of 64 queries (default 8) */
-  int rederive_streams;        /* uvaia_gpu_db_rederive: its chunks alternate over 1..3 streams (default 3: all chunks in flight at once, the first still done first) */
+  int rederive_streams;        /* uvaia_gpu_db_rederive: its chunks alternate over 1..3 streams (default: 3 for a rebuild of up to three chunks -- all in flight at once, the first still done first --, 1 from four chunks on) */
   int ball_gather;             /* radius search: the references' planes on the columns of query->idx are gathered 1 = by a pass of its own over the
                                   references that go on to the queries, 2 = by the consensus pass itself, for every reference (default 2) */
   int query_tables;            /* the scans' query-side tables (plane words, column classes, rare columns, compressed planes, item streams) are built
@@ -97,6 +97,8 @@ typedef struct {
   int head_scan;               /* resident search over the column-compressed scan: 2 = the stream's first 128 references take the four-counter scan, so that the
                                   heaps fill without a memory round trip per admission; 0 / 1 = they go through the slices like the rest (default: the
                                   63 blocks of that scan run for 0.4 ms on their own, more than the hundred round trips they save) */
+  int derive_waves;            /* the kernel that derives a tile's planes for the query set runs 4, 8 or 16 waves per tile (0 = the library's choice: 4;
+                                  measured alike at config[1]); same arrays from every width */
 } uvaia_gpu_tuning;
 /* Diagnostics: a copy of one of the query-side tables the scans read, as the open call left it on the device (tests compare the two ways
  * of building them).  which: 0 query plane words, 1 recoded planes (default mode), 2 ambiguity-word lists, 3 column classes, 4 rare-column
@@ -129,7 +131,9 @@ int uvaia_gpu_push (uvaia_gpu_ctx *ctx, const char *const *seq, const int *non_n
 int uvaia_gpu_drain (uvaia_gpu_ctx *ctx, int *n_items, int *max_incompatible, int *scores, int64_t *ordinals);
 int uvaia_gpu_heap_slots (const uvaia_gpu_ctx *ctx);      /* max(2,heap_size) */
 int uvaia_gpu_n_query (const uvaia_gpu_ctx *ctx);
-/* Back to the state right after uvaia_gpu_open() (heaps empty); a resident database is kept. */
+/* Back to the state right after uvaia_gpu_open() (heaps empty, entered flags of the resident database cleared); a resident database is
+ * kept.  Asynchronous: one kernel launch, ordered before every later call on the context (pushes, searches, slice replays, state
+ * import / export, uvaia_gpu_drain, uvaia_gpu_entered_flags) and behind the searches issued before it; it does not wait for the device. */
 int uvaia_gpu_reset (uvaia_gpu_ctx *ctx);
 
 /* ---- HBM-resident database (the measured configuration: references packed once, scanned many times) ----
@@ -341,9 +345,17 @@ size_t uvaia_gpu_db_tile_bytes (const uvaia_gpu_ctx *ctx);
 int    uvaia_gpu_db_clear (uvaia_gpu_ctx *ctx);                      /* empties the resident database, keeps its capacity */
 /* Rebuilds, for every resident reference, the planes the scan reads for the open query set (the appends build them for the rows
  * they add): the per-reference share of the work that depends on the query set (the reference does it implicitly, its loops
- * read the raw sequences through idx_c / idx_m / idx, src/nearest.c:428-510).  Asynchronous; later searches wait for it.  Call
- * between searches (after uvaia_gpu_sync), e.g. to time a search of a resident database together with this work. */
+ * read the raw sequences through idx_c / idx_m / idx, src/nearest.c:428-510).  Asynchronous; later searches wait for it, and it
+ * queues behind searches still in flight (after uvaia_gpu_sync there are none and its first launch is issued at once).  Call between
+ * searches, e.g. to time a search of a resident database together with this work. */
 int    uvaia_gpu_db_rederive (uvaia_gpu_ctx *ctx);
+/* Introspection (tests compare the block widths of the deriving kernel array for array): what the column-compressed scan reads of the
+ * first n_tiles tiles of 64 references, as the appends or the last uvaia_gpu_db_rederive left it (a rebuild in flight is waited for).
+ * With G = ceil(ceil(nchar / 32) / 4) word groups and, from uvaia_gpu_export_query_table(.., 10, ..), P = word groups of the gathered
+ * polymorphic + rare columns:  e [n_tiles][G][64] 16-byte words (the plane of matches with the constant query columns),
+ * grp [n_tiles][G][64] uint32 (its and the valid-site plane's popcounts per group),  poly [n_tiles][P][3][64] 16-byte words (the gathered
+ * columns),  tot [n_tiles * 64] int (matches with the constant columns per reference). */
+int    uvaia_gpu_db_derived_export (uvaia_gpu_ctx *ctx, size_t n_tiles, void *e, uint32_t *grp, void *poly, int *tot);
 int    uvaia_gpu_db_side_row_ints (void);
 int    uvaia_gpu_db_export (uvaia_gpu_ctx *ctx, size_t first_tile, size_t n_tiles, void *planes, int *non_n, int *side_rows);
 int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const int *non_n, const int *side_rows, int n_ref);

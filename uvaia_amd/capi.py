@@ -19,7 +19,7 @@ SYMBOLS = [
     "uvaia_gpu_state_bytes", "uvaia_gpu_state_export", "uvaia_gpu_state_import", "uvaia_gpu_slice_scan", "uvaia_gpu_slice_replay",
     "uvaia_gpu_entered_flags", "uvaia_gpu_state_range_bytes", "uvaia_gpu_state_export_range", "uvaia_gpu_state_import_range",
     "uvaia_gpu_slice_replay_range", "uvaia_gpu_slice_buffers", "uvaia_gpu_scan_bytes_per_ref", "uvaia_gpu_derived_bytes_per_ref", "uvaia_gpu_scan_variant", "uvaia_gpu_set_query_tile", "uvaia_gpu_packed_bytes_per_ref",
-    "uvaia_gpu_db_tile_bytes", "uvaia_gpu_db_side_row_ints", "uvaia_gpu_db_export", "uvaia_gpu_db_append_packed", "uvaia_gpu_db_clear", "uvaia_gpu_db_rederive",
+    "uvaia_gpu_db_tile_bytes", "uvaia_gpu_db_side_row_ints", "uvaia_gpu_db_export", "uvaia_gpu_db_append_packed", "uvaia_gpu_db_clear", "uvaia_gpu_db_rederive", "uvaia_gpu_db_derived_export",
     "uvaia_gpu_set_active_queries", "uvaia_gpu_max_tolerance", "uvaia_gpu_search_resident_pool",
     "uvaia_gpu_db_set_shard", "uvaia_gpu_shard_rows", "uvaia_gpu_shard_scan", "uvaia_gpu_scan_wait", "uvaia_gpu_replay_wait", "uvaia_gpu_set_snapshot", "uvaia_gpu_shard_replay",
     "uvaia_gpu_mark", "uvaia_gpu_stream_wait_mark", "uvaia_gpu_wait_stream",
@@ -43,7 +43,7 @@ class GpuError(RuntimeError):
 class Tuning(C.Structure):
     """uvaia_gpu_tuning: optional knobs of uvaia_gpu_open_tuned (0 = the library's choice); they change speed, never results."""
     _fields_ = [("subslice_refs", C.c_size_t), ("rare_max", C.c_int), ("scan", C.c_int), ("serial", C.c_int),
-                ("scan_tiles_per_wave", C.c_int), ("scan_waves_per_block", C.c_int), ("rederive_streams", C.c_int), ("ball_gather", C.c_int), ("query_tables", C.c_int), ("replay_extras", C.c_int), ("replay_cus", C.c_int), ("scan_streams", C.c_int), ("pipeline", C.c_int), ("head_scan", C.c_int)]
+                ("scan_tiles_per_wave", C.c_int), ("scan_waves_per_block", C.c_int), ("rederive_streams", C.c_int), ("ball_gather", C.c_int), ("query_tables", C.c_int), ("replay_extras", C.c_int), ("replay_cus", C.c_int), ("scan_streams", C.c_int), ("pipeline", C.c_int), ("head_scan", C.c_int), ("derive_waves", C.c_int)]
 
     SCAN = {"auto": 0, "packed": 1, "compressed": 2, "wide": 3}
 
@@ -148,6 +148,7 @@ def load_library():
         "uvaia_gpu_db_tile_bytes": (C.c_size_t, [vp]),
         "uvaia_gpu_db_clear": (C.c_int, [vp]),
         "uvaia_gpu_db_rederive": (C.c_int, [vp]),
+        "uvaia_gpu_db_derived_export": (C.c_int, [vp, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "uvaia_gpu_db_side_row_ints": (C.c_int, []),
         "uvaia_gpu_db_export": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_void_p, pi, pi]),
         "uvaia_gpu_db_append_packed": (C.c_int, [vp, C.c_void_p, pi, pi, C.c_int]),
@@ -646,6 +647,18 @@ class Engine:
         if n.value:
             self._chk(self.L.uvaia_gpu_export_query_table(self.ctx, int(which), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
         return out
+
+    def db_derived(self, n_tiles):
+        """uvaia_gpu_db_derived_export: (e, grp, poly, tot) of the first n_tiles tiles as the column-compressed scan reads them."""
+        W4 = ((self.nchar + 31) // 32 + 3) // 4
+        counts = self.query_table(10).view(np.int32)
+        NG = int(counts[2]) + int(counts[3])
+        e = np.zeros((n_tiles, W4, 64, 4), dtype=np.uint32)
+        grp = np.zeros((n_tiles, W4, 64), dtype=np.uint32)
+        poly = np.zeros((n_tiles, NG, 3, 64, 4), dtype=np.uint32)
+        tot = np.zeros(n_tiles * 64, dtype=np.int32)
+        self._chk(self.L.uvaia_gpu_db_derived_export(self.ctx, int(n_tiles), e.ctypes.data, grp.ctypes.data, poly.ctypes.data, tot.ctypes.data))
+        return e, grp, poly, tot
 
     def ball_kernel_ms(self, reset=False):
         """Device ms since the last reset of (consensus pass, gather of the asked references, pair scan)."""

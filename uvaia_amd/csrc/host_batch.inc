@@ -114,6 +114,7 @@ int uvaia_gpu_drain(uvaia_gpu_ctx *c, int *n_items, int *max_incompatible, int *
 {
   if (!c || !n_items || !scores || !ordinals) return c ? fail(c, UVAIA_GPU_EINVAL, "NULL output") : UVAIA_GPU_EINVAL;
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  planes_idle(c, true, false);
   const size_t ne = (size_t)c->nq * (c->k + 1);
   std::vector<int> h(ne * HEAP_ENTRY), T(c->nq);
   HIPCHK(c, hipMemcpy(h.data(), c->d_heap, h.size() * sizeof(int), hipMemcpyDeviceToHost));

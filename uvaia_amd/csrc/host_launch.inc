@@ -174,6 +174,38 @@ int pack_query_row(const uint8_t *code_tab, const char *row, int nchar, int lo, 
   return 0;
 }
 
+// derive_all_kernel's column split (query table 9): for each block width -- 4, 8, 16 waves per tile, in this order -- a section of
+// 3 (NWV + 1) ints: the word groups where each wave starts (equal shares of W4, uneven where it is no multiple; a wave has none where
+// W4 < NWV), and the dense and the rare gathered bits before each of those boundaries.  One routine for both builders of the tables.
+constexpr int DERIVE_SPLIT_INTS = 3 * (5 + 9 + 17);
+inline int derive_split_offset(int nwv) { return nwv == 4 ? 0 : nwv == 8 ? 3 * 5 : 3 * (5 + 9); }
+inline void build_derive_split(const uint32_t *cls, const uint32_t *rmask, int W4, int *split)
+{
+  for (int nwv : {4, 8, 16}) {
+    int *s = split + derive_split_offset(nwv);
+    for (int v = 0; v <= nwv; v++) s[v] = (int)((long long)W4 * v / nwv);
+    int nd = 0, nr = 0, w = 0;
+    for (int v = 0; v <= nwv; v++) {
+      for (; w < s[v] * 4; w++) { nd += __builtin_popcount(cls[(size_t)w * 4 + 3]); nr += __builtin_popcount(rmask[(size_t)w]); }
+      s[nwv + 1 + v] = nd; s[2 * (nwv + 1) + v] = nr;
+    }
+  }
+}
+
+// Book-keeping of what uvaia_gpu_db_rederive has to queue behind (uvaia_gpu_ctx::planes_busy): planes_touch = work that reads or writes the
+// derived planes goes onto `st` now; planes_fenced = `ev` has just been recorded on `st` (an event re-recorded on another stream no longer
+// stands for the stream it was recorded on before); planes_idle = the host has waited for `stream` (main) or for the scan streams.
+inline int planes_slot(const uvaia_gpu_ctx *c, hipStream_t st) { for (int i = 0; i < 3; i++) if (st && st == c->scan_streams[i]) return 1 + i; return 0; }
+inline void planes_touch(uvaia_gpu_ctx *c, hipStream_t st) { const int i = planes_slot(c, st); c->planes_busy[i] = true; c->planes_ev[i] = nullptr; }
+inline void planes_fenced(uvaia_gpu_ctx *c, hipStream_t st, hipEvent_t ev)
+{
+  const int i = planes_slot(c, st);
+  for (int j = 0; j < 4; j++) if (j != i && c->planes_ev[j] == ev) c->planes_ev[j] = nullptr;
+  if (c->planes_busy[i]) c->planes_ev[i] = ev;
+}
+inline void planes_idle(uvaia_gpu_ctx *c, bool main, bool scans)
+{ for (int i = 0; i < 4; i++) if (i == 0 ? main : scans) { c->planes_busy[i] = false; c->planes_ev[i] = nullptr; } }
+
 // a pair of timing events for one scan launch: from the pool if it has any
 int take_scan_events(uvaia_gpu_ctx *c, ScanEvt &ev)
 {
@@ -242,6 +274,7 @@ int launch_scan2(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int
   }
   const uint32_t *qp = c->acgt ? c->d_qp : c->d_qp2;
   if (c->scan_variant == 2) {
+    planes_touch(c, stream);
     const int *tote = s.tote + tile_first * 64;
     constexpr int QS = 64;                       // queries of a super-tile of scan3_kernel
     if (c->act_q0 % QS) return fail(c, UVAIA_GPU_ESTATE, "the scan works on super-tiles of %d queries: active queries start at a multiple of that", QS);
@@ -322,6 +355,8 @@ int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
 {
   const dim3 grid(L.q1 - L.q0), block(64);
   const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int);
+  c->entered_clean = 0;                      // every replay sets entered flags
+  if (L.poly) planes_touch(c, L.stream);     // (on-demand counters from the derived planes)
   if (c->fullscan) {
 #define REPLAY(A) hipLaunchKernelGGL((replay_kernel<A>), grid, block, lds, L.stream, c->d_cnt, L.ppad, c->d_rt, c->d_tr, L.nonn, L.rb, L.re, L.ord_base, c->d_heap, c->d_n, c->d_T, c->d_snap, L.entered, c->k)
     if (c->acgt) REPLAY(true); else REPLAY(false);
@@ -385,17 +420,25 @@ int derive_rows(uvaia_gpu_ctx *c, const TileStore &s, long long slot0, int n_ref
 {
   if (!st) st = c->stream;
   if (c->fullscan || c->scan_variant != 2 || n_ref <= 0 || !c->d_split) return 0;     // only the column-compressed scan reads derived planes
+  if (st == c->stream) planes_touch(c, st);       // (the rebuild's own streams are in order among themselves)
   const long long a = slot0 / 64, t1 = (slot0 + n_ref - 1) / 64;
   const int nblk = (int)(t1 - a + 1);
-#define DERIVE_ALL(A, V) hipLaunchKernelGGL((derive_all_kernel<A, V>), dim3(nblk), dim3(256), 0, st, s.planes, a, a, c->W4, c->d_cls, c->d_rmask, c->d_split, c->NP4, c->NR4, s.ev, s.tote, s.grp, s.poly)
-  if (c->acgt) { if (v_in_place) DERIVE_ALL(true, false); else DERIVE_ALL(true, true); }
-  else         { if (v_in_place) DERIVE_ALL(false, false); else DERIVE_ALL(false, true); }
+  // Waves per tile: the same arrays from every width.  Four unless tuning.derive_waves asks for 8 or 16 -- measured at config[1], one box,
+  // interleaved: 2.93 / 2.96 / 2.97 ms per step with 4 / 8 / 16 everywhere, 2.92-2.95 with 16 for a rebuild's first chunk and 4 or 8 beside the
+  // scans; the first chunk of 273 tiles takes 101-105 us at 4 waves and 103 at 16 (DESIGN.md 4.2: a launch of that size is not bound by a
+  // wave's chain of loads).
+  const int waves = c->derive_waves ? c->derive_waves : 4;
+#define DERIVE_ALL_W(A, V, N) hipLaunchKernelGGL((derive_all_kernel<A, V, N>), dim3(nblk), dim3(64 * N), 0, st, s.planes, a, a, c->W4, c->d_cls, c->d_rmask, c->d_split + derive_split_offset(N), c->NP4, c->NR4, s.ev, s.tote, s.grp, s.poly)
+#define DERIVE_ALL(A, V) { if (waves == 8) DERIVE_ALL_W(A, V, 8); else if (waves == 16) DERIVE_ALL_W(A, V, 16); else DERIVE_ALL_W(A, V, 4); }
+  if (c->acgt) { if (v_in_place) DERIVE_ALL(true, false) else DERIVE_ALL(true, true) }
+  else         { if (v_in_place) DERIVE_ALL(false, false) else DERIVE_ALL(false, true) }
 #undef DERIVE_ALL
+#undef DERIVE_ALL_W
   HIPCHK(c, hipGetLastError());
   return 0;
 }
 
-int sync_scan_streams(uvaia_gpu_ctx *c) { for (hipStream_t st : c->scan_streams) if (st) HIPCHK(c, hipStreamSynchronize(st)); return 0; }
+int sync_scan_streams(uvaia_gpu_ctx *c) { for (hipStream_t st : c->scan_streams) if (st) HIPCHK(c, hipStreamSynchronize(st)); planes_idle(c, false, true); return 0; }
 int sync_derive_streams(uvaia_gpu_ctx *c) { for (hipStream_t st : c->derive_streams) if (st) HIPCHK(c, hipStreamSynchronize(st)); return 0; }
 
 template <class T> int regrow(uvaia_gpu_ctx *c, T *&p, size_t n) { if (p) hipFree(p); p = nullptr; HIPCHK(c, hipMalloc(&p, n * sizeof(T))); return 0; }
@@ -454,6 +497,7 @@ int pack_rows(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t
   }
   { int rc = derive_rows(c, s, slot0, n_ref); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->stream));     // scans may start on another stream: the packed and derived planes must be complete
+  planes_idle(c, true, false);
   int bad = 0;
   HIPCHK(c, hipMemcpy(&bad, c->d_err, sizeof(int), hipMemcpyDeviceToHost));
   if (bad) {

@@ -45,7 +45,8 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   memset(&tn, 0, sizeof tn);
   if (tune) tn = *tune;
   if (tn.scan < 0 || tn.scan > UVAIA_GPU_SCAN_WIDE || tn.query_tables < 0 || tn.query_tables > 2 || (tn.scan_tiles_per_wave != 0 && tn.scan_tiles_per_wave != 1 && tn.scan_tiles_per_wave != 2 && tn.scan_tiles_per_wave != 4) ||
-      (tn.scan_waves_per_block != 0 && tn.scan_waves_per_block != 4 && tn.scan_waves_per_block != 8) || (tn.subslice_refs != 0 && tn.subslice_refs < 64))
+      (tn.scan_waves_per_block != 0 && tn.scan_waves_per_block != 4 && tn.scan_waves_per_block != 8) || (tn.subslice_refs != 0 && tn.subslice_refs < 64) ||
+      (tn.derive_waves != 0 && tn.derive_waves != 4 && tn.derive_waves != 8 && tn.derive_waves != 16))
     return fail(nullptr, UVAIA_GPU_EINVAL, "bad tuning values");
   if (!out) return fail(nullptr, UVAIA_GPU_EINVAL, "ctx is NULL");
   *out = nullptr;
@@ -79,6 +80,7 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   if (tn.scan_streams > 100 && tn.scan_streams < 200) c->first_slice_pct = tn.scan_streams == 199 ? 0 : tn.scan_streams - 100;
   if (tn.pipeline == 2) c->pipeline = true;
   if (tn.head_scan == 2) c->head_full = true;
+  c->derive_waves = tn.derive_waves;
   if (tn.ball_gather == 1 || tn.ball_gather == 2) c->ball_fused = tn.ball_gather == 2;
   if (tn.rederive_streams >= 1 && tn.rederive_streams <= 3) { c->derive_nstreams = tn.rederive_streams; c->derive_forced = true; }
   // the default scan keeps per-pair deficits in 16-bit halves (LDS counters): alignments of more than ~49 000 columns take the
@@ -254,13 +256,18 @@ int uvaia_gpu_export_query_table(uvaia_gpu_ctx *c, int which, void *out, size_t 
 int uvaia_gpu_reset(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipMemsetAsync(c->d_heap, 0, (size_t)c->nq * (c->k + 1) * HEAP_ENTRY * sizeof(int), c->stream));
-  hipLaunchKernelGGL(init_state_kernel, dim3((c->nq + 255) / 256), dim3(256), 0, c->stream, c->d_T, c->d_n, c->nq, c->nchar);
+  // One launch on `stream` and no wait for it: heaps, tolerances, item counts, the batch snapshot and the entered flags are only ever read
+  // or written in `stream`'s order -- the replays and snapshots of every search path (push, resident, slices, reference shards and groups),
+  // the state hand-over of the ring, uvaia_gpu_set_snapshot; the replay kernels of the masked replay stream run between two events of
+  // `stream` (uvaia_gpu_slice_replay_range) -- and what the host reads (uvaia_gpu_drain, uvaia_gpu_entered_flags) waits for `stream` first.
+  // The scans hold no such state: a step's first scan is issued while this kernel runs.
+  const size_t heap16 = (size_t)c->nq * (c->k + 1) * HEAP_ENTRY * sizeof(int) / 16;
+  const size_t ent = (c->d_entered && c->db_n) ? std::min(c->entered_cap / 64 * 64, ((c->db_n + 63) / 64) * 64) : 0;
+  const size_t work = std::max(std::max(heap16, ent / 16), (size_t)c->nq);
+  hipLaunchKernelGGL(reset_state_kernel, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, c->stream,
+                     reinterpret_cast<uint4 *>(c->d_heap), heap16, c->d_T, c->d_n, c->nq, c->nchar, c->d_snap, reinterpret_cast<uint4 *>(c->d_entered), ent / 16);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(c->d_snap, &c->nchar, sizeof(int), hipMemcpyHostToDevice, c->stream));   // cq->max_incompatible = n_sites (src/nearest.c:375)
-  if (c->d_entered && c->db_n) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
-  if (int rc = sync_scan_streams(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->entered_clean = ent;
   return 0;
 }
 

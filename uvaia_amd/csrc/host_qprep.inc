@@ -99,14 +99,9 @@ int build_query_tables_device(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const 
   // (what the polymorphic and the rare columns can take away has to fit the scan's 16-bit deficits: see host_qtables.inc)
   if (c->scan_variant == 2 && (size_t)c->NP4 * 128 + (size_t)c->NR4 * 128 > SCAN3_BIAS - 256) c->scan_variant = 0;
   {   // derive_all_kernel: word groups per wave and the bit positions its gathered columns start at
-    int split[15];
-    for (int v = 0; v <= 4; v++) split[v] = (int)((long long)c->W4 * v / 4);
-    for (int v = 0; v <= 4; v++) {
-      int nd = 0, nr = 0;
-      for (int w = 0; w < split[v] * 4; w++) { nd += __builtin_popcount(cls[(size_t)w * 4 + 3]); nr += __builtin_popcount(rmask[(size_t)w]); }
-      split[5 + v] = nd; split[10 + v] = nr;
-    }
-    QALLOC(c->d_split, 15, false);
+    int split[DERIVE_SPLIT_INTS];
+    build_derive_split(cls.data(), rmask.data(), c->W4, split);
+    QALLOC(c->d_split, DERIVE_SPLIT_INTS, false);
     OPENCHK(hipMemcpyAsync(c->d_split, split, sizeof split, hipMemcpyHostToDevice, s));
     OPENCHK(hipStreamSynchronize(s));                         // (split lives on this frame)
     c->qtab[9] = {c->d_split, sizeof split};

@@ -144,13 +144,8 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
       OPENCHK(hipMalloc(&c->d_rmask, rmask.size() * 4)); OPENCHK(hipMemcpy(c->d_rmask, rmask.data(), rmask.size() * 4, hipMemcpyHostToDevice));
       c->qtab[3] = {c->d_cls, cls.size() * 4}; c->qtab[4] = {c->d_rmask, rmask.size() * 4}; c->qtab[6] = {c->d_qrare, qrare.size() * 4};
       {   // derive_all_kernel: word groups per wave and the bit positions its gathered columns start at
-        int split[15];
-        for (int v = 0; v <= 4; v++) split[v] = (int)((long long)c->W4 * v / 4);
-        for (int v = 0; v <= 4; v++) {
-          int nd = 0, nr = 0;
-          for (int w = 0; w < split[v] * 4; w++) { nd += __builtin_popcount(cls[(size_t)w * 4 + 3]); nr += __builtin_popcount(rmask[(size_t)w]); }
-          split[5 + v] = nd; split[10 + v] = nr;
-        }
+        int split[DERIVE_SPLIT_INTS];
+        build_derive_split(cls.data(), rmask.data(), c->W4, split);
         OPENCHK(hipMalloc(&c->d_split, sizeof split)); OPENCHK(hipMemcpy(c->d_split, split, sizeof split, hipMemcpyHostToDevice));
         c->qtab[9] = {c->d_split, sizeof split};
       }

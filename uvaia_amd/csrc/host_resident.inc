@@ -15,6 +15,7 @@ int uvaia_gpu_db_reserve(uvaia_gpu_ctx *c, size_t cap)
   c->db_local_tiles = dtiles;
   c->peer_db[c->shard_rank] = c->db.planes; c->peer_amb[c->shard_rank] = c->db.amb;
   c->db_cap = tiles * 64 - 64;
+  c->entered_clean = 0;
   if (c->entered_cap < tiles * 64) {
     hipFree(c->d_entered); c->d_entered = nullptr;
     HIPCHK(c, hipMalloc(&c->d_entered, tiles * 64)); c->entered_cap = tiles * 64;
@@ -122,6 +123,23 @@ int uvaia_gpu_db_export(uvaia_gpu_ctx *c, size_t first_tile, size_t n_tiles, voi
   return 0;
 }
 
+int uvaia_gpu_db_derived_export(uvaia_gpu_ctx *c, size_t n_tiles, void *e, uint32_t *grp, void *poly, int *tot)
+{ // introspection: what derive_all_kernel left for the first n_tiles tiles, after any rebuild in flight
+  if (!c || !e || !grp || !poly || !tot) return UVAIA_GPU_EINVAL;
+  if (c->fullscan || c->scan_variant != 2 || !c->db.ev) return fail(c, UVAIA_GPU_ESTATE, "only the column-compressed scan keeps planes derived for the query set");
+  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard numbers its derived tiles by piece: read them from a plain context");
+  if (n_tiles * 64 > ((c->db_n + 63) / 64) * 64) return fail(c, UVAIA_GPU_EINVAL, "tiles 0..%zu lie outside the database", n_tiles);
+  if (!n_tiles) return 0;
+  { int rc = settle_derive(c); if (rc) return rc; }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t W4 = (size_t)c->W4, NG = (size_t)(c->NP4 + c->NR4);
+  HIPCHK(c, hipMemcpy2D(e, 1024, c->db.ev, 2048, 1024, n_tiles * W4, hipMemcpyDeviceToHost));        // [tile][w4][E, V][64] uint4: the E halves
+  HIPCHK(c, hipMemcpy(grp, c->db.grp, n_tiles * W4 * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (NG) HIPCHK(c, hipMemcpy(poly, c->db.poly, n_tiles * NG * 3 * 64 * sizeof(uint4), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(tot, c->db.tote, n_tiles * 64 * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *non_n, const int *side_rows, int n_ref)
 {
   if (!c) return UVAIA_GPU_EINVAL;
@@ -222,7 +240,9 @@ static std::vector<SubSlice> plan_subslices(const uvaia_gpu_ctx *c, size_t first
     const size_t each = ((len + ns - 1) / ns + 63) / 64 * 64;
     // A pool's first slice is 70 % of an equal share: the first replay -- the heaps filling and turning over, the longest of the chain of
     // replays, which ends a step at config[1] -- starts that much earlier, and so does the first scan after a rebuild of the derived planes
-    // (round 4, one box, interleaved twice: 3.16 ms per step with equal slices, 3.14-3.16 / 3.00-3.07 / 3.07 with 50 / 65 / 80 %).
+    // (round 4, one box, interleaved twice: 3.16 ms per step with equal slices, 3.14-3.16 / 3.00-3.07 / 3.07 with 50 / 65 / 80 %; again
+    // behind the asynchronous reset and the unfenced rebuild, interleaved three times: 2.944 / 2.887 / 2.918 / 2.928 with 50 / 65 / 70 / 80 %,
+    // the same configuration run twice 2.918 and 2.951 -- no difference to tell from that: 70 % stays).
     if (c->first_slice_pct > 0 && c->first_slice_pct < 100 && ns >= 3 && !c->subslice_forced) {
       const size_t first_n = std::max<size_t>(64, each * (size_t)c->first_slice_pct / 100 / 64 * 64), rest = len - first_n;
       const size_t each2 = ((rest + (ns - 1) - 1) / (ns - 1) + 63) / 64 * 64;
@@ -244,15 +264,6 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
   if (!c) return UVAIA_GPU_EINVAL;
   if (!c->db.planes || !c->db_n || c->fullscan || c->scan_variant != 2) return 0;
   HIPCHK(c, hipSetDevice(c->device));
-  {   // searches still in flight read the planes: the rebuild queues behind them
-    hipStream_t busy[4] = {c->stream, c->scan_streams[0], c->scan_streams[1], c->scan_streams[2]};
-    for (int i = 0; i < 4; i++) {
-      if (!busy[i]) continue;
-      if (!c->derive_fence[i]) HIPCHK(c, hipEventCreateWithFlags(&c->derive_fence[i], hipEventDisableTiming));
-      HIPCHK(c, hipEventRecord(c->derive_fence[i], busy[i]));
-      for (int j = 0; j < c->derive_nstreams; j++) HIPCHK(c, hipStreamWaitEvent(c->derive_streams[j], c->derive_fence[i], 0));
-    }
-  }
   std::vector<SubSlice> plan;
   if (c->shard_world == 1) plan = plan_subslices(c, 0, c->db_n, c->max_pool);
   else {   // reference shards: the chunks are the context's own pieces, which is what it scans (uvaia_gpu_shard_scan)
@@ -260,23 +271,41 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
     for (size_t a = (size_t)c->shard_rank * piece; a < c->db_n; a += piece * (size_t)c->shard_world) plan.push_back({a, std::min(piece, c->db_n - a), false});
   }
   // Chunks over several streams are all in flight at once: the rebuild as a whole ends sooner, its FIRST chunk -- what the first scan
-  // waits for -- later.  That pays for up to three chunks (config[1]); a long stream rebuilds in order on one stream (1 M references:
-  // 64 queries 9.25 -> 8.65 ms per search, 256 queries 12.7 -> 11.4).
+  // waits for -- later.  That pays for up to three chunks; from four on -- config[1] since its first slice is 70 % of a share, and every
+  // long stream -- the rebuild runs in order on one stream (1 M references: 64 queries 9.25 -> 8.65 ms per search, 256 queries 12.7 -> 11.4;
+  // config[1], four chunks forced onto 1 / 2 / 3 streams, interleaved three times: 2.951 / 2.959 / 2.992 ms per step).
   const int n_derive_streams = (c->derive_forced || plan.size() <= 3) ? c->derive_nstreams : 1;
+  // Searches still in flight read the planes (and an append may be writing them): the streams the rebuild uses queue behind them.  A
+  // stream the host has waited for since the last such work holds nothing to wait for -- after uvaia_gpu_sync none does, and the first
+  // chunk below is the call's first runtime call that reaches the device; a busy one is waited for through the event the search left
+  // behind its last scan or replay, or through a record of the rebuild's own where there is none.
+  {
+    hipStream_t busy[4] = {c->stream, c->scan_streams[0], c->scan_streams[1], c->scan_streams[2]};
+    for (int i = 0; i < 4; i++) {
+      if (!busy[i] || !c->planes_busy[i]) continue;
+      hipEvent_t e = c->planes_ev[i];
+      if (!e) {
+        if (!c->derive_fence[i]) HIPCHK(c, hipEventCreateWithFlags(&c->derive_fence[i], hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->derive_fence[i], busy[i]));
+        planes_fenced(c, busy[i], e = c->derive_fence[i]);
+      }
+      for (int j = 0; j < n_derive_streams; j++) HIPCHK(c, hipStreamWaitEvent(c->derive_streams[j], e, 0));
+    }
+  }
   size_t k = 0;
   long long t_done = 0;                 // slices that are not tile aligned share a tile: it belongs to the earlier chunk
   for (const SubSlice &sl : plan) {
     const long long t0 = std::max(t_done, (long long)(sl.first / 64)), t1 = (long long)((sl.first + sl.n + 63) / 64);
     if (t0 >= t1) continue;
     t_done = t1;
-    if (k == c->derive_chunks.size()) {
+    hipStream_t ds = c->derive_streams[k % (size_t)n_derive_streams];
+    int rc = for_owned_tiles(c, t0, t1, [&](long long, long long lt, long long nt) -> int { return derive_rows(c, c->db, lt * 64, (int)(nt * 64), ds, true); });
+    if (rc) return rc;
+    if (k == c->derive_chunks.size()) {   // (a chunk's event is made behind its launch: the first launch waits for nothing it does not need)
       uvaia_gpu_ctx::DeriveChunk d{0, 0, nullptr};
       HIPCHK(c, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
       c->derive_chunks.push_back(d);
     }
-    hipStream_t ds = c->derive_streams[k % (size_t)n_derive_streams];
-    int rc = for_owned_tiles(c, t0, t1, [&](long long, long long lt, long long nt) -> int { return derive_rows(c, c->db, lt * 64, (int)(nt * 64), ds, true); });
-    if (rc) return rc;
     c->derive_chunks[k].t0 = t0; c->derive_chunks[k].t1 = t1;
     HIPCHK(c, hipEventRecord(c->derive_chunks[k].done, ds));
     k++;
@@ -359,7 +388,9 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
   if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: use uvaia_gpu_shard_scan / uvaia_gpu_shard_replay (or a group)");
   if (pool < 1 || pool > c->max_pool) return fail(c, UVAIA_GPU_EINVAL, "pool must be in [1, max_pool=%zu]", c->max_pool);
   if (!c->db_n) return 0;
-  HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
+  // the flags of this search only: cleared here unless uvaia_gpu_reset has just done it (no replay since: launch_replay withdraws the mark)
+  if (c->entered_clean < ((c->db_n + 63) / 64) * 64) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
+  c->entered_clean = 0;
   if (!c->fullscan) {
     // The heaps fill on the stream's first references, and over the column-compressed scan every admission is a round trip to memory for
     // the pair's other counters (replay2_kernel): a hundred of them in a row for EVERY query before anything else happens (a quarter of
@@ -413,6 +444,7 @@ int uvaia_gpu_sync(uvaia_gpu_ctx *c)
   if (int rc = sync_scan_streams(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream));
+  planes_idle(c, true, true);
   { int rc = pipe_check(c); if (rc) return rc; }
   return collect_events(c);
 }
@@ -575,6 +607,7 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
   int rc = launch_scan2(c, c->db, b.tf, b.tiles, b.cnt, b.tiles * 64, bytes, ss, b.tmin, b.rb, b.re, b.rt, c->use_ext ? b.ext : nullptr, b.rtp, b.tb8, progress);
   if (rc) return rc;
   HIPCHK(c, hipEventRecord(b.scan_done, ss));
+  planes_fenced(c, ss, b.scan_done);
   return 0;
 }
 
@@ -608,6 +641,7 @@ int uvaia_gpu_slice_replay_range(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, in
   if (rc) return rc;
   if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[1], rs)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->rep_ev[1], 0)); }
   HIPCHK(c, hipEventRecord(b.replay_done, c->stream));
+  planes_fenced(c, c->stream, b.replay_done);
   b.replay_recorded = true;
   c->last = {&c->db, b.tf, b.tiles, b.re - b.rb, b.rb, ppad, b.rt};
   return 0;

@@ -1048,10 +1048,20 @@ __global__ void snapshot_kernel(const int *__restrict__ T, int nq, int *__restri
   if (threadIdx.x == 0) *snap = red[0];
 }
 
-__global__ void init_state_kernel(int *__restrict__ T, int *__restrict__ n, int nq, int nchar)
+// uvaia_gpu_reset in one launch (grid-stride): empty heaps, T = nchar and n = 0 for every query (src/nearest.c:375,387 ; src/min_heap.c:56),
+// the batch snapshot = nchar (cq->max_incompatible = n_sites, src/nearest.c:375) and the entered flags of the resident database cleared.
+// heap16 / entered16: length of the two arrays in units of 16 bytes (both are whole multiples: a heap entry is 32 bytes, the flags come in
+// tiles of 64).
+__global__ __launch_bounds__(256)
+void reset_state_kernel(uint4 *__restrict__ heap, size_t heap16, int *__restrict__ T, int *__restrict__ n, int nq, int nchar,
+                        int *__restrict__ snap, uint4 *__restrict__ entered, size_t entered16)
 {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nq) { T[i] = nchar; n[i] = 0; }    // src/nearest.c:375,387 ; src/min_heap.c:56
+  const size_t stride = (size_t)gridDim.x * blockDim.x, i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+  for (size_t i = i0; i < heap16; i += stride) heap[i] = z;
+  for (size_t i = i0; i < entered16; i += stride) entered[i] = z;
+  for (size_t i = i0; i < (size_t)nq; i += stride) { T[i] = nchar; n[i] = 0; }
+  if (i0 == 0) *snap = nchar;
 }
 
 // untruncated score vectors of a batch, for parity tests: out[(i*nq+q)*6+s]

@@ -15,12 +15,17 @@
 
 // derive_all_kernel: the E / V planes, the group counts and the gathered polymorphic and rare columns in one pass over the packed planes (each byte of a
 // reference read once).
-// One block per tile; wave v takes the contiguous word groups split[v] .. split[v+1]-1, writes their E/V planes and group counts,
-// and bit-gathers the dense polymorphic and the rare columns it meets, one 32-bit word of the gathered planes at a time.  A
-// wave's gathered bits start at a bit position the host computed (split[5+v] dense, split[10+v] rare); the (at most three per
-// section) output words that hold bits of two waves are OR-ed together in LDS and written after the barrier, every other word
-// goes straight to memory.  Kept under 64 VGPRs: every tile of a 100 000-reference database is resident at once.
-//   split[15] = { w4 boundaries [5], dense bits before each boundary [5], rare bits before each boundary [5] }
+// One block of NWV waves (4, 8 or 16) per tile; wave v takes the contiguous word groups split[v] .. split[v+1]-1 (none where the
+// alignment has fewer groups than the block has waves), writes their E/V planes and group counts, and bit-gathers the dense polymorphic
+// and the rare columns it meets, one 32-bit word of the gathered planes at a time.  A wave's gathered bits start at a bit position the
+// host computed (split[NWV+1+v] dense, split[2(NWV+1)+v] rare); the output words that hold bits of several waves -- a wave's first and
+// its last word at most, NWV-1 per section in all -- are OR-ed together in LDS and written after the barrier by the wave behind the
+// lowest boundary inside the word, every other word goes straight to memory.  Kept under 64 VGPRs: every tile of a 100 000-reference
+// database is resident at once.  The block's width only decides how long a wave's chain of dependent loads is (58 groups at 4 waves and
+// 30 000 columns, 15 at 16), which measured makes no difference to a launch's time (DESIGN.md 4.2; four is the default): the arrays it
+// writes are the same byte for byte.
+//   split[3 (NWV + 1)] = { w4 boundaries [NWV+1], dense bits before each boundary [NWV+1], rare bits before each boundary [NWV+1] }: the
+//   section for NWV of the context's table (build_derive_split)
 typedef uint32_t u32x4_nt __attribute__((ext_vector_type(4)));
 static __device__ __forceinline__ void st_stream(uint4 *p, const uint4 &v)
 { // written once, read by a later kernel: no reason to keep the lines in L2
@@ -29,9 +34,10 @@ static __device__ __forceinline__ void st_stream(uint4 *p, const uint4 &v)
 }
 struct GatherStage { uint32_t bL, bH, bI; int fill, ow; };
 
+template <int NWV>
 static __device__ __forceinline__ int shared_slot(const int *__restrict__ bit, int word)
-{ // boundary 1..3 that lies inside output word `word` (lowest such), or 0
-  for (int k = 1; k <= 3; k++) if ((bit[k] & 31) != 0 && (bit[k] >> 5) == word) return k;
+{ // boundary 1..NWV-1 that lies inside output word `word` (lowest such: with many waves and few columns several may), or 0
+  for (int k = 1; k < NWV; k++) if ((bit[k] & 31) != 0 && (bit[k] >> 5) == word) return k;
   return 0;
 }
 // one bit of x (uniform position b) moved to bit `at` and merged into acc: v_bfe_u32 + v_lshl_or_b32
@@ -42,17 +48,17 @@ static __device__ __forceinline__ uint32_t take_bit(uint32_t x, int b, int at, u
 
 // WRITE_V = false: the V plane of every group is in place already (it does not depend on the query set: written when the rows
 // were appended) and is left alone; E, the group counts and the gathered planes are rebuilt.
-template <bool ACGT, bool WRITE_V>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8)))
+template <bool ACGT, bool WRITE_V, int NWV>
+__global__ __launch_bounds__(64 * NWV) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void derive_all_kernel(const uint4 *__restrict__ tiles, long long tile_base, long long dtile_base, int W4,
                        const uint32_t *__restrict__ cls, const uint32_t *__restrict__ rmask,
                        const int *__restrict__ split, int NP4, int NR4,
                        uint4 *__restrict__ ev, int *__restrict__ tot_e, uint32_t *__restrict__ grp, uint4 *__restrict__ poly)
 {
   constexpr int P = ACGT ? 3 : 4;
-  __shared__ int partial[4][64];
-  __shared__ uint32_t shr[6][3][64];               // [section * 3 + boundary - 1][plane][lane]
-  for (int i = threadIdx.x; i < 6 * 3 * 64; i += 256) (&shr[0][0][0])[i] = 0u;
+  __shared__ int partial[NWV][64];
+  __shared__ uint32_t shr[2 * (NWV - 1)][3][64];   // [section * (NWV - 1) + boundary - 1][plane][lane]
+  for (int i = threadIdx.x; i < 2 * (NWV - 1) * 3 * 64; i += 64 * NWV) (&shr[0][0][0])[i] = 0u;
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // packed tile read / tile of the derived arrays written: the same number unless the references are sharded over several GPUs
@@ -63,23 +69,27 @@ void derive_all_kernel(const uint4 *__restrict__ tiles, long long tile_base, lon
   const int NG = NP4 + NR4;
   uint32_t *po = reinterpret_cast<uint32_t *>(poly + (size_t)tile * NG * 3 * 64 + lane);   // word j of group g, plane p: po[((g*3+p)*64)*4 + j]
   const int lo = split[wv], hi = split[wv + 1];
-  const int *dbit = split + 5, *rbit = split + 10;
+  const int *dbit = split + (NWV + 1), *rbit = split + 2 * (NWV + 1);
 
   GatherStage D, R;
   D.bL = D.bH = D.bI = 0u; D.fill = dbit[wv] & 31; D.ow = dbit[wv] >> 5;
   R.bL = R.bH = R.bI = 0u; R.fill = rbit[wv] & 31; R.ow = rbit[wv] >> 5;
-  // output words shared with a neighbouring wave, per section and boundary (-1: that boundary falls between two words)
-  int sw[2][3];
+  // The output words this wave shares with others, per section: its first one (the boundary before it falls inside a word) and its last
+  // one (the boundary behind it does); -1: none.  sk = the LDS slot of that word: the lowest boundary inside it (a word may hold the bits
+  // of more than two waves, and then the first and the last word of a wave in the middle are the same one).
+  int sw[2][2], sk[2][2];
 #pragma unroll
   for (int sec = 0; sec < 2; sec++) {
     const int *bit = sec ? rbit : dbit;
+    sw[sec][0] = (bit[wv] & 31) != 0 ? (bit[wv] >> 5) : -1;
+    sw[sec][1] = (wv + 1 < NWV && (bit[wv + 1] & 31) != 0) ? (bit[wv + 1] >> 5) : -1;
 #pragma unroll
-    for (int k = 1; k <= 3; k++) sw[sec][k - 1] = (bit[k] & 31) != 0 ? (bit[k] >> 5) : -1;
+    for (int e = 0; e < 2; e++) sk[sec][e] = sw[sec][e] >= 0 ? shared_slot<NWV>(bit, sw[sec][e]) : 0;
   }
   auto push_word = [&](GatherStage &g, int sec) {     // the staged bits are word ow of the section's gathered planes
-    const int k = (sw[sec][0] == g.ow) ? 1 : (sw[sec][1] == g.ow) ? 2 : (sw[sec][2] == g.ow) ? 3 : 0;
+    const int k = (sw[sec][0] == g.ow) ? sk[sec][0] : (sw[sec][1] == g.ow) ? sk[sec][1] : 0;
     if (k) {
-      uint32_t (*dst)[64] = shr[sec * 3 + k - 1];
+      uint32_t (*dst)[64] = shr[sec * (NWV - 1) + k - 1];
       if (g.bL) atomicOr(&dst[0][lane], g.bL);
       if (g.bH) atomicOr(&dst[1][lane], g.bH);
       if (g.bI) atomicOr(&dst[2][lane], g.bI);
@@ -138,21 +148,24 @@ void derive_all_kernel(const uint4 *__restrict__ tiles, long long tile_base, lon
   }
   if (NP4 && D.fill > 0) push_word(D, 0);            // the last, incomplete word of this wave's columns
   if (NR4 && R.fill > 0) push_word(R, 1);
-  if (wv == 3) {                                     // zero words that complete the last group of each section
-    for (int w = (dbit[4] + 31) >> 5; w < NP4 * 4; w++) { uint32_t *d = po + (size_t)(w >> 2) * 3 * 256 + (w & 3); d[0] = 0u; d[256] = 0u; d[512] = 0u; }
-    for (int w = (rbit[4] + 31) >> 5; w < NR4 * 4; w++) { uint32_t *d = po + (size_t)(NP4 + (w >> 2)) * 3 * 256 + (w & 3); d[0] = 0u; d[256] = 0u; d[512] = 0u; }
+  if (wv == NWV - 1) {                               // zero words that complete the last group of each section
+    for (int w = (dbit[NWV] + 31) >> 5; w < NP4 * 4; w++) { uint32_t *d = po + (size_t)(w >> 2) * 3 * 256 + (w & 3); d[0] = 0u; d[256] = 0u; d[512] = 0u; }
+    for (int w = (rbit[NWV] + 31) >> 5; w < NR4 * 4; w++) { uint32_t *d = po + (size_t)(NP4 + (w >> 2)) * 3 * 256 + (w & 3); d[0] = 0u; d[256] = 0u; d[512] = 0u; }
   }
   partial[wv][lane] = te;
   __syncthreads();
-  if (wv == 0) tot_e[tile * 64 + lane] = partial[0][lane] + partial[1][lane] + partial[2][lane] + partial[3][lane];
-  else {
-    // wave k writes the word shared across boundary k (once per word: the lowest boundary inside it owns it)
+  if (wv == 0) {
+    int t_all = 0;
+#pragma unroll
+    for (int v = 0; v < NWV; v++) t_all += partial[v][lane];
+    tot_e[tile * 64 + lane] = t_all;
+  } else {
+    // wave k writes the word shared across boundary k (once per word: the lowest boundary inside it owns it) -- also a wave without word
+    // groups of its own, which has come here all the same
     for (int sec = 0; sec < 2; sec++) {
-      const int *bit = sec ? rbit : dbit;
-      if ((sec ? NR4 : NP4) == 0 || (bit[wv] & 31) == 0) continue;
-      const int w = bit[wv] >> 5;
-      if (shared_slot(bit, w) != wv) continue;
-      const uint32_t (*src)[64] = shr[sec * 3 + wv - 1];
+      if ((sec ? NR4 : NP4) == 0 || sw[sec][0] < 0 || sk[sec][0] != wv) continue;
+      const int w = sw[sec][0];
+      const uint32_t (*src)[64] = shr[sec * (NWV - 1) + wv - 1];
       uint32_t *d = po + (size_t)((sec ? NP4 : 0) + (w >> 2)) * 3 * 256 + (w & 3);
       d[0] = src[0][lane]; d[256] = src[1][lane]; d[512] = src[2][lane];
     }

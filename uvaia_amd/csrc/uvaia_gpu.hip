@@ -123,6 +123,11 @@ struct uvaia_gpu_ctx {
   std::vector<DeriveChunk> derive_chunks;
   hipEvent_t derive_fence[4] = {};
   size_t derive_pending = 0;          // chunks of the last rederive a scan may still have to wait for
+  // What a rebuild has to queue behind: planes_busy[i] = work that reads or writes the derived planes (a column-compressed scan, a replay,
+  // an append's derive) was issued on the stream since the host last waited for it -- [0] `stream` (the masked replay stream is spliced into
+  // its order), [1..3] scan_streams; planes_ev[i] = an event the search recorded on that stream behind the last such work (a slice's
+  // scan_done / replay_done), null where there is none and the rebuild records one of its own (planes_touch / planes_fenced / planes_idle)
+  bool planes_busy[4] = {}; hipEvent_t planes_ev[4] = {};
   // pipelined search (column-compressed scan): the replay of a slice runs next to its scan and follows its progress counters
   // (off unless tuning.pipeline = 2: measured slower at config[1])
   bool pipeline = false, pipeline_now = false, pipe_used = false;
@@ -148,7 +153,8 @@ struct uvaia_gpu_ctx {
   int NP = 0, NP4 = 0;           // polymorphic columns counted densely
   int NR = 0, NR4 = 0, rare_max = -1;   // "rare" columns: all but <= rare_max queries carry the same base; sparse (items), groups follow the dense ones
   uint32_t *d_rmask = nullptr;   // [W4*4] mask of the rare columns
-  int *d_split = nullptr;        // derive_all_kernel: w4 range and first gathered bit of each of its four waves
+  int *d_split = nullptr;        // derive_all_kernel: w4 range and first gathered bit of each of its waves, a section per block width (build_derive_split)
+  int derive_waves = 0;          // tuning.derive_waves: 4, 8 or 16 waves per tile for every launch of it (0: derive_rows' caller decides)
   // reference shards (uvaia_gpu_db_set_shard): the stream is dealt in pieces of shard_pt tiles, piece p belongs to rank p % world; the packed
   // planes of ALL references are resident (the replay reads them), the planes derived for the query set only for the owned pieces
   int shard_rank = 0, shard_world = 1; long long shard_pt = 0;
@@ -211,6 +217,7 @@ struct uvaia_gpu_ctx {
   int4 *d_rt = nullptr, *d_tr = nullptr;   // [pool_pad]
   uint8_t *d_entered = nullptr;  // [pool_pad] (push) or [db_cap] (resident)
   size_t entered_cap = 0;
+  size_t entered_clean = 0;      // leading bytes of d_entered that uvaia_gpu_reset cleared with no replay issued since (a search that follows need not clear them again)
   uint8_t *d_stage = nullptr;    // device staging for raw characters (2 x PACK_CHUNK rows)
   uint8_t *h_stage = nullptr;    // pinned host staging (2 x PACK_CHUNK rows)
   hipEvent_t stage_free[2] = {}; bool stage_busy[2] = {};
