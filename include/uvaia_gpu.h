@@ -91,12 +91,8 @@ typedef struct {
                                   none otherwise), -1 = none, n > 0 = n; 1000 * t + n also sets the replay's staging depth to t = 32, 16 or 8 tiles */
   int scan_streams;            /* resident search: consecutive slices' scans alternate over 1..3 streams (0 = the library's choice by launch size);
                                   100 + p (p = 1..98): a pool's first slice is p % of an equal share (default 70), 199: equal slices */
-  int pipeline;                /* resident search over the column-compressed scan: 2 = a slice's replay runs next to its scan and follows its progress counters
-                                  (slices then merge into long launches); 0 / 1 = the replay of a slice starts when its scan has ended (default: the
-                                  thousand waiting replay waves cost the scan a block per CU, measured slower at config[1]) */
-  int head_scan;               /* resident search over the column-compressed scan: 2 = the stream's first 128 references take the four-counter scan, so that the
-                                  heaps fill without a memory round trip per admission; 0 / 1 = they go through the slices like the rest (default: the
-                                  63 blocks of that scan run for 0.4 ms on their own, more than the hundred round trips they save) */
+  int pipeline;                /* reserved: accepted and ignored (the pipelined replay it selected was removed) */
+  int head_scan;               /* reserved: accepted and ignored (the four-counter head it selected was removed) */
   int derive_waves;            /* the kernel that derives a tile's planes for the query set runs 4, 8 or 16 waves per tile (0 = the library's choice: 4;
                                   measured alike at config[1]); same arrays from every width */
 } uvaia_gpu_tuning;

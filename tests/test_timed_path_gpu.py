@@ -80,10 +80,11 @@ def test_config1_regime_sub_slices_equal_oracle(config1_sample):
         gold.check(rows, T, np.nonzero(ent)[0])
 
 
-def test_config1_regime_pipelined_replay_equals_oracle(config1_sample):
-    """tuning.pipeline = 2: one long scan launch per merged slice, its replay launched with it and following the scan's progress counters
-    stripe by stripe (write-through counters, agent-scope loads); tuning.head_scan = 2: the first 128 references through the four-counter
-    scan and its replay.  Same heaps, tolerances and dump flags."""
+def test_config1_regime_five_unaligned_slices_reserved_tuning_equals_oracle(config1_sample):
+    """A pool above the reference count (max_pool = 65 536) cut into five sub-slices of 1 600 references that are not tile aligned, through
+    the ring of four counter buffers, two steps over the same resident database.  tuning.pipeline and tuning.head_scan are reserved: the
+    values given here are accepted and ignored (the pipelined replay and the four-counter head they once selected are gone).  Same heaps,
+    tolerances and dump flags."""
     gen, qs, qn, refs, oq, gold = config1_sample
     pq = hostlib.PreparedQuery(qs, qn)
     with pq.open_engine(nbest=100, max_pool=65536, tuning={"pipeline": 2, "head_scan": 2, "subslice_refs": 1600}) as eng:
@@ -91,6 +92,42 @@ def test_config1_regime_pipelined_replay_equals_oracle(config1_sample):
         for _ in range(2):
             rows, T, ent = _timed_step(eng, 65536)
             gold.check(rows, T, np.nonzero(ent)[0])
+
+
+def test_reserved_tuning_fields_change_nothing():
+    """tuning.pipeline = 2 and tuning.head_scan = 2 are accepted and ignored, at the smallest shape at which the modes they once selected
+    engaged: 70 queries in default mode (two super-tiles of the column-compressed scan, above the 32 queries of the replay extras) without
+    a constant-and-complete column, 2 000 columns, 4 200 resident references (above the old head's 4 096, not a multiple of 64),
+    sub-slices of 640 references: seven slices, so the ring of four counter buffers wraps.  The engine with the two values set leaves
+    the same heaps, tolerances and dump flags as the default one, array for array, after the same number of scan launches, and both
+    leave the oracle's."""
+    nq, n_ref, nchar = 70, 4200, 2000
+    gen = hostlib.Synth(nchar, seed=20241008, preset=0)
+    qs, _ = gen.generate_bytes(QUERY_INDEX0, nq)
+    qn = _names(nq, "query_")
+    refs, _ = gen.generate_bytes(0, n_ref)
+    oq = O.Query(qs, qn)
+    gold = O.search(oq, refs, _names(n_ref), pool=n_ref, nbest=20, ambig_r=0.5)
+    pq = hostlib.PreparedQuery(qs, qn)
+    assert pq.ntax == oq.ntax == nq and len(pq.idx_c) == 0
+    got = []
+    for extra in ({}, {"pipeline": 2, "head_scan": 2}):
+        with pq.open_engine(nbest=20, max_pool=n_ref, tuning=dict(extra, subslice_refs=640)) as eng:
+            assert eng.scan_variant() == 2
+            _load(eng, gen, 0, n_ref)
+            eng.reset()
+            eng.db_rederive()
+            ent = eng.search_resident(n_ref)
+            eng.sync()
+            n, T, sc, od = eng.drain()
+            launches = eng.scan_stats()[1]
+        assert capi.finalise_heaps(n, sc, od) == _want(gold, nq) and list(T) == gold.final_T
+        assert list(np.nonzero(ent)[0]) == list(gold.saved)
+        held = (np.arange(sc.shape[1])[None, :] >= 1) & (np.arange(sc.shape[1])[None, :] <= np.asarray(n)[:, None])   # heap layout: slots 1 .. n
+        got.append((np.array(n), np.array(T), sc[held], od[held], ent, launches))
+    for a, b in zip(got[0][:5], got[1][:5]):
+        assert np.array_equal(a, b)
+    assert got[0][5] == got[1][5] == 7                       # one scan launch per slice in both: nothing merged, no head batch
 
 
 def test_config1_regime_streaming_push_equals_oracle(config1_sample):

@@ -229,12 +229,12 @@ file_compress_t
 biomcmc_open_compress (const char *path, const char *mode)
 {
   file_compress_t fc = (file_compress_t) biomcmc_malloc (sizeof (struct file_compress_struct));
-  fc->filename = strdup (path); fc->fp = NULL; fc->piped = 0; fc->writing = (mode[0] != 'r'); fc->at_eof = 0;
+  fc->filename = strdup (path); fc->fp = NULL; fc->from_popen = 0; fc->writing = (mode[0] != 'r'); fc->at_eof = 0;
   char *quoted = shell_quote (path), *cmd = (char *) biomcmc_malloc (strlen (quoted) + 64);
   if (mode[0] == 'r') {
     const char *tool = decompressor_for (path);
     if (!tool) { free (quoted); free (cmd); biomcmc_error ("cannot open file %s for reading", path); }
-    if (*tool) { sprintf (cmd, "%s %s", tool, quoted); fc->fp = popen (cmd, "r"); fc->piped = 1; }
+    if (*tool) { sprintf (cmd, "%s %s", tool, quoted); fc->fp = popen (cmd, "r"); fc->from_popen = 1; }
     else fc->fp = fopen (path, "r");
     if (fc->fp) setvbuf (fc->fp, NULL, _IOFBF, 1u << 22);     /* 30 kb lines: the default 4 KiB buffer costs a refill per eighth of a line */
   } else {
@@ -242,7 +242,7 @@ biomcmc_open_compress (const char *path, const char *mode)
     if (ends_with (path, ".xz") && tool_available ("xz")) tool = "xz -T0 -c";   /* all cores: the dump of a large search is hundreds of MB of text */
     else if (ends_with (path, ".bz2") && tool_available ("bzip2")) tool = "bzip2 -c";
     else if (ends_with (path, ".gz") && tool_available ("gzip")) tool = "gzip -c";
-    if (tool) { sprintf (cmd, "%s > %s", tool, quoted); fc->fp = popen (cmd, "w"); fc->piped = 1; }
+    if (tool) { sprintf (cmd, "%s > %s", tool, quoted); fc->fp = popen (cmd, "w"); fc->from_popen = 1; }
     else fc->fp = fopen (path, "w");
   }
   free (quoted); free (cmd);
@@ -255,7 +255,7 @@ biomcmc_close_compress (file_compress_t fc)
 {
   if (!fc) return;
   int status = 0;
-  if (fc->fp) status = fc->piped ? pclose (fc->fp) : fclose (fc->fp);
+  if (fc->fp) status = fc->from_popen ? pclose (fc->fp) : fclose (fc->fp);
   /* A decompressor that fails in the middle of a stream looks like end of data to getline(): a search over a truncated or
    * corrupt reference file must not pass for a complete one.  (A reader closed before its end of data kills the tool with
    * SIGPIPE: that is not an error.)  A failing compressor (disk full, killed xz) leaves an unusable output file: say so. */

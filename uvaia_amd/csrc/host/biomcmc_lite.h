@@ -38,7 +38,7 @@ typedef struct file_compress_struct *file_compress_t;
 struct file_compress_struct {
   char *filename;
   FILE *fp;
-  int piped;           /* fp comes from popen() */
+  int from_popen;      /* fp comes from popen() */
   int writing, at_eof; /* opened for writing; a read hit end of data (then a failing decompressor means truncated input) */
 };
 

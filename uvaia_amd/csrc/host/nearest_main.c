@@ -1,6 +1,6 @@
 /*
  * nearest_main.c -- `uvaia`: for every query sequence, the closest neighbours in a (streamed) reference alignment.
- * Same options, progress messages, output files and table columns as the reference's src/nearest.c; the batch loop
+ * Same options, status messages, output files and table columns as the reference's src/nearest.c; the batch loop
  * (src/nearest.c:288-306) runs on the GPU through include/uvaia_gpu.h.  Own code.
  */
 #define _GNU_SOURCE

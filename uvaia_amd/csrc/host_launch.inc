@@ -111,8 +111,8 @@ void store_free(TileStore &s)
 }
 void slice_free(SliceBuf &b)
 {
-  for (void *p : {(void *)b.cnt, (void *)b.tmin, (void *)b.ext, (void *)b.rtp, (void *)b.tb8, (void *)b.rt, (void *)b.progress}) hipFree(p);
-  for (hipEvent_t e : {b.scan_done, b.scan_started, b.replay_done}) if (e) hipEventDestroy(e);
+  for (void *p : {(void *)b.cnt, (void *)b.tmin, (void *)b.ext, (void *)b.rtp, (void *)b.tb8, (void *)b.rt}) hipFree(p);
+  for (hipEvent_t e : {b.scan_done, b.replay_done}) if (e) hipEventDestroy(e);
   b = SliceBuf();
 }
 
@@ -247,8 +247,7 @@ int launch_pair_extras(uvaia_gpu_ctx *c, const TileStore &s, long long tile_firs
 // rt (nullable unless the query set has constant-and-complete columns): the untruncated consensus pre-score of the slice's references,
 // by the packed-plane scans themselves or, next to the column-compressed scan, by consensus_rt_kernel on the same stream
 int launch_scan2(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, uint32_t *out, int ppad, double bytes, hipStream_t stream,
-                 int2 *tmin, int r_lo, int r_hi, int4 *rt, uint32_t *ext = nullptr /* default mode, packed-plane scan: the other two counters of every pair */, uint32_t *rtp = nullptr, uint4 *tb8 = nullptr,
-                 unsigned *progress = nullptr /* column-compressed scan, pipelined search: zeroed counters, one per stripe of SCAN_STRIPE_TILES tiles */)
+                 int2 *tmin, int r_lo, int r_hi, int4 *rt, uint32_t *ext = nullptr /* default mode, packed-plane scan: the other two counters of every pair */, uint32_t *rtp = nullptr, uint4 *tb8 = nullptr)
 {
   if (n_tiles <= 0) return 0;
   if (!stream) stream = c->stream;
@@ -281,9 +280,8 @@ int launch_scan2(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int
     const int st_first = c->act_q0 / QS, n_st = (c->act_q1 + QS - 1) / QS - st_first;
     const int R = c->scan_R;
     dim3 grid3(scan_grid_size(n_st, (n_tiles + R - 1) / R));
-#define SCAN3_LAUNCH(NWW, A, RR) hipLaunchKernelGGL((scan3_kernel<NWW, A, RR>), grid3, dim3(64 * NWW), 0, stream, s.ev, s.poly, tile_first, n_tiles, c->W4, c->NP4, c->NP4 + c->NR4, c->d_qpl, c->d_stream, c->d_sdir, s.grp, tote, tot_tile0, out, ppad, n_st, tmin, r_lo, r_hi, st_first, progress)
+#define SCAN3_LAUNCH(NWW, A, RR) hipLaunchKernelGGL((scan3_kernel<NWW, A, RR>), grid3, dim3(64 * NWW), 0, stream, s.ev, s.poly, tile_first, n_tiles, c->W4, c->NP4, c->NP4 + c->NR4, c->d_qpl, c->d_stream, c->d_sdir, s.grp, tote, tot_tile0, out, ppad, n_st, tmin, r_lo, r_hi, st_first)
 #define SCAN3_NW(A, RR) { if (c->scan_NW == 8) SCAN3_LAUNCH(8, A, RR); else SCAN3_LAUNCH(4, A, RR); }
-    if (progress) { consensus_rt(); HIPCHK(c, hipGetLastError()); }     // pipelined: the pre-score is complete before any block of the scan reports progress
     if (R == 4)      { if (c->acgt) SCAN3_LAUNCH(8, true, 4); else SCAN3_LAUNCH(8, false, 4); }     // four tiles per wave: eight waves only (open_tuned)
     else if (R == 2) { if (c->acgt) SCAN3_NW(true, 2) else SCAN3_NW(false, 2) }
     else             { if (c->acgt) SCAN3_NW(true, 1) else SCAN3_NW(false, 1) }
@@ -291,7 +289,7 @@ int launch_scan2(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int
 #undef SCAN3_LAUNCH
     HIPCHK(c, hipGetLastError());
     if (c->profile) { HIPCHK(c, hipEventRecord(ev_.b, stream)); ev_.bytes = bytes; c->evts.push_back(ev_); }
-    if (!progress) consensus_rt();
+    consensus_rt();
     HIPCHK(c, hipGetLastError());
     if (tb8 && !c->acgt) {     // 33-128 queries, default mode: the sharp bounds replay3_kernel walks (the other two counters of every pair: launch_pair_extras)
       hipLaunchKernelGGL(tile_bounds_kernel, dim3((unsigned)n_tiles), dim3(256), 0, stream, out, ppad, n_tiles, c->nq, r_lo, r_hi, tb8, cons ? rt : (const int4 *)nullptr, rtp);
@@ -349,7 +347,6 @@ struct ReplayLaunch {
   int rb, re; long long ord_base;
   const uint32_t *qpl; const uint4 *poly; int nr4; const uint32_t *qrare;   // on-demand counters from the planes derived for the query set (null, 0: from the packed ones)
   int prefetch;                                                             // candidates of a tile whose on-demand counters are requested ahead: 1, 2 or 3
-  const unsigned *progress; unsigned blocks_per_group; int scan_R; int *pipe_err;   // pipelined search (null, 0, 2, null otherwise: the kernel's defaults)
 };
 int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
 {
@@ -373,7 +370,7 @@ int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
     const int2 *tmin = (c->scan_variant == 2 || c->scan_variant == 0) ? L.tmin : nullptr;
 #define REPLAY2(A, B, PF_) hipLaunchKernelGGL((replay2_kernel<A, B, PF_>), grid, block, lds + (size_t)lq_words * 4 + 128, L.stream, L.cnt, L.ppad, L.rt, c->d_cp, L.nonn, L.amb, L.rb, L.re, L.ord_base, \
                                               c->d_heap, c->d_n, c->d_T, c->d_snap, L.entered, c->k, L.planes, L.tile_first, c->W4, c->d_qp, c->d_amb_q, c->d_stats, L.q0, tmin, L.qpl, lq_words, c->replay_prio, \
-                                              L.poly, c->NP4 + c->NR4, c->NP4, L.nr4, L.qrare, L.progress, L.blocks_per_group, L.scan_R, L.pipe_err)
+                                              L.poly, c->NP4 + c->NR4, c->NP4, L.nr4, L.qrare)
 #define REPLAY2_PF(A, B) { if (L.prefetch == 1) REPLAY2(A, B, 1); else if (L.prefetch == 2) REPLAY2(A, B, 2); else REPLAY2(A, B, 3); }
     if (c->acgt) { if (c->n_idx_c > 0) REPLAY2_PF(true, true) else REPLAY2_PF(true, false) }
     else         { if (c->n_idx_c > 0) REPLAY2_PF(false, true) else REPLAY2_PF(false, false) }
@@ -387,7 +384,7 @@ int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
 // One batch = one pool of the reference (src/nearest.c:288-306), on tiles [tile_first, tile_first+n_tiles) of the store;
 // references r_begin..r_end-1 (relative to the first tile) are the batch, in order.
 int run_batch(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_tiles, int r_begin, int r_end,
-              long long ord_base, size_t cnt4_cols = 0 /* four-counter scan: columns its counter buffer is sized for (0: a whole pool) */)
+              long long ord_base)
 {
   if (r_end <= r_begin) return 0;   // an empty trailing batch only refreshes cq->max_incompatible (src/nearest.c:290-291)
   const int ppad = n_tiles * 64;
@@ -402,13 +399,13 @@ int run_batch(uvaia_gpu_ctx *c, const TileStore &s, long long tile_first, int n_
   uint32_t *ext = c->use_ext ? b.ext : nullptr;
   int rc = 0;
   if (c->fullscan) {
-    rc = ensure_cnt4(c, (size_t)c->nq_pad * (cnt4_cols ? std::max<size_t>(cnt4_cols, (size_t)ppad) : c->pool_pad)); if (rc) return rc;
+    rc = ensure_cnt4(c, (size_t)c->nq_pad * c->pool_pad); if (rc) return rc;
     rc = launch_scan(c, s, tile_first, n_tiles, c->d_qp, c->nq, c->d_cnt, ppad, bytes);
   } else rc = launch_scan2(c, s, tile_first, n_tiles, b.cnt, ppad, bytes, nullptr, b.tmin, r_begin, r_end, b.rt, ext, b.rtp, b.tb8);
   if (rc) return rc;
   rc = launch_replay(c, {c->stream, 0, c->nq, b.cnt, ext, ppad, b.rt, b.rtp, b.tmin, b.tb8,
                              s.planes, tile_first, s.nonn + tile_first * 64, s.amb + tile_first * 64 * AMB_ROW, c->d_entered + tile_first * 64, r_begin, r_end, ord_base,
-                             c->scan_variant == 2 ? c->d_qpl : nullptr, s.poly, c->NR4, c->d_qrare, 3, nullptr, 0, 2, nullptr});
+                             c->scan_variant == 2 ? c->d_qpl : nullptr, s.poly, c->NR4, c->d_qrare, 3});
   if (rc) return rc;
   c->last = {&s, tile_first, n_tiles, r_end - r_begin, r_begin, ppad, c->fullscan ? c->d_rt : b.rt};
   return 0;

@@ -12,7 +12,7 @@ void uvaia_gpu_close(uvaia_gpu_ctx *c)
   for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
   for (hipEvent_t e : c->rows_evs) hipEventDestroy(e);
   void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga,
-                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pipe_err, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc, c->d_wsel, c->d_win4};
+                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc, c->d_wsel, c->d_win4};
   for (void *p : dev) if (p) hipFree(p);
   store_free(c->batch); store_free(c->db);
   for (SliceBuf &b : c->slice) slice_free(b);
@@ -78,8 +78,6 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   if (tn.subslice_refs) { c->subslice = tn.subslice_refs; c->subslice_forced = true; }
   if (tn.scan_streams >= 1 && tn.scan_streams <= 3) c->scan_nstreams_forced = tn.scan_streams;
   if (tn.scan_streams > 100 && tn.scan_streams < 200) c->first_slice_pct = tn.scan_streams == 199 ? 0 : tn.scan_streams - 100;
-  if (tn.pipeline == 2) c->pipeline = true;
-  if (tn.head_scan == 2) c->head_full = true;
   c->derive_waves = tn.derive_waves;
   if (tn.ball_gather == 1 || tn.ball_gather == 2) c->ball_fused = tn.ball_gather == 2;
   if (tn.rederive_streams >= 1 && tn.rederive_streams <= 3) { c->derive_nstreams = tn.rederive_streams; c->derive_forced = true; }
@@ -284,7 +282,7 @@ size_t uvaia_gpu_scan_bytes_per_ref(const uvaia_gpu_ctx *c)
 
 int uvaia_gpu_scan_variant(const uvaia_gpu_ctx *c)
 { // which pair scan this context runs: 2 column-compressed (scan3_kernel), 0 two counters over the packed planes (scan2_*_kernel;
-  // default for at most 16 queries), 1 its LDS-broadcast form, -1 four counters (alignments above 49 000 columns)
+  // default for at most 16 queries), -1 four counters (alignments above 49 000 columns)
   return !c ? -2 : c->fullscan ? -1 : c->scan_variant;
 }
 

@@ -314,40 +314,10 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
   return 0;
 }
 
-// a replay of the pipelined search that gave up waiting for its scan leaves a flag: the search is reported as failed
-static int pipe_check(uvaia_gpu_ctx *c)
-{
-  if (!c->pipe_used || !c->d_pipe_err) return 0;
-  int bad = 0;
-  HIPCHK(c, hipMemcpy(&bad, c->d_pipe_err, sizeof(int), hipMemcpyDeviceToHost));
-  c->pipe_used = false;
-  if (bad) { HIPCHK(c, hipMemset(c->d_pipe_err, 0, sizeof(int))); return fail(c, UVAIA_GPU_EHIP, "pipelined search: a replay gave up waiting for the scan of its slice (results are incomplete)"); }
-  return 0;
-}
-
 // Two streams and a ring of NBUF counter buffers: the scan needs no state, so it runs up to NBUF-1 slices ahead of the replay.
 // snapshot >= 0: the first pool's snapshot is given (query shards: the maximum over all ranks); only valid for a single pool.
-static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs_in, int64_t ordinal_of_db0, int snapshot)
+static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs, int64_t ordinal_of_db0, int snapshot)
 {
-  // Pipelined search (column-compressed scan, one GPU): a slice's replay is launched together with its scan and follows the scan's
-  // progress counters stripe by stripe (scan3_kernel / replay2_kernel), so a slice no longer pays a scan launch's ramp and tail (about
-  // 70 us, round 4) nor waits for the slowest query of the slice before the next replay may start -- slices can be long.  The first
-  // sub-slice stays as it is (its scan waits for the first chunk of the rebuilt planes only), the following ones of the same pool are
-  // merged while the pair counters of the launch stay within half a gigabyte.
-  std::vector<SubSlice> subs = subs_in;
-  const bool piped = c->pipeline && c->scan_variant == 2 && !c->use_ext && !c->fullscan && !c->serial && c->shard_world == 1 && subs_in.size() > 1;
-  if (piped) {
-    const size_t rows = std::min<size_t>((size_t)c->nq_pad, ((size_t)c->act_q1 + 63) / 64 * 64);
-    const size_t cap_refs = std::max<size_t>(subs_in[0].n, std::min<size_t>(262144, ((size_t)512 << 20) / (rows * 4) / 64 * 64));
-    subs.clear();
-    for (size_t i = 0; i < subs_in.size(); i++) {
-      const bool first_of_pool = subs_in[i].pool_start, second_of_pool = i > 0 && subs_in[i - 1].pool_start;
-      if (!subs.empty() && !first_of_pool && !second_of_pool && subs.back().n + subs_in[i].n <= cap_refs && !(c->n_idx_c > 0 && subs.back().n + subs_in[i].n > c->max_pool)) subs.back().n += subs_in[i].n;
-      else subs.push_back(subs_in[i]);
-    }
-  }
-  struct PipeGuard { uvaia_gpu_ctx *c; ~PipeGuard() { c->pipeline_now = false; } } guard{c};
-  c->pipeline_now = piped;
   const size_t ns = subs.size();
   size_t issued = 0;
   {   // a launch of fewer waves than ~2 rounds of the chip's 8 192 wave slots leaves it half empty at start and end: let such
@@ -392,23 +362,7 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
   if (c->entered_clean < ((c->db_n + 63) / 64) * 64) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
   c->entered_clean = 0;
   if (!c->fullscan) {
-    // The heaps fill on the stream's first references, and over the column-compressed scan every admission is a round trip to memory for
-    // the pair's other counters (replay2_kernel): a hundred of them in a row for EVERY query before anything else happens (a quarter of
-    // the first slice's replay at config[1]).  The first two tiles therefore go through the four-counter scan and its replay, which needs
-    // nothing on demand -- the same machine over the same references in the same order, so the state it leaves is the one the slices
-    // continue from.  Only without constant-and-complete query columns: there pools do not matter and the head is not a batch of its own.
-    // (Measured at config[1], round 4: 3.43 against 3.14 ms per step -- the four-counter scan of two tiles is 63 blocks, each a chain of 234
-    // word groups x 16 queries, 0.4 ms whatever else the chip does, and the replay that follows it waits for it.  Off unless asked for.)
-    size_t head = 0;
-    if (c->scan_variant == 2 && c->head_full && c->n_idx_c == 0 && c->db_n > 4096 && !c->serial) {
-      head = 128;
-      const bool fs = c->fullscan, prof = c->profile;
-      c->fullscan = true; c->profile = false;               // (not one of the scan launches the statistics are about)
-      const int rc = run_batch(c, c->db, 0, 2, 0, (int)head, (long long)ordinal0, 128);
-      c->fullscan = fs; c->profile = prof;
-      if (rc) return rc;
-    }
-    int rc = run_subslices(c, plan_subslices(c, head, c->db_n - head, pool), ordinal0, -1);
+    int rc = run_subslices(c, plan_subslices(c, 0, c->db_n, pool), ordinal0, -1);
     if (rc) return rc;
   } else
   for (size_t a = 0; a < c->db_n; a += pool) {
@@ -422,7 +376,6 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
   if (entered) {
     HIPCHK(c, hipMemcpyAsync(entered, c->d_entered, c->db_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    { int rc = pipe_check(c); if (rc) return rc; }
     return collect_events(c);
   }
   return 0;
@@ -445,7 +398,6 @@ int uvaia_gpu_sync(uvaia_gpu_ctx *c)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream));
   planes_idle(c, true, true);
-  { int rc = pipe_check(c); if (rc) return rc; }
   return collect_events(c);
 }
 
@@ -587,24 +539,8 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
   b.tiles = n ? (int)((first + n + 63) / 64 - first / 64) : 0;
   b.rb = (int)(first - (size_t)b.tf * 64); b.re = b.rb + (int)n;
   b.scanned = true; b.cons_done = false;
-  // pipelined (run_subslices, column-compressed scan): zeroed progress counters, one per stripe of tiles; the replay may start once they are zero
-  unsigned *progress = nullptr;
-  b.piped = false;
-  if (c->pipeline_now && c->scan_variant == 2 && b.tiles > 0) {
-    const size_t stripes = (size_t)(b.tiles + SCAN_STRIPE_TILES - 1) / SCAN_STRIPE_TILES;
-    if (stripes > b.progress_cap) {
-      if (b.progress) { HIPCHK(c, hipStreamSynchronize(c->stream)); if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream)); hipFree(b.progress); b.progress = nullptr; }
-      HIPCHK(c, hipMalloc(&b.progress, (stripes + 64) * sizeof(unsigned))); b.progress_cap = stripes + 64;
-    }
-    if (!b.scan_started) HIPCHK(c, hipEventCreateWithFlags(&b.scan_started, hipEventDisableTiming));
-    if (!c->d_pipe_err) { HIPCHK(c, hipMalloc(&c->d_pipe_err, sizeof(int))); HIPCHK(c, hipMemset(c->d_pipe_err, 0, sizeof(int))); }
-    progress = b.progress;
-    HIPCHK(c, hipMemsetAsync(progress, 0, stripes * sizeof(unsigned), ss));
-    HIPCHK(c, hipEventRecord(b.scan_started, ss));
-    b.piped = true; c->pipe_used = true;
-  }
   const double bytes = (double)n * (double)c->W4 * 16.0 * c->P + (double)c->nq * (double)c->W4 * 16.0 * c->P;
-  int rc = launch_scan2(c, c->db, b.tf, b.tiles, b.cnt, b.tiles * 64, bytes, ss, b.tmin, b.rb, b.re, b.rt, c->use_ext ? b.ext : nullptr, b.rtp, b.tb8, progress);
+  int rc = launch_scan2(c, c->db, b.tf, b.tiles, b.cnt, b.tiles * 64, bytes, ss, b.tmin, b.rb, b.re, b.rt, c->use_ext ? b.ext : nullptr, b.rtp, b.tb8);
   if (rc) return rc;
   HIPCHK(c, hipEventRecord(b.scan_done, ss));
   planes_fenced(c, ss, b.scan_done);
@@ -622,7 +558,7 @@ int uvaia_gpu_slice_replay_range(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, in
   if (q0 < 0 || q1 > c->nq || q1 < q0) return fail(c, UVAIA_GPU_EINVAL, "bad query range [%d,%d)", q0, q1);
   if (take_snapshot) { hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T + c->act_q0, c->act_q1 - c->act_q0, c->d_snap); b.cons_done = false; }
   if (b.re <= b.rb || q1 == q0) return 0;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, b.piped ? b.scan_started : b.scan_done, 0));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, b.scan_done, 0));
   const int ppad = b.tiles * 64;
   // (packed-plane scan, default mode: the scan left every counter of every pair -- the replay without a round trip per admission)
   const uint32_t *ext = c->use_ext ? b.ext : nullptr;
@@ -633,11 +569,9 @@ int uvaia_gpu_slice_replay_range(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, in
   // latency it hides (measured on one box: config[1] 3.69 / 3.54 / 3.60 ms per step with 3 / 2 / 1, 4 queries x 1 M references
   // 4.37 / 4.03 / 3.89; with 6 or 8 over 7 ms): two for large query sets, one -- request, then use -- for a handful of queries.
   const int pf = (q1 - q0) <= 64 ? 1 : 2;
-  const unsigned blocks_per_group = (unsigned)((c->act_q1 + 63) / 64 - c->act_q0 / 64);      // the scan's super-tiles of 64 queries
   int rc = launch_replay(c, {rs, q0, q1, b.cnt, ext, ppad, b.rt, b.rtp, b.tmin, b.tb8,
                              c->db.planes, b.tf, c->db.nonn + b.tf * 64, c->db.amb + b.tf * 64 * AMB_ROW, c->d_entered + b.tf * 64, b.rb, b.re, (long long)ordinal0,
-                             (c->scan_variant == 2 && c->shard_world == 1) ? c->d_qpl : nullptr, c->db.poly, c->NR4, c->d_qrare, pf,
-                             b.piped ? b.progress : nullptr, blocks_per_group, c->scan_R, c->d_pipe_err});
+                             (c->scan_variant == 2 && c->shard_world == 1) ? c->d_qpl : nullptr, c->db.poly, c->NR4, c->d_qrare, pf});
   if (rc) return rc;
   if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[1], rs)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->rep_ev[1], 0)); }
   HIPCHK(c, hipEventRecord(b.replay_done, c->stream));

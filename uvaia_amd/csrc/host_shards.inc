@@ -191,7 +191,7 @@ int uvaia_gpu_shard_replay(uvaia_gpu_ctx *c, const void *cnt, const void *tmin, 
   // (--acgt: dist_unique of the pairs that reach a heap is counted from them too, the scan's per-pair count stays on the scanning rank)
   return launch_replay(c, {c->stream, q0, q1, cntp, nullptr, ppad, rt, nullptr, tminp, nullptr,
                            c->peer_db[owner], ltf, nonn, amb, c->d_entered + tf * 64, rb, re, (long long)ordinal0,
-                           nullptr, nullptr, 0, nullptr, 3, nullptr, 0, 2, nullptr});
+                           nullptr, nullptr, 0, nullptr, 3});
 }
 
 // ---- a group of contexts in ONE process (the C command line's --devices): the reference-shard protocol above with peer copies as

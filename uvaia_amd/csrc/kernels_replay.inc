@@ -340,7 +340,7 @@ static __device__ __forceinline__ void iupac_word_extra(const uint32_t *__restri
 // Default mode: text_matches - ACGT_matches and partial_matches - text_matches of one pair.  Both differences live on
 // sites where the query or the reference carries a partially ambiguous code, so only the alignment words listed for
 // either sequence are visited (all words if a list overflowed).  Whole wave cooperates; result in every lane.
-// (one word's contribution given both sets of four planes: iupac_planes_extra, kernels_scan_history.inc)
+// (one word's contribution given both sets of four planes: iupac_planes_extra, kernels_scan2.inc)
 
 // Single round trip: the reference's side row (count, listed words and their planes) is one coalesced 256-B load, the
 // reference planes at the query's listed words are requested at the same time (they do not depend on the row), and the
@@ -461,9 +461,7 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
                                                       const uint32_t *__restrict__ qfull, const int *__restrict__ amb_q,
                                                       unsigned long long *__restrict__ stats, int q_first, const int2 *__restrict__ tmin,
                                                       const uint32_t *__restrict__ qpl /* column-compressed scan: the queries' compressed polymorphic planes; else null */, int lq_words, int prio_,
-                                                      const uint4 *__restrict__ polyp, int NPT, int NP4, int NR4, const uint32_t *__restrict__ qrare,
-                                                      const unsigned *__restrict__ progress = nullptr /* pipelined search: the scan of this slice is still running; per stripe of 64 tiles, the blocks done */,
-                                                      unsigned blocks_per_group = 0 /* ... blocks of the scan per group of scan_R tiles (its super-tiles) */, int scan_R = 2, int *__restrict__ pipe_err = nullptr)
+                                                      const uint4 *__restrict__ polyp, int NPT, int NP4, int NR4, const uint32_t *__restrict__ qrare)
 {
   extern __shared__ int h[];
   if (prio_) __builtin_amdgcn_s_setprio(3);     // few latency-bound waves on the critical path: win issue arbitration against co-resident scan waves
@@ -510,7 +508,7 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
 #define TT_START(x)
 #define TT_ADD(acc, x)
 #endif
-  // software pipeline: the counters of round i+1 are requested before round i is processed (the kernel is latency bound:
+  // prefetch: the counters of round i+1 are requested before round i is processed (the kernel is latency bound:
   // one wave per query, a few hundred dependent rounds)
   // Traversal.  Tiles (64 references) whose smallest mismatch count is not below the current tolerance cannot produce an
   // admission, and the tolerance only changes through admissions; so the wave walks the tile minima (64 tiles per load) and
@@ -526,35 +524,13 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
   constexpr int PD = 4;
   int2 nbq[PD];
 #pragma unroll
-  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && !progress && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
+  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
   for (int tb = 0; tb < n_slice_tiles; tb += 64) {
     int tm = 0x7fffffff, tk = 0x7fffffff;            // tile bounds: smallest mismatch count, largest first key
-    if (progress) {
-      // Pipelined: the scan that writes this slice's counters is running next to this kernel.  A round of 64 tiles is one stripe of its
-      // progress counters: wait until every block that writes into the stripe has counted itself (they release at agent scope before they
-      // do), acquire, and only then read the stripe's bounds and counters.  The wait is bounded: a scan that never comes costs seconds,
-      // not the machine -- the wave gives up, says so, and the host reports the search as failed.
-      const int tiles_here = min(64, (ppad >> 6) - tb);
-      const unsigned expect = blocks_per_group * (unsigned)((tiles_here + scan_R - 1) / scan_R);
-      // (a thousand waves polling one word every microsecond keep its L2 channel busy for everybody: a wave that finds its stripe unfinished
-      // sleeps for about 10 us between looks -- a stripe takes the scan some 80 us)
-      unsigned spins = 0;
-      while (__hip_atomic_load(progress + (tb >> 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < expect) {
-#pragma unroll
-        for (int z = 0; z < 3; z++) __builtin_amdgcn_s_sleep(127);
-        if (++spins > (1u << 20)) { if (lane == 0 && pipe_err) atomicExch(pipe_err, 1); return; }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      if (use_tmin && tb + lane < n_slice_tiles) {
-        const unsigned long long b_ = __hip_atomic_load(reinterpret_cast<const unsigned long long *>(tmrow + tb + lane), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        tm = (int)(unsigned)b_; tk = (int)(unsigned)(b_ >> 32);
-      }
-    } else {
     if (tb + lane < n_slice_tiles) { tm = nbq[0].x; tk = nbq[0].y; }
 #pragma unroll
     for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];
     if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];
-    }
     // a tile can admit only if some reference passes the gate and (heap full) some reference's first key reaches the worst kept one
     // With consensus counters (CONS) a pre-score cut short at the snapshot lowers a pair's mismatch count, but never below the
     // snapshot, and never raises its first key: the bounds stay valid with "tm < T" widened to "tm < T or snapshot < T".
@@ -574,8 +550,8 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
           const int r = (tb + tsel[i]) * 64 + lane;
           valid[i] = (r >= r_begin && r < r_end);
           if (valid[i]) {
-            // (unpacked where it is used: nothing here may wait for the load, up to D of them are in flight; pipelined: an agent-scope load)
-            craw[i] = progress ? __hip_atomic_load(crow + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : crow[r];
+            // (unpacked where it is used: nothing here may wait for the load, up to D of them are in flight)
+            craw[i] = crow[r];
             if (CONS) a[i] = rt[r];
             if (CONS || ACGT) nn[i] = nonn[r];
           }

@@ -1,4 +1,4 @@
-// kernels_scan_history.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): the four-counter scan (introspection, radius search, query pruning, alignments above 49 000 columns), the two-counter scans over the packed planes (what up to 16 queries run: one query tile, every reference byte read once, nothing derived) and their LDS-broadcast variant from the kernel history.
+// kernels_scan2.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): the four-counter scans scan_iupac_kernel / scan_acgt_kernel (introspection, radius search, query pruning, alignments above 49 000 columns), the two-counter scans over the packed planes scan2_iupac_kernel / scan2_acgt_kernel (what up to 16 queries run: one query tile, every reference byte read once, nothing derived), pair_extras_kernel and tile_bounds_kernel (the other two counters of every pair and the sharp tile bounds, behind the column-compressed scan), and the device helpers the scans share (load_qwords, scan_work_item, wave_max_dpp).
 
 // ------------------------------------------------------------------------------------------------------------
 // device: the four-counter pair scan

@@ -194,16 +194,22 @@ void derive_all_kernel(const uint4 *__restrict__ tiles, long long tile_base, lon
 // takes queries 16 w .. 16 w + 15 of the super-tile.
 // stream (dwords), per super-tile; sdir[stile][4 NW] = for wave w: {first dword of its group records, their number} at [2w], then
 // {first dword of its rare records, their number} at [2 NW + 2w]:
-//   record = { w4 * 2048 (byte offset of the group's E plane in the tile; the group's grp[] row sits at byte offset w4 * 256),
-//              n_full4 = ceil(n_full / 4) | word-item counts << 4 (5 bits per word of the group),  n_generic,
-//              length of the record in dwords }  + 4 n_full4 LDS offsets (padded with the scratch row)
+//   record = { w4 * 2048 (byte offset of the group's E plane in the tile, V plane 1 KiB further; the group's grp[] row sits at byte offset
+//              w4 * 256) | bit 0: some word item of the record is a run item,
+//              n_full4 = ceil(n_full / 4) | n_generic << 16,
+//              word-item counts of the group's four words, 8 bits each,
+//              length of the record in dwords }
+//            + 4 n_full4 LDS offsets of the queries that are all-N in the group (padded with the scratch row)
 //            + n_generic x { ~qI & constMask [4],  ~qV (default) / ~qI (--acgt) [4],  LDS offset, 0, 0, 0 }
-//            + word items { ~qI & constMask, ~qV, LDS offset, 0 } of the queries that are dirty in ONE word of the group only, listed word
-//              by word
-//   rare record (after the group records) = { byte offset of a rare group's planes in the tile's gathered planes, word-item counts << 4, 0, 0 }
+//            + word items { ~qI & constMask, ~qV, LDS offset, byte mask of the group's full words } of the queries that are dirty in ONE
+//              word of the group only, or whose other dirty words hold no valid query character (run items: a non-zero byte mask, those
+//              words give the reference's own counts), listed word by word
+//   two zero headers { 0, 0, 0, 4 } end the group records of a super-tile (the walk runs two headers ahead)
+//   rare record (after them) = { byte offset of a rare group's planes in the tile's gathered planes, word-item counts of 8 bits each, 0, 0 }
 //            + items { sites, their lo bits, their hi bits, LDS offset }, word by word
 //   LDS offsets are byte offsets of a query's counter row inside the block's counters: (query within the super-tile) * 256 * R
 //   (the host builds the stream for the R the context runs); the scratch row is row 64.
+//   The whole stream is padded by 64 dwords: items and headers are requested past the end.
 // qpl[q][p4][L,H,I,-][4]: compressed planes of the polymorphic columns
 template <int R> struct Scan3Acc;
 template <> struct Scan3Acc<1> { typedef uint32_t type; };
@@ -245,7 +251,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 8)))
                                                      const uint32_t *__restrict__ sdir, const uint32_t *__restrict__ grp,
                                                      const int *__restrict__ tot_e, const int *__restrict__ tot_v,
                                                      uint32_t *__restrict__ out, int ppad, int n_stiles, int2 *__restrict__ tmin, int r_lo, int r_hi,
-                                                     int stile_first, unsigned *__restrict__ progress /* nullable: per stripe of SCAN_STRIPE_TILES tiles, the blocks that have finished it */)
+                                                     int stile_first)
 {
   constexpr int QT = QS / NW;                                  // queries a wave takes in phase 1 and in the epilogue
   static_assert((NW == 4 || NW == 8 || NW == 16) && (QS == 64 || QS == 128) && QT >= 4 && QT <= 16, "waves and queries of a super-tile");
@@ -563,11 +569,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 8)))
       if (!live[rr]) continue;                                          // wave-uniform
       const uint32_t pk = acc_part(pkk, rr);
       const int c0 = (ACGT ? te[rr] : te[rr] + NP4 * 128) - ((int)(pk & 0xFFFFu) - (int)RARE_BIAS), c1 = tv[rr] - (int)(pk >> 16);
-      // (pipelined: write-through stores at agent scope -- what lets the block signal without writing its XCD's whole L2 back)
-#ifndef PIPE_PLAIN_STORES
-      if (progress) __hip_atomic_store(out + (size_t)(q0 + q) * ppad + r[rr], (uint32_t)c0 | ((uint32_t)c1 << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else
-#endif
       out[(size_t)(q0 + q) * ppad + r[rr]] = (uint32_t)c0 | ((uint32_t)c1 << 16);
       const int mm = ACGT ? c0 : c1 - c0, kk = ACGT ? c1 - c0 : c0;
       // both bounds by DPP (wave_max_dpp: no trip through the LDS crossbar per step); the counts are below 2^16: the smallest mismatch count is
@@ -576,19 +577,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4, 8)))
       const int m = mx_m ? (int)(65536u - mx_m) : 0x7fffffff, k = mx_k ? (int)(mx_k - 1u) : (int)0x80000000;
       if (lane == 0) {
         int2 *tp = tmin + (size_t)(q0 + q) * (ppad >> 6) + trel[rr];
-        if (progress) __hip_atomic_store(reinterpret_cast<unsigned long long *>(tp), (unsigned long long)(unsigned)m | ((unsigned long long)(unsigned)k << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *tp = make_int2(m, k);
+        *tp = make_int2(m, k);
       }
     }
     __builtin_amdgcn_sched_barrier(0);                                // one query at a time: keeps the epilogue from inflating the register budget
-  }
-  // Pipelined search (host_resident.inc): the replay of this slice runs NEXT to this launch and opens a stripe of tiles once every block
-  // that writes into it has said so.  The counters and bounds left the block as write-through (agent-scope) stores; every storing wave
-  // drains them, the block meets, one lane counts the block.  (A release fence here -- buffer_wbl2: the whole L2 of the XCD written back
-  // by each of 4 176 blocks -- made the launch 1.5 times longer, round 4.)
-  if (progress) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(progress + (trel0 / SCAN_STRIPE_TILES), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }

@@ -68,8 +68,6 @@ constexpr int AMB_ROW = 64;            // ints per REFERENCE side row (256 B, on
                                        //   [0] count (uncapped)  [1..11] word indices  [12 + 4k + p] plane p of the k-th listed word
 constexpr int PACK_CHUNK = 4096;       // references per host->device staging round (multiple of 64)
 constexpr uint32_t SCAN3_BIAS = 16384u; // scan3_kernel: bias of a pair's low counter half (what the rare items and, --acgt, the polymorphic columns may take away)
-constexpr int SCAN_STRIPE_TILES = 64;  // pipelined search: tiles of 64 references per stripe of the scan's progress counters = one round of the replay's walk (a block of scan3_kernel
-                                       // takes R <= 4 consecutive tiles starting at a multiple of R: it never straddles two stripes)
 constexpr int NBUF = 4;                // counter buffers: the scan may run this many slices ahead of the gate/replay
 
 thread_local std::string g_open_error;
@@ -98,9 +96,8 @@ struct SliceBuf {
   int4 *rt = nullptr;            // per reference of a slice: untruncated consensus pre-score (query sets with constant-and-complete columns)
   size_t cap = 0;                // pairs the buffer holds (grown when a slice needs more: slices may exceed a pool, see plan_subslices)
   int tiles = 0, rb = 0, re = 0; long long tf = 0;     // the slice scanned into it: tiles, first and end reference relative to its first tile, that tile
-  bool scanned = false, cons_done = false, piped = false;
-  unsigned *progress = nullptr; size_t progress_cap = 0;   // pipelined search: the scan's progress counters, one per stripe
-  hipEvent_t scan_done = nullptr, scan_started = nullptr, replay_done = nullptr;
+  bool scanned = false, cons_done = false;
+  hipEvent_t scan_done = nullptr, replay_done = nullptr;
   bool replay_recorded = false;
 };
 
@@ -128,10 +125,6 @@ struct uvaia_gpu_ctx {
   // its order), [1..3] scan_streams; planes_ev[i] = an event the search recorded on that stream behind the last such work (a slice's
   // scan_done / replay_done), null where there is none and the rebuild records one of its own (planes_touch / planes_fenced / planes_idle)
   bool planes_busy[4] = {}; hipEvent_t planes_ev[4] = {};
-  // pipelined search (column-compressed scan): the replay of a slice runs next to its scan and follows its progress counters
-  // (off unless tuning.pipeline = 2: measured slower at config[1])
-  bool pipeline = false, pipeline_now = false, pipe_used = false;
-  int *d_pipe_err = nullptr;
   SliceBuf slice[NBUF];                   // the counter buffers; the push path (run_batch) works in slice[0]
   bool use_ext = false;                   // the scan leaves the extras and replay3_kernel runs (default mode: packed-plane scan, or the column-compressed one up to 128 queries)
   size_t subslice = 25088;                // resident search: pools are cut into slices of about this size (exact: see search_resident).  (32 768 until round 4: at config[1]
@@ -166,7 +159,6 @@ struct uvaia_gpu_ctx {
   bool serial = false;           // tuning.serial: no scan/replay overlap (to time the kernels in isolation)
   int replay_lq = -1;            // replay caches the query's planes in LDS (22 KB per block): -1 = only with few queries (see open)
   int replay_prio = 1;           // replay waves raise their issue priority
-  bool head_full = false;        // tuning.head_scan = 2: the stream's first two tiles go through the four-counter scan (heaps fill without on-demand fetches; measured slower)
   int replay_half = 32;          // tiles per staging buffer of replay3_kernel (32, 16 or 8: its LDS decides how many of its blocks share a compute unit)
   int replay_cus = 0;            // compute units set aside for the replay kernels of the resident search (0: none, the streams share the chip by priority)
   hipStream_t rep_stream = nullptr; hipEvent_t rep_ev[2] = {};   // ... the stream masked to them, and the events that splice its kernels into `stream`'s order
@@ -287,7 +279,7 @@ void fill_code_table(uint8_t *t)
 #include "kernels_pack.inc"
 #include "kernels_rows.inc"
 #include "kernels_consensus.inc"
-#include "kernels_scan_history.inc"
+#include "kernels_scan2.inc"
 #include "kernels_scan3.inc"
 #include "kernels_replay.inc"
 #include "kernels_ball.inc"
