@@ -10,7 +10,7 @@ The edge table: which line each group is aimed at (kernels_ball.inc unless anoth
   A  columns gathered, their number    `if (__builtin_expect(++fill == 32, 0)) flush(o);`  `if (j == 3) {` of BitGather::flush (a group is written when
      and placement                     word ow & 3 == 3 closes)  `if (fill > 0) flush(o); while (ow < end_word) flush(o);` of finish  `hot.take(wd, mk[j], o);
                                        cold.take(wd, mk[4 + j], o);` (two walkers, one tile)  ensure_qgather: `if (n_idx >= 2 * BALL_HOT_COLS) {`,
-                                       `c->NH4 = n_hot / 128;`, `c->NG4 = std::max(1, ...)`, the masks' `(col >> 7) * 8 + (i < n_hot ? 0 : 4) + ((col >> 5) & 3)`
+                                       `c->ball.NH4 = n_hot / 128;`, `c->ball.NG4 = std::max(1, ...)`, the masks' `(col >> 7) * 8 + (i < n_hot ? 0 : 4) + ((col >> 5) & 3)`
                                        ball_gather_queries_kernel: `const int i = ow * 32 + b; if (i >= n_cols) break;`
   B  query tiles                       ball_scan_kernel: `uint32_t alive = q0 + QT <= nq ? ... : (1u << (nq - q0)) - 1u;`  `if (((alive >> q) & 1u) &&
                                        acc[q] < limit) key = ((unsigned long long)(unsigned)(q0 + q) << 32) | (unsigned)acc[q];`  `atomicMin(&first_key[k], key);`
@@ -21,8 +21,8 @@ The edge table: which line each group is aimed at (kernels_ball.inc unless anoth
   D  stage 1's arithmetic              ball_stage1_kernel: `int md = min(dc, radius);`  `md += min(dm, radius);`  `if (2 * md >= radius) ask = true; else
                                        md = 2 * md;`  `if (has_c) {`  `if (has_m) {`
   E  the survivor list, buffers        ball_stage1_kernel: `const int k = atomicAdd(n_survivors, 1); survivors[k] = r; cdist[k] = md;`  host_ball.inc:
-     reused                            `const int mt = (n_ask + 63) / 64;`  `if (c->ball_tiles_cap < (size_t)mt) {`  `hipMemsetAsync(c->d_ball_key, 0xFF,
-                                       (size_t)mt * 64 * ...)`  `c->ball_cap < (size_t)n_tiles * 64`  `if (fused && c->ball_ga_tiles < (size_t)n_tiles) {`
+     reused                            `const int mt = (n_ask + 63) / 64;`  `if (c->ball.d_key.cap < (size_t)mt * 64) {`  `hipMemsetAsync(c->ball.d_key, 0xFF,
+                                       (size_t)mt * 64 * ...)`  `b->reserve(c, cap)` of the three result arrays  `if (fused && c->ball.d_ga.reserve(c, (size_t)n_tiles * tile_u4))`
   F  ranges and batch sizes            ball_stage1_kernel: `if (r < r_lo || r >= r_hi) return;`  `mindist[r - r_lo] = md;`  ball_finish2_kernel:
                                        `mindist[list[k] - r_lo]`  host_ball.inc: the arguments of ball_range in uvaia_gpu_ball_resident, `if (first + n >
                                        c->db_n)`, `if ((size_t)n_ref > c->max_pool)` of uvaia_gpu_ball and uvaia_gpu_ball_packed"""
@@ -37,7 +37,7 @@ import oracle_lib as O
 # ---- copies of the code's constants; each moves with the line it mirrors
 QTB = 16                    # `constexpr int QTB = 16;`  queries of one wave of ball_scan_kernel (ball_range, host_ball.inc)
 BALL_HOT_COLS = 256         # `constexpr int BALL_HOT_COLS = 256;`  (ensure_qgather, host_launch.inc)
-GROUP_COLS = 128            # `c->NG4 = std::max(1, c->NH4 + (n_idx - n_hot + 127) / 128);`  columns of a word group (a uint4 of 32-column words)
+GROUP_COLS = 128            # `c->ball.NG4 = std::max(1, c->ball.NH4 + (n_idx - n_hot + 127) / 128);`  columns of a word group (a uint4 of 32-column words)
 WORD_COLS = 32              # `if (__builtin_expect(++fill == 32, 0)) flush(o);`  (BitGather::take, kernels_ball.inc)
 TILE = 64                   # `const int k = blockIdx.x * 64 + lane;`  references of a tile (ball_compact_kernel, ball_gather_cols_kernel)
 TILES_PER_BLOCK = 4         # `const int trel = blockIdx.x * 4 + wave;`  (ball_stage1_kernel); `const int tile = grp * 4 + wave;` (ball_scan_kernel)
@@ -198,7 +198,7 @@ def gather_layout(q):
         is_hot = np.zeros(n_idx, dtype=bool)
         is_hot[by_score[:n_hot]] = True
         order = np.concatenate([order[is_hot], order[~is_hot]])
-    NH4 = n_hot // GROUP_COLS                                       # `c->NH4 = n_hot / 128;`
+    NH4 = n_hot // GROUP_COLS                                       # `c->ball.NH4 = n_hot / 128;`
     NG4 = max(1, NH4 + (n_idx - n_hot + GROUP_COLS - 1) // GROUP_COLS)
     return Layout(order, n_hot, NH4, NG4, score)
 

@@ -13,21 +13,20 @@ int uvaia_gpu_agree_on_polymorphic(uvaia_gpu_ctx *c, const char *const *seq, int
   if (rc) return rc;
   const int n_tiles = (n_seq + 63) / 64, ppad = n_tiles * 64;
   rc = ensure_cnt4(c, (size_t)c->nq_pad * c->pool_pad); if (rc) return rc;
-  const bool prof = c->profile; c->profile = false;     // not the nearest-neighbour scan the statistics describe
+  const bool prof = c->stats.profile; c->stats.profile = false;     // not the nearest-neighbour scan the statistics describe
   rc = ensure_qpoly(c); if (rc) return rc;
-  rc = launch_scan(c, c->batch, 0, n_tiles, c->d_qpoly, c->nq, c->d_cnt, ppad, 0.0);
-  c->profile = prof;
+  rc = launch_scan(c, c->batch, 0, n_tiles, c->tab.d_qpoly, c->nq, c->state.d_cnt, ppad, 0.0);
+  c->stats.profile = prof;
   if (rc) return rc;
-  uint8_t *d_out = nullptr;
+  DevBuf<uint8_t> d_out;
   const size_t bytes = (size_t)n_seq * c->nq;
-  HIPCHK(c, hipMalloc(&d_out, bytes));
+  if (int rc_ = d_out.reserve(c, bytes)) return rc_;
   dim3 grid((n_seq + 255) / 256, c->nq);
-  if (c->acgt) hipLaunchKernelGGL((agree_kernel<true>), grid, dim3(256), 0, c->stream, c->d_cnt, ppad, c->nq, n_seq, d_out);
-  else         hipLaunchKernelGGL((agree_kernel<false>), grid, dim3(256), 0, c->stream, c->d_cnt, ppad, c->nq, n_seq, d_out);
+  if (c->acgt) hipLaunchKernelGGL((agree_kernel<true>), grid, dim3(256), 0, c->st.stream, c->state.d_cnt, ppad, c->nq, n_seq, d_out);
+  else         hipLaunchKernelGGL((agree_kernel<false>), grid, dim3(256), 0, c->st.stream, c->state.d_cnt, ppad, c->nq, n_seq, d_out);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_out);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->st.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st.stream);
   if (e != hipSuccess) return fail(c, UVAIA_GPU_EHIP, "agree_on_polymorphic: %s", hipGetErrorString(e));
   return 0;
 }
@@ -51,26 +50,30 @@ int uvaia_gpu_query_columns(const char *const *seq, int n_query, int nchar, size
   const size_t pitch = ((size_t)nchar + 63) / 64 * 64;
   const int batch = (int)std::max<size_t>(64, std::min<size_t>(4096, ((size_t)96 << 20) / pitch) / 64 * 64);      // rows per batch: at most 96 MB of staging
   const int groups = batch / 64;
-  uint8_t *h_rows = nullptr, *d_rows = nullptr, *d_pf = nullptr, *d_pl = nullptr, *d_first = nullptr, *d_flags = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t freed[2] = {nullptr, nullptr};
-  auto done = [&](int rc) { if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); } for (int i = 0; i < 2; i++) if (freed[i]) hipEventDestroy(freed[i]);
-                            hipFree(d_rows); hipFree(d_pf); hipFree(d_pl); hipFree(d_first); hipFree(d_flags); if (h_rows) hipHostFree(h_rows); return rc; };
-#define QCHK(call) HIP_TRY(call, return done(fail(nullptr, code_, "%s failed: %s", #call, hipGetErrorString(e_))))      /* no context: release what this call made */
-  QCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  QCHK(hipHostMalloc(&h_rows, (size_t)2 * batch * pitch, hipHostMallocDefault));
-  QCHK(hipMalloc(&d_rows, (size_t)2 * batch * pitch));
-  QCHK(hipMalloc(&d_pf, (size_t)groups * nchar)); QCHK(hipMalloc(&d_pl, (size_t)groups * nchar));
-  QCHK(hipMalloc(&d_first, (size_t)nchar)); QCHK(hipMalloc(&d_flags, (size_t)nchar));
+  // no context: what this call makes goes with this frame, last to first -- the wait for the stream, the events and arrays, the stream
+  Stream st;
+  PinnedBuf h_rows;
+  DevBuf<uint8_t> d_rows, d_pf, d_pl, d_first, d_flags;
+  Event freed[2];
+  struct Wait { const Stream &s; ~Wait() { if (s) hipStreamSynchronize(s); } } wait_{st};
+  uvaia_gpu_ctx *const none = nullptr;
+#define QCHK(call) HIPCHK(none, call)
+  QCHK(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+  if (int rc = h_rows.alloc(none, (size_t)2 * batch * pitch)) return rc;
+  if (int rc = d_rows.reserve(none, (size_t)2 * batch * pitch)) return rc;
+  if (int rc = d_pf.reserve(none, (size_t)groups * nchar)) return rc;
+  if (int rc = d_pl.reserve(none, (size_t)groups * nchar)) return rc;
+  if (int rc = d_first.reserve(none, (size_t)nchar)) return rc;
+  if (int rc = d_flags.reserve(none, (size_t)nchar)) return rc;
   QCHK(hipMemsetAsync(d_first, 'N', (size_t)nchar, st)); QCHK(hipMemsetAsync(d_flags, 0, (size_t)nchar, st));
-  for (int i = 0; i < 2; i++) QCHK(hipEventCreateWithFlags(&freed[i], hipEventDisableTiming));
+  for (Event &e : freed) if (int rc = e.make(none, hipEventDisableTiming)) return rc;
   const unsigned gx = (unsigned)((hi - lo + 255) / 256);
   int k = 0;
   for (int a = 0; a < n_query; a += batch, k++) {
     const int m = std::min(batch, n_query - a), b = k & 1;
     if (k >= 2) QCHK(hipEventSynchronize(freed[b]));                 // the staging half's previous batch has been consumed
     uint8_t *hb = h_rows + (size_t)b * batch * pitch, *db = d_rows + (size_t)b * batch * pitch;
-    for (int i = 0; i < m; i++) if (!seq[a + i]) return done(fail(nullptr, UVAIA_GPU_EINVAL, "query %d is NULL", a + i));
+    for (int i = 0; i < m; i++) if (!seq[a + i]) return fail(nullptr, UVAIA_GPU_EINVAL, "query %d is NULL", a + i);
     parallel_for(m, [&](int i) { memcpy(hb + (size_t)i * pitch, seq[a + i], (size_t)nchar); });
     QCHK(hipMemcpyAsync(db, hb, (size_t)m * pitch, hipMemcpyHostToDevice, st));
     const int ng = (m + 63) / 64;
@@ -88,7 +91,7 @@ int uvaia_gpu_query_columns(const char *const *seq, int n_query, int nchar, size
     consensus[c] = (flags[(size_t)c] & 1) ? '#' : (char)first[(size_t)c];
     some_missing[c] = (flags[(size_t)c] & 2) ? 1 : 0;
   }
-  return done(0);
+  return 0;
 }
 
 int uvaia_gpu_push(uvaia_gpu_ctx *c, const char *const *seq, const int *non_n, int n_ref, int64_t ordinal0, uint8_t *entered)
@@ -102,24 +105,24 @@ int uvaia_gpu_push(uvaia_gpu_ctx *c, const char *const *seq, const int *non_n, i
   rc = pack_rows(c, seq, nullptr, 0, non_n, n_ref, c->batch, 0);
   if (rc) return rc;
   const int n_tiles = (n_ref + 63) / 64;
-  HIPCHK(c, hipMemsetAsync(c->d_entered, 0, (size_t)n_tiles * 64, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->state.d_entered, 0, (size_t)n_tiles * 64, c->st.stream));
   rc = run_batch(c, c->batch, 0, n_tiles, 0, n_ref, ordinal0);
   if (rc) return rc;
-  if (entered) HIPCHK(c, hipMemcpyAsync(entered, c->d_entered, (size_t)n_ref, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (entered) HIPCHK(c, hipMemcpyAsync(entered, c->state.d_entered, (size_t)n_ref, hipMemcpyDeviceToHost, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   return collect_events(c);
 }
 
 int uvaia_gpu_drain(uvaia_gpu_ctx *c, int *n_items, int *max_incompatible, int *scores, int64_t *ordinals)
 {
   if (!c || !n_items || !scores || !ordinals) return c ? fail(c, UVAIA_GPU_EINVAL, "NULL output") : UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   planes_idle(c, true, false);
   const size_t ne = (size_t)c->nq * (c->k + 1);
   std::vector<int> h(ne * HEAP_ENTRY), T(c->nq);
-  HIPCHK(c, hipMemcpy(h.data(), c->d_heap, h.size() * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(n_items, c->d_n, (size_t)c->nq * sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(T.data(), c->d_T, (size_t)c->nq * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h.data(), c->state.d_heap, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(n_items, c->state.d_n, (size_t)c->nq * sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(T.data(), c->state.d_T, (size_t)c->nq * sizeof(int), hipMemcpyDeviceToHost));
   for (size_t e = 0; e < ne; e++) {
     for (int s = 0; s < 6; s++) scores[e * 6 + s] = h[e * HEAP_ENTRY + s];
     ordinals[e] = (int64_t)(((uint64_t)(uint32_t)h[e * HEAP_ENTRY + 7] << 32) | (uint32_t)h[e * HEAP_ENTRY + 6]);

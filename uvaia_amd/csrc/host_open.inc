@@ -7,32 +7,13 @@ const char *uvaia_gpu_last_error(const uvaia_gpu_ctx *ctx) { return ctx ? ctx->e
 void uvaia_gpu_close(uvaia_gpu_ctx *c)
 {
   if (!c) return;
-  if (c->stream) hipStreamSynchronize(c->stream);
-  for (auto &e : c->evts) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
-  for (hipEvent_t e : c->ev_pool) hipEventDestroy(e);
-  for (hipEvent_t e : c->rows_evs) hipEventDestroy(e);
-  void *dev[] = {c->d_idx_cols, c->d_qg, c->d_ball_masks, c->d_ball_key, c->d_split, c->d_qrare, c->d_rmask, c->d_cls, c->d_qpl, c->d_stream, c->d_sdir, c->d_mindist, c->d_ball_list, c->d_ball_cdist, c->d_ball_n, c->d_ball_tiles, c->d_ball_ga,
-                 c->d_qp2, c->d_amb_q, c->d_stats, c->d_qp, c->d_cp, c->d_cpm, c->d_qpoly, c->d_pmask, c->d_heap, c->d_n, c->d_T, c->d_snap, c->d_err, c->d_cnt, c->d_rt, c->d_tr, c->d_entered, c->d_stage, c->d_pk, c->d_rows, c->d_row_idx, c->d_rsel, c->d_rcnt, c->d_roff, c->d_rexc, c->d_wsel, c->d_win4};
-  for (void *p : dev) if (p) hipFree(p);
-  store_free(c->batch); store_free(c->db);
-  for (SliceBuf &b : c->slice) slice_free(b);
-  if (c->h_stage) hipHostFree(c->h_stage);
-  for (int i = 0; i < 2; i++) if (c->stage_free[i]) hipEventDestroy(c->stage_free[i]);
-  for (int i = 0; i < 16; i++) if (c->order_ev[i]) hipEventDestroy(c->order_ev[i]);
-  for (int i = 0; i < 4; i++) if (c->ball_ev[i]) hipEventDestroy(c->ball_ev[i]);
-  if (c->copy_stream) { hipStreamSynchronize(c->copy_stream); hipStreamDestroy(c->copy_stream); }
-  for (auto &sl : c->wstage) { for (void *p : {(void *)sl.planes, (void *)sl.nonn, (void *)sl.side}) if (p) hipFree(p); for (hipEvent_t e : {sl.copied, sl.read}) if (e) hipEventDestroy(e); }
-  for (int i = 0; i < 5; i++) if (c->win_ev[i]) hipEventDestroy(c->win_ev[i]);
-  for (int i = 0; i < 64; i++) for (int j = 0; j < 2; j++) if (c->ipc_opened[i][j]) hipIpcCloseMemHandle(c->ipc_opened[i][j]);
-  for (int i = 0; i < 8; i++) for (int j = 0; j < 3; j++) if (c->mark_ev[i][j]) hipEventDestroy(c->mark_ev[i][j]);
-  for (int i_ = 0; i_ < 3; i_++) if (c->derive_streams[i_]) { hipStreamSynchronize(c->derive_streams[i_]); hipStreamDestroy(c->derive_streams[i_]); }
-  for (auto &d : c->derive_chunks) hipEventDestroy(d.done);
-  for (int i = 0; i < 4; i++) if (c->derive_fence[i]) hipEventDestroy(c->derive_fence[i]);
-  if (c->scan_stream) hipStreamDestroy(c->scan_stream);
-  for (int i = 1; i < 3; i++) if (c->scan_streams[i]) hipStreamDestroy(c->scan_streams[i]);
-  if (c->stream) hipStreamDestroy(c->stream);
-  if (c->rep_stream) { hipStreamSynchronize(c->rep_stream); hipStreamDestroy(c->rep_stream); }
-  for (int i = 0; i < 2; i++) if (c->rep_ev[i]) hipEventDestroy(c->rep_ev[i]);
+  // the streams that may still hold work are waited for; what was mapped from other processes is unmapped; everything else the context
+  // holds goes with its members (host_ctx.inc)
+  if (c->st.stream) hipStreamSynchronize(c->st.stream);
+  if (c->win.copy_stream) hipStreamSynchronize(c->win.copy_stream);
+  for (hipStream_t st : c->st.derive_streams) if (st) hipStreamSynchronize(st);
+  if (c->st.rep_stream) hipStreamSynchronize(c->st.rep_stream);
+  for (auto &rank : c->shard.ipc_opened) for (void *p : rank) if (p) hipIpcCloseMemHandle(p);
   delete c;
 }
 
@@ -76,11 +57,11 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   if (tn.scan_waves_per_block) c->scan_NW = tn.scan_waves_per_block;
   if (c->scan_R == 4 && c->scan_NW != 8) { delete c; return fail(nullptr, UVAIA_GPU_EINVAL, "four reference tiles per wave go with eight waves per block"); }
   if (tn.subslice_refs) { c->subslice = tn.subslice_refs; c->subslice_forced = true; }
-  if (tn.scan_streams >= 1 && tn.scan_streams <= 3) c->scan_nstreams_forced = tn.scan_streams;
+  if (tn.scan_streams >= 1 && tn.scan_streams <= 3) c->st.scan_nstreams_forced = tn.scan_streams;
   if (tn.scan_streams > 100 && tn.scan_streams < 200) c->first_slice_pct = tn.scan_streams == 199 ? 0 : tn.scan_streams - 100;
   c->derive_waves = tn.derive_waves;
-  if (tn.ball_gather == 1 || tn.ball_gather == 2) c->ball_fused = tn.ball_gather == 2;
-  if (tn.rederive_streams >= 1 && tn.rederive_streams <= 3) { c->derive_nstreams = tn.rederive_streams; c->derive_forced = true; }
+  if (tn.ball_gather == 1 || tn.ball_gather == 2) c->ball.fused = tn.ball_gather == 2;
+  if (tn.rederive_streams >= 1 && tn.rederive_streams <= 3) { c->st.derive_nstreams = tn.rederive_streams; c->st.derive_forced = true; }
   // the default scan keeps per-pair deficits in 16-bit halves (LDS counters): alignments of more than ~49 000 columns take the
   // four-counter scan instead (32-bit counts, same results, slower)
   if (c->nchar > 49000) c->fullscan = true;
@@ -90,6 +71,7 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   if ((size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int) + 128 > 160 * 1024) { delete c; return fail(nullptr, UVAIA_GPU_EINVAL, "nbest=%d does not fit the per-query LDS heap (max 5115)", heap_size); }
 
 #define OPENCHK(call) HIP_TRY(call, { const int rc_ = fail(nullptr, code_, "%s failed: %s", #call, hipGetErrorString(e_)); uvaia_gpu_close(c); return rc_; })      /* while opening: the half-made context goes away */
+#define OPENBUF(buf, n) do { if (const int rc_ = (buf).reserve(nullptr, (n))) { uvaia_gpu_close(c); return rc_; } } while (0)
   // packed-plane scan in default mode: the scan also leaves text - ACGT matches and partial - text matches of every pair (scan2_extras)
   // and the replay needs no memory round trip per admission (replay3_kernel)
   // (Over the column-compressed scan, 33-128 queries, two kernels after the scan can make the same arrays -- pair_extras_kernel,
@@ -121,28 +103,25 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
       const int ncu = prop.multiProcessorCount, words = (ncu + 31) / 32;
       std::vector<uint32_t> m_rep((size_t)words, 0u), m_scan((size_t)words, 0u);
       for (int b = 0; b < ncu; b++) (b < rep_cus ? m_rep : m_scan)[(size_t)b >> 5] |= 1u << (b & 31);
-      // (c->stream stays the stream everything of the replay is ordered on -- and the one packing, the radius search and the push path
+      // (c->st.stream stays the stream everything of the replay is ordered on -- and the one packing, the radius search and the push path
       // run on, with the whole chip; a replay kernel of the resident search is put on rep_stream between two events: host_resident.inc)
       hipStream_t st[7] = {};
       bool ok = hipExtStreamCreateWithCUMask(&st[0], (uint32_t)words, m_rep.data()) == hipSuccess;
       for (int i = 1; i < 7 && ok; i++) ok = hipExtStreamCreateWithCUMask(&st[i], (uint32_t)words, m_scan.data()) == hipSuccess;
-      if (ok) ok = hipEventCreateWithFlags(&c->rep_ev[0], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->rep_ev[1], hipEventDisableTiming) == hipSuccess;
+      if (ok) ok = hipEventCreateWithFlags(&c->st.rep_ev[0].e, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&c->st.rep_ev[1].e, hipEventDisableTiming) == hipSuccess;
       if (ok) {
-        c->rep_stream = st[0]; c->scan_stream = st[1]; c->scan_streams[0] = st[1]; c->scan_streams[1] = st[2]; c->scan_streams[2] = st[3];
-        for (int i = 0; i < 3; i++) c->derive_streams[i] = st[4 + i];
+        c->st.rep_stream.s = st[0];
+        for (int i = 0; i < 3; i++) { c->st.scan_streams[i].s = st[1 + i]; c->st.derive_streams[i].s = st[4 + i]; }
         split = true; c->replay_cus = rep_cus;
       } else { (void)hipGetLastError(); for (int i = 0; i < 7; i++) if (st[i]) hipStreamDestroy(st[i]); }
     }
-    OPENCHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_greatest));
+    OPENCHK(hipStreamCreateWithPriority(&c->st.stream.s, hipStreamNonBlocking, prio_greatest));
     if (!split) {
-      OPENCHK(hipStreamCreateWithPriority(&c->scan_stream, hipStreamNonBlocking, prio_least));
-      c->scan_streams[0] = c->scan_stream;
-      for (int i = 1; i < 3; i++) OPENCHK(hipStreamCreateWithPriority(&c->scan_streams[i], hipStreamNonBlocking, prio_least));
+      for (int i = 0; i < 3; i++) OPENCHK(hipStreamCreateWithPriority(&c->st.scan_streams[i].s, hipStreamNonBlocking, prio_least));
       // between the scan (lowest) and the replay (highest): its blocks take the slots scan blocks free, ahead of the next scan blocks
-      for (int i = 0; i < 3; i++) OPENCHK(hipStreamCreateWithPriority(&c->derive_streams[i], hipStreamNonBlocking, (prio_least + prio_greatest) / 2));
+      for (int i = 0; i < 3; i++) OPENCHK(hipStreamCreateWithPriority(&c->st.derive_streams[i].s, hipStreamNonBlocking, (prio_least + prio_greatest) / 2));
     }
-    for (SliceBuf &b : c->slice) { OPENCHK(hipEventCreateWithFlags(&b.scan_done, hipEventDisableTiming)); OPENCHK(hipEventCreateWithFlags(&b.replay_done, hipEventDisableTiming)); }
-    c->derive_stream = c->derive_streams[0];
+    for (SliceBuf &b : c->slice) { OPENCHK(hipEventCreateWithFlags(&b.scan_done.e, hipEventDisableTiming)); OPENCHK(hipEventCreateWithFlags(&b.replay_done.e, hipEventDisableTiming)); }
   }
   uint8_t code_tab[256]; fill_code_table(code_tab);
   OPENCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_code), code_tab, 256));
@@ -164,60 +143,59 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
   {  // the queries restricted to query->idx are the query planes under the mask of those columns: kept as the mask (ensure_qpoly)
     std::vector<uint32_t> pmask((size_t)c->W4 * 4, 0u);
     for (int sidx = lo; sidx < hi; sidx++) if (in_p[(size_t)sidx]) pmask[(size_t)sidx >> 5] |= 1u << (sidx & 31);
-    OPENCHK(hipMalloc(&c->d_pmask, pmask.size() * 4)); OPENCHK(hipMemcpy(c->d_pmask, pmask.data(), pmask.size() * 4, hipMemcpyHostToDevice));
+    OPENBUF(c->tab.d_pmask, pmask.size()); OPENCHK(hipMemcpy(c->tab.d_pmask, pmask.data(), pmask.size() * 4, hipMemcpyHostToDevice));
     std::vector<int> cols;
     for (int sidx = lo; sidx < hi; sidx++) if (in_p[(size_t)sidx]) cols.push_back(sidx);
-    c->n_idx = (int)cols.size(); c->NG4 = std::max(1, ((c->n_idx + 31) / 32 + 3) / 4);
-    c->idx_cols = cols;
+    c->ball.n_idx = (int)cols.size(); c->ball.NG4 = std::max(1, ((c->ball.n_idx + 31) / 32 + 3) / 4);
+    c->ball.idx_cols = cols;
     cols.resize(cols.size() + 1, 0);
-    OPENCHK(hipMalloc(&c->d_idx_cols, cols.size() * sizeof(int))); OPENCHK(hipMemcpy(c->d_idx_cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
+    OPENBUF(c->ball.d_idx_cols, cols.size()); OPENCHK(hipMemcpy(c->ball.d_idx_cols, cols.data(), cols.size() * sizeof(int), hipMemcpyHostToDevice));
   }
-  OPENCHK(hipMalloc(&c->d_stage, (size_t)2 * PACK_CHUNK * c->pitch));
-  OPENCHK(hipHostMalloc(&c->h_stage, (size_t)2 * PACK_CHUNK * c->pitch, hipHostMallocDefault));
+  OPENBUF(c->d_stage, (size_t)2 * PACK_CHUNK * c->pitch);
+  if (const int rc_ = c->h_stage.alloc(nullptr, (size_t)2 * PACK_CHUNK * c->pitch)) { uvaia_gpu_close(c); return rc_; }
   memset(c->h_stage, 'N', (size_t)2 * PACK_CHUNK * c->pitch);
-  for (int i = 0; i < 2; i++) OPENCHK(hipEventCreateWithFlags(&c->stage_free[i], hipEventDisableTiming));
+  for (int i = 0; i < 2; i++) OPENCHK(hipEventCreateWithFlags(&c->stage_free[i].e, hipEventDisableTiming));
   // the query-side tables of the scans (query planes, column classes, rare columns, compressed planes, item streams): built on the
   // device from the raw rows (host_qprep.inc) or, on request, by host threads (host_qtables.inc); same bytes either way
   if (tn.query_tables == 1) { const int rc_ = build_query_tables_host(c, q, tn, code_tab, lo, hi, in_p); if (rc_) { uvaia_gpu_close(c); return rc_; } }
   else                      { const int rc_ = build_query_tables_device(c, q, tn, lo, hi);               if (rc_) { uvaia_gpu_close(c); return rc_; } }
-  OPENCHK(hipMalloc(&c->d_cp, cp.size() * 4)); OPENCHK(hipMemcpy(c->d_cp, cp.data(), cp.size() * 4, hipMemcpyHostToDevice));
-  OPENCHK(hipMalloc(&c->d_cpm, cpm.size() * 4)); OPENCHK(hipMemcpy(c->d_cpm, cpm.data(), cpm.size() * 4, hipMemcpyHostToDevice));
+  OPENBUF(c->tab.d_cp, cp.size()); OPENCHK(hipMemcpy(c->tab.d_cp, cp.data(), cp.size() * 4, hipMemcpyHostToDevice));
+  OPENBUF(c->tab.d_cpm, cpm.size()); OPENCHK(hipMemcpy(c->tab.d_cpm, cpm.data(), cpm.size() * 4, hipMemcpyHostToDevice));
 
   // ---- state
-  OPENCHK(hipMalloc(&c->d_heap, (size_t)c->nq * (c->k + 1) * HEAP_ENTRY * sizeof(int)));
-  OPENCHK(hipMalloc(&c->d_n, (size_t)c->nq * sizeof(int)));
-  OPENCHK(hipMalloc(&c->d_T, (size_t)c->nq * sizeof(int)));
-  OPENCHK(hipMalloc(&c->d_snap, sizeof(int)));
-  OPENCHK(hipMalloc(&c->d_err, sizeof(int)));
-  OPENCHK(hipMemset(c->d_err, 0, sizeof(int)));
+  OPENBUF(c->state.d_heap, (size_t)c->nq * (c->k + 1) * HEAP_ENTRY);
+  OPENBUF(c->state.d_n, (size_t)c->nq);
+  OPENBUF(c->state.d_T, (size_t)c->nq);
+  OPENBUF(c->state.d_snap, 1);
+  OPENBUF(c->state.d_err, 1);
+  OPENCHK(hipMemset(c->state.d_err, 0, sizeof(int)));
   // ---- batch buffers
   // (the buffers of a streamed batch -- packed tiles, their derived planes, side rows: 25 KB per reference of max_pool -- are allocated
   // by the first call that streams sequences in: ensure_batch_buffers)
   SliceBuf &b0 = c->slice[0];      // (the push path works in it: sized for a pool)
-  if (!c->fullscan) { OPENCHK(hipMalloc(&b0.cnt, (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t))); b0.cap = (size_t)c->nq_pad * c->pool_pad; }
+  if (!c->fullscan) OPENBUF(b0.cnt, (size_t)c->nq_pad * c->pool_pad);
   if (c->use_ext) {
-    OPENCHK(hipMalloc(&b0.ext, (size_t)c->nq_pad * c->pool_pad * sizeof(uint32_t)));
-    OPENCHK(hipMalloc(&b0.tb8, (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(uint4)));
-    OPENCHK(hipMalloc(&b0.rtp, c->pool_pad * sizeof(uint32_t)));
+    OPENBUF(b0.ext, (size_t)c->nq_pad * c->pool_pad);
+    OPENBUF(b0.tb8, (size_t)c->nq_pad * (c->pool_pad / 64));
+    OPENBUF(b0.rtp, c->pool_pad);
     OPENCHK(hipMemset(b0.rtp, 0, c->pool_pad * sizeof(uint32_t)));
     const size_t l3 = replay3_lds_bytes(c);
-    if (l3 > 160 * 1024) { uvaia_gpu_close(c); return fail(nullptr, UVAIA_GPU_EINVAL, "nbest=%d does not fit the LDS of the replay next to its staging buffers", heap_size); }
     // (every instantiation launch_replay can launch with more than the default dynamic LDS: here and below)
 #define BIGLDS(K, N) OPENCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(&K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(N)))
     BIGLDS((replay3_kernel<true, 32>), l3); BIGLDS((replay3_kernel<false, 32>), l3); BIGLDS((replay3_kernel<true, 16>), l3);
     BIGLDS((replay3_kernel<false, 16>), l3); BIGLDS((replay3_kernel<true, 8>), l3); BIGLDS((replay3_kernel<false, 8>), l3);
   }
-  OPENCHK(hipMalloc(&b0.tmin, (size_t)c->nq_pad * (c->pool_pad / 64) * sizeof(int2)));
-  OPENCHK(hipMalloc(&b0.rt, c->pool_pad * sizeof(int4)));
+  OPENBUF(b0.tmin, (size_t)c->nq_pad * (c->pool_pad / 64));
+  OPENBUF(b0.rt, c->pool_pad);
   OPENCHK(hipMemset(b0.rt, 0, c->pool_pad * sizeof(int4)));
-  OPENCHK(hipMalloc(&c->d_stats, 16 * sizeof(unsigned long long)));
-  OPENCHK(hipMemset(c->d_stats, 0, 16 * sizeof(unsigned long long)));
-  OPENCHK(hipMalloc(&c->d_rt, c->pool_pad * sizeof(int4)));
-  OPENCHK(hipMalloc(&c->d_tr, c->pool_pad * sizeof(int4)));
-  OPENCHK(hipMemset(c->d_rt, 0, c->pool_pad * sizeof(int4)));      // stay zero when idx_c is empty (the pre-score is skipped)
-  OPENCHK(hipMemset(c->d_tr, 0, c->pool_pad * sizeof(int4)));
-  OPENCHK(hipMalloc(&c->d_entered, c->pool_pad)); c->entered_cap = c->pool_pad;
-  OPENCHK(hipMemset(c->d_entered, 0, c->pool_pad));
+  OPENBUF(c->stats.d_stats, 16);
+  OPENCHK(hipMemset(c->stats.d_stats, 0, 16 * sizeof(unsigned long long)));
+  OPENBUF(c->state.d_rt, c->pool_pad);
+  OPENBUF(c->state.d_tr, c->pool_pad);
+  OPENCHK(hipMemset(c->state.d_rt, 0, c->pool_pad * sizeof(int4)));      // stay zero when idx_c is empty (the pre-score is skipped)
+  OPENCHK(hipMemset(c->state.d_tr, 0, c->pool_pad * sizeof(int4)));
+  OPENBUF(c->state.d_entered, c->pool_pad);
+  OPENCHK(hipMemset(c->state.d_entered, 0, c->pool_pad));
   const size_t lds = (size_t)(c->k + 1) * HEAP_ENTRY * sizeof(int) + 128;      // heap + the listed-words bitmap of replay2_kernel
   if (lds > 64 * 1024) {
     BIGLDS(replay_kernel<true>, lds); BIGLDS(replay_kernel<false>, lds);
@@ -226,6 +204,7 @@ int uvaia_gpu_open_tuned(uvaia_gpu_ctx **out, const uvaia_gpu_query *q, int heap
 #undef BIGHEAP
   }
 #undef BIGLDS
+#undef OPENBUF
 #undef OPENCHK
   int rc = uvaia_gpu_reset(c);
   if (rc) { g_open_error = c->err; uvaia_gpu_close(c); return rc; }
@@ -237,16 +216,16 @@ int uvaia_gpu_export_query_table(uvaia_gpu_ctx *c, int which, void *out, size_t 
 {
   if (!c || !n_bytes || which < 0 || which > 10) return UVAIA_GPU_EINVAL;
   if (which == 10) {
-    const int v[11] = {c->NP, c->NR, c->NP4, c->NR4, c->rare_max, c->scan_variant, c->need_e_groups, c->need_v_groups, c->need_g_groups, c->need_r_groups, c->replay_lq};
+    const int v[11] = {c->tab.NP, c->tab.NR, c->tab.NP4, c->tab.NR4, c->tab.rare_max, c->scan_variant, c->tab.need_e_groups, c->tab.need_v_groups, c->tab.need_g_groups, c->tab.need_r_groups, c->replay_lq};
     *n_bytes = sizeof v;
     if (out && cap >= sizeof v) memcpy(out, v, sizeof v);
     return UVAIA_GPU_OK;
   }
-  *n_bytes = c->qtab[which].p ? c->qtab[which].n : 0;
+  *n_bytes = c->tab.qtab[which].p ? c->tab.qtab[which].n : 0;
   if (out && *n_bytes && cap >= *n_bytes) {
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out, c->qtab[which].p, *n_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipStreamSynchronize(c->st.stream));
+    HIPCHK(c, hipMemcpy(out, c->tab.qtab[which].p, *n_bytes, hipMemcpyDeviceToHost));
   }
   return UVAIA_GPU_OK;
 }
@@ -260,12 +239,12 @@ int uvaia_gpu_reset(uvaia_gpu_ctx *c)
   // `stream` (uvaia_gpu_slice_replay_range) -- and what the host reads (uvaia_gpu_drain, uvaia_gpu_entered_flags) waits for `stream` first.
   // The scans hold no such state: a step's first scan is issued while this kernel runs.
   const size_t heap16 = (size_t)c->nq * (c->k + 1) * HEAP_ENTRY * sizeof(int) / 16;
-  const size_t ent = (c->d_entered && c->db_n) ? std::min(c->entered_cap / 64 * 64, ((c->db_n + 63) / 64) * 64) : 0;
+  const size_t ent = (c->state.d_entered && c->db_n) ? std::min(c->state.d_entered.cap / 64 * 64, ((c->db_n + 63) / 64) * 64) : 0;
   const size_t work = std::max(std::max(heap16, ent / 16), (size_t)c->nq);
-  hipLaunchKernelGGL(reset_state_kernel, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, c->stream,
-                     reinterpret_cast<uint4 *>(c->d_heap), heap16, c->d_T, c->d_n, c->nq, c->nchar, c->d_snap, reinterpret_cast<uint4 *>(c->d_entered), ent / 16);
+  hipLaunchKernelGGL(reset_state_kernel, dim3((unsigned)std::min<size_t>(1024, (work + 255) / 256)), dim3(256), 0, c->st.stream,
+                     reinterpret_cast<uint4 *>(c->state.d_heap.p), heap16, c->state.d_T, c->state.d_n, c->nq, c->nchar, c->state.d_snap, reinterpret_cast<uint4 *>(c->state.d_entered.p), ent / 16);
   HIPCHK(c, hipGetLastError());
-  c->entered_clean = ent;
+  c->state.entered_clean = ent;
   return 0;
 }
 
@@ -277,19 +256,19 @@ size_t uvaia_gpu_scan_bytes_per_ref(const uvaia_gpu_ctx *c)
   // some query tile needs (groups where every query is clean are never loaded) + three planes of the gathered polymorphic columns
   if (!c) return 0;
   return (c->fullscan || c->scan_variant != 2) ? (size_t)c->W4 * 16 * c->P
-                                                : (size_t)(c->need_e_groups + c->need_v_groups) * 16 + (size_t)c->need_g_groups * 4 + (size_t)(c->NP4 + c->need_r_groups) * 16 * 3;
+                                                : (size_t)(c->tab.need_e_groups + c->tab.need_v_groups) * 16 + (size_t)c->tab.need_g_groups * 4 + (size_t)(c->tab.NP4 + c->tab.need_r_groups) * 16 * 3;
 }
 
 int uvaia_gpu_scan_variant(const uvaia_gpu_ctx *c)
 { // which pair scan this context runs: 2 column-compressed (scan3_kernel), 0 two counters over the packed planes (scan2_*_kernel;
-  // default for at most 16 queries), -1 four counters (alignments above 49 000 columns)
+  // default for at most 32 queries), -1 four counters (alignments above 49 000 columns)
   return !c ? -2 : c->fullscan ? -1 : c->scan_variant;
 }
 
 size_t uvaia_gpu_derived_bytes_per_ref(const uvaia_gpu_ctx *c)
 { // bytes per reference uvaia_gpu_db_rederive writes for the open query set (E, group counts, gathered columns, total)
   if (!c || c->fullscan || c->scan_variant != 2) return 0;
-  return (size_t)c->W4 * 16 + (size_t)c->W4 * 4 + (size_t)(c->NP4 + c->NR4) * 48 + 4;   // E, grp, gathered planes, total; V is written once by the appends
+  return (size_t)c->W4 * 16 + (size_t)c->W4 * 4 + (size_t)(c->tab.NP4 + c->tab.NR4) * 48 + 4;   // E, grp, gathered planes, total; V is written once by the appends
 }
 
 int uvaia_gpu_set_query_tile(uvaia_gpu_ctx *c, int qt)

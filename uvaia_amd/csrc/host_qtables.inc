@@ -22,8 +22,8 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
       return fail(nullptr, UVAIA_GPU_EALPHABET, "query %d holds byte 0x%02x outside the supported alphabet", i, bad_byte[(size_t)i]);
     }
   }
-  OPENCHK(hipMalloc(&c->d_qp, qp.size() * 4)); OPENCHK(hipMemcpy(c->d_qp, qp.data(), qp.size() * 4, hipMemcpyHostToDevice));
-  c->qtab[0] = {c->d_qp, qp.size() * 4};
+  if (int rc_ = c->tab.d_qp.reserve(nullptr, qp.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_qp, qp.data(), qp.size() * 4, hipMemcpyHostToDevice));
+  c->tab.qtab[0] = {c->tab.d_qp, qp.size() * 4};
   {  // recoded planes and ambiguity-word lists for the two-counter path
     std::vector<int> ambq((size_t)c->nq * AMB_STRIDE, 0);
     if (!c->acgt) {
@@ -36,8 +36,8 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
         d4[0] = (s6[1] | s6[3]) & one; d4[1] = (s6[2] | s6[3]) & one; d4[2] = one; d4[3] = s6[4];
         if (s6[4] & ~one) { int &cnt = ambq[(size_t)i * AMB_STRIDE]; if (cnt < AMB_CAP) ambq[(size_t)i * AMB_STRIDE + 1 + cnt] = w; cnt++; }
       } });
-      OPENCHK(hipMalloc(&c->d_qp2, qp2.size() * 4)); OPENCHK(hipMemcpy(c->d_qp2, qp2.data(), qp2.size() * 4, hipMemcpyHostToDevice));
-      c->qtab[1] = {c->d_qp2, qp2.size() * 4};
+      if (int rc_ = c->tab.d_qp2.reserve(nullptr, qp2.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_qp2, qp2.data(), qp2.size() * 4, hipMemcpyHostToDevice));
+      c->tab.qtab[1] = {c->tab.d_qp2, qp2.size() * 4};
     }
     {  // column classes and compressed/dirty query planes for scan3_kernel
       const int Wp = c->W4 * 4;
@@ -63,10 +63,10 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
       // sparse item on the gathered planes of the rare columns.  Dense work remains for the truly polymorphic columns only.
       std::vector<uint32_t> rmask((size_t)Wp, 0u);
       {
-        c->rare_max = tn.rare_max > 0 ? tn.rare_max : tn.rare_max < 0 ? 0 : (c->nq < 64 ? 0 : std::min(64, std::max(4, c->nq / 64)));
-        if (c->fullscan || c->scan_variant != 2) c->rare_max = 0;
+        c->tab.rare_max = tn.rare_max > 0 ? tn.rare_max : tn.rare_max < 0 ? 0 : (c->nq < 64 ? 0 : std::min(64, std::max(4, c->nq / 64)));
+        if (c->fullscan || c->scan_variant != 2) c->tab.rare_max = 0;
       }
-      if (c->rare_max > 0) {
+      if (c->tab.rare_max > 0) {
         parallel_for(Wp, [&](int w) {
           const uint32_t pm = cls[(size_t)w * 4 + 3];
           if (!pm) return;
@@ -79,7 +79,7 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
             const int b = __builtin_ctz(m);
             int major = 0, total = 0;
             for (int k = 0; k < 4; k++) { total += cnt[(size_t)b * 4 + k]; if (cnt[(size_t)b * 4 + k] > cnt[(size_t)b * 4 + major]) major = k; }
-            if (total - cnt[(size_t)b * 4 + major] > c->rare_max) continue;
+            if (total - cnt[(size_t)b * 4 + major] > c->tab.rare_max) continue;
             const uint32_t bit = 1u << b;
             cls[(size_t)w * 4 + 0] = (cls[(size_t)w * 4 + 0] & ~bit) | ((major & 1) ? bit : 0u);
             cls[(size_t)w * 4 + 1] = (cls[(size_t)w * 4 + 1] & ~bit) | ((major & 2) ? bit : 0u);
@@ -87,16 +87,16 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
           }
         });
       }
-      for (int w = 0; w < Wp; w++) { c->NP += __builtin_popcount(cls[(size_t)w * 4 + 3]); c->NR += __builtin_popcount(rmask[(size_t)w]); }
-      c->NP4 = ((c->NP + 31) / 32 + 3) / 4;
-      c->NR4 = ((c->NR + 31) / 32 + 3) / 4;
+      for (int w = 0; w < Wp; w++) { c->tab.NP += __builtin_popcount(cls[(size_t)w * 4 + 3]); c->tab.NR += __builtin_popcount(rmask[(size_t)w]); }
+      c->tab.NP4 = ((c->tab.NP + 31) / 32 + 3) / 4;
+      c->tab.NR4 = ((c->tab.NR + 31) / 32 + 3) / 4;
       // the compressed scan keeps a pair's deficit in 16 bits around SCAN3_BIAS: what the polymorphic and the rare columns can take away
       // has to stay below it (16 000 such columns of at most 49 000: no SARS-CoV-2 query set comes near); else the packed-plane scan
-      if (c->scan_variant == 2 && (size_t)c->NP4 * 128 + (size_t)c->NR4 * 128 > SCAN3_BIAS - 256) c->scan_variant = 0;
+      if (c->scan_variant == 2 && (size_t)c->tab.NP4 * 128 + (size_t)c->tab.NR4 * 128 > SCAN3_BIAS - 256) c->scan_variant = 0;
       struct RareWord { int word; uint32_t m, l, h; };                  // one query's minority sites in one compressed word of the rare columns
       std::vector<std::vector<RareWord>> rare_q((size_t)c->nq_pad);
-      std::vector<uint32_t> qrare((size_t)c->nq * std::max(c->NR4, 1) * 12, 0u);
-      const size_t prow = (size_t)std::max(c->NP4, 1) * 16, crow = (size_t)c->W4 * 8;
+      std::vector<uint32_t> qrare((size_t)c->nq * std::max(c->tab.NR4, 1) * 12, 0u);
+      const size_t prow = (size_t)std::max(c->tab.NP4, 1) * 16, crow = (size_t)c->W4 * 8;
       std::vector<uint32_t> qpl((size_t)c->nq_pad * prow, 0u), qcv((size_t)c->nq_pad * crow, 0u), flg((size_t)(c->nq_pad / 16) * c->W4 * 2, 0u);
       parallel_for(c->nq_pad / 16, [&](int tile_) { for (int i = tile_ * 16; i < tile_ * 16 + 16; i++) {   // a tile's 16 queries share flag words
         int k = 0, kr = 0;                                           // compressed bit position among the dense / the rare columns
@@ -114,7 +114,7 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
           const uint32_t nI = ~eqb & cls[(size_t)w * 4 + 2], nV = ~qV;
           for (uint32_t m = rmask[(size_t)w]; m; m &= m - 1, kr++) {
             const int b = __builtin_ctz(m);
-            if (real) { uint32_t *d = qrare.data() + ((size_t)i * c->NR4 * 4 + (size_t)(kr >> 5)) * 3;
+            if (real) { uint32_t *d = qrare.data() + ((size_t)i * c->tab.NR4 * 4 + (size_t)(kr >> 5)) * 3;
                         d[0] |= ((qL >> b) & 1u) << (kr & 31); d[1] |= ((qH >> b) & 1u) << (kr & 31); d[2] |= ((qI >> b) & 1u) << (kr & 31); }
             if (!real || !((qI >> b) & 1u) || ((eqb >> b) & 1u)) continue;          // only ACGT queries that differ from the majority
             if (rare_q[(size_t)i].empty() || rare_q[(size_t)i].back().word != (kr >> 5)) rare_q[(size_t)i].push_back({kr >> 5, 0u, 0u, 0u});
@@ -134,23 +134,23 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
         uint32_t u = 0;
         uint32_t uy = 0;
         for (int t = 0; t < c->nq_pad / 16; t++) { u |= flg[((size_t)t * c->W4 + g) * 2]; uy |= flg[((size_t)t * c->W4 + g) * 2 + 1]; }
-        c->need_e_groups += (u & 0xFFFFu) != 0; c->need_v_groups += (u >> 16) != 0; c->need_g_groups += uy != 0;
+        c->tab.need_e_groups += (u & 0xFFFFu) != 0; c->tab.need_v_groups += (u >> 16) != 0; c->tab.need_g_groups += uy != 0;
       }
       // Next to a running scan (8 blocks x 16.9 KB of LDS per CU) a replay block with the 22 KB query row fits once per CU, without
       // it seven times: with many queries the replay then waits for LDS, not for work (5.48 -> 5.04 ms per config[1] search).
       if (c->replay_lq < 0) c->replay_lq = (c->nq < 256) ? 1 : 0;
-      OPENCHK(hipMalloc(&c->d_cls, cls.size() * 4)); OPENCHK(hipMemcpy(c->d_cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
-      OPENCHK(hipMalloc(&c->d_qrare, qrare.size() * 4)); OPENCHK(hipMemcpy(c->d_qrare, qrare.data(), qrare.size() * 4, hipMemcpyHostToDevice));
-      OPENCHK(hipMalloc(&c->d_rmask, rmask.size() * 4)); OPENCHK(hipMemcpy(c->d_rmask, rmask.data(), rmask.size() * 4, hipMemcpyHostToDevice));
-      c->qtab[3] = {c->d_cls, cls.size() * 4}; c->qtab[4] = {c->d_rmask, rmask.size() * 4}; c->qtab[6] = {c->d_qrare, qrare.size() * 4};
+      if (int rc_ = c->tab.d_cls.reserve(nullptr, cls.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_cls, cls.data(), cls.size() * 4, hipMemcpyHostToDevice));
+      if (int rc_ = c->tab.d_qrare.reserve(nullptr, qrare.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_qrare, qrare.data(), qrare.size() * 4, hipMemcpyHostToDevice));
+      if (int rc_ = c->tab.d_rmask.reserve(nullptr, rmask.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_rmask, rmask.data(), rmask.size() * 4, hipMemcpyHostToDevice));
+      c->tab.qtab[3] = {c->tab.d_cls, cls.size() * 4}; c->tab.qtab[4] = {c->tab.d_rmask, rmask.size() * 4}; c->tab.qtab[6] = {c->tab.d_qrare, qrare.size() * 4};
       {   // derive_all_kernel: word groups per wave and the bit positions its gathered columns start at
         int split[DERIVE_SPLIT_INTS];
         build_derive_split(cls.data(), rmask.data(), c->W4, split);
-        OPENCHK(hipMalloc(&c->d_split, sizeof split)); OPENCHK(hipMemcpy(c->d_split, split, sizeof split, hipMemcpyHostToDevice));
-        c->qtab[9] = {c->d_split, sizeof split};
+        if (int rc_ = c->tab.d_split.reserve(nullptr, DERIVE_SPLIT_INTS)) return rc_; OPENCHK(hipMemcpy(c->tab.d_split, split, sizeof split, hipMemcpyHostToDevice));
+        c->tab.qtab[9] = {c->tab.d_split, sizeof split};
       }
-      OPENCHK(hipMalloc(&c->d_qpl, qpl.size() * 4)); OPENCHK(hipMemcpy(c->d_qpl, qpl.data(), qpl.size() * 4, hipMemcpyHostToDevice));
-      c->qtab[5] = {c->d_qpl, qpl.size() * 4};
+      if (int rc_ = c->tab.d_qpl.reserve(nullptr, qpl.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_qpl, qpl.data(), qpl.size() * 4, hipMemcpyHostToDevice));
+      c->tab.qtab[5] = {c->tab.d_qpl, qpl.size() * 4};
       // the item stream of every query tile (layout: see scan3_kernel)
       const int NWs = c->scan_NW, QS = 64;
       const uint32_t row_b = 256u * (uint32_t)c->scan_R;      // bytes of a query's counter row in a wave's LDS block: 64 lanes x R tiles x 4
@@ -159,7 +159,7 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
       struct TileStream { std::vector<uint32_t> u; std::vector<Rec> rec, rare; };
       const int n_st = c->nq_pad / QS;
       std::vector<TileStream> ts((size_t)n_st);
-      std::vector<uint8_t> rare_groups_needed((size_t)std::max(c->NR4, 1), 0);
+      std::vector<uint8_t> rare_groups_needed((size_t)std::max(c->tab.NR4, 1), 0);
       parallel_for(n_st, [&](int st) {
         TileStream &S = ts[(size_t)st];
         std::vector<uint32_t> &strm = S.u;
@@ -217,12 +217,12 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
         strm.push_back(0u); strm.push_back(0u); strm.push_back(0u); strm.push_back(4u);
         // rare records: { byte offset of the rare group's planes in the tile's gathered planes, word-item counts (8 bits each), 0, 0 }
         // + items { sites, their lo bits, their hi bits, LDS offset } listed word by word
-        for (int r4 = 0; r4 < c->NR4; r4++) {
+        for (int r4 = 0; r4 < c->tab.NR4; r4++) {
           uint32_t nw[4] = {0, 0, 0, 0};
           for (int ql = 0; ql < QS; ql++) for (const RareWord &rw : rare_q[(size_t)st * QS + ql]) if ((rw.word >> 2) == r4) nw[rw.word & 3]++;
           if (!(nw[0] | nw[1] | nw[2] | nw[3])) continue;
           S.rare.push_back({strm.size(), nw[0] + nw[1] + nw[2] + nw[3]});
-          strm.push_back((uint32_t)(c->NP4 + r4) * 3072u); strm.push_back(nw[0] | nw[1] << 8 | nw[2] << 16 | nw[3] << 24); strm.push_back(0u); strm.push_back(0u);
+          strm.push_back((uint32_t)(c->tab.NP4 + r4) * 3072u); strm.push_back(nw[0] | nw[1] << 8 | nw[2] << 16 | nw[3] << 24); strm.push_back(0u); strm.push_back(0u);
           for (int j = 0; j < 4; j++)
             for (int ql = 0; ql < QS; ql++) for (const RareWord &rw : rare_q[(size_t)st * QS + ql]) if (rw.word == r4 * 4 + j) {
               strm.push_back(rw.m); strm.push_back(rw.l); strm.push_back(rw.h); strm.push_back((uint32_t)ql * row_b);
@@ -254,14 +254,14 @@ int build_query_tables_host(uvaia_gpu_ctx *c, const uvaia_gpu_query *q, const uv
         split4(S.rare, base, S.u.size() - 8, &sdir[(size_t)st * 4 * NWs + 2 * NWs]);
         strm.insert(strm.end(), S.u.begin(), S.u.end());
       }
-      for (uint8_t u : rare_groups_needed) c->need_r_groups += u;
+      for (uint8_t u : rare_groups_needed) c->tab.need_r_groups += u;
       strm.resize(strm.size() + 64, 0u);                                // the kernel prefetches items and headers past the end
-      OPENCHK(hipMalloc(&c->d_stream, strm.size() * 4)); OPENCHK(hipMemcpy(c->d_stream, strm.data(), strm.size() * 4, hipMemcpyHostToDevice));
-      OPENCHK(hipMalloc(&c->d_sdir, sdir.size() * 4)); OPENCHK(hipMemcpy(c->d_sdir, sdir.data(), sdir.size() * 4, hipMemcpyHostToDevice));
-      c->qtab[7] = {c->d_stream, strm.size() * 4}; c->qtab[8] = {c->d_sdir, sdir.size() * 4};
+      if (int rc_ = c->tab.d_stream.reserve(nullptr, strm.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_stream, strm.data(), strm.size() * 4, hipMemcpyHostToDevice));
+      if (int rc_ = c->tab.d_sdir.reserve(nullptr, sdir.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_sdir, sdir.data(), sdir.size() * 4, hipMemcpyHostToDevice));
+      c->tab.qtab[7] = {c->tab.d_stream, strm.size() * 4}; c->tab.qtab[8] = {c->tab.d_sdir, sdir.size() * 4};
     }
-    OPENCHK(hipMalloc(&c->d_amb_q, ambq.size() * sizeof(int))); OPENCHK(hipMemcpy(c->d_amb_q, ambq.data(), ambq.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->qtab[2] = {c->d_amb_q, ambq.size() * sizeof(int)};
+    if (int rc_ = c->tab.d_amb_q.reserve(nullptr, ambq.size())) return rc_; OPENCHK(hipMemcpy(c->tab.d_amb_q, ambq.data(), ambq.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->tab.qtab[2] = {c->tab.d_amb_q, ambq.size() * sizeof(int)};
   }
   return 0;
 #undef OPENCHK

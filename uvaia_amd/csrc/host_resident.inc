@@ -10,29 +10,14 @@ int uvaia_gpu_db_reserve(uvaia_gpu_ctx *c, size_t cap)
   const size_t tiles = (cap + 63) / 64 + 1;
   // reference shards: everything that is kept per reference -- packed planes, side rows, counts, derived planes -- for the owned pieces
   // only (+ one tile: a piece may end inside the capacity's last tile)
-  const size_t dtiles = derived_tiles(c, tiles) + (c->shard_world > 1 ? 1 : 0);
+  const size_t dtiles = derived_tiles(c, tiles) + (c->shard.world > 1 ? 1 : 0);
   if (int rc = store_alloc(c, c->db, dtiles)) return rc;
   c->db_local_tiles = dtiles;
-  c->peer_db[c->shard_rank] = c->db.planes; c->peer_amb[c->shard_rank] = c->db.amb;
+  c->shard.peer_db[c->shard.rank] = c->db.planes; c->shard.peer_amb[c->shard.rank] = c->db.amb;
   c->db_cap = tiles * 64 - 64;
-  c->entered_clean = 0;
-  if (c->entered_cap < tiles * 64) {
-    hipFree(c->d_entered); c->d_entered = nullptr;
-    HIPCHK(c, hipMalloc(&c->d_entered, tiles * 64)); c->entered_cap = tiles * 64;
-  }
-  HIPCHK(c, hipMemset(c->d_entered, 0, c->entered_cap));
-  return 0;
-}
-
-// side rows of slots slot0 .. slot0 + n_ref - 1 of the resident database in their fixed form (side_rows_canonical_kernel: what an export, and
-// with it a packed database file, holds must not depend on the timing of pack_refs_kernel's waves); returns when it is done
-static int db_canonical_side_rows(uvaia_gpu_ctx *c, long long slot0, int n_ref)
-{
-  if (c->acgt || n_ref <= 0 || !c->db.amb) return 0;
-  const long long t0 = slot0 / 64, t1 = (slot0 + n_ref - 1) / 64;
-  hipLaunchKernelGGL(side_rows_canonical_kernel, dim3((unsigned)(t1 - t0 + 1)), dim3(64), 0, c->stream, c->db.planes, c->W4, t0, slot0, n_ref, c->db.amb);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->state.entered_clean = 0;
+  if (int rc = c->state.d_entered.reserve(c, tiles * 64)) return rc;
+  HIPCHK(c, hipMemset(c->state.d_entered, 0, c->state.d_entered.cap));
   return 0;
 }
 
@@ -41,27 +26,22 @@ static int db_append_common(uvaia_gpu_ctx *c, const char *const *seq, const char
   if (!c) return UVAIA_GPU_EINVAL;
   if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
   if (n_ref == 0) return 0;
-  { int rc = settle_derive(c); if (rc) return rc; }
-  if (c->db_n + (size_t)n_ref > c->db_cap) {
-    if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
-    int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc;
-  }
+  if (int rc = db_make_room(c, (size_t)n_ref)) return rc;
   // reference shards: the caller hands every context the whole stream; a context stages, packs and keeps the references of its own
   // pieces (local slot = local tile * 64 + position in the tile) and only counts the others
   const long long s0 = (long long)c->db_n, s1 = s0 + n_ref;
   for (long long a = s0; a < s1;) {
-    const long long pe = c->shard_world == 1 ? s1 : std::min(s1, (a / (c->shard_pt * 64) + 1) * c->shard_pt * 64);
+    const long long pe = c->shard.world == 1 ? s1 : std::min(s1, (a / (c->shard.pt * 64) + 1) * c->shard.pt * 64);
     if (owns_tile(c, a / 64)) {
       const long long off = a - s0, local = dtile_of(c, a / 64) * 64 + a % 64;
       int rc = pack_rows(c, seq ? seq + off : nullptr, rows ? rows + (size_t)off * pitch : nullptr, pitch, non_n ? non_n + off : nullptr, (int)(pe - a), c->db, local);
       if (rc) return rc;
-      rc = db_canonical_side_rows(c, local, (int)(pe - a));
+      rc = db_canonical_side_rows(c, local, (int)(pe - a), true);
       if (rc) return rc;
     }
     a = pe;
   }
-  c->db_n += (size_t)n_ref;
-  c->win_n = 0;                                        // rows that did not come through the staged calls: no four-plane image covers them
+  db_commit(c, c->db_n + (size_t)n_ref, 0);
   return 0;
 }
 
@@ -69,7 +49,7 @@ int uvaia_gpu_db_skip(uvaia_gpu_ctx *c, size_t n_ref)
 { // the next n_ref references of the stream belong to other ranks' pieces: nothing to keep, the stream position moves on
   if (!c) return UVAIA_GPU_EINVAL;
   if (!n_ref) return 0;
-  if (c->db_n + n_ref > c->db_cap) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
+  if (c->db_n + n_ref > c->db_cap) return db_refuse_full(c);
   for (size_t a = c->db_n; a < c->db_n + n_ref; a = (a / 64 + 1) * 64)
     if (owns_tile(c, (long long)(a / 64))) return fail(c, UVAIA_GPU_EINVAL, "reference %zu belongs to a piece of this context: it cannot be skipped", a);
   c->db_n += n_ref;
@@ -90,17 +70,17 @@ size_t uvaia_gpu_db_size(const uvaia_gpu_ctx *c) { return c ? c->db_n : 0; }
 int uvaia_gpu_db_clear(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  c->win_n = 0;                                        // the four-plane image of a loaded window goes with the rows
+  c->win.n = 0;                                        // the four-plane image of a loaded window goes with the rows
   if (!c->db.planes || !c->db_n) { c->db_n = 0; return 0; }
   { int rc = settle_derive(c); if (rc) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   if (int rc = sync_scan_streams(c)) return rc;
-  const size_t tiles = c->shard_world == 1 ? (c->db_n + 63) / 64 : c->db_local_tiles;       // lanes past the last reference of a tile must read as zero planes
-  HIPCHK(c, hipMemsetAsync(c->db.planes, 0, tiles * (size_t)c->W4 * c->P * 64 * sizeof(uint4), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.nonn, 0, tiles * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.tot, 0, tiles * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.amb, 0, tiles * 64 * AMB_ROW * sizeof(int), c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t tiles = c->shard.world == 1 ? (c->db_n + 63) / 64 : c->db_local_tiles;       // lanes past the last reference of a tile must read as zero planes
+  HIPCHK(c, hipMemsetAsync(c->db.planes, 0, tiles * (size_t)c->W4 * c->P * 64 * sizeof(uint4), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.nonn, 0, tiles * 64 * sizeof(int), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.tot, 0, tiles * 64 * sizeof(int), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.amb, 0, tiles * 64 * AMB_ROW * sizeof(int), c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   c->db_n = 0;
   return 0;
 }
@@ -112,12 +92,12 @@ int uvaia_gpu_db_export(uvaia_gpu_ctx *c, size_t first_tile, size_t n_tiles, voi
 {
   if (!c || !planes || !non_n || !side_rows) return UVAIA_GPU_EINVAL;
   if (c->acgt) return fail(c, UVAIA_GPU_ESTATE, "the interchange form is the four IUPAC planes: export from a default-mode context");
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard holds its own pieces only: export from a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard holds its own pieces only: export from a plain context");
   if ((first_tile + n_tiles) * 64 > ((c->db_n + 63) / 64) * 64) return fail(c, UVAIA_GPU_EINVAL, "tiles %zu..%zu lie outside the database", first_tile, first_tile + n_tiles);
   if (!n_tiles) return 0;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   const size_t tb = uvaia_gpu_db_tile_bytes(c);
-  HIPCHK(c, hipMemcpy(planes, reinterpret_cast<const char *>(c->db.planes) + first_tile * tb, n_tiles * tb, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(planes, reinterpret_cast<const char *>(c->db.planes.p) + first_tile * tb, n_tiles * tb, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(non_n, c->db.nonn + first_tile * 64, n_tiles * 64 * sizeof(int), hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(side_rows, c->db.amb + first_tile * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyDeviceToHost));
   return 0;
@@ -127,12 +107,12 @@ int uvaia_gpu_db_derived_export(uvaia_gpu_ctx *c, size_t n_tiles, void *e, uint3
 { // introspection: what derive_all_kernel left for the first n_tiles tiles, after any rebuild in flight
   if (!c || !e || !grp || !poly || !tot) return UVAIA_GPU_EINVAL;
   if (c->fullscan || c->scan_variant != 2 || !c->db.ev) return fail(c, UVAIA_GPU_ESTATE, "only the column-compressed scan keeps planes derived for the query set");
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard numbers its derived tiles by piece: read them from a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard numbers its derived tiles by piece: read them from a plain context");
   if (n_tiles * 64 > ((c->db_n + 63) / 64) * 64) return fail(c, UVAIA_GPU_EINVAL, "tiles 0..%zu lie outside the database", n_tiles);
   if (!n_tiles) return 0;
   { int rc = settle_derive(c); if (rc) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t W4 = (size_t)c->W4, NG = (size_t)(c->NP4 + c->NR4);
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  const size_t W4 = (size_t)c->W4, NG = (size_t)(c->tab.NP4 + c->tab.NR4);
   HIPCHK(c, hipMemcpy2D(e, 1024, c->db.ev, 2048, 1024, n_tiles * W4, hipMemcpyDeviceToHost));        // [tile][w4][E, V][64] uint4: the E halves
   HIPCHK(c, hipMemcpy(grp, c->db.grp, n_tiles * W4 * 64 * sizeof(uint32_t), hipMemcpyDeviceToHost));
   if (NG) HIPCHK(c, hipMemcpy(poly, c->db.poly, n_tiles * NG * 3 * 64 * sizeof(uint4), hipMemcpyDeviceToHost));
@@ -147,11 +127,7 @@ int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *
   if (n_ref == 0) return 0;
   if (!planes || !non_n || (!c->acgt && !side_rows)) return fail(c, UVAIA_GPU_EINVAL, "NULL packed arrays");
   if (c->db_n % 64) return fail(c, UVAIA_GPU_ESTATE, "packed tiles can only follow a whole number of tiles (database holds %zu references)", c->db_n);
-  { int rc = settle_derive(c); if (rc) return rc; }
-  if (c->db_n + (size_t)n_ref > c->db_cap) {
-    if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
-    int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc;
-  }
+  if (int rc = db_make_room(c, (size_t)n_ref)) return rc;
   const size_t tb = uvaia_gpu_db_tile_bytes(c), n_tiles_all = ((size_t)n_ref + 63) / 64;
   const long long t0g = (long long)(c->db_n / 64);
   // (reference shards: only the tiles of the context's own pieces are copied in, under their local numbers)
@@ -159,33 +135,27 @@ int uvaia_gpu_db_append_packed(uvaia_gpu_ctx *c, const void *planes, const int *
     const size_t n_tiles = (size_t)nt, off = (size_t)(gt - t0g);
     const char *pl = reinterpret_cast<const char *>(planes) + off * tb;
     if (!c->acgt) {     // same form as the resident planes: straight into place, then the totals
-      HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->db.planes) + (size_t)t0 * tb, pl, n_tiles * tb, hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL((import_tiles_kernel<4>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->db.planes + (size_t)t0 * c->W4 * 4 * 64, c->W4, (uint4 *)nullptr, t0, c->db.tot);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipMemcpyAsync(c->db.amb + (size_t)t0 * 64 * AMB_ROW, side_rows + off * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(c->db.planes.p) + (size_t)t0 * tb, pl, n_tiles * tb, hipMemcpyHostToDevice, c->st.stream));
+      if (int rc = db_import_tiles(c, nullptr, t0, n_tiles)) return rc;
+      HIPCHK(c, hipMemcpyAsync(c->db.amb + (size_t)t0 * 64 * AMB_ROW, side_rows + off * 64 * AMB_ROW, n_tiles * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->st.stream));
     } else {            // re-code through a staging buffer, a few tiles at a time
       const size_t chunk = 64;
-      uint4 *d_tmp = nullptr;
-      HIPCHK(c, hipMalloc(&d_tmp, chunk * tb));
+      DevBuf<uint4> d_tmp;
+      if (int rc = d_tmp.reserve(c, chunk * tb / sizeof(uint4))) return rc;
       for (size_t a = 0; a < n_tiles; a += chunk) {
         const size_t m = std::min(chunk, n_tiles - a);
-        hipError_t e = hipMemcpyAsync(d_tmp, pl + a * tb, m * tb, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) { hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)m), dim3(256), 0, c->stream, d_tmp, c->W4, c->db.planes, t0 + (long long)a, c->db.tot); e = hipGetLastError(); }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { hipFree(d_tmp); return fail(c, UVAIA_GPU_EHIP, "import of packed tiles: %s", hipGetErrorString(e)); }
+        HIPCHK(c, hipMemcpyAsync(d_tmp, pl + a * tb, m * tb, hipMemcpyHostToDevice, c->st.stream));
+        if (int rc = db_import_tiles(c, d_tmp, t0 + (long long)a, m)) return rc;
+        HIPCHK(c, hipStreamSynchronize(c->st.stream));
       }
-      hipFree(d_tmp);
     }
-    HIPCHK(c, hipMemcpyAsync(c->db.nonn + (size_t)t0 * 64, non_n + off * 64, n_tiles * 64 * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb + (size_t)t0 * 64 * AMB_ROW,
-                       c->db.nonn + (size_t)t0 * 64, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->db.nonn + (size_t)t0 * 64, non_n + off * 64, n_tiles * 64 * sizeof(int), hipMemcpyHostToDevice, c->st.stream));
+    if (int rc = db_sanitise_import(c, (size_t)t0 * 64, n_tiles * 64)) return rc;
     return derive_rows(c, c->db, t0 * 64, (int)(n_tiles * 64));
   });
   if (rc) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->db_n += (size_t)n_ref;
-  c->win_n = 0;
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  db_commit(c, c->db_n + (size_t)n_ref, 0);
   return 0;
 }
 
@@ -200,7 +170,7 @@ static std::vector<SubSlice> plan_subslices(const uvaia_gpu_ctx *c, size_t first
   std::vector<SubSlice> subs;
   // with few queries the replay is negligible and small launches only cost: one slice per pool then.  The sub-slice length is
   // tuned for 63 query tiles (1 000 queries); with fewer active tiles (query shards) it grows so that a launch still fills the chip
-  const int nq_act = c->act_q1 - c->act_q0, nqt = (c->act_q1 + 15) / 16 - c->act_q0 / 16;
+  const int nqt = (c->act_q1 + 15) / 16 - c->act_q0 / 16;
   // Pool boundaries act through the snapshot only, and the snapshot only through the consensus counters: without constant-and-
   // complete query columns (n_idx_c == 0) they have no effect at all and the slices are laid over the whole range.
   if (c->n_idx_c == 0) pool = std::max<size_t>(n, 1);
@@ -215,7 +185,6 @@ static std::vector<SubSlice> plan_subslices(const uvaia_gpu_ctx *c, size_t first
   // four slices per pool, none below 65 536 references.
   if (nqt < 4) sub = std::min(pool, std::max<size_t>(65536, ((pool + 3) / 4 + 63) / 64 * 64));
   if (c->subslice_forced) sub = std::min(pool, c->subslice);
-  (void)nq_act;
   for (size_t a = first; a < first + n; a += pool) {
     const size_t pe = std::min(first + n, a + pool);
     if (nqt < HEAD_TAIL_NQT && !c->subslice_forced && pe - a >= 8 * 65536) {
@@ -265,31 +234,31 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
   if (!c->db.planes || !c->db_n || c->fullscan || c->scan_variant != 2) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   std::vector<SubSlice> plan;
-  if (c->shard_world == 1) plan = plan_subslices(c, 0, c->db_n, c->max_pool);
+  if (c->shard.world == 1) plan = plan_subslices(c, 0, c->db_n, c->max_pool);
   else {   // reference shards: the chunks are the context's own pieces, which is what it scans (uvaia_gpu_shard_scan)
-    const size_t piece = (size_t)c->shard_pt * 64;
-    for (size_t a = (size_t)c->shard_rank * piece; a < c->db_n; a += piece * (size_t)c->shard_world) plan.push_back({a, std::min(piece, c->db_n - a), false});
+    const size_t piece = (size_t)c->shard.pt * 64;
+    for (size_t a = (size_t)c->shard.rank * piece; a < c->db_n; a += piece * (size_t)c->shard.world) plan.push_back({a, std::min(piece, c->db_n - a), false});
   }
   // Chunks over several streams are all in flight at once: the rebuild as a whole ends sooner, its FIRST chunk -- what the first scan
   // waits for -- later.  That pays for up to three chunks; from four on -- config[1] since its first slice is 70 % of a share, and every
   // long stream -- the rebuild runs in order on one stream (1 M references: 64 queries 9.25 -> 8.65 ms per search, 256 queries 12.7 -> 11.4;
   // config[1], four chunks forced onto 1 / 2 / 3 streams, interleaved three times: 2.951 / 2.959 / 2.992 ms per step).
-  const int n_derive_streams = (c->derive_forced || plan.size() <= 3) ? c->derive_nstreams : 1;
+  const int n_derive_streams = (c->st.derive_forced || plan.size() <= 3) ? c->st.derive_nstreams : 1;
   // Searches still in flight read the planes (and an append may be writing them): the streams the rebuild uses queue behind them.  A
   // stream the host has waited for since the last such work holds nothing to wait for -- after uvaia_gpu_sync none does, and the first
   // chunk below is the call's first runtime call that reaches the device; a busy one is waited for through the event the search left
   // behind its last scan or replay, or through a record of the rebuild's own where there is none.
   {
-    hipStream_t busy[4] = {c->stream, c->scan_streams[0], c->scan_streams[1], c->scan_streams[2]};
+    hipStream_t busy[4] = {c->st.stream, c->st.scan_streams[0], c->st.scan_streams[1], c->st.scan_streams[2]};
     for (int i = 0; i < 4; i++) {
-      if (!busy[i] || !c->planes_busy[i]) continue;
-      hipEvent_t e = c->planes_ev[i];
+      if (!busy[i] || !c->st.planes_busy[i]) continue;
+      hipEvent_t e = c->st.planes_ev[i];
       if (!e) {
-        if (!c->derive_fence[i]) HIPCHK(c, hipEventCreateWithFlags(&c->derive_fence[i], hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->derive_fence[i], busy[i]));
-        planes_fenced(c, busy[i], e = c->derive_fence[i]);
+        if (int rc = c->st.derive_fence[i].make(c, hipEventDisableTiming)) return rc;
+        HIPCHK(c, hipEventRecord(c->st.derive_fence[i], busy[i]));
+        planes_fenced(c, busy[i], e = c->st.derive_fence[i]);
       }
-      for (int j = 0; j < n_derive_streams; j++) HIPCHK(c, hipStreamWaitEvent(c->derive_streams[j], e, 0));
+      for (int j = 0; j < n_derive_streams; j++) HIPCHK(c, hipStreamWaitEvent(c->st.derive_streams[j], e, 0));
     }
   }
   size_t k = 0;
@@ -298,19 +267,18 @@ int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
     const long long t0 = std::max(t_done, (long long)(sl.first / 64)), t1 = (long long)((sl.first + sl.n + 63) / 64);
     if (t0 >= t1) continue;
     t_done = t1;
-    hipStream_t ds = c->derive_streams[k % (size_t)n_derive_streams];
+    hipStream_t ds = c->st.derive_streams[k % (size_t)n_derive_streams];
     int rc = for_owned_tiles(c, t0, t1, [&](long long, long long lt, long long nt) -> int { return derive_rows(c, c->db, lt * 64, (int)(nt * 64), ds, true); });
     if (rc) return rc;
-    if (k == c->derive_chunks.size()) {   // (a chunk's event is made behind its launch: the first launch waits for nothing it does not need)
-      uvaia_gpu_ctx::DeriveChunk d{0, 0, nullptr};
-      HIPCHK(c, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
-      c->derive_chunks.push_back(d);
+    if (k == c->st.derive_chunks.size()) {   // (a chunk's event is made behind its launch: the first launch waits for nothing it does not need)
+      c->st.derive_chunks.emplace_back();
+      if (int rc = c->st.derive_chunks.back().done.make(c, hipEventDisableTiming)) { c->st.derive_chunks.pop_back(); return rc; }
     }
-    c->derive_chunks[k].t0 = t0; c->derive_chunks[k].t1 = t1;
-    HIPCHK(c, hipEventRecord(c->derive_chunks[k].done, ds));
+    c->st.derive_chunks[k].t0 = t0; c->st.derive_chunks[k].t1 = t1;
+    HIPCHK(c, hipEventRecord(c->st.derive_chunks[k].done, ds));
     k++;
   }
-  c->derive_pending = k;
+  c->st.derive_pending = k;
   return 0;
 }
 
@@ -332,8 +300,8 @@ static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs, in
     // (and with the scan-side extras over the column-compressed scan -- tuning.replay_extras = 2, 33-128 queries -- the replays on their own
     // compute units are the chain: scans in order, each done as early as can be; three at a time 5.25 ms of scans + replays per million
     // references at 64 queries, one after the other 4.40.  Without the extras the three streams stand: 7.98 against 8.22 ms per step.)
-    c->scan_nstreams = (waves && waves < 16000 && nqt >= 4 && !c->use_ext) ? 3 : 1;
-    if (c->scan_nstreams_forced) c->scan_nstreams = c->scan_nstreams_forced;
+    c->st.scan_nstreams = (waves && waves < 16000 && nqt >= 4 && !c->use_ext) ? 3 : 1;
+    if (c->st.scan_nstreams_forced) c->st.scan_nstreams = c->st.scan_nstreams_forced;
   }
   for (size_t i = 0; i < ns; i++) {
     const bool serial_ = c->serial;
@@ -344,10 +312,10 @@ static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs, in
       if (serial_) (void)sync_scan_streams(c);
     }
     int take = subs[i].pool_start ? 1 : 0;
-    if (take && snapshot >= 0) { HIPCHK(c, hipMemcpyAsync(c->d_snap, &snapshot, sizeof(int), hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); take = 0; }
+    if (take && snapshot >= 0) { HIPCHK(c, hipMemcpyAsync(c->state.d_snap, &snapshot, sizeof(int), hipMemcpyHostToDevice, c->st.stream)); HIPCHK(c, hipStreamSynchronize(c->st.stream)); take = 0; }
     int rc = uvaia_gpu_slice_replay(c, (int)(i % NBUF), ordinal_of_db0 + (long long)subs[i].first, take);
     if (rc) return rc;
-    if (serial_) hipStreamSynchronize(c->stream);
+    if (serial_) hipStreamSynchronize(c->st.stream);
   }
   return 0;
 }
@@ -355,12 +323,12 @@ static int run_subslices(uvaia_gpu_ctx *c, const std::vector<SubSlice> &subs, in
 int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, uint8_t *entered)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: use uvaia_gpu_shard_scan / uvaia_gpu_shard_replay (or a group)");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: use uvaia_gpu_shard_scan / uvaia_gpu_shard_replay (or a group)");
   if (pool < 1 || pool > c->max_pool) return fail(c, UVAIA_GPU_EINVAL, "pool must be in [1, max_pool=%zu]", c->max_pool);
   if (!c->db_n) return 0;
   // the flags of this search only: cleared here unless uvaia_gpu_reset has just done it (no replay since: launch_replay withdraws the mark)
-  if (c->entered_clean < ((c->db_n + 63) / 64) * 64) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, ((c->db_n + 63) / 64) * 64, c->stream));
-  c->entered_clean = 0;
+  if (c->state.entered_clean < ((c->db_n + 63) / 64) * 64) HIPCHK(c, hipMemsetAsync(c->state.d_entered, 0, ((c->db_n + 63) / 64) * 64, c->st.stream));
+  c->state.entered_clean = 0;
   if (!c->fullscan) {
     int rc = run_subslices(c, plan_subslices(c, 0, c->db_n, pool), ordinal0, -1);
     if (rc) return rc;
@@ -374,8 +342,8 @@ int uvaia_gpu_search_resident(uvaia_gpu_ctx *c, size_t pool, int64_t ordinal0, u
     if (rc) return rc;
   }
   if (entered) {
-    HIPCHK(c, hipMemcpyAsync(entered, c->d_entered, c->db_n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(entered, c->state.d_entered, c->db_n, hipMemcpyDeviceToHost, c->st.stream));
+    HIPCHK(c, hipStreamSynchronize(c->st.stream));
     return collect_events(c);
   }
   return 0;
@@ -393,10 +361,10 @@ int uvaia_gpu_sync(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
   if (int rc = sync_derive_streams(c)) return rc;
-  c->derive_pending = 0;
+  c->st.derive_pending = 0;
   if (int rc = sync_scan_streams(c)) return rc;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->rep_stream) HIPCHK(c, hipStreamSynchronize(c->rep_stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  if (c->st.rep_stream) HIPCHK(c, hipStreamSynchronize(c->st.rep_stream));
   planes_idle(c, true, true);
   return collect_events(c);
 }
@@ -406,23 +374,22 @@ int uvaia_gpu_last_batch_scores(uvaia_gpu_ctx *c, int *out, int n_ref)
   if (!c || !out) return UVAIA_GPU_EINVAL;
   if (n_ref != c->last.n || !c->last.store) return fail(c, UVAIA_GPU_ESTATE, "last batch held %d references, not %d", c->last.n, n_ref);
   const int *nonn = c->last.store->nonn + c->last.tile_first * 64;
-  int *d_out = nullptr;
+  DevBuf<int> d_out;
   const size_t bytes = (size_t)n_ref * c->nq * 6 * sizeof(int);
   if (!c->fullscan) {   // the production path keeps two counters per pair: recount the batch with the four-counter kernel
     int rc = ensure_cnt4(c, (size_t)c->nq_pad * c->last.ppad); if (rc) return rc;
-    const bool prof = c->profile; c->profile = false;
-    rc = launch_scan(c, *c->last.store, c->last.tile_first, c->last.n_tiles, c->d_qp, c->nq, c->d_cnt, c->last.ppad, 0.0);
-    c->profile = prof;
+    const bool prof = c->stats.profile; c->stats.profile = false;
+    rc = launch_scan(c, *c->last.store, c->last.tile_first, c->last.n_tiles, c->tab.d_qp, c->nq, c->state.d_cnt, c->last.ppad, 0.0);
+    c->stats.profile = prof;
     if (rc) return rc;
   }
-  HIPCHK(c, hipMalloc(&d_out, bytes));
+  if (int rc = d_out.reserve(c, bytes / sizeof(int))) return rc;
   dim3 grid((n_ref + 255) / 256, c->nq);
-  if (c->acgt) hipLaunchKernelGGL((batch_scores_kernel<true>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
-  else         hipLaunchKernelGGL((batch_scores_kernel<false>), grid, dim3(256), 0, c->stream, c->d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
+  if (c->acgt) hipLaunchKernelGGL((batch_scores_kernel<true>), grid, dim3(256), 0, c->st.stream, c->state.d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
+  else         hipLaunchKernelGGL((batch_scores_kernel<false>), grid, dim3(256), 0, c->st.stream, c->state.d_cnt, c->last.ppad, c->last.rt, nonn, c->last.rbegin, n_ref, c->nq, d_out);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_out);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->st.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st.stream);
   if (e != hipSuccess) return fail(c, UVAIA_GPU_EHIP, "batch_scores: %s", hipGetErrorString(e));
   return 0;
 }
@@ -431,21 +398,21 @@ int uvaia_gpu_scan_stats(uvaia_gpu_ctx *c, double *ms, long long *launches, doub
 {
   if (!c) return UVAIA_GPU_EINVAL;
   int rc = collect_events(c); if (rc) return rc;
-  if (ms) *ms = c->scan_ms;
-  if (launches) *launches = c->scan_launches;
-  if (bytes) *bytes = c->scan_bytes;
-  if (reset) { c->scan_ms = 0; c->scan_bytes = 0; c->scan_launches = 0; }
+  if (ms) *ms = c->stats.scan_ms;
+  if (launches) *launches = c->stats.scan_launches;
+  if (bytes) *bytes = c->stats.scan_bytes;
+  if (reset) { c->stats.scan_ms = 0; c->stats.scan_bytes = 0; c->stats.scan_launches = 0; }
   return 0;
 }
 
 int uvaia_gpu_replay_stats(uvaia_gpu_ctx *c, unsigned long long out[3], int reset)
 {
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   unsigned long long h[3] = {0, 0, 0};
-  HIPCHK(c, hipMemcpy(h, c->d_stats, sizeof h, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(h, c->stats.d_stats, sizeof h, hipMemcpyDeviceToHost));
   out[0] = h[0]; out[1] = h[1]; out[2] = h[2];
-  if (reset) HIPCHK(c, hipMemset(c->d_stats, 0, sizeof h));
+  if (reset) HIPCHK(c, hipMemset(c->stats.d_stats, 0, sizeof h));
   return 0;
 }
 
@@ -453,20 +420,20 @@ int uvaia_gpu_replay_timing(uvaia_gpu_ctx *c, unsigned long long out[12], int re
 { // diagnostics of an engine built with -DREPLAY_TIMING (zeros otherwise): wall-clock ticks (100 MHz) summed over the replay waves --
   // waiting for staged counters, requesting them, inside opened tiles, of that inside admissions, late fetches, their number, whole waves
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(out, c->d_stats + 4, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (reset) HIPCHK(c, hipMemset(c->d_stats + 4, 0, 12 * sizeof(unsigned long long)));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  HIPCHK(c, hipMemcpy(out, c->stats.d_stats + 4, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (reset) HIPCHK(c, hipMemset(c->stats.d_stats + 4, 0, 12 * sizeof(unsigned long long)));
   return 0;
 }
 
 int uvaia_gpu_replay_tiles_opened(uvaia_gpu_ctx *c, unsigned long long *out, int reset)
 { // (query, tile of 64 references) pairs whose counters the replay of the packed-plane scan looked at since the last reset
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   unsigned long long h3 = 0;
-  HIPCHK(c, hipMemcpy(&h3, c->d_stats + 3, sizeof h3, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&h3, c->stats.d_stats + 3, sizeof h3, hipMemcpyDeviceToHost));
   *out = h3;
-  if (reset) HIPCHK(c, hipMemset(c->d_stats + 3, 0, sizeof h3));
+  if (reset) HIPCHK(c, hipMemset(c->stats.d_stats + 3, 0, sizeof h3));
   return 0;
 }
 
@@ -486,13 +453,13 @@ int uvaia_gpu_state_export_range(uvaia_gpu_ctx *c, void *dst, int q0, int q1)
   if (!c || !dst || q0 < 0 || q1 > c->nq || q1 < q0) return UVAIA_GPU_EINVAL;
   int *d = (int *)dst;
   const size_t nqr = (size_t)(q1 - q0), he = (size_t)(c->k + 1) * HEAP_ENTRY;
-  HIPCHK(c, hipMemcpyAsync(d, c->d_snap, sizeof(int), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(d, c->state.d_snap, sizeof(int), hipMemcpyDefault, c->st.stream));
   if (nqr) {
-    HIPCHK(c, hipMemcpyAsync(d + 4, c->d_n + q0, nqr * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + 4 + nqr, c->d_T + q0, nqr * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d + 4 + 2 * nqr, c->d_heap + (size_t)q0 * he, nqr * he * sizeof(int), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d + 4, c->state.d_n + q0, nqr * sizeof(int), hipMemcpyDefault, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(d + 4 + nqr, c->state.d_T + q0, nqr * sizeof(int), hipMemcpyDefault, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(d + 4 + 2 * nqr, c->state.d_heap + (size_t)q0 * he, nqr * he * sizeof(int), hipMemcpyDefault, c->st.stream));
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   return 0;
 }
 
@@ -501,13 +468,13 @@ int uvaia_gpu_state_import_range(uvaia_gpu_ctx *c, const void *src, int q0, int 
   if (!c || !src || q0 < 0 || q1 > c->nq || q1 < q0) return UVAIA_GPU_EINVAL;
   const int *d = (const int *)src;
   const size_t nqr = (size_t)(q1 - q0), he = (size_t)(c->k + 1) * HEAP_ENTRY;
-  HIPCHK(c, hipMemcpyAsync(c->d_snap, d, sizeof(int), hipMemcpyDefault, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->state.d_snap, d, sizeof(int), hipMemcpyDefault, c->st.stream));
   if (nqr) {
-    HIPCHK(c, hipMemcpyAsync(c->d_n + q0, d + 4, nqr * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_T + q0, d + 4 + nqr, nqr * sizeof(int), hipMemcpyDefault, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_heap + (size_t)q0 * he, d + 4 + 2 * nqr, nqr * he * sizeof(int), hipMemcpyDefault, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->state.d_n + q0, d + 4, nqr * sizeof(int), hipMemcpyDefault, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(c->state.d_T + q0, d + 4 + nqr, nqr * sizeof(int), hipMemcpyDefault, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(c->state.d_heap + (size_t)q0 * he, d + 4 + 2 * nqr, nqr * he * sizeof(int), hipMemcpyDefault, c->st.stream));
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // src may be reused or freed once this returns
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));     // src may be reused or freed once this returns
   return 0;
 }
 
@@ -519,7 +486,7 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
 {
   if (!c || buf < 0 || buf >= NBUF) return UVAIA_GPU_EINVAL;
   if (c->fullscan) return fail(c, UVAIA_GPU_ESTATE, "ring mode needs the two-counter scan");
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: use uvaia_gpu_shard_scan / uvaia_gpu_shard_replay");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: use uvaia_gpu_shard_scan / uvaia_gpu_shard_replay");
   if (first + n > c->db_n) return fail(c, UVAIA_GPU_EINVAL, "slice [%zu,+%zu) outside the database", first, n);
   // a slice is at most a pool when the batch snapshot can matter (n_idx_c > 0); otherwise pools have no effect and slices are free
   if (n > c->max_pool && c->n_idx_c > 0) return fail(c, UVAIA_GPU_EINVAL, "slice of %zu references above max_pool %zu", n, c->max_pool);
@@ -529,10 +496,10 @@ int uvaia_gpu_slice_scan(uvaia_gpu_ctx *c, size_t first, size_t n, int buf)
   const size_t qtile = c->scan_variant == 2 ? 64 : 16;
   const size_t rows = std::min<size_t>((size_t)c->nq_pad, ((size_t)c->act_q1 + qtile - 1) / qtile * qtile);
   if (int rc = slice_reserve(c, b, rows * ppad_, ppad_)) return rc;
-  hipStream_t ss = c->scan_streams[c->scan_nstreams > 1 ? (c->scan_rr++ % c->scan_nstreams) : 0];
+  hipStream_t ss = c->st.scan_streams[c->st.scan_nstreams > 1 ? (c->st.scan_rr++ % c->st.scan_nstreams) : 0];
   if (b.replay_recorded) HIPCHK(c, hipStreamWaitEvent(ss, b.replay_done, 0));   // the buffer's previous reader
-  for (size_t k = 0; k < c->derive_pending; k++) {                                          // planes being rebuilt (uvaia_gpu_db_rederive)
-    const auto &d = c->derive_chunks[k];
+  for (size_t k = 0; k < c->st.derive_pending; k++) {                                          // planes being rebuilt (uvaia_gpu_db_rederive)
+    const auto &d = c->st.derive_chunks[k];
     if (d.t0 < (long long)((first + n + 63) / 64) && d.t1 > (long long)(first / 64)) HIPCHK(c, hipStreamWaitEvent(ss, d.done, 0));
   }
   b.tf = (long long)(first / 64);
@@ -556,26 +523,26 @@ int uvaia_gpu_slice_replay_range(uvaia_gpu_ctx *c, int buf, int64_t ordinal0, in
   SliceBuf &b = c->slice[buf];
   if (!b.scanned) return fail(c, UVAIA_GPU_ESTATE, "slice_replay without slice_scan");
   if (q0 < 0 || q1 > c->nq || q1 < q0) return fail(c, UVAIA_GPU_EINVAL, "bad query range [%d,%d)", q0, q1);
-  if (take_snapshot) { hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T + c->act_q0, c->act_q1 - c->act_q0, c->d_snap); b.cons_done = false; }
+  if (take_snapshot) { hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->st.stream, c->state.d_T + c->act_q0, c->act_q1 - c->act_q0, c->state.d_snap); b.cons_done = false; }
   if (b.re <= b.rb || q1 == q0) return 0;
-  HIPCHK(c, hipStreamWaitEvent(c->stream, b.scan_done, 0));
+  HIPCHK(c, hipStreamWaitEvent(c->st.stream, b.scan_done, 0));
   const int ppad = b.tiles * 64;
   // (packed-plane scan, default mode: the scan left every counter of every pair -- the replay without a round trip per admission)
   const uint32_t *ext = c->use_ext ? b.ext : nullptr;
-  // (the replay's own compute units: the kernel runs on the masked stream, spliced into c->stream's order by two events)
-  hipStream_t rs = (c->rep_stream && ext) ? c->rep_stream : c->stream;
-  if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[0], c->stream)); HIPCHK(c, hipStreamWaitEvent(rs, c->rep_ev[0], 0)); }
+  // (the replay's own compute units: the kernel runs on the masked stream, spliced into c->st.stream's order by two events)
+  hipStream_t rs = (c->st.rep_stream && ext) ? c->st.rep_stream : c->st.stream;
+  if (rs != c->st.stream) { HIPCHK(c, hipEventRecord(c->st.rep_ev[0], c->st.stream)); HIPCHK(c, hipStreamWaitEvent(rs, c->st.rep_ev[0], 0)); }
   // Candidates of a tile whose on-demand counters are requested ahead.  The bookkeeping of the request slots costs more than the
   // latency it hides (measured on one box: config[1] 3.69 / 3.54 / 3.60 ms per step with 3 / 2 / 1, 4 queries x 1 M references
   // 4.37 / 4.03 / 3.89; with 6 or 8 over 7 ms): two for large query sets, one -- request, then use -- for a handful of queries.
   const int pf = (q1 - q0) <= 64 ? 1 : 2;
   int rc = launch_replay(c, {rs, q0, q1, b.cnt, ext, ppad, b.rt, b.rtp, b.tmin, b.tb8,
-                             c->db.planes, b.tf, c->db.nonn + b.tf * 64, c->db.amb + b.tf * 64 * AMB_ROW, c->d_entered + b.tf * 64, b.rb, b.re, (long long)ordinal0,
-                             (c->scan_variant == 2 && c->shard_world == 1) ? c->d_qpl : nullptr, c->db.poly, c->NR4, c->d_qrare, pf});
+                             c->db.planes, b.tf, c->db.nonn + b.tf * 64, c->db.amb + b.tf * 64 * AMB_ROW, c->state.d_entered + b.tf * 64, b.rb, b.re, (long long)ordinal0,
+                             (c->scan_variant == 2 && c->shard.world == 1) ? c->tab.d_qpl : nullptr, c->db.poly, c->tab.NR4, c->tab.d_qrare, pf});
   if (rc) return rc;
-  if (rs != c->stream) { HIPCHK(c, hipEventRecord(c->rep_ev[1], rs)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->rep_ev[1], 0)); }
-  HIPCHK(c, hipEventRecord(b.replay_done, c->stream));
-  planes_fenced(c, c->stream, b.replay_done);
+  if (rs != c->st.stream) { HIPCHK(c, hipEventRecord(c->st.rep_ev[1], rs)); HIPCHK(c, hipStreamWaitEvent(c->st.stream, c->st.rep_ev[1], 0)); }
+  HIPCHK(c, hipEventRecord(b.replay_done, c->st.stream));
+  planes_fenced(c, c->st.stream, b.replay_done);
   b.replay_recorded = true;
   c->last = {&c->db, b.tf, b.tiles, b.re - b.rb, b.rb, ppad, b.rt};
   return 0;
@@ -591,9 +558,9 @@ int uvaia_gpu_set_active_queries(uvaia_gpu_ctx *c, int q0, int q1)
   if (!c) return UVAIA_GPU_EINVAL;
   // (with reference shards the range only selects whose tolerances uvaia_gpu_max_tolerance looks at -- every scan covers all queries --
   // and may start anywhere; a range that is scanned starts at a super-tile of 64 queries)
-  if (q0 < 0 || q1 > c->nq || q1 <= q0 || ((q0 % 64) && c->shard_world == 1))
+  if (q0 < 0 || q1 > c->nq || q1 <= q0 || ((q0 % 64) && c->shard.world == 1))
     return fail(c, UVAIA_GPU_EINVAL, "active queries [%d,%d): need 0 <= q0 < q1 <= %d and q0 a multiple of 64", q0, q1, c->nq);
-  if ((c->fullscan || c->scan_variant != 2) && c->shard_world == 1) { if (q0 != 0 || q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "query shards need the default scan"); }
+  if ((c->fullscan || c->scan_variant != 2) && c->shard.world == 1) { if (q0 != 0 || q1 != c->nq) return fail(c, UVAIA_GPU_ESTATE, "query shards need the default scan"); }
   c->act_q0 = q0; c->act_q1 = q1;
   return 0;
 }
@@ -601,13 +568,12 @@ int uvaia_gpu_set_active_queries(uvaia_gpu_ctx *c, int q0, int q1)
 int uvaia_gpu_max_tolerance(uvaia_gpu_ctx *c, int *out)
 { // max over the active queries of max_incompatible: a rank's contribution to the batch snapshot (src/nearest.c:290-291)
   if (!c || !out) return UVAIA_GPU_EINVAL;
-  int *d_tmp = nullptr;
-  HIPCHK(c, hipMalloc(&d_tmp, sizeof(int)));
-  hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->stream, c->d_T + c->act_q0, c->act_q1 - c->act_q0, d_tmp);
+  DevBuf<int> d_tmp;
+  if (int rc = d_tmp.reserve(c, 1)) return rc;
+  hipLaunchKernelGGL(snapshot_kernel, dim3(1), dim3(256), 0, c->st.stream, c->state.d_T + c->act_q0, c->act_q1 - c->act_q0, d_tmp);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_tmp, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  hipFree(d_tmp);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_tmp, sizeof(int), hipMemcpyDeviceToHost, c->st.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->st.stream);
   if (e != hipSuccess) return fail(c, UVAIA_GPU_EHIP, "max_tolerance: %s", hipGetErrorString(e));
   return 0;
 }
@@ -615,9 +581,9 @@ int uvaia_gpu_max_tolerance(uvaia_gpu_ctx *c, int *out)
 int uvaia_gpu_entered_flags(uvaia_gpu_ctx *c, uint8_t *out, int clear)
 { // "entered any heap" flags of the resident database accumulated by slice replays (and by search_resident)
   if (!c) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (out && c->db_n) HIPCHK(c, hipMemcpy(out, c->d_entered, c->db_n, hipMemcpyDeviceToHost));
-  if (clear && c->db_n) HIPCHK(c, hipMemset(c->d_entered, 0, ((c->db_n + 63) / 64) * 64));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  if (out && c->db_n) HIPCHK(c, hipMemcpy(out, c->state.d_entered, c->db_n, hipMemcpyDeviceToHost));
+  if (clear && c->db_n) HIPCHK(c, hipMemset(c->state.d_entered, 0, ((c->db_n + 63) / 64) * 64));
   return 0;
 }
 

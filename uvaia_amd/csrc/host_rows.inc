@@ -33,21 +33,21 @@ int rows_last_selected(uvaia_gpu_ctx *c, const int *row_index, int n_sel, long l
 
 int rows_upload_selection(uvaia_gpu_ctx *c, const int *row_index, int n_sel)
 {
-  if (c->rsel_cap < (size_t)n_sel) { c->rsel_cap = 0; if (int rc = regrow(c, c->d_rsel, (size_t)n_sel)) return rc; c->rsel_cap = (size_t)n_sel; }
-  HIPCHK(c, hipMemcpyAsync(c->d_rsel, row_index, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (int rc = c->rows.d_sel.reserve(c, (size_t)n_sel)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->rows.d_sel, row_index, (size_t)n_sel * sizeof(int), hipMemcpyHostToDevice, c->st.stream));
   return 0;
 }
 
 // timing of the three kernels: pair i of the event pool brackets one launch, read after the stream has been waited for
-int rows_event_pair(uvaia_gpu_ctx *c, size_t i, hipEvent_t **ev)
+int rows_event_pair(uvaia_gpu_ctx *c, size_t i, Event **ev)
 {
-  while (c->rows_evs.size() < 2 * (i + 1)) { hipEvent_t e; HIPCHK(c, hipEventCreate(&e)); c->rows_evs.push_back(e); }
-  *ev = &c->rows_evs[2 * i];
+  while (c->rows.evs.size() < 2 * (i + 1)) { Event e; if (int rc = e.make(c)) return rc; c->rows.evs.push_back(std::move(e)); }
+  *ev = &c->rows.evs[2 * i];
   return 0;
 }
 int rows_add_ms(uvaia_gpu_ctx *c, int which, size_t n_pairs)
 {
-  for (size_t i = 0; i < n_pairs; i++) { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, c->rows_evs[2 * i], c->rows_evs[2 * i + 1])); c->rows_ms[which] += ms; }
+  for (size_t i = 0; i < n_pairs; i++) { float ms = 0; HIPCHK(c, hipEventElapsedTime(&ms, c->rows.evs[2 * i], c->rows.evs[2 * i + 1])); c->rows.ms[which] += ms; }
   return 0;
 }
 
@@ -63,23 +63,23 @@ int uvaia_gpu_rows_census(uvaia_gpu_ctx *c, const void *d_rows, size_t pitch, in
   HIPCHK(c, hipSetDevice(c->device));
   if (int rc = rows_check_block(c, d_rows, pitch, (long long)n - 1)) return rc;
   const size_t need = 2 * (size_t)n + 1;               // valid sites, records, and the bad-byte flag behind them: one copy back
-  if (c->rcnt_cap < need) { c->rcnt_cap = 0; if (int rc = regrow(c, c->d_rcnt, need)) return rc; c->rcnt_cap = need; }
-  int *d_flag = c->d_rcnt + 2 * (size_t)n;
-  HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
-  hipEvent_t *ev; if (int rc = rows_event_pair(c, 0, &ev)) return rc;
-  HIPCHK(c, hipEventRecord(ev[0], c->stream));
+  if (int rc = c->rows.d_cnt.reserve(c, need)) return rc;
+  int *d_flag = c->rows.d_cnt + 2 * (size_t)n;
+  HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(int), c->st.stream));
+  Event *ev; if (int rc = rows_event_pair(c, 0, &ev)) return rc;
+  HIPCHK(c, hipEventRecord(ev[0], c->st.stream));
   const uint8_t *rows = reinterpret_cast<const uint8_t *>(d_rows);
-  if ((uint32_t)c->nchar > c->run_cut) hipLaunchKernelGGL((rows_census_kernel<true>), dim3((unsigned)n), dim3(ROWS_TPB), 0, c->stream, rows, pitch, c->nchar, c->run_cut, c->d_rcnt, c->d_rcnt + n, d_flag);
-  else                                 hipLaunchKernelGGL((rows_census_kernel<false>), dim3((unsigned)n), dim3(ROWS_TPB), 0, c->stream, rows, pitch, c->nchar, c->run_cut, c->d_rcnt, c->d_rcnt + n, d_flag);
+  if ((uint32_t)c->nchar > c->rows.run_cut) hipLaunchKernelGGL((rows_census_kernel<true>), dim3((unsigned)n), dim3(ROWS_TPB), 0, c->st.stream, rows, pitch, c->nchar, c->rows.run_cut, c->rows.d_cnt, c->rows.d_cnt + n, d_flag);
+  else                                 hipLaunchKernelGGL((rows_census_kernel<false>), dim3((unsigned)n), dim3(ROWS_TPB), 0, c->st.stream, rows, pitch, c->nchar, c->rows.run_cut, c->rows.d_cnt, c->rows.d_cnt + n, d_flag);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev[1], c->stream));
-  c->rows_host.resize(need);
-  HIPCHK(c, hipMemcpyAsync(c->rows_host.data(), c->d_rcnt, need * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipEventRecord(ev[1], c->st.stream));
+  c->rows.host.resize(need);
+  HIPCHK(c, hipMemcpyAsync(c->rows.host.data(), c->rows.d_cnt, need * sizeof(int), hipMemcpyDeviceToHost, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   if (int rc = rows_add_ms(c, 0, 1)) return rc;
-  memcpy(non_n, c->rows_host.data(), (size_t)n * sizeof(int));
-  memcpy(n_exc, c->rows_host.data() + n, (size_t)n * sizeof(int));
-  if (c->rows_host[2 * (size_t)n]) return fail(c, UVAIA_GPU_EALPHABET, "a reference sequence holds a byte outside ACGT / MRWSYKVHDB / NX-?O.");
+  memcpy(non_n, c->rows.host.data(), (size_t)n * sizeof(int));
+  memcpy(n_exc, c->rows.host.data() + n, (size_t)n * sizeof(int));
+  if (c->rows.host[2 * (size_t)n]) return fail(c, UVAIA_GPU_EALPHABET, "a reference sequence holds a byte outside ACGT / MRWSYKVHDB / NX-?O.");
   return 0;
 }
 
@@ -88,16 +88,12 @@ int uvaia_gpu_db_append_device(uvaia_gpu_ctx *c, const void *d_rows, size_t pitc
   if (!c) return UVAIA_GPU_EINVAL;
   if (n_sel < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
   if (n_sel == 0) return 0;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard takes its references from the host (uvaia_gpu_db_append)");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard takes its references from the host (uvaia_gpu_db_append)");
   HIPCHK(c, hipSetDevice(c->device));
   long long last = -1;
   if (int rc = rows_last_selected(c, row_index, n_sel, &last)) return rc;
   if (int rc = rows_check_block(c, d_rows, pitch, last)) return rc;
-  { int rc = settle_derive(c); if (rc) return rc; }
-  if (c->db_n + (size_t)n_sel > c->db_cap) {
-    if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
-    int rc = uvaia_gpu_db_reserve(c, (size_t)n_sel); if (rc) return rc;
-  }
+  if (int rc = db_make_room(c, (size_t)n_sel)) return rc;
   if (row_index) { if (int rc = rows_upload_selection(c, row_index, n_sel)) return rc; }
   const TileStore &s = c->db;
   const uint8_t *rows = reinterpret_cast<const uint8_t *>(d_rows);
@@ -106,36 +102,20 @@ int uvaia_gpu_db_append_device(uvaia_gpu_ctx *c, const void *d_rows, size_t pitc
   for (int done = 0, k = 0; done < n_sel; done += PACK_CHUNK, k ^= 1) {
     const int m = std::min(PACK_CHUNK, n_sel - done);
     uint8_t *ds = c->d_stage + (size_t)k * PACK_CHUNK * c->pitch;
-    hipEvent_t *ev; if (int rc = rows_event_pair(c, pairs, &ev)) return rc;
-    HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)m), dim3(ROWS_TPB), 0, c->stream, rows, pitch, c->nchar, row_index ? c->d_rsel : (const int *)nullptr, done, ds, c->pitch);
+    Event *ev; if (int rc = rows_event_pair(c, pairs, &ev)) return rc;
+    HIPCHK(c, hipEventRecord(ev[0], c->st.stream));
+    hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)m), dim3(ROWS_TPB), 0, c->st.stream, rows, pitch, c->nchar, row_index ? c->rows.d_sel : (const int *)nullptr, done, ds, c->pitch);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(ev[1], c->stream));
+    HIPCHK(c, hipEventRecord(ev[1], c->st.stream));
     pairs++;
-    const long long s0 = (long long)c->db_n + done, t0 = s0 / 64, t1 = (s0 + m - 1) / 64;
-    const int nblk = (int)(t1 - t0 + 1);
-    int *nn_out = non_n ? nullptr : s.nonn;
-    if (c->acgt) hipLaunchKernelGGL((pack_refs_kernel<3>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, s.planes, t0, nn_out, (int *)nullptr, s.tot, c->d_err);
-    else         hipLaunchKernelGGL((pack_refs_kernel<4>), dim3(nblk), dim3(256), 0, c->stream, ds, c->pitch, c->nchar, s0, m, c->W4, s.planes, t0, nn_out, s.amb, s.tot, c->d_err);
-    HIPCHK(c, hipGetLastError());
-    if (non_n) HIPCHK(c, hipMemcpyAsync(s.nonn + s0, non_n + done, (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (int rc = launch_pack_chunk(c, ds, m, s, (long long)c->db_n + done, non_n ? non_n + done : nullptr)) return rc;
   }
-  if (!c->acgt) {                                      // the side rows in their fixed form, as uvaia_gpu_db_append leaves them
-    const long long s0 = (long long)c->db_n, t0 = s0 / 64, t1 = (s0 + n_sel - 1) / 64;
-    hipLaunchKernelGGL(side_rows_canonical_kernel, dim3((unsigned)(t1 - t0 + 1)), dim3(64), 0, c->stream, s.planes, c->W4, t0, s0, n_sel, s.amb);
-    HIPCHK(c, hipGetLastError());
-  }
+  if (int rc = db_canonical_side_rows(c, (long long)c->db_n, n_sel, false)) return rc;      // as uvaia_gpu_db_append leaves them; the wait is the one below
   { int rc = derive_rows(c, s, (long long)c->db_n, n_sel); if (rc) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));          // the caller may overwrite its rows, scans may start on another stream
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));          // the caller may overwrite its rows, scans may start on another stream
   if (int rc = rows_add_ms(c, 1, pairs)) return rc;
-  int bad = 0;
-  HIPCHK(c, hipMemcpy(&bad, c->d_err, sizeof(int), hipMemcpyDeviceToHost));
-  if (bad) {
-    HIPCHK(c, hipMemset(c->d_err, 0, sizeof(int)));
-    return fail(c, UVAIA_GPU_EALPHABET, "a reference sequence holds a byte outside ACGT / MRWSYKVHDB / NX-?O.");
-  }
-  c->db_n += (size_t)n_sel;
-  c->win_n = 0;                                        // (as the other appends that are not the staged ones)
+  if (int rc = take_pack_error(c)) return rc;
+  db_commit(c, c->db_n + (size_t)n_sel, 0);
   return 0;
 }
 
@@ -152,59 +132,59 @@ int uvaia_gpu_rows_exceptions(uvaia_gpu_ctx *c, const void *d_rows, size_t pitch
   if (int rc = rows_last_selected(c, row_index, n_sel, &last)) return rc;
   if (int rc = rows_check_block(c, d_rows, pitch, last)) return rc;
   if (row_index) { if (int rc = rows_upload_selection(c, row_index, n_sel)) return rc; }
-  if (c->roff_cap < (size_t)n_sel + 1) { c->roff_cap = 0; if (int rc = regrow(c, c->d_roff, (size_t)n_sel + 1)) return rc; c->roff_cap = (size_t)n_sel + 1; }
-  HIPCHK(c, hipMemcpyAsync(c->d_roff, offsets, ((size_t)n_sel + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+  if (int rc = c->rows.d_off.reserve(c, (size_t)n_sel + 1)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->rows.d_off, offsets, ((size_t)n_sel + 1) * sizeof(unsigned long long), hipMemcpyHostToDevice, c->st.stream));
   const size_t need = (size_t)total + 1;               // the records, and the flag behind them: one copy back
-  if (c->rexc_cap < need) { c->rexc_cap = 0; if (int rc = regrow(c, c->d_rexc, need)) return rc; c->rexc_cap = need; }
-  int *d_flag = reinterpret_cast<int *>(c->d_rexc + total);
-  HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(uint2), c->stream));
-  hipEvent_t *ev; if (int rc = rows_event_pair(c, 0, &ev)) return rc;
-  HIPCHK(c, hipEventRecord(ev[0], c->stream));
+  if (int rc = c->rows.d_exc.reserve(c, need)) return rc;
+  int *d_flag = reinterpret_cast<int *>(c->rows.d_exc + total);
+  HIPCHK(c, hipMemsetAsync(d_flag, 0, sizeof(uint2), c->st.stream));
+  Event *ev; if (int rc = rows_event_pair(c, 0, &ev)) return rc;
+  HIPCHK(c, hipEventRecord(ev[0], c->st.stream));
   const uint8_t *rows = reinterpret_cast<const uint8_t *>(d_rows);
-  const int *sel = row_index ? c->d_rsel : nullptr;
-  if ((uint32_t)c->nchar > c->run_cut) hipLaunchKernelGGL((rows_fill_exceptions_kernel<true>), dim3((unsigned)n_sel), dim3(ROWS_TPB), 0, c->stream, rows, pitch, c->nchar, c->run_cut, sel, c->d_roff, c->d_rexc, d_flag);
-  else                                 hipLaunchKernelGGL((rows_fill_exceptions_kernel<false>), dim3((unsigned)n_sel), dim3(ROWS_TPB), 0, c->stream, rows, pitch, c->nchar, c->run_cut, sel, c->d_roff, c->d_rexc, d_flag);
+  const int *sel = row_index ? c->rows.d_sel : nullptr;
+  if ((uint32_t)c->nchar > c->rows.run_cut) hipLaunchKernelGGL((rows_fill_exceptions_kernel<true>), dim3((unsigned)n_sel), dim3(ROWS_TPB), 0, c->st.stream, rows, pitch, c->nchar, c->rows.run_cut, sel, c->rows.d_off, c->rows.d_exc, d_flag);
+  else                                 hipLaunchKernelGGL((rows_fill_exceptions_kernel<false>), dim3((unsigned)n_sel), dim3(ROWS_TPB), 0, c->st.stream, rows, pitch, c->nchar, c->rows.run_cut, sel, c->rows.d_off, c->rows.d_exc, d_flag);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(ev[1], c->stream));
-  c->rexc_host.resize((size_t)(total - first) + 1);
-  HIPCHK(c, hipMemcpyAsync(c->rexc_host.data(), c->d_rexc + first, c->rexc_host.size() * sizeof(uint2), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipEventRecord(ev[1], c->st.stream));
+  c->rows.exc_host.resize((size_t)(total - first) + 1);
+  HIPCHK(c, hipMemcpyAsync(c->rows.exc_host.data(), c->rows.d_exc + first, c->rows.exc_host.size() * sizeof(uint2), hipMemcpyDeviceToHost, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   if (int rc = rows_add_ms(c, 2, 1)) return rc;
-  if (c->rexc_host.back().x) return fail(c, UVAIA_GPU_EINVAL, "the offsets do not hold the exception records of these rows (take them from uvaia_gpu_rows_census)");
-  if (total > first) memcpy(reinterpret_cast<char *>(exc_out) + first * sizeof(uint2), c->rexc_host.data(), (size_t)(total - first) * sizeof(uint2));
+  if (c->rows.exc_host.back().x) return fail(c, UVAIA_GPU_EINVAL, "the offsets do not hold the exception records of these rows (take them from uvaia_gpu_rows_census)");
+  if (total > first) memcpy(reinterpret_cast<char *>(exc_out) + first * sizeof(uint2), c->rows.exc_host.data(), (size_t)(total - first) * sizeof(uint2));
   return 0;
 }
 
 int uvaia_gpu_db_drop_tiles(uvaia_gpu_ctx *c, size_t n_tiles)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: tiles are dropped from a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: tiles are dropped from a plain context");
   const size_t have = (c->db_n + 63) / 64;
   if (n_tiles > have) return fail(c, UVAIA_GPU_EINVAL, "%zu tiles to drop, the database holds %zu", n_tiles, have);
   if (n_tiles == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = settle_derive(c); if (rc) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   if (int rc = sync_scan_streams(c)) return rc;
   const size_t rest = c->db_n > n_tiles * 64 ? c->db_n - n_tiles * 64 : 0, rest_tiles = (rest + 63) / 64;
   const size_t pw = (size_t)c->W4 * c->P * 64;         // uint4 per tile
   for (size_t t = 0; t < rest_tiles; t++) {            // towards the front, tile by tile: a copy never overlaps itself
     const size_t f = n_tiles + t;
-    HIPCHK(c, hipMemcpyAsync(c->db.planes + t * pw, c->db.planes + f * pw, pw * sizeof(uint4), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->db.nonn + t * 64, c->db.nonn + f * 64, 64 * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->db.tot + t * 64, c->db.tot + f * 64, 64 * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->db.amb + t * 64 * AMB_ROW, c->db.amb + f * 64 * AMB_ROW, (size_t)64 * AMB_ROW * sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->db.planes + t * pw, c->db.planes + f * pw, pw * sizeof(uint4), hipMemcpyDeviceToDevice, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(c->db.nonn + t * 64, c->db.nonn + f * 64, 64 * sizeof(int), hipMemcpyDeviceToDevice, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(c->db.tot + t * 64, c->db.tot + f * 64, 64 * sizeof(int), hipMemcpyDeviceToDevice, c->st.stream));
+    HIPCHK(c, hipMemcpyAsync(c->db.amb + t * 64 * AMB_ROW, c->db.amb + f * 64 * AMB_ROW, (size_t)64 * AMB_ROW * sizeof(int), hipMemcpyDeviceToDevice, c->st.stream));
   }
   const size_t z = have - rest_tiles;                  // lanes past the last reference must read as zero planes (uvaia_gpu_db_clear)
-  HIPCHK(c, hipMemsetAsync(c->db.planes + rest_tiles * pw, 0, z * pw * sizeof(uint4), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.nonn + rest_tiles * 64, 0, z * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.tot + rest_tiles * 64, 0, z * 64 * sizeof(int), c->stream));
-  HIPCHK(c, hipMemsetAsync(c->db.amb + rest_tiles * 64 * AMB_ROW, 0, z * 64 * AMB_ROW * sizeof(int), c->stream));
-  if (c->d_entered) HIPCHK(c, hipMemsetAsync(c->d_entered, 0, std::min(c->entered_cap, have * 64), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->db.planes + rest_tiles * pw, 0, z * pw * sizeof(uint4), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.nonn + rest_tiles * 64, 0, z * 64 * sizeof(int), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.tot + rest_tiles * 64, 0, z * 64 * sizeof(int), c->st.stream));
+  HIPCHK(c, hipMemsetAsync(c->db.amb + rest_tiles * 64 * AMB_ROW, 0, z * 64 * AMB_ROW * sizeof(int), c->st.stream));
+  if (c->state.d_entered) HIPCHK(c, hipMemsetAsync(c->state.d_entered, 0, std::min(c->state.d_entered.cap, have * 64), c->st.stream));
   c->db_n = rest;
-  c->win_n = 0;                                        // the four-plane image of a window is not moved with the tiles
+  c->win.n = 0;                                        // the four-plane image of a window is not moved with the tiles
   { int rc = derive_rows(c, c->db, 0, (int)rest); if (rc) return rc; }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   return 0;
 }
 
@@ -212,15 +192,15 @@ int uvaia_gpu_rows_set_run_cut(uvaia_gpu_ctx *c, unsigned cut)
 {
   if (!c) return UVAIA_GPU_EINVAL;
   if (cut > ROWS_RUN_CUT) return fail(c, UVAIA_GPU_EINVAL, "a record holds run lengths up to %u", ROWS_RUN_CUT);
-  c->run_cut = cut ? cut : ROWS_RUN_CUT;
+  c->rows.run_cut = cut ? cut : ROWS_RUN_CUT;
   return 0;
 }
 
 void uvaia_gpu_rows_kernel_ms(uvaia_gpu_ctx *c, double out[3], int reset)
 {
   if (!c) return;
-  if (out) for (int i = 0; i < 3; i++) out[i] = c->rows_ms[i];
-  if (reset) c->rows_ms[0] = c->rows_ms[1] = c->rows_ms[2] = 0.;
+  if (out) for (int i = 0; i < 3; i++) out[i] = c->rows.ms[i];
+  if (reset) c->rows.ms[0] = c->rows.ms[1] = c->rows.ms[2] = 0.;
 }
 
 }  // extern "C"

@@ -15,7 +15,7 @@ int uvaia_gpu_db_set_shard(uvaia_gpu_ctx *c, int rank, int world, size_t piece_r
   if (world > 1 && (piece_refs < 64 || piece_refs % 64 || piece_refs > c->max_pool)) return fail(c, UVAIA_GPU_EINVAL, "a piece holds a whole number of tiles of 64 references, at most max_pool = %zu (got %zu)", c->max_pool, piece_refs);
   if (c->db.planes || c->db_n) return fail(c, UVAIA_GPU_ESTATE, "the reference shard is set before the database is reserved");
   if (world > 1 && c->fullscan) return fail(c, UVAIA_GPU_ESTATE, "reference shards need the two-counter scans (alignments up to 49 000 columns)");
-  c->shard_rank = rank; c->shard_world = world; c->shard_pt = world > 1 ? (long long)(piece_refs / 64) : 0;
+  c->shard.rank = rank; c->shard.world = world; c->shard.pt = world > 1 ? (long long)(piece_refs / 64) : 0;
   return 0;
 }
 
@@ -38,12 +38,12 @@ int uvaia_gpu_shard_scan(uvaia_gpu_ctx *c, size_t first, size_t n, void *cnt, vo
   const long long tf = (long long)(first / 64);
   const int n_tiles = (int)((first + n + 63) / 64 - first / 64);
   if ((size_t)n_tiles * 64 > c->pool_pad) return fail(c, UVAIA_GPU_EINVAL, "range of %zu references above max_pool %zu", n, c->max_pool);
-  if (c->shard_world > 1 && (!owns_tile(c, tf) || tf / c->shard_pt != (tf + n_tiles - 1) / c->shard_pt))
+  if (c->shard.world > 1 && (!owns_tile(c, tf) || tf / c->shard.pt != (tf + n_tiles - 1) / c->shard.pt))
     return fail(c, UVAIA_GPU_ESTATE, "references [%zu,+%zu) are not inside one piece of this context's reference shard", first, n);
   const long long ltf = dtile_of(c, tf);            // the context's own number of the piece's first tile
-  hipStream_t ss = c->scan_streams[0];
-  for (size_t k = 0; k < c->derive_pending; k++) {
-    const auto &d = c->derive_chunks[k];
+  hipStream_t ss = c->st.scan_streams[0];
+  for (size_t k = 0; k < c->st.derive_pending; k++) {
+    const auto &d = c->st.derive_chunks[k];
     if (d.t0 < tf + n_tiles && d.t1 > tf) HIPCHK(c, hipStreamWaitEvent(ss, d.done, 0));
   }
   const int rb = (int)(first - (size_t)tf * 64);
@@ -67,7 +67,7 @@ int uvaia_gpu_scan_wait(uvaia_gpu_ctx *c)
 int uvaia_gpu_replay_wait(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   return 0;
 }
 
@@ -79,30 +79,30 @@ int uvaia_gpu_mark(uvaia_gpu_ctx *c, int what, int slot)
 {
   if (!c || slot < 0 || slot >= 8 || (what != UVAIA_GPU_SCANS && what != UVAIA_GPU_REPLAYS)) return c ? fail(c, UVAIA_GPU_EINVAL, "mark: what = scans or replays, slot 0..7") : UVAIA_GPU_EINVAL;
   for (int i = 0; i < 3; i++) {
-    hipEvent_t &e = c->mark_ev[slot][i];
-    hipStream_t st = what == UVAIA_GPU_SCANS ? c->scan_streams[i] : (i == 0 ? c->stream : nullptr);
-    c->mark_set[slot][i] = false;
+    Event &e = c->st.mark_ev[slot][i];
+    hipStream_t st = what == UVAIA_GPU_SCANS ? c->st.scan_streams[i] : (i == 0 ? c->st.stream : nullptr);
+    c->st.mark_set[slot][i] = false;
     if (!st) continue;
-    if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (int rc = e.make(c, hipEventDisableTiming)) return rc;
     HIPCHK(c, hipEventRecord(e, st));
-    c->mark_set[slot][i] = true;
+    c->st.mark_set[slot][i] = true;
   }
   return 0;
 }
 int uvaia_gpu_stream_wait_mark(uvaia_gpu_ctx *c, void *stream, int slot)
 {
   if (!c || slot < 0 || slot >= 8) return c ? fail(c, UVAIA_GPU_EINVAL, "slot 0..7") : UVAIA_GPU_EINVAL;
-  for (int i = 0; i < 3; i++) if (c->mark_set[slot][i]) HIPCHK(c, hipStreamWaitEvent((hipStream_t)stream, c->mark_ev[slot][i], 0));
+  for (int i = 0; i < 3; i++) if (c->st.mark_set[slot][i]) HIPCHK(c, hipStreamWaitEvent((hipStream_t)stream, c->st.mark_ev[slot][i], 0));
   return 0;
 }
 int uvaia_gpu_wait_stream(uvaia_gpu_ctx *c, int what, void *stream)
 {
   if (!c || (what != UVAIA_GPU_SCANS && what != UVAIA_GPU_REPLAYS)) return c ? fail(c, UVAIA_GPU_EINVAL, "wait_stream: what = scans or replays") : UVAIA_GPU_EINVAL;
-  hipEvent_t &e = c->order_ev[c->order_rr++ % 16];
-  if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  Event &e = c->st.order_ev[c->st.order_rr++ % 16];
+  if (int rc = e.make(c, hipEventDisableTiming)) return rc;
   HIPCHK(c, hipEventRecord(e, (hipStream_t)stream));
-  if (what == UVAIA_GPU_REPLAYS) HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
-  else for (int i = 0; i < 3; i++) if (c->scan_streams[i]) HIPCHK(c, hipStreamWaitEvent(c->scan_streams[i], e, 0));
+  if (what == UVAIA_GPU_REPLAYS) HIPCHK(c, hipStreamWaitEvent(c->st.stream, e, 0));
+  else for (int i = 0; i < 3; i++) if (c->st.scan_streams[i]) HIPCHK(c, hipStreamWaitEvent(c->st.scan_streams[i], e, 0));
   return 0;
 }
 
@@ -111,8 +111,8 @@ int uvaia_gpu_wait_stream(uvaia_gpu_ctx *c, int what, void *stream)
 int uvaia_gpu_set_snapshot(uvaia_gpu_ctx *c, int snapshot)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipMemcpyAsync(c->d_snap, &snapshot, sizeof(int), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->state.d_snap, &snapshot, sizeof(int), hipMemcpyHostToDevice, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   return 0;
 }
 
@@ -121,8 +121,8 @@ int uvaia_gpu_set_snapshot(uvaia_gpu_ctx *c, int snapshot)
 // them for the few pairs that reach the exact comparison.
 int uvaia_gpu_shard_set_peer(uvaia_gpu_ctx *c, int rank, const void *planes, const void *side_rows)
 {
-  if (!c || rank < 0 || rank >= 64 || rank >= std::max(1, c->shard_world)) return c ? fail(c, UVAIA_GPU_EINVAL, "rank %d", rank) : UVAIA_GPU_EINVAL;
-  c->peer_db[rank] = (const uint4 *)planes; c->peer_amb[rank] = (const int *)side_rows;
+  if (!c || rank < 0 || rank >= 64 || rank >= std::max(1, c->shard.world)) return c ? fail(c, UVAIA_GPU_EINVAL, "rank %d", rank) : UVAIA_GPU_EINVAL;
+  c->shard.peer_db[rank] = (const uint4 *)planes; c->shard.peer_amb[rank] = (const int *)side_rows;
   return 0;
 }
 const void *uvaia_gpu_shard_planes(const uvaia_gpu_ctx *c) { return c ? c->db.planes : nullptr; }
@@ -140,25 +140,25 @@ int uvaia_gpu_shard_ipc_handles(uvaia_gpu_ctx *c, void *out)
 }
 int uvaia_gpu_shard_ipc_open(uvaia_gpu_ctx *c, int rank, const void *handles)
 { // maps another process's arrays (its uvaia_gpu_shard_ipc_handles) as the source of rank `rank`'s pieces
-  if (!c || !handles || rank < 0 || rank >= 64 || rank >= c->shard_world || rank == c->shard_rank) return c ? fail(c, UVAIA_GPU_EINVAL, "rank %d", rank) : UVAIA_GPU_EINVAL;
+  if (!c || !handles || rank < 0 || rank >= 64 || rank >= c->shard.world || rank == c->shard.rank) return c ? fail(c, UVAIA_GPU_EINVAL, "rank %d", rank) : UVAIA_GPU_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
   hipIpcMemHandle_t h[2];
   memcpy(h, handles, sizeof h);
-  for (int i = 0; i < 2; i++) if (c->ipc_opened[rank][i]) { hipIpcCloseMemHandle(c->ipc_opened[rank][i]); c->ipc_opened[rank][i] = nullptr; }
-  HIPCHK(c, hipIpcOpenMemHandle(&c->ipc_opened[rank][0], h[0], hipIpcMemLazyEnablePeerAccess));
-  HIPCHK(c, hipIpcOpenMemHandle(&c->ipc_opened[rank][1], h[1], hipIpcMemLazyEnablePeerAccess));
-  c->peer_db[rank] = (const uint4 *)c->ipc_opened[rank][0]; c->peer_amb[rank] = (const int *)c->ipc_opened[rank][1];
+  for (int i = 0; i < 2; i++) if (c->shard.ipc_opened[rank][i]) { hipIpcCloseMemHandle(c->shard.ipc_opened[rank][i]); c->shard.ipc_opened[rank][i] = nullptr; }
+  HIPCHK(c, hipIpcOpenMemHandle(&c->shard.ipc_opened[rank][0], h[0], hipIpcMemLazyEnablePeerAccess));
+  HIPCHK(c, hipIpcOpenMemHandle(&c->shard.ipc_opened[rank][1], h[1], hipIpcMemLazyEnablePeerAccess));
+  c->shard.peer_db[rank] = (const uint4 *)c->shard.ipc_opened[rank][0]; c->shard.peer_amb[rank] = (const int *)c->shard.ipc_opened[rank][1];
   return 0;
 }
 
 int uvaia_gpu_shard_ipc_close(uvaia_gpu_ctx *c)
 { // unmaps what uvaia_gpu_shard_ipc_open mapped: before the ranks that own the arrays free them (every rank closes, then a barrier, then the contexts go)
   if (!c) return UVAIA_GPU_EINVAL;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
   for (int r = 0; r < 64; r++) {
     bool any = false;
-    for (int i = 0; i < 2; i++) if (c->ipc_opened[r][i]) { hipIpcCloseMemHandle(c->ipc_opened[r][i]); c->ipc_opened[r][i] = nullptr; any = true; }
-    if (any) { c->peer_db[r] = nullptr; c->peer_amb[r] = nullptr; }
+    for (int i = 0; i < 2; i++) if (c->shard.ipc_opened[r][i]) { hipIpcCloseMemHandle(c->shard.ipc_opened[r][i]); c->shard.ipc_opened[r][i] = nullptr; any = true; }
+    if (any) { c->shard.peer_db[r] = nullptr; c->shard.peer_amb[r] = nullptr; }
   }
   return 0;
 }
@@ -176,21 +176,21 @@ int uvaia_gpu_shard_replay(uvaia_gpu_ctx *c, const void *cnt, const void *tmin, 
   const long long tf = (long long)(first / 64);
   const int n_tiles = (int)((first + n + 63) / 64 - first / 64), ppad = n_tiles * 64;
   if ((size_t)ppad > c->pool_pad) return fail(c, UVAIA_GPU_EINVAL, "range of %zu references above max_pool %zu", n, c->max_pool);
-  if (owner < 0 || owner >= std::max(1, c->shard_world) || (c->shard_world > 1 && (int)((tf / c->shard_pt) % c->shard_world) != owner))
+  if (owner < 0 || owner >= std::max(1, c->shard.world) || (c->shard.world > 1 && (int)((tf / c->shard.pt) % c->shard.world) != owner))
     return fail(c, UVAIA_GPU_EINVAL, "references [%zu,+%zu) are not a piece of rank %d", first, n, owner);
-  if (!c->peer_db[owner] || (!c->acgt && !c->peer_amb[owner])) return fail(c, UVAIA_GPU_ESTATE, "the arrays of rank %d are not known to this context (uvaia_gpu_shard_set_peer / uvaia_gpu_shard_ipc_open)", owner);
+  if (!c->shard.peer_db[owner] || (!c->acgt && !c->shard.peer_amb[owner])) return fail(c, UVAIA_GPU_ESTATE, "the arrays of rank %d are not known to this context (uvaia_gpu_shard_set_peer / uvaia_gpu_shard_ipc_open)", owner);
   const int rb = (int)(first - (size_t)tf * 64), re = rb + (int)n;
   const long long ltf = dtile_of(c, tf);            // the piece's first tile in its owner's numbering
   // the kernel indexes rows by query number: shift the bases so that row q0 is the buffer's first row
   const uint32_t *cntp = (const uint32_t *)cnt - (ptrdiff_t)q0 * ppad;
   const int2 *tminp = (const int2 *)tmin - (ptrdiff_t)q0 * (ppad / 64);
   const int *nonn = (const int *)aux;
-  const int4 *rt = c->n_idx_c > 0 ? (const int4 *)(reinterpret_cast<const char *>(aux) + (size_t)ppad * sizeof(int)) : c->d_rt;
-  const int *amb = c->peer_amb[owner] ? c->peer_amb[owner] + ltf * 64 * AMB_ROW : nullptr;
+  const int4 *rt = c->n_idx_c > 0 ? (const int4 *)(reinterpret_cast<const char *>(aux) + (size_t)ppad * sizeof(int)) : c->state.d_rt;
+  const int *amb = c->shard.peer_amb[owner] ? c->shard.peer_amb[owner] + ltf * 64 * AMB_ROW : nullptr;
   // the owner's packed planes and side rows; no derived planes of another rank: the on-demand counters come from the packed ones
   // (--acgt: dist_unique of the pairs that reach a heap is counted from them too, the scan's per-pair count stays on the scanning rank)
-  return launch_replay(c, {c->stream, q0, q1, cntp, nullptr, ppad, rt, nullptr, tminp, nullptr,
-                           c->peer_db[owner], ltf, nonn, amb, c->d_entered + tf * 64, rb, re, (long long)ordinal0,
+  return launch_replay(c, {c->st.stream, q0, q1, cntp, nullptr, ppad, rt, nullptr, tminp, nullptr,
+                           c->shard.peer_db[owner], ltf, nonn, amb, c->state.d_entered + tf * 64, rb, re, (long long)ordinal0,
                            nullptr, nullptr, 0, nullptr, 3});
 }
 
@@ -416,7 +416,7 @@ int uvaia_gpu_group_search_resident(uvaia_gpu_group *g, size_t pool, int64_t ord
   for (int i = 0; i < g->n; i++) {
     if (uvaia_gpu_db_size(g->ctx[(size_t)i]) != total) return gfail(g, UVAIA_GPU_ESTATE, "members hold different databases");
     GCHK(g, hipSetDevice(g->ctx[(size_t)i]->device));
-    GCHK(g, hipMemsetAsync(g->ctx[(size_t)i]->d_entered, 0, ((total + 63) / 64) * 64, g->ctx[(size_t)i]->stream));
+    GCHK(g, hipMemsetAsync(g->ctx[(size_t)i]->state.d_entered, 0, ((total + 63) / 64) * 64, g->ctx[(size_t)i]->st.stream));
   }
   if (!total) return 0;
   if (!g->cons) pool = total;                          // batches act through the snapshot only (see plan_subslices)
@@ -464,9 +464,9 @@ int uvaia_gpu_group_search_resident(uvaia_gpu_group *g, size_t pool, int64_t ord
           if (pc.owner != i) continue;
           uvaia_gpu_ctx *cx = g->ctx[(size_t)i]; auto &mo = g->m[(size_t)i];
           WCHK(i, hipSetDevice(cx->device));
-          for (int d = 0; d < g->n; d++) if (g->m[(size_t)d].fetched_rec[bsel]) WCHK(i, hipStreamWaitEvent(cx->scan_streams[0], g->m[(size_t)d].fetched[bsel], 0));
+          for (int d = 0; d < g->n; d++) if (g->m[(size_t)d].fetched_rec[bsel]) WCHK(i, hipStreamWaitEvent(cx->st.scan_streams[0], g->m[(size_t)d].fetched[bsel], 0));
           WCTX(i, uvaia_gpu_shard_scan(cx, pc.first, pc.n, mo.send_cnt[bsel], mo.send_tmin[bsel], mo.send_aux[bsel]));
-          WCHK(i, hipEventRecord(mo.scanned[bsel], cx->scan_streams[0]));
+          WCHK(i, hipEventRecord(mo.scanned[bsel], cx->st.scan_streams[0]));
         }
         return 0;
       });
@@ -488,13 +488,13 @@ int uvaia_gpu_group_search_resident(uvaia_gpu_group *g, size_t pool, int64_t ord
           WCHK(d, hipMemcpyPeerAsync(md.recv_aux[bsel] + slot * g->aux_piece, cd->device, mo.send_aux[bsel], g->ctx[(size_t)pc.owner]->device, uvaia_gpu_shard_aux_bytes(cd, tiles), md.copy));
         }
         WCHK(d, hipEventRecord(md.fetched[bsel], md.copy)); md.fetched_rec[bsel] = true;
-        WCHK(d, hipStreamWaitEvent(cd->stream, md.fetched[bsel], 0));
+        WCHK(d, hipStreamWaitEvent(cd->st.stream, md.fetched[bsel], 0));
         for (size_t k = s0; k < s1 && myrows; k++) {
           const Piece &pc = pieces[k]; const size_t slot = k - s0;
           WCTX(d, uvaia_gpu_shard_replay(cd, md.recv_cnt[bsel] + slot * myrows * (g->piece + 64), md.recv_tmin[bsel] + slot * myrows * ((g->piece + 64) / 64),
                                          md.recv_aux[bsel] + slot * g->aux_piece, pc.owner, pc.first, pc.n, ordinal0 + (int64_t)pc.first, g->q0[(size_t)d], g->q1[(size_t)d]));
         }
-        WCHK(d, hipEventRecord(md.replayed[bsel], cd->stream)); md.replayed_rec[bsel] = true;
+        WCHK(d, hipEventRecord(md.replayed[bsel], cd->st.stream)); md.replayed_rec[bsel] = true;
         return 0;
       });
       if (rc) return rc;

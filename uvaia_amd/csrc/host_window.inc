@@ -7,6 +7,9 @@ extern "C" {
 
 static_assert(AMB_ROW == 64, "select_tiles_kernel moves a side row with one wave");
 
+// tiles each of the two staging slots holds room for: slot 1's planes are the last array uvaia_gpu_db_stage_reserve makes
+static size_t stage_tiles(const uvaia_gpu_ctx *c) { return c->win.stage[1].planes.cap / ((size_t)c->W4 * 4 * 64); }
+
 size_t uvaia_gpu_free_bytes(uvaia_gpu_ctx *c)
 {
   if (!c || hipSetDevice(c->device) != hipSuccess) return 0;
@@ -18,27 +21,23 @@ size_t uvaia_gpu_free_bytes(uvaia_gpu_ctx *c)
 int uvaia_gpu_db_stage_reserve(uvaia_gpu_ctx *c, size_t n_tiles)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
   if (n_tiles < 1 || n_tiles > (size_t)(0x7FFFFFFF / 64)) return fail(c, UVAIA_GPU_EINVAL, "staging capacity of %zu tiles", n_tiles);
   HIPCHK(c, hipSetDevice(c->device));
-  if (!c->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-  for (auto &sl : c->wstage) {
-    if (!sl.copied) HIPCHK(c, hipEventCreateWithFlags(&sl.copied, hipEventDisableTiming));
-    if (!sl.read) HIPCHK(c, hipEventCreateWithFlags(&sl.read, hipEventDisableTiming));
+  if (!c->win.copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->win.copy_stream.s, hipStreamNonBlocking));
+  for (auto &sl : c->win.stage) {
+    if (int rc = sl.copied.make(c, hipEventDisableTiming)) return rc;
+    if (int rc = sl.read.make(c, hipEventDisableTiming)) return rc;
   }
-  if (n_tiles <= c->wstage_tiles) return 0;
-  HIPCHK(c, hipStreamSynchronize(c->copy_stream));          // nothing may still use the slots that go
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->wstage_tiles = 0;
-  const size_t tb = uvaia_gpu_db_tile_bytes(c);
-  for (auto &sl : c->wstage) {
-    for (void *p : {(void *)sl.planes, (void *)sl.nonn, (void *)sl.side}) if (p) hipFree(p);
-    sl.planes = nullptr; sl.nonn = nullptr; sl.side = nullptr; sl.n_tiles = 0; sl.read_recorded = false;
-    HIPCHK(c, hipMalloc(&sl.nonn, n_tiles * 64 * sizeof(int)));
-    HIPCHK(c, hipMalloc(&sl.side, n_tiles * 64 * AMB_ROW * sizeof(int)));
-    HIPCHK(c, hipMalloc(&sl.planes, n_tiles * tb));
+  if (n_tiles <= stage_tiles(c)) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->win.copy_stream));          // nothing may still use the slots that go
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  for (auto &sl : c->win.stage) { sl.planes.release(); sl.nonn.release(); sl.side.release(); sl.n_tiles = 0; sl.read_recorded = false; }    // both first: the capacity is slot 1's
+  for (auto &sl : c->win.stage) {
+    if (int rc = sl.nonn.reserve(c, n_tiles * 64)) return rc;
+    if (int rc = sl.side.reserve(c, n_tiles * 64 * AMB_ROW)) return rc;
+    if (int rc = sl.planes.reserve(c, n_tiles * (size_t)c->W4 * 4 * 64)) return rc;
   }
-  c->wstage_tiles = n_tiles;
   return 0;
 }
 
@@ -46,10 +45,10 @@ int uvaia_gpu_db_stage_reserve(uvaia_gpu_ctx *c, size_t n_tiles)
 static int check_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
   if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
   if (n_ref < 0) return fail(c, UVAIA_GPU_EINVAL, "negative count");
-  const long long staged = (long long)c->wstage[slot].n_tiles * 64;
+  const long long staged = (long long)c->win.stage[slot].n_tiles * 64;
   if (n_ref > 0 && !staged) return fail(c, UVAIA_GPU_ESTATE, "staging slot %d holds no tiles: uvaia_gpu_db_stage_packed comes first", slot);
   if (!sel && n_ref > staged) return fail(c, UVAIA_GPU_EINVAL, "%d references asked of the %lld staged in slot %d", n_ref, staged, slot);
   if (sel) for (int k = 0; k < n_ref; k++)
@@ -61,81 +60,73 @@ static int check_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 static int upload_sel(uvaia_gpu_ctx *c, const int *sel, int n_ref)
 {
   if (!sel) return 0;
-  if (c->wsel_cap < (size_t)n_ref) { c->wsel_cap = 0; if (int rc = regrow(c, c->d_wsel, (size_t)n_ref)) return rc; c->wsel_cap = (size_t)n_ref; }
-  HIPCHK(c, hipMemcpyAsync(c->d_wsel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (int rc = c->win.d_sel.reserve(c, (size_t)n_ref)) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->win.d_sel, sel, (size_t)n_ref * sizeof(int), hipMemcpyHostToDevice, c->st.stream));
   return 0;
 }
 
 // the end of a load: the third event, the wait, the device time of the selection and of what followed it
 static int finish_staged(uvaia_gpu_ctx *c)
 {
-  HIPCHK(c, hipEventRecord(c->win_ev[2], c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));     // scans start on other streams: the packed and derived planes must be complete
+  HIPCHK(c, hipEventRecord(c->win.ev[2], c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));     // scans start on other streams: the packed and derived planes must be complete
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, c->win_ev[0], c->win_ev[1]) == hipSuccess) c->win_ms[0] += ms;
-  if (hipEventElapsedTime(&ms, c->win_ev[1], c->win_ev[2]) == hipSuccess) c->win_ms[1] += ms;
+  if (hipEventElapsedTime(&ms, c->win.ev[0], c->win.ev[1]) == hipSuccess) c->win.ms[0] += ms;
+  if (hipEventElapsedTime(&ms, c->win.ev[1], c->win.ev[2]) == hipSuccess) c->win.ms[1] += ms;
   return 0;
 }
 
 int uvaia_gpu_db_load_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 {
   if (int rc = check_staged(c, slot, sel, n_ref)) return rc;
-  auto &sl = c->wstage[slot];
+  auto &sl = c->win.stage[slot];
   HIPCHK(c, hipSetDevice(c->device));
   { int rc = uvaia_gpu_db_clear(c); if (rc) return rc; }
-  c->win_n = 0;
+  c->win.n = 0;
   if (n_ref == 0) return 0;
   if ((size_t)n_ref > c->db_cap) { int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc; }
-  const size_t n_tiles = ((size_t)n_ref + 63) / 64, tile_u4 = (size_t)c->W4 * 4 * 64;
-  if (c->acgt && c->win4_tiles < n_tiles) {       // the four-plane image of a window: as many tiles as the resident store holds
-    const size_t cap = std::max(n_tiles, c->db_cap / 64 + 1);
-    hipFree(c->d_win4); c->d_win4 = nullptr; c->win4_tiles = 0;
-    HIPCHK(c, hipMalloc(&c->d_win4, cap * tile_u4 * sizeof(uint4)));
-    c->win4_tiles = cap;
-  }
+  const size_t n_tiles = ((size_t)n_ref + 63) / 64;
+  bool grown = false;
+  if (int rc = win_image_room(c, n_tiles, &grown)) return rc;
   if (int rc = upload_sel(c, sel, n_ref)) return rc;
-  for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
-  uint4 *four = c->acgt ? c->d_win4 : c->db.planes;
-  HIPCHK(c, hipEventRecord(c->win_ev[0], c->stream));
-  hipLaunchKernelGGL(select_tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->stream, sl.planes, sl.nonn, c->acgt ? (const int *)nullptr : sl.side, sel ? c->d_wsel : (const int *)nullptr, n_ref, c->W4,
+  for (Event &e : c->win.ev) if (int rc = e.make(c)) return rc;
+  HIPCHK(c, hipStreamWaitEvent(c->st.stream, sl.copied, 0));
+  uint4 *four = c->acgt ? c->win.d_four.p : c->db.planes.p;
+  HIPCHK(c, hipEventRecord(c->win.ev[0], c->st.stream));
+  hipLaunchKernelGGL(select_tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c->st.stream, sl.planes, sl.nonn, c->acgt ? (const int *)nullptr : sl.side, sel ? c->win.d_sel : (const int *)nullptr, n_ref, c->W4,
                      four, c->db.nonn, c->acgt ? (int *)nullptr : c->db.amb);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->win_ev[1], c->stream));
-  HIPCHK(c, hipEventRecord(sl.read, c->stream)); sl.read_recorded = true;
+  HIPCHK(c, hipEventRecord(c->win.ev[1], c->st.stream));
+  HIPCHK(c, hipEventRecord(sl.read, c->st.stream)); sl.read_recorded = true;
   // from here on as uvaia_gpu_db_append_packed: re-coding (--acgt) and totals, the checks on what came from outside, the derived planes
-  if (c->acgt) hipLaunchKernelGGL((import_tiles_kernel<3>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->d_win4, c->W4, c->db.planes, 0LL, c->db.tot);
-  else         hipLaunchKernelGGL((import_tiles_kernel<4>), dim3((unsigned)n_tiles), dim3(256), 0, c->stream, c->db.planes, c->W4, (uint4 *)nullptr, 0LL, c->db.tot);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)((n_tiles * 64 + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb, c->db.nonn, (long long)(n_tiles * 64), c->W4 * 4, c->nchar);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = db_import_tiles(c, c->win.d_four, 0, n_tiles)) return rc;
+  if (int rc = db_sanitise_import(c, 0, n_tiles * 64)) return rc;
   { int rc = derive_rows(c, c->db, 0, (int)(n_tiles * 64)); if (rc) return rc; }
   if (int rc = finish_staged(c)) return rc;
-  c->db_n = (size_t)n_ref;
-  c->win_n = n_ref;
+  db_commit(c, (size_t)n_ref, n_ref);
   return 0;
 }
 
 int uvaia_gpu_db_stage_packed_at(uvaia_gpu_ctx *c, int slot, size_t tile_offset, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->shard_world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
   if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
   if (n_tiles < 0 || (n_tiles > 0 && (!planes || !non_n || (!c->acgt && !side_rows)))) return fail(c, UVAIA_GPU_EINVAL, "NULL packed arrays");
-  if (tile_offset > c->wstage_tiles || (size_t)n_tiles > c->wstage_tiles - tile_offset)
-    return fail(c, UVAIA_GPU_ESTATE, "%d tiles at tile %zu exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, tile_offset, c->wstage_tiles);
+  if (tile_offset > stage_tiles(c) || (size_t)n_tiles > stage_tiles(c) - tile_offset)
+    return fail(c, UVAIA_GPU_ESTATE, "%d tiles at tile %zu exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, tile_offset, stage_tiles(c));
   HIPCHK(c, hipSetDevice(c->device));
-  auto &sl = c->wstage[slot];
+  auto &sl = c->win.stage[slot];
   const size_t before = tile_offset ? (size_t)sl.n_tiles : 0;      // a piece at tile 0 starts the slot afresh
   sl.n_tiles = 0;
-  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
+  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->win.copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
   if (n_tiles) {
     const size_t tb = uvaia_gpu_db_tile_bytes(c), nt = (size_t)n_tiles;
-    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(sl.planes) + tile_offset * tb, planes, nt * tb, hipMemcpyHostToDevice, c->copy_stream));
-    HIPCHK(c, hipMemcpyAsync(sl.nonn + tile_offset * 64, non_n, nt * 64 * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
-    if (!c->acgt) HIPCHK(c, hipMemcpyAsync(sl.side + tile_offset * 64 * AMB_ROW, side_rows, nt * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->copy_stream));
+    HIPCHK(c, hipMemcpyAsync(reinterpret_cast<char *>(sl.planes.p) + tile_offset * tb, planes, nt * tb, hipMemcpyHostToDevice, c->win.copy_stream));
+    HIPCHK(c, hipMemcpyAsync(sl.nonn + tile_offset * 64, non_n, nt * 64 * sizeof(int), hipMemcpyHostToDevice, c->win.copy_stream));
+    if (!c->acgt) HIPCHK(c, hipMemcpyAsync(sl.side + tile_offset * 64 * AMB_ROW, side_rows, nt * 64 * AMB_ROW * sizeof(int), hipMemcpyHostToDevice, c->win.copy_stream));
   }
-  HIPCHK(c, hipEventRecord(sl.copied, c->copy_stream));        // the copy stream runs in order: this one covers the earlier pieces too
+  HIPCHK(c, hipEventRecord(sl.copied, c->win.copy_stream));        // the copy stream runs in order: this one covers the earlier pieces too
   sl.n_tiles = (int)std::max(before, tile_offset + (size_t)n_tiles);
   return 0;
 }
@@ -148,48 +139,36 @@ int uvaia_gpu_db_stage_packed(uvaia_gpu_ctx *c, int slot, const void *planes, co
 int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n_ref)
 {
   if (int rc = check_staged(c, slot, sel, n_ref)) return rc;
-  auto &sl = c->wstage[slot];
+  auto &sl = c->win.stage[slot];
   if (n_ref == 0) return 0;
   HIPCHK(c, hipSetDevice(c->device));
-  { int rc = settle_derive(c); if (rc) return rc; }
-  if (c->db_n + (size_t)n_ref > c->db_cap) {
-    if (c->db_n) return fail(c, UVAIA_GPU_ESTATE, "database capacity %zu exceeded: call uvaia_gpu_db_reserve first", c->db_cap);
-    int rc = uvaia_gpu_db_reserve(c, (size_t)n_ref); if (rc) return rc;
-  }
+  if (int rc = db_make_room(c, (size_t)n_ref)) return rc;
   const size_t n0 = c->db_n, n1 = n0 + (size_t)n_ref;
   const long long t0 = (long long)(n0 / 64), t1 = (long long)((n1 - 1) / 64);
   // the four-plane image the text is decoded from (uvaia_gpu_db_unpack_rows): the resident planes themselves in a default-mode context; an
   // --acgt context keeps it next to them, and it is whole as long as every resident reference came through load_staged / append_staged
-  bool image = n1 <= 0x7FFFFFFFu && (!c->acgt || n0 == 0 || (c->win_n > 0 && (size_t)c->win_n == n0));
-  if (c->acgt && c->win4_tiles < c->db_cap / 64 + 1) {
-    if (n0) image = false;                              // (what it held goes with the old array)
-    const size_t cap = c->db_cap / 64 + 1;
-    hipFree(c->d_win4); c->d_win4 = nullptr; c->win4_tiles = 0;
-    HIPCHK(c, hipMalloc(&c->d_win4, cap * (size_t)c->W4 * 4 * 64 * sizeof(uint4)));
-    c->win4_tiles = cap;
-  }
+  bool image = n1 <= 0x7FFFFFFFu && (!c->acgt || n0 == 0 || (c->win.n > 0 && (size_t)c->win.n == n0)), grown = false;
+  if (int rc = win_image_room(c, c->db_cap / 64 + 1, &grown)) return rc;
+  if (grown && n0) image = false;                       // (what it held goes with the old array)
   if (n0 % 64) { if (int rc = sync_scan_streams(c)) return rc; }      // the derived planes of the first tile are rebuilt: no scan may still read them
   if (int rc = upload_sel(c, sel, n_ref)) return rc;
-  for (hipEvent_t &e : c->win_ev) if (!e) HIPCHK(c, hipEventCreate(&e));
-  HIPCHK(c, hipStreamWaitEvent(c->stream, sl.copied, 0));
-  HIPCHK(c, hipEventRecord(c->win_ev[0], c->stream));
+  for (Event &e : c->win.ev) if (int rc = e.make(c)) return rc;
+  HIPCHK(c, hipStreamWaitEvent(c->st.stream, sl.copied, 0));
+  HIPCHK(c, hipEventRecord(c->win.ev[0], c->st.stream));
   const unsigned nblk = (unsigned)(t1 - t0 + 1);
-  const int *d_sel = sel ? c->d_wsel : (const int *)nullptr;
-  if (c->acgt) hipLaunchKernelGGL((append_lanes_kernel<3>), dim3(nblk), dim3(256), 0, c->stream, sl.planes, sl.nonn, (const int *)nullptr, d_sel, (long long)n0, n_ref, c->W4,
-                                  c->db.planes, c->d_win4, t0, c->db.nonn, (int *)nullptr, c->db.tot);
-  else         hipLaunchKernelGGL((append_lanes_kernel<4>), dim3(nblk), dim3(256), 0, c->stream, sl.planes, sl.nonn, sl.side, d_sel, (long long)n0, n_ref, c->W4,
+  const int *d_sel = sel ? c->win.d_sel : (const int *)nullptr;
+  if (c->acgt) hipLaunchKernelGGL((append_lanes_kernel<3>), dim3(nblk), dim3(256), 0, c->st.stream, sl.planes, sl.nonn, (const int *)nullptr, d_sel, (long long)n0, n_ref, c->W4,
+                                  c->db.planes, c->win.d_four, t0, c->db.nonn, (int *)nullptr, c->db.tot);
+  else         hipLaunchKernelGGL((append_lanes_kernel<4>), dim3(nblk), dim3(256), 0, c->st.stream, sl.planes, sl.nonn, sl.side, d_sel, (long long)n0, n_ref, c->W4,
                                   c->db.planes, (uint4 *)nullptr, t0, c->db.nonn, c->db.amb, c->db.tot);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->win_ev[1], c->stream));
-  HIPCHK(c, hipEventRecord(sl.read, c->stream)); sl.read_recorded = true;
+  HIPCHK(c, hipEventRecord(c->win.ev[1], c->st.stream));
+  HIPCHK(c, hipEventRecord(sl.read, c->st.stream)); sl.read_recorded = true;
   // as uvaia_gpu_db_append_packed, for the rows added: the checks on what came from outside, the derived planes of their tiles
-  hipLaunchKernelGGL(sanitise_import_kernel, dim3((unsigned)(((size_t)n_ref + 255) / 256)), dim3(256), 0, c->stream, c->acgt ? (int *)nullptr : c->db.amb + n0 * AMB_ROW, c->db.nonn + n0,
-                     (long long)n_ref, c->W4 * 4, c->nchar);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = db_sanitise_import(c, n0, (size_t)n_ref)) return rc;
   { int rc = derive_rows(c, c->db, (long long)n0, n_ref); if (rc) return rc; }
   if (int rc = finish_staged(c)) return rc;
-  c->db_n = n1;
-  c->win_n = image ? (int)n1 : 0;
+  db_commit(c, n1, image ? (int)n1 : 0);
   return 0;
 }
 
@@ -197,15 +176,15 @@ int uvaia_gpu_db_append_staged(uvaia_gpu_ctx *c, int slot, const int *sel, int n
 int uvaia_gpu_db_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *rows, size_t pitch)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  const int count = (c->win_n && (size_t)c->win_n == c->db_n) ? c->win_n : 0;     // (the database changed since the load: the window is gone)
-  for (int i = 3; i < 5; i++) if (!c->win_ev[i]) HIPCHK(c, hipEventCreate(&c->win_ev[i]));
-  return unpack_rows_from(c, c->acgt ? c->d_win4 : c->db.planes, count, "loaded window", "uvaia_gpu_db_load_staged", index, n, rows, pitch, c->win_ev + 3, &c->win_ms[2]);
+  const int count = (c->win.n && (size_t)c->win.n == c->db_n) ? c->win.n : 0;     // (the database changed since the load: the window is gone)
+  for (int i = 3; i < 5; i++) if (int rc = c->win.ev[i].make(c)) return rc;
+  return unpack_rows_from(c, c->acgt ? c->win.d_four : c->db.planes, count, "loaded window", "uvaia_gpu_db_load_staged", index, n, rows, pitch, c->win.ev + 3, &c->win.ms[2]);
 }
 
 void uvaia_gpu_window_ms(uvaia_gpu_ctx *c, double out[3], int reset)
 {
   if (!c) return;
-  for (int i = 0; i < 3; i++) { out[i] = c->win_ms[i]; if (reset) c->win_ms[i] = 0.; }
+  for (int i = 0; i < 3; i++) { out[i] = c->win.ms[i]; if (reset) c->win.ms[i] = 0.; }
 }
 
 }  // extern "C"

@@ -762,11 +762,15 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
 // to wait for until the data is used.  Written as inline assembly on purpose: the compiler makes every LDS read that follows a
 // global_load_lds it knows of wait for ALL of them (it cannot tell the staging rows apart), which would serialise the half round being
 // worked on with the one in flight.  The waits are placed by hand (replay_wait_staged); the compiler's own vmcnt waits only get
-// stricter by loads it does not know of (the counter is in order).  M0 holds the LDS address; nothing else in these kernels uses M0.
+// stricter by loads it does not know of (the counter is in order).  M0 holds the LDS address: both helpers write it and declare it clobbered.
+// (the compiler reserves M0 and says so for every clobber that names it; the declaration stays for the day it keeps a value there)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
 static __device__ __forceinline__ void lds_dma_dword(const void *g, uint32_t lds_byte_addr)
-{ asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)), "v"(g) : "memory"); }
+{ asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dword %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)), "v"(g) : "memory", "m0"); }
 static __device__ __forceinline__ void lds_dma_dwordx4(const void *g, uint32_t lds_byte_addr)      // 16 bytes per lane, lane l's at lds_byte_addr + 16 l
-{ asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)), "v"(g) : "memory"); }
+{ asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(__builtin_amdgcn_readfirstlane(lds_byte_addr)), "v"(g) : "memory", "m0"); }
+#pragma clang diagnostic pop
 static __device__ __forceinline__ void replay_wait_staged() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ const uint4 g_replay_zero16 = {0u, 0u, 0u, 0u};        // what a lane past the slice's last tile stages as its bounds
 typedef __attribute__((address_space(3))) void replay_lds_void;
