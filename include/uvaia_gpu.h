@@ -392,6 +392,16 @@ int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const
  *                  empty; db_clear, the other appends and db_drop_tiles end the image, and db_unpack_rows then answers UVAIA_GPU_ESTATE).  Refusals as
  *                  load_staged, before anything is launched; capacity as uvaia_gpu_db_append_packed (reserve before the first append).
  *                  Several packed files load as one stream this way, and a merge is stage -> append_staged -> export.
+ *   stage_compact_at  the compact sibling of stage_packed_at, for a piece of a version 2 packed database (uvaia_amd/csrc/host/uvdb.h): same
+ *                  slot and offset rules, same refusals, same ordering against the loads.  base: one reference's worth of planes;
+ *                  head_idx / lit_idx: the n_tiles * 64 + 1 offsets of the staged lanes as the file holds them; heads / lits: the START
+ *                  of the file's two record sections, which the offsets count from (only the records of the staged lanes are read);
+ *                  non_n as for stage_packed_at.  The base, the piece's records and counts go to buffers the context owns, and
+ *                  expand_tiles_kernel writes the dense tiles into the slot; the side rows are made there from the expanded planes in
+ *                  the fixed form of uvaia_gpu_db_export (an --acgt context keeps none).  load_staged, append_staged and
+ *                  db_unpack_rows cannot tell how a slot was filled.  The heads must have passed uvdb_open's checks; the kernel bounds
+ *                  every access all the same.  The host arrays must stay as they are until the slot has been loaded.
+ *   compact_ms     device time in ms since the last reset of [0] expand_tiles_kernel, [1] the side-row pass (waits for the last expansion)
  *   window_ms      device time in ms since the last reset of [0] the selection, [1] totals, checks and derived planes after it, [2] the decode
  *   free_bytes     free memory of the context's device as the runtime reports it (0: the runtime could not tell) */
 int uvaia_gpu_db_stage_reserve (uvaia_gpu_ctx *ctx, size_t n_tiles);
@@ -399,6 +409,9 @@ int uvaia_gpu_db_stage_packed (uvaia_gpu_ctx *ctx, int slot, const void *planes,
 int uvaia_gpu_db_load_staged (uvaia_gpu_ctx *ctx, int slot, const int *sel, int n_ref);
 int uvaia_gpu_db_stage_packed_at (uvaia_gpu_ctx *ctx, int slot, size_t tile_offset, const void *planes, const int *non_n, const int *side_rows, int n_tiles);
 int uvaia_gpu_db_append_staged (uvaia_gpu_ctx *ctx, int slot, const int *sel, int n_ref);
+int uvaia_gpu_db_stage_compact_at (uvaia_gpu_ctx *ctx, int slot, size_t tile_offset, const void *base, const uint64_t *head_idx, const uint32_t *heads,
+                                   const uint64_t *lit_idx, const void *lits, const int *non_n, int n_tiles);
+void uvaia_gpu_compact_ms (uvaia_gpu_ctx *ctx, double out[2], int reset);
 int uvaia_gpu_db_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
 void uvaia_gpu_window_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 size_t uvaia_gpu_free_bytes (uvaia_gpu_ctx *ctx);

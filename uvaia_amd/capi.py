@@ -30,7 +30,7 @@ SYMBOLS = [
     "uvaia_gpu_group_db_size", "uvaia_gpu_group_reset", "uvaia_gpu_group_search_resident", "uvaia_gpu_group_push", "uvaia_gpu_group_drain", "uvaia_gpu_group_sync",
     "uvaia_gpu_rows_census", "uvaia_gpu_db_append_device", "uvaia_gpu_rows_exceptions", "uvaia_gpu_db_drop_tiles", "uvaia_gpu_rows_kernel_ms", "uvaia_gpu_rows_set_run_cut",
     "uvaia_gpu_db_stage_reserve", "uvaia_gpu_db_stage_packed", "uvaia_gpu_db_load_staged", "uvaia_gpu_db_unpack_rows", "uvaia_gpu_window_ms", "uvaia_gpu_free_bytes",
-    "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged",
+    "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged", "uvaia_gpu_db_stage_compact_at", "uvaia_gpu_compact_ms",
 ]
 
 
@@ -194,6 +194,8 @@ def load_library():
         "uvaia_gpu_db_load_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
         "uvaia_gpu_db_stage_packed_at": (C.c_int, [vp, C.c_int, C.c_size_t, C.c_void_p, pi, pi, C.c_int]),
         "uvaia_gpu_db_append_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
+        "uvaia_gpu_db_stage_compact_at": (C.c_int, [vp, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, pi, C.c_int]),
+        "uvaia_gpu_compact_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_db_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_window_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
@@ -613,6 +615,34 @@ class Engine:
         self._staged_at.setdefault(int(slot), []).append((planes, non_n, side_rows))
         self._chk(self.L.uvaia_gpu_db_stage_packed_at(self.ctx, int(slot), int(tile_offset), planes.ctypes.data, non_n.ctypes.data_as(C.POINTER(C.c_int)),
                                                       side_rows.ctypes.data_as(C.POINTER(C.c_int)), int(n_tiles)))
+
+    def db_stage_compact_at(self, slot, tile_offset, base, head_idx, heads, lit_idx, lits, non_n, n_tiles):
+        """db_stage_packed_at for a piece of a compact (version 2) packed database: base row, the n_tiles * 64 + 1 offsets of the staged lanes
+        into the file's heads and lits sections (given from their start), the lanes' valid-site counts; the tiles are expanded in the slot"""
+        base = np.ascontiguousarray(base, dtype=np.uint32)
+        head_idx = np.ascontiguousarray(head_idx, dtype=np.uint64)
+        lit_idx = np.ascontiguousarray(lit_idx, dtype=np.uint64)
+        heads = np.ascontiguousarray(heads, dtype=np.uint32)
+        lits = np.ascontiguousarray(lits, dtype=np.uint32)
+        non_n = np.ascontiguousarray(non_n, dtype=np.int32)
+        lanes = int(n_tiles) * 64
+        if base.size * 4 * 64 != self.L.uvaia_gpu_db_tile_bytes(self.ctx) or head_idx.size < lanes + 1 or lit_idx.size < lanes + 1 or non_n.size < lanes:
+            raise ValueError("arrays shorter than %d tiles" % n_tiles)
+        if lanes and (heads.size < int(head_idx[lanes]) or lits.size < int(lit_idx[lanes]) * 4):
+            raise ValueError("records shorter than the index says")
+        if not hasattr(self, "_staged_at"):
+            self._staged_at = {}
+        if int(tile_offset) == 0:
+            self._staged_at[int(slot)] = []
+        self._staged_at.setdefault(int(slot), []).append((base, head_idx, heads, lit_idx, lits, non_n))
+        self._chk(self.L.uvaia_gpu_db_stage_compact_at(self.ctx, int(slot), int(tile_offset), base.ctypes.data, head_idx.ctypes.data, heads.ctypes.data,
+                                                       lit_idx.ctypes.data, lits.ctypes.data, non_n.ctypes.data_as(C.POINTER(C.c_int)), int(n_tiles)))
+
+    def compact_ms(self, reset=False):
+        """Device ms since the last reset of (expand_tiles_kernel, the side-row pass after it)."""
+        out = (C.c_double * 2)()
+        self.L.uvaia_gpu_compact_ms(self.ctx, out, int(reset))
+        return tuple(out)
 
     def db_append_staged(self, slot, sel, n_ref):
         """references sel[0 .. n_ref) of the slot (None: the first n_ref) go behind the resident ones, at any database size"""

@@ -204,6 +204,10 @@ main (int argc, char **argv)
     printf ("  --devices=<list>                 with --packed: one GPU context per listed device (e.g. 0-3 or 0,0), chunks are dealt out among them\n");
     return help ? EXIT_SUCCESS : EXIT_FAILURE;
   }
+  for (int f = 0; f < n_packed; f++) if (uvdb_file_version (packed_files[f]) == 2) {     /* the radius search reads dense tiles from the mapping */
+    fprintf (stderr, "uvaiaball --packed: %s is a compact packed database (`uvaiapack --compact`), which this search does not read; convert it with `uvaiapack --merge -o dense.uvdb %s`\n", packed_files[f], packed_files[f]);
+    return EXIT_FAILURE;
+  }
   if (ambig_q < 0.001) ambig_q = 0.001;
   if (ambig_q > 1.) ambig_q = 1.;
   if (ambig_r < 0.001) ambig_r = 0.001;

@@ -265,6 +265,10 @@ main (int argc, char **argv)
     }
     return (help && !errors) ? EXIT_SUCCESS : EXIT_FAILURE;
   }
+  for (int f = 0; f < n_packed; f++) if (uvdb_file_version (packed_files[f]) == 2) {     /* the clustering decodes dense tiles from the mapping */
+    fprintf (stderr, "uvaiaclust --packed: %s is a compact packed database (`uvaiapack --compact`), which the clustering does not read; convert it with `uvaiapack --merge -o dense.uvdb %s`\n", packed_files[f], packed_files[f]);
+    return EXIT_FAILURE;
+  }
   if (dist < 0) dist = 0;                                                  /* src/cluster.c:131-132 */
   if (snps < 0) snps = 0;
   fprintf (stderr, "Experimental program: %s package: %s\n", basename (argv[0]), UVAIA_PACKAGE_STRING);

@@ -43,7 +43,7 @@ usage (const char *prog, int long_help)
   printf ("  -a, --query_ambiguity=<double>   maximum allowed ambiguity for QUERY sequence to be excluded (default=0.5)\n");
   printf ("  -p, --pool=<int>                 Pool size, i.e. how many reference seqs are sent to the GPU per batch (defaults to 64 per host thread; larger is faster)\n");
   printf ("  -r, --reference=<ref.fa(.gz,.xz)> aligned reference sequences (can be several files)\n");
-  printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): loaded as it is, no text parsing; can be several\n                                   files, searched in the order given as one database (all packed with the same -A: see `uvaiapack --merge -A`)\n");
+  printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): loaded as it is, no text parsing; can be several\n                                   files, searched in the order given as one database (all packed with the same -A: see `uvaiapack --merge -A`).\n                                   Compact files (`uvaiapack --compact`) are expanded on the GPU, on one device (not with a --devices list of several)\n");
   printf ("  --window=<refs>                  with --packed: keep only this many references on the GPU at a time (rounded up to whole pools and tiles\n                                   of 64), for a database larger than GPU memory; chosen automatically when the database does not fit\n");
   printf ("  --window-report                  with --packed: one line on stderr with the GPU's free memory before and after and the time of the window steps\n");
   printf ("  <seqs.fa(.gz,.xz)>               aligned query sequences\n");
@@ -113,6 +113,11 @@ parse_options (int argc, char **argv)
   if (o.window_given && o.window < 1) { fprintf (stderr, "--window: expected a positive number of references\n"); exit (EXIT_FAILURE); }
   if (o.n_packed > UVDB_SET_MAX_FILES) { fprintf (stderr, "--packed: at most %d files\n", UVDB_SET_MAX_FILES); exit (EXIT_FAILURE); }
   if (o.window_given && o.n_devices > 1) { fprintf (stderr, "--window works on one GPU: give --device, not a --devices list of several\n"); exit (EXIT_FAILURE); }
+  /* a compact file is expanded in a staging slot of one GPU; a group of devices gathers lanes on the host from the dense tiles of the mapping */
+  for (int f = 0; o.n_devices > 1 && f < o.n_packed; f++) if (uvdb_file_version (o.packed_files[f]) == 2) {
+    fprintf (stderr, "--devices with several GPUs: %s is a compact packed database (`uvaiapack --compact`), which is searched on one GPU only; convert it with `uvaiapack --merge -o dense.uvdb %s`\n", o.packed_files[f], o.packed_files[f]);
+    exit (EXIT_FAILURE);
+  }
   return o;
 }
 
@@ -140,8 +145,10 @@ stage_range (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t a,
   for (int p = 0; p < np; p++) {
     uvdb_reader db = set->db[pieces[p].file];
     const uint64_t t0 = pieces[p].first_tile;
-    if (uvaia_gpu_db_stage_packed_at (gpu, slot, (size_t) pieces[p].slot_tile, uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) pieces[p].n_tiles))
-      biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    const int rc = db->h.version == 2     /* a compact file's tiles are expanded in the slot, a set may mix both kinds */
+      ? uvaia_gpu_db_stage_compact_at (gpu, slot, (size_t) pieces[p].slot_tile, db->base, db->head_idx + t0 * 64, db->heads, db->lit_idx + t0 * 64, db->lits, db->non_n + t0 * 64, (int) pieces[p].n_tiles)
+      : uvaia_gpu_db_stage_packed_at (gpu, slot, (size_t) pieces[p].slot_tile, uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) pieces[p].n_tiles);
+    if (rc) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
   }
   return !keep && np == 1 && sel[0] == 0;
 }

@@ -8,6 +8,10 @@
  * the texts the inputs were packed from, byte for byte.  The tiles of an input are staged as the file holds them and its references
  * appended behind the resident ones on the device (uvaia_gpu_db_append_staged: an input rarely ends on a tile boundary); a tighter -A
  * drops rows through the selection of that call.
+ *
+ * `uvaiapack --compact` writes version 2 of the format (uvdb.h: a base row and per-reference differences, expanded on the GPU by
+ * `uvaia --packed`), from texts or, with --merge, from packed inputs of either version; --merge without it reads both versions and
+ * writes version 1, the way back to the dense file.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -26,12 +30,15 @@ usage (const char *prog)
 {
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("Packs an aligned reference FASTA into the bit-plane database the MI355X engine searches without parsing text.\n\n");
-  printf (" %s [-hv] [-A <double>] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
-  printf (" %s --merge [-A <double>] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n\n", prog);
+  printf (" %s [-hv] [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
+  printf (" %s --merge [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n\n", prog);
   printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` is run with the value of its file\n");
   printf ("  --merge                          the inputs are packed databases: joins them, in order, into the file that packing their texts together gives.\n");
   printf ("                                   -A then defaults to the inputs' common value; a smaller one drops the rows it excludes, a larger one than\n");
   printf ("                                   an input's is refused (that input no longer holds the rows it would keep)\n");
+  printf ("  --compact                        write the compact form: one base row and, per reference, the 32-site words that differ from it; several times\n");
+  printf ("                                   smaller for genomes of one pathogen.  `uvaia --packed` expands it on the GPU (one device); `uvaiaball` and\n");
+  printf ("                                   `uvaiaclust` need the dense file, which `--merge -o dense.uvdb compact.uvdb` writes.  --merge reads both forms\n");
   printf ("  -o, --output=<file>              packed database to write\n");
   printf ("  --device=<int>                   GPU to use (default: current device)\n");
   printf ("Sequences that still have to be aligned: `uvaialign --packed <out.uvdb>` writes the same file straight from the aligner, without the text in between.\n");
@@ -40,7 +47,7 @@ usage (const char *prog)
 /* `uvaiapack --merge`.  Whole tiles are exported once MERGE_BATCH references are resident and dropped from the front of the resident
  * database (uvaia_gpu_db_drop_tiles); the partly filled last tile stays resident and the next input's references go on filling it. */
 static int
-merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r, int device)
+merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r, int device, int compact)
 {
   enum { MERGE_BATCH = PACK_BATCH, CHUNK_TILES = PACK_BATCH / 64 };
   char msg[1024];
@@ -53,6 +60,7 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
   for (int f = 0; f < n_in; f++) if (ambig_r > set->db[f]->h.ref_ambiguity)
     biomcmc_error ("--merge: -A %g is looser than the -A %g that packed database %s was filtered with: it does not hold the rows that filter dropped", ambig_r, set->db[f]->h.ref_ambiguity, in[f]);
   const int nchar = (int) set->nchar, non_n_ref = (int) (nchar * (1. - ambig_r));      /* the threshold of the text path below */
+  if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);
 
   uvaia_gpu_ctx *gpu = NULL;
   {
@@ -73,7 +81,7 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
   void *planes = biomcmc_malloc ((size_t) (2 * CHUNK_TILES) * tb);
   int *tile_nonn = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * sizeof (int)), *side = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * row * sizeof (int));
   int *sel = (int *) biomcmc_malloc (MERGE_BATCH * sizeof (int));
-  uvdb_writer w = uvdb_create (out, nchar, tb, (int) row, ambig_r);
+  uvdb_writer w = compact ? uvdb_create_compact (out, nchar, tb, (int) row, ambig_r) : uvdb_create (out, nchar, tb, (int) row, ambig_r);
   if (!w) biomcmc_error ("cannot create %s", out);
   long count = 0, kept = 0;
   int slot = 0;
@@ -92,7 +100,8 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
       }
       kept += m;
       if (!m) continue;
-      if (uvaia_gpu_db_stage_packed (gpu, slot, uvdb_tile_planes (db, t), db->non_n + r0, uvdb_tile_side_rows (db, t), (int) nt) ||
+      if ((db->h.version == 2 ? uvaia_gpu_db_stage_compact_at (gpu, slot, 0, db->base, db->head_idx + r0, db->heads, db->lit_idx + r0, db->lits, db->non_n + r0, (int) nt)
+                              : uvaia_gpu_db_stage_packed (gpu, slot, uvdb_tile_planes (db, t), db->non_n + r0, uvdb_tile_side_rows (db, t), (int) nt)) ||
           uvaia_gpu_db_append_staged (gpu, slot, (uint64_t) m == r1 - r0 ? NULL : sel, m)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
       slot ^= 1;
       const size_t whole = uvaia_gpu_db_size (gpu) / 64;
@@ -121,9 +130,9 @@ main (int argc, char **argv)
 {
   double ambig_r = 0.5;
   const char *out = NULL;
-  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0;
+  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0, compact = 0;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {0, 0, 0, 0}};
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {"compact", no_argument, 0, 1004}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
@@ -131,12 +140,13 @@ main (int argc, char **argv)
     case 'o': out = optarg; break;
     case 1002: device = atoi (optarg); break;
     case 1003: merge = 1; break;
+    case 1004: compact = 1; break;
     default: errors++;
   }
   if (errors || !out || optind >= argc) { printf ("Error when reading arguments from command line:\n"); usage (basename (argv[0])); return EXIT_FAILURE; }
   if (ambig_r < 0.001) ambig_r = 0.001;
   if (ambig_r > 1.) ambig_r = 1.;
-  if (merge) return merge_main (argc - optind, argv + optind, out, have_ambig, ambig_r, device);
+  if (merge) return merge_main (argc - optind, argv + optind, out, have_ambig, ambig_r, device, compact);
   int64_t time0[2];
   biomcmc_get_time (time0);
 
@@ -171,7 +181,8 @@ main (int argc, char **argv)
           planes = biomcmc_malloc ((PACK_BATCH / 64) * tb);
           tile_nonn = (int *) biomcmc_malloc (PACK_BATCH * sizeof (int));
           side = (int *) biomcmc_malloc ((size_t) PACK_BATCH * (size_t) uvaia_gpu_db_side_row_ints () * sizeof (int));
-          w = uvdb_create (out, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r);
+          if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);
+          w = compact ? uvdb_create_compact (out, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r) : uvdb_create (out, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r);
           if (!w) biomcmc_error ("cannot create %s", out);
         }
         /* as the reference's fill loop (src/nearest.c:263-278): low-quality records are dropped first, only then must the length fit */

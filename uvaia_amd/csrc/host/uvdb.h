@@ -15,6 +15,30 @@
  *   exc      (uint32 pos, uint32 len<<8 | char)   runs of invalid sites whose character is not 'N' ('-', '?', 'X', 'O', '.'):
  *            with them the exact (upper-case) text of a reference is recovered from its planes, as the .aln.xz dump needs
  * References that fail the -A filter or the length check are not stored: the filter value is recorded in the header.
+ *
+ * Version 2, the compact form (`uvaiapack --compact`): a disk and transport format only.  Aligned genomes of one pathogen are nearly
+ * identical column by column, so the file holds one base row and, per reference, the 32-site words in which it differs from the base.
+ * Header, non_n, name_idx, names, exc_idx and exc keep their version 1 form; planes and side are replaced (the side rows are a pure
+ * function of the planes and are not stored):
+ *   base     W4*4 x 16 bytes         one reference's worth of planes, [word group][plane A,C,G,T] 16-byte words (header field off_planes).
+ *            A plane bit is set exactly when it is set in more than half of the first min (n_ref, UVDB_BASE_SAMPLE) stored references;
+ *            bits at and beyond nchar are zero.  Correctness never depends on the base: the rule makes files reproducible.
+ *   non_n    n_tiles*64 x int32      as version 1
+ *   head_idx (n_tiles*64+1) x uint64 record offsets into heads (header field off_side), one entry per LANE of the dense tiles
+ *   heads    uint32 records (header field reserved[0]): first_word:16 | n_words:11 | literal:1 | code:4, most significant first.  Word w of
+ *            a reference covers sites 32w .. 32w+31; n_words is 1 .. 2047.  A fill head (literal = 0) says every site of those words has the
+ *            4-bit set `code`: plane p of each word is all ones if bit p of code is set, zero otherwise (code 0: an N or gap run).  A
+ *            literal head says the next n_words x 4 dwords of lits are planes A, C, G, T of each of those words.
+ *   lit_idx  (n_tiles*64+1) x uint64 offsets into lits, in words of 16 bytes (header field reserved[1])
+ *   lits     16 bytes per literal word, starts at the next multiple of 64 behind lit_idx
+ * The two index sections cover the lanes of whole tiles, not n_ref + 1 entries: the lanes past the last reference are all-zero rows
+ * encoded against the base like any other, so that a staged range of whole tiles (uvaia_gpu_db_stage_compact_at, include/uvaia_gpu.h)
+ * expands to the zero lanes a dense file holds without knowing where the file ends.
+ * Canonical encoding: a word equal to the base's word has no record; a differing word whose four planes are each 0 or 0xFFFFFFFF is a
+ * fill, any other a literal; adjacent words of the same kind (fills: and the same code) are one head, cut only at 2047 words; heads
+ * ascend and never overlap; the padding words beyond nchar never differ from the base.  first_word has 16 bits: a compact file is
+ * refused for nchar > UVDB_COMPACT_MAX_NCHAR.  uvdb_open checks every index and every head of a version 2 file (OpenMP: it is a pass
+ * over the whole file), so the device never sees an unchecked head.
  * Several files are read as one stream through uvdb_set.h (a repeated --packed); `uvaiapack --merge` joins files into the one file their
  * texts would have been packed to, and is where a recorded -A is tightened (a filter cannot be loosened: the rows are not there).
  */
@@ -43,6 +67,15 @@ struct uvdb_header {
 
 typedef struct { uint32_t pos, len_char; } uvdb_exc;
 
+#define UVDB_BASE_SAMPLE 4096            /* references the base row of a version 2 file is the majority of */
+#define UVDB_COMPACT_MAX_NCHAR 2097152   /* 65 536 words of 32 sites: what first_word counts */
+#define UVDB_HEAD_MAX_WORDS 2047
+#define UVDB_HEAD(first, n, lit, code) (((uint32_t) (first) << 16) | ((uint32_t) (n) << 5) | ((uint32_t) (lit) << 4) | (uint32_t) (code))
+#define UVDB_HEAD_FIRST(h)   ((uint32_t) (h) >> 16)
+#define UVDB_HEAD_WORDS(h)   (((uint32_t) (h) >> 5) & 0x7FFu)
+#define UVDB_HEAD_LITERAL(h) (((uint32_t) (h) >> 4) & 1u)
+#define UVDB_HEAD_CODE(h)    ((uint32_t) (h) & 15u)
+
 /* ---- writer: tiles are appended in stream order, the index sections go to the end on close */
 typedef struct uvdb_writer_struct *uvdb_writer;
 uvdb_writer uvdb_create (const char *filename, int nchar, size_t tile_bytes, int side_row_ints, double ref_ambiguity);
@@ -55,6 +88,10 @@ int uvdb_add_reference_runs (uvdb_writer w, const char *name, const uvdb_exc *ru
 /* the next n_tiles tiles in the engine's export form */
 int uvdb_add_tiles (uvdb_writer w, size_t n_tiles, const void *planes, const int *non_n, const int *side_rows);
 int uvdb_close (uvdb_writer w);       /* 0 on success */
+/* a version 2 file: the same calls follow.  The writer ignores side rows (NULL will do); it keeps the tiles until it has UVDB_BASE_SAMPLE
+ * references or is closed, then fixes the base and encodes that chunk and all later ones on the host.  NULL also for
+ * nchar > UVDB_COMPACT_MAX_NCHAR. */
+uvdb_writer uvdb_create_compact (const char *filename, int nchar, size_t tile_bytes, int side_row_ints, double ref_ambiguity);
 
 /* ---- reader: the file is mapped read-only; every pointer below points into the mapping */
 typedef struct uvdb_reader_struct {
@@ -63,11 +100,21 @@ typedef struct uvdb_reader_struct {
   const uint64_t *name_idx; const char *names;
   const uint64_t *exc_idx; const uvdb_exc *exc;
   const int32_t *non_n;
+  /* version 2 only (NULL otherwise) */
+  const uint32_t *base; const uint64_t *head_idx; const uint32_t *heads; const uint64_t *lit_idx; const uint32_t *lits;
 } *uvdb_reader;
 uvdb_reader uvdb_open (const char *filename, char *errbuf, size_t errlen);
 const char *uvdb_name (uvdb_reader r, uint64_t i);
+/* version of the file's header without opening it (0: not a packed database or unreadable): for refusals before any other work */
+uint32_t uvdb_file_version (const char *filename);
+/* both NULL for a version 2 reader, which holds no dense tiles: every caller handles that or refuses the file earlier */
 const void *uvdb_tile_planes (uvdb_reader r, uint64_t tile);        /* h.tile_bytes per tile, consecutive tiles are contiguous */
 const int32_t *uvdb_tile_side_rows (uvdb_reader r, uint64_t tile);   /* 64 * h.side_row_ints ints per tile, contiguous */
+/* Tiles first_tile .. first_tile + n_tiles - 1 as dense tiles, expanded on the CPU (a version 1 reader: copied): planes_out n_tiles x
+ * h.tile_bytes; side_rows_out (may be NULL) n_tiles x 64 x h.side_row_ints ints in the fixed form of the engine's side_rows_canonical_kernel
+ * -- the partially ambiguous words in ascending order, the first UVDB_SIDE_LISTED listed with their planes, [0] their total.  Lanes
+ * past n_ref come out as zeros.  0 on success. */
+int uvdb_expand_tiles (uvdb_reader r, uint64_t first_tile, uint64_t n_tiles, void *planes_out, int32_t *side_rows_out);
 /* exact upper-case text of reference i (nchar + 1 bytes) */
 void uvdb_unpack_reference (uvdb_reader r, uint64_t i, char *out);
 /* the second half of it: the exception runs of reference i written over a row of nchar characters decoded from its planes elsewhere

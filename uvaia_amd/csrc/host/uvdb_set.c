@@ -152,6 +152,7 @@ uvdb_set_direct_tiles (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b,
   uint64_t l = 0;
   if (!s || keep || b <= a || b > n || n != s->n_ref || store % 64) return -1;
   if (uvdb_set_locate (s, a, &f, &l) || l % 64 || b > s->first[f + 1]) return -1;
+  if (s->db[f]->h.version != 1) return -1;           /* a compact file holds no dense tiles: its chunks are staged and expanded */
   if ((b - a) % 64 && b != n) return -1;
   if (file) *file = f;
   if (first_tile) *first_tile = l / 64;

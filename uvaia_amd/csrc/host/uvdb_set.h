@@ -47,7 +47,7 @@ void uvdb_set_unpack_reference (uvdb_set s, uint64_t i, char *out);
 size_t uvdb_set_runs (uvdb_set s, uint64_t i, const uvdb_exc **runs);
 
 /* A piece of a staging slot: n_tiles whole tiles of `file` from first_tile on, which land at tile slot_tile of the slot
- * (uvaia_gpu_db_stage_packed_at). */
+ * (uvaia_gpu_db_stage_packed_at; uvaia_gpu_db_stage_compact_at for a file of version 2). */
 typedef struct { int file; uint64_t first_tile, n_tiles, slot_tile; } uvdb_set_piece;
 
 /* The multi-file form of uvdb_window_span.  Kept-stream positions [a, b), a < b: per file that holds some of them, the contiguous tiles
@@ -62,8 +62,9 @@ int uvdb_set_span (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uvd
  * (uvaia_gpu_db_append_packed: whole tiles behind whole tiles), without staging or gathering.  Yes (0, and *file, *first_tile: the b - a
  * references are the first of the tiles of that file from first_tile on) when nothing is left out (keep == NULL, n = references of the
  * stream), the range lies in one file and starts at lane 0 of one of its tiles, b - a is a multiple of 64 or b == n (the stream ends with
- * the range, so the lanes behind it in its last tile are the file's padding), and store is a multiple of 64.  Otherwise -1, as for an
- * empty range and for one past the stream. */
+ * the range, so the lanes behind it in its last tile are the file's padding), store is a multiple of 64, and the file holds dense tiles
+ * (version 1: the tiles of a compact file exist only once they are expanded in a staging slot).  Otherwise -1, as for an empty range and
+ * for one past the stream. */
 int uvdb_set_direct_tiles (uvdb_set s, const uint64_t *keep, uint64_t a, uint64_t b, uint64_t n, uint64_t store, int *file, uint64_t *first_tile);
 
 #ifdef __cplusplus

@@ -213,6 +213,9 @@ struct uvaia_gpu_ctx {
     DevBuf<int> d_sel;
     DevBuf<uint4> d_four; int n = 0;      // n: references of the window loaded last (0: none)
     Event ev[5]; double ms[3] = {0., 0., 0.};            // device time of selection, import + derive, decode
+    // uvaia_gpu_db_stage_compact_at: what a compact piece is expanded from -- the base row, the piece's index entries, heads and literals -- on
+    // the copy stream's order, so one set serves both slots; device time of the expansion and of the side-row pass
+    struct Compact { DevBuf<uint4> base; DevBuf<unsigned long long> hidx, lidx; DevBuf<uint32_t> heads, lits; Event ev[3]; bool timed = false; double ms[2] = {0., 0.}; } compact;
   } win;
   // ---- reference shards (uvaia_gpu_db_set_shard): the stream is dealt in pieces of pt tiles, piece p belongs to rank p % world; the packed
   // planes of ALL references are resident (the replay reads them), the planes derived for the query set only for the owned pieces

@@ -131,6 +131,83 @@ int uvaia_gpu_db_stage_packed_at(uvaia_gpu_ctx *c, int slot, size_t tile_offset,
   return 0;
 }
 
+// device time of the expansion queued last, once it has run (the events are recorded anew by every uvaia_gpu_db_stage_compact_at)
+static void compact_harvest(uvaia_gpu_ctx *c)
+{
+  auto &k = c->win.compact;
+  if (!k.timed) return;
+  k.timed = false;
+  if (hipEventSynchronize(k.ev[2]) != hipSuccess) { (void)hipGetLastError(); return; }
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, k.ev[0], k.ev[1]) == hipSuccess) k.ms[0] += ms;
+  if (hipEventElapsedTime(&ms, k.ev[1], k.ev[2]) == hipSuccess) k.ms[1] += ms;
+}
+
+int uvaia_gpu_db_stage_compact_at(uvaia_gpu_ctx *c, int slot, size_t tile_offset, const void *base, const uint64_t *head_idx, const uint32_t *heads,
+                                  const uint64_t *lit_idx, const void *lits, const int *non_n, int n_tiles)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  if (n_tiles < 0 || (n_tiles > 0 && (!base || !head_idx || !lit_idx || !non_n))) return fail(c, UVAIA_GPU_EINVAL, "NULL compact arrays");
+  if (tile_offset > stage_tiles(c) || (size_t)n_tiles > stage_tiles(c) - tile_offset)
+    return fail(c, UVAIA_GPU_ESTATE, "%d tiles at tile %zu exceed the staging capacity of %zu: call uvaia_gpu_db_stage_reserve first", n_tiles, tile_offset, stage_tiles(c));
+  const size_t nt = (size_t)n_tiles, lanes = nt * 64;
+  uint64_t nh = 0, nl = 0;
+  if (n_tiles) {
+    if (head_idx[lanes] < head_idx[0] || lit_idx[lanes] < lit_idx[0]) return fail(c, UVAIA_GPU_EINVAL, "compact index arrays that decrease");
+    nh = head_idx[lanes] - head_idx[0]; nl = lit_idx[lanes] - lit_idx[0];
+    if ((nh && !heads) || (nl && !lits)) return fail(c, UVAIA_GPU_EINVAL, "NULL compact arrays");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  auto &sl = c->win.stage[slot];
+  auto &k = c->win.compact;
+  const size_t before = tile_offset ? (size_t)sl.n_tiles : 0;      // a piece at tile 0 starts the slot afresh
+  sl.n_tiles = 0;
+  if (sl.read_recorded) HIPCHK(c, hipStreamWaitEvent(c->win.copy_stream, sl.read, 0));       // the load that still reads the slot's previous tiles
+  if (n_tiles) {
+    compact_harvest(c);
+    for (Event &e : k.ev) if (int rc = e.make(c)) return rc;
+    // the copy stream runs in order: the buffers are free again once the expansion queued before has read them (a buffer that grows is
+    // released by a call that waits for the device)
+    const size_t W4 = (size_t)c->W4;
+    if (int rc = k.base.reserve(c, W4 * 4)) return rc;
+    if (int rc = k.hidx.reserve(c, lanes + 1)) return rc;
+    if (int rc = k.lidx.reserve(c, lanes + 1)) return rc;
+    if (int rc = k.heads.reserve(c, (size_t)nh + 1)) return rc;
+    if (int rc = k.lits.reserve(c, (size_t)nl * 4 + 4)) return rc;
+    hipStream_t cs = c->win.copy_stream;
+    HIPCHK(c, hipMemcpyAsync(k.base, base, W4 * 4 * sizeof(uint4), hipMemcpyHostToDevice, cs));
+    HIPCHK(c, hipMemcpyAsync(k.hidx, head_idx, (lanes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
+    HIPCHK(c, hipMemcpyAsync(k.lidx, lit_idx, (lanes + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
+    if (nh) HIPCHK(c, hipMemcpyAsync(k.heads, heads + head_idx[0], (size_t)nh * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
+    if (nl) HIPCHK(c, hipMemcpyAsync(k.lits, static_cast<const char *>(lits) + lit_idx[0] * 16, (size_t)nl * 16, hipMemcpyHostToDevice, cs));
+    HIPCHK(c, hipMemcpyAsync(sl.nonn + tile_offset * 64, non_n, lanes * sizeof(int), hipMemcpyHostToDevice, cs));
+    uint4 *dst = sl.planes.p + tile_offset * W4 * 4 * 64;
+    HIPCHK(c, hipEventRecord(k.ev[0], cs));
+    hipLaunchKernelGGL(expand_tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, cs, k.base, k.hidx, k.heads, (unsigned long long)nh, k.lidx, k.lits, (unsigned long long)nl, c->W4, dst);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(k.ev[1], cs));
+    if (!c->acgt) {                                               // (an --acgt context keeps no side rows)
+      hipLaunchKernelGGL(side_rows_staged_kernel, dim3((unsigned)n_tiles), dim3(64), 0, cs, dst, c->W4, sl.side + tile_offset * 64 * AMB_ROW);
+      HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(k.ev[2], cs));
+    k.timed = true;
+  }
+  HIPCHK(c, hipEventRecord(sl.copied, c->win.copy_stream));        // the copy stream runs in order: this one covers the earlier pieces too
+  sl.n_tiles = (int)std::max(before, tile_offset + (size_t)n_tiles);
+  return 0;
+}
+
+void uvaia_gpu_compact_ms(uvaia_gpu_ctx *c, double out[2], int reset)
+{
+  if (!c) return;
+  if (hipSetDevice(c->device) != hipSuccess) { (void)hipGetLastError(); return; }
+  compact_harvest(c);
+  for (int i = 0; i < 2; i++) { out[i] = c->win.compact.ms[i]; if (reset) c->win.compact.ms[i] = 0.; }
+}
+
 int uvaia_gpu_db_stage_packed(uvaia_gpu_ctx *c, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles)
 {
   return uvaia_gpu_db_stage_packed_at(c, slot, 0, planes, non_n, side_rows, n_tiles);

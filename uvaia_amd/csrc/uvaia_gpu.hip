@@ -80,6 +80,7 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "kernels_replay.inc"
 #include "kernels_ball.inc"
 #include "kernels_qprep.inc"
+#include "kernels_expand.inc"
 
 // ------------------------------------------------------------------------------------------------------------
 // host side, in sections (one translation unit: the kernels above are templates the sections instantiate); the context and everything
