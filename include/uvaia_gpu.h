@@ -90,7 +90,8 @@ typedef struct {
                                   library's choice (where replay_extras applies as many as hold one replay block per query at once, 8 up to 32 queries;
                                   none otherwise), -1 = none, n > 0 = n; 1000 * t + n also sets the replay's staging depth to t = 32, 16 or 8 tiles */
   int scan_streams;            /* resident search: consecutive slices' scans alternate over 1..3 streams (0 = the library's choice by launch size);
-                                  100 + p (p = 1..98): a pool's first slice is p % of an equal share (default 70), 199: equal slices */
+                                  100 + p (p = 1..98): a pool's first slice is p % of an equal share, 199: equal slices
+                                  (the library's choice: equal slices in default mode with a large query set, else 70) */
   int pipeline;                /* reserved: accepted and ignored (the pipelined replay it selected was removed) */
   int head_scan;               /* reserved: accepted and ignored (the four-counter head it selected was removed) */
   int derive_waves;            /* the kernel that derives a tile's planes for the query set runs 4, 8 or 16 waves per tile (0 = the library's choice: 4;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What happens between two steps of bench.py at config[1], from a rocprofv3 trace (kernel trace + HIP API trace + memory copies, csv):
-per step, the interval from the end of the previous step's last replay2_kernel to the start of the step's first scan3_kernel -- the
+per step, the interval from the end of the previous step's last replay2_kernel (or replay2_lean_kernel) to the start of the step's first scan3_kernel -- the
 kernels and copies inside it, the time the device does nothing, and the runtime calls the host makes meanwhile.
 
   rocprofv3 --kernel-trace --hip-trace --memory-copy-trace --output-format csv -d DIR -o NAME -- python bench.py --gpus 1 --steps 20 --warmup 5
@@ -37,7 +37,7 @@ def main():
     kern = sorted(rows(args.prefix + "_kernel_trace.csv"), key=lambda r: int(r["Start_Timestamp"]))
     api = [r for r in rows(args.prefix + "_hip_api_trace.csv") if r["Domain"].startswith("HIP_RUNTIME")]
     cop = rows(args.prefix + "_memory_copy_trace.csv")
-    replays = [r for r in kern if short(r["Kernel_Name"]) == "replay2_kernel"]
+    replays = [r for r in kern if short(r["Kernel_Name"]) in ("replay2_kernel", "replay2_lean_kernel")]
     scans = [r for r in kern if short(r["Kernel_Name"]) == "scan3_kernel"]
     per_step = len(replays) // (len([r for r in kern if short(r["Kernel_Name"]) == "snapshot_kernel"]) or 1)
     # a step ends with its last replay; the next one's first scan is the first scan that starts after it

@@ -137,7 +137,8 @@ struct uvaia_gpu_ctx {
                                           // four slices of 25 024 references instead of three of 33 334 cost 9 % more scan time -- a launch carries about 70 us of ramp and
                                           // tail -- and still end 4 % sooner: the first replay starts earlier, the last one is shorter)
   bool subslice_forced = false;           // the length was given (tests): taken as it is
-  int first_slice_pct = 70;               // a pool's first slice is this share of an equal one (tuning.scan_streams = 100 + p sets p; 199 = equal slices)
+  int first_slice_pct = -1;               // a pool's first slice is this share of an equal one, 0 = equal slices (tuning.scan_streams = 100 + p sets p; 199 = equal slices);
+                                          // -1 = the library's choice: equal slices where replay2_lean_kernel runs, 70 elsewhere (see plan_subslices)
   int nq = 0, nq_pad = 0, nchar = 0, W = 0, W4 = 0, P = 4, NQ = 6, acgt = 0, k = 2, qt = 16, n_idx_c = 0, n_idx_m = 0;
   size_t trim = 0;
   size_t max_pool = 0, pool_pad = 0;

@@ -327,6 +327,8 @@ struct ReplayLaunch {
   const uint32_t *qpl; const uint4 *poly; int nr4; const uint32_t *qrare;   // on-demand counters from the planes derived for the query set (null, 0: from the packed ones)
   int prefetch;                                                             // candidates of a tile whose on-demand counters are requested ahead: 1, 2 or 3
 };
+// the regime replay2_lean_kernel is written for, as far as the context decides it (launch_replay adds what a launch decides)
+static bool lean_replay_context(const uvaia_gpu_ctx *c) { return !c->fullscan && !c->use_ext && !c->acgt && c->n_idx_c == 0 && c->k <= 127; }
 int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
 {
   const dim3 grid(L.q1 - L.q0), block(64);
@@ -350,8 +352,16 @@ int launch_replay(uvaia_gpu_ctx *c, const ReplayLaunch &L)
                                               c->state.d_heap, c->state.d_n, c->state.d_T, c->state.d_snap, L.entered, c->k, L.planes, L.tile_first, c->W4, c->tab.d_qp, c->tab.d_amb_q, c->stats.d_stats, L.q0, L.tmin, L.qpl, lq_words, c->replay_prio, \
                                               L.poly, c->tab.NP4 + c->tab.NR4, c->tab.NP4, L.nr4, L.qrare)
 #define REPLAY2_PF(A, B) { if (L.prefetch == 1) REPLAY2(A, B, 1); else if (L.prefetch == 2) REPLAY2(A, B, 2); else REPLAY2(A, B, 3); }
-    if (c->acgt) { if (c->n_idx_c > 0) REPLAY2_PF(true, true) else REPLAY2_PF(true, false) }
-    else         { if (c->n_idx_c > 0) REPLAY2_PF(false, true) else REPLAY2_PF(false, false) }
+    // default mode, no consensus pre-score, two candidates requested ahead, the query's planes in memory, a lane per inner node of the
+    // heap: the regime of a large query set (config[1]) has the kernel written for it (a build with -DREPLAY_TIMING keeps the one with the probes)
+    bool lean = lean_replay_context(c) && L.prefetch == 2 && lq_words == 0;
+#ifdef REPLAY_TIMING
+    lean = false;
+#endif
+    if (lean) hipLaunchKernelGGL(replay2_lean_kernel, grid, block, lds + 128, L.stream, L.cnt, L.ppad, L.nonn, L.amb, L.rb, L.re, L.ord_base, c->state.d_heap, c->state.d_n, c->state.d_T, L.entered, c->k,
+                                 L.planes, L.tile_first, c->W4, c->tab.d_qp, c->tab.d_amb_q, c->stats.d_stats, L.q0, L.tmin, c->replay_prio);
+    else if (c->acgt) { if (c->n_idx_c > 0) REPLAY2_PF(true, true) else REPLAY2_PF(true, false) }
+    else              { if (c->n_idx_c > 0) REPLAY2_PF(false, true) else REPLAY2_PF(false, false) }
 #undef REPLAY2_PF
 #undef REPLAY2
   }

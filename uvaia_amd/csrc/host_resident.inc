@@ -207,13 +207,19 @@ static std::vector<SubSlice> plan_subslices(const uvaia_gpu_ctx *c, size_t first
     // one launch, not a full one plus a sliver whose launch latency and replay would sit on the critical path
     const size_t len = pe - a, ns = std::max<size_t>(1, (len + sub / 2) / sub);
     const size_t each = ((len + ns - 1) / ns + 63) / 64 * 64;
-    // A pool's first slice is 70 % of an equal share: the first replay -- the heaps filling and turning over, the longest of the chain of
+    // A pool's first slice was 70 % of an equal share from round 4 on (and is where tuning.scan_streams asks for a share): the first replay -- the heaps filling and turning over, the longest of the chain of
     // replays, which ends a step at config[1] -- starts that much earlier, and so does the first scan after a rebuild of the derived planes
     // (round 4, one box, interleaved twice: 3.16 ms per step with equal slices, 3.14-3.16 / 3.00-3.07 / 3.07 with 50 / 65 / 80 %; again
     // behind the asynchronous reset and the unfenced rebuild, interleaved three times: 2.944 / 2.887 / 2.918 / 2.928 with 50 / 65 / 70 / 80 %,
     // the same configuration run twice 2.918 and 2.951 -- no difference to tell from that: 70 % stays).
-    if (c->first_slice_pct > 0 && c->first_slice_pct < 100 && ns >= 3 && !c->subslice_forced) {
-      const size_t first_n = std::max<size_t>(64, each * (size_t)c->first_slice_pct / 100 / 64 * 64), rest = len - first_n;
+    // With replay2_lean_kernel the chain of replays has slack at config[1] (its third replay ends 0.22 ms before the last scan does) and the
+    // scans are the step: a short first slice only makes their launches less even.  Interleaved three times, 50 / 60 / 70 / 80 / 90 % and
+    // equal slices: 2.726 / 2.724 / 2.722 / 2.701 / 2.675 / 2.669 ms per step (medians; the parent's spread over five runs is 0.028) -- equal
+    // slices are the default where that kernel runs (elsewhere the 70 % stays: nothing measured there speaks for a change -- config[2], --acgt,
+    // with equal slices 200.4 against 199.8 ms per step, inside the parent's spread of 1.4), and the share stays a tuning value.
+    const int first_pct = c->first_slice_pct >= 0 ? c->first_slice_pct : ((lean_replay_context(c) && c->replay_lq == 0) ? 0 : 70);
+    if (first_pct > 0 && first_pct < 100 && ns >= 3 && !c->subslice_forced) {
+      const size_t first_n = std::max<size_t>(64, each * (size_t)first_pct / 100 / 64 * 64), rest = len - first_n;
       const size_t each2 = ((rest + (ns - 1) - 1) / (ns - 1) + 63) / 64 * 64;
       subs.push_back({a, first_n, true});
       for (size_t x = a + first_n; x < pe; x += each2) subs.push_back({x, std::min(each2, pe - x), false});

@@ -745,6 +745,173 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
 #undef TT_ADD
 }
 
+// replay2_kernel<false, false, 2> for heaps of at most 127 entries and the query's planes read from memory (no LDS copy): the regime of a
+// large query set in default mode without constant-and-complete columns.  The same machine -- the tile bounds select the tiles, D of them in
+// flight in stream order, the same ballot, the same exact comparison (wave_iupac_request / wave_iupac_finish, assemble_scores, lex_better),
+// the same heap operations --, written so that a wave keeps 128 registers or fewer (DESIGN.md 4.4: one such wave on a SIMD leaves room for
+// three blocks of the scan on the compute unit instead of two):
+//   * one copy of the per-tile body: the group is a bit mask of the tiles in flight, their counters a queue that moves up by one per tile;
+//   * two request slots with fixed roles (`cur`: the candidate at the head of the mask, `nxt`: the one behind it) instead of slots that are
+//     searched and matched per candidate;
+//   * what is uniform over the wave -- the worst kept keys, the candidate's scores -- is held as scalars;
+//   * no argument, array or branch of --acgt, of the consensus pre-score or of the larger heaps.
+__global__ __launch_bounds__(64) void replay2_lean_kernel(const uint32_t *__restrict__ cnt /* first | second << 16 per pair */, int ppad, const int *__restrict__ nonn, const int *__restrict__ amb,
+                                                           int r_begin, int r_end, long long ord_base, int *__restrict__ heap_g, int *__restrict__ n_g, int *__restrict__ T_g,
+                                                           uint8_t *__restrict__ entered, int k /* <= 127 */, const uint4 *__restrict__ db, long long tile_first, int W4,
+                                                           const uint32_t *__restrict__ qfull, const int *__restrict__ amb_q, unsigned long long *__restrict__ stats, int q_first,
+                                                           const int2 *__restrict__ tmin, int prio_)
+{
+  extern __shared__ int h[];
+  if (prio_) __builtin_amdgcn_s_setprio(3);
+  const int q = blockIdx.x + q_first, lane = threadIdx.x;
+  int *hg = heap_g + (size_t)q * (k + 1) * HEAP_ENTRY;
+  int n = min(max(n_g[q], 0), k), T = T_g[q];       // clamp: an imported state blob is external input
+  for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) h[i] = hg[i];
+  __syncthreads();
+  bool full = (n == k);
+  int W[6] = {0, 0, 0, 0, 0, 0};
+  int mc = 0;
+  if (full) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) W[i] = __builtin_amdgcn_readfirstlane(h[HEAP_ENTRY + i]);
+    mc = wave_minchild_init(h, n, lane);
+  }
+  const uint32_t *crow = cnt + (size_t)q * ppad;
+  const uint32_t *qw = qfull + (size_t)q * W4 * 4 * 6;
+  const int aqv = (lane < AMB_STRIDE) ? amb_q[(size_t)q * AMB_STRIDE + lane] : 0;      // the query's ambiguity-word list, one int per lane
+  const int aq_n = __builtin_amdgcn_readlane(aqv, 0);                                   // how many words it lists
+  const int aq_w = __shfl(aqv, 1 + ((lane < aq_n && lane < AMB_CAP) ? lane : 0));       // lane l: the l-th listed word
+  uint32_t *qlisted = reinterpret_cast<uint32_t *>(h + (k + 1) * HEAP_ENTRY);           // 32-word bitmap of the listed words
+  if (lane < 32) qlisted[lane] = 0u;
+  __syncthreads();
+  if (lane < aq_n && aq_n <= AMB_CAP) atomicOr(&qlisted[aq_w >> 5], 1u << (aq_w & 31));
+  __syncthreads();
+  bool dirty = false;
+  unsigned n_admit = 0, n_demand = 0, n_dense = 0;
+  const bool use_tmin = tmin != nullptr;
+  const int2 *tmrow = use_tmin ? tmin + (size_t)q * (ppad >> 6) : nullptr;
+  const int n_slice_tiles = (r_end + 63) >> 6;
+  constexpr int D = 8, PD = 4;      // tiles in flight; rounds of bounds requested ahead (as replay2_kernel)
+  int2 nbq[PD];
+#pragma unroll
+  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
+  for (int tb = 0; tb < n_slice_tiles; tb += 64) {
+    int tm = 0x7fffffff, tk = 0x7fffffff;            // tile bounds: smallest mismatch count, largest first key
+    if (tb + lane < n_slice_tiles) { tm = nbq[0].x; tk = nbq[0].y; }
+#pragma unroll
+    for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];
+    if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];
+    auto needed = [&]() -> unsigned long long { return __ballot(tm < T && (!full || tk >= W[0])); };
+    unsigned long long P = needed();
+    while (P) {
+      // the group: the first D needed tiles, their counters requested together (unpacked where they are used)
+      unsigned long long G;
+      uint32_t craw[D];
+      {
+        unsigned long long rest = P;
+#pragma unroll
+        for (int i = 0; i < D; i++) {
+          craw[i] = 0u;
+          if (rest) {
+            const int r = (tb + (__ffsll((long long)rest) - 1)) * 64 + lane;
+            if (r >= r_begin && r < r_end) craw[i] = crow[r];
+            rest &= rest - 1;
+          }
+        }
+        G = P & ~rest;
+      }
+#pragma unroll 1
+      while (G) {
+        const int t = __ffsll((long long)G) - 1;     // the tile at the head of the group; G keeps the ones behind it
+        G &= G - 1;
+        const uint32_t c0 = craw[0];
+#pragma unroll
+        for (int i = 0; i + 1 < D; i++) craw[i] = craw[i + 1];
+        const int K0 = (int)(c0 & 0xFFFFu), K3 = (int)(c0 >> 16);       // ACGT matches, the pair's valid count
+        const int T_used = T;
+        const int base_u = (tb + t) * 64;
+        const bool valid = (base_u + lane >= r_begin && base_u + lane < r_end);
+        auto may_enter = [&]() -> bool { return valid && K3 - K0 < T && (!full || K0 >= W[0]); };
+        unsigned long long mask = __ballot(may_enter());
+        auto request = [&](int i_) -> ExtraReq {
+          const int rl_ = base_u + i_;
+          ExtraReq e = wave_iupac_request(db, (size_t)tile_first + (size_t)(rl_ >> 6), rl_ & 63, W4, amb + (size_t)rl_ * AMB_ROW, aq_n, aq_w, lane);
+          e.nn = nonn[rl_];
+          return e;
+        };
+        // the head of the mask and the candidate behind it are kept requested: the requests depend on the reference only, so one whose
+        // candidate drops out of the mask after an admission is merely wasted
+        ExtraReq nxt;
+        int nxt_i = -1;
+        while (mask) {
+          const int i = __ffsll((long long)mask) - 1;
+          const unsigned long long behind = mask & (mask - 1);
+          const int i2 = behind ? (__ffsll((long long)behind) - 1) : -1;
+          ExtraReq cur;
+          if (nxt_i == i) { cur = nxt; nxt_i = -1; }
+          else cur = request(i);
+          if (i2 >= 0 && nxt_i != i2) { nxt = request(i2); nxt_i = i2; }
+          const int rl = base_u + i;                                      // index relative to the first tile of the batch
+          const int cx = __builtin_amdgcn_readlane(K0, i), cy = __builtin_amdgcn_readlane(K3, i);
+          const size_t tile_abs = (size_t)tile_first + (size_t)(rl >> 6);
+          int Si[6], mi;
+          n_demand++;
+          bool dense;
+          const int2 d = wave_iupac_finish(cur, db, tile_abs, rl & 63, W4, qw, qlisted, aq_n, lane, dense);
+          n_dense += dense;
+          const int dx = __builtin_amdgcn_readfirstlane(d.x), dy = __builtin_amdgcn_readfirstlane(d.y);
+          assemble_scores<false>(make_int4(cx, cx + dx, cx + dx + dy, cy), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), __builtin_amdgcn_readfirstlane(cur.nn), Si, mi);
+          const bool accept = (mi < T) && (!full || lex_better(Si, W));   // src/nearest.c:488-496 + heap_insert :93-117
+          if (!accept) { mask = behind; continue; }
+          {
+            const long long ord = ord_base + (rl - r_begin);
+            int v = (int)(unsigned)(ord & 0xffffffffll);                   // lanes l and l + 8 hold int l of the new entry
+            if ((lane & 7) == 7) v = (int)(ord >> 32);
+#pragma unroll
+            for (int sidx = 0; sidx < 6; sidx++) if ((lane & 7) == sidx) v = Si[sidx];
+            if (lane == 0) entered[rl] = 1;
+            if (full) wave_replace_root_mc(h, n, v, mc, lane, W, Si);      // (leaves the new root's keys in W)
+            else {
+              if (lane < HEAP_ENTRY) h[(n + 1) * HEAP_ENTRY + lane] = v;
+              __syncthreads();
+              wave_sift_up(h, n + 1, lane);
+            }
+          }
+          const bool was_full = full;
+          if (!full) n++;
+          dirty = true; n_admit++;
+          __syncthreads();
+          full = (n == k);
+          if (full) {
+            if (!was_full) {
+#pragma unroll
+              for (int sidx = 0; sidx < 6; sidx++) W[sidx] = __builtin_amdgcn_readfirstlane(h[HEAP_ENTRY + sidx]);
+              mc = wave_minchild_init(h, n, lane);
+            }
+            T = entry_mismatches<false>(W) + 1;                            // src/nearest.c:506-508
+          }
+          mask = __ballot(lane > i && may_enter());
+        }
+        P &= ~(1ull << t);                                                // this tile is done
+        if (T != T_used) {
+          // Needed tiles under the new tolerance, after this one.  A lower tolerance only removes tiles: the ones in flight are
+          // processed anyway (their ballots come out empty).  A higher tolerance can add a tile that lies BEFORE the last tile in
+          // flight; only then is the group formed again to keep the stream order.
+          P = needed() & ~((2ull << t) - 1ull);
+          if (T > T_used && G && (P & ~G & ((1ull << (63 - __clzll((long long)G))) - 1ull)) != 0ull) break;
+          P |= G;                                                         // keep the tiles in flight in the pending set
+        }
+      }
+    }
+  }
+  if (dirty) {
+    __syncthreads();
+    for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) hg[i] = h[i];
+    if (lane == 0) { n_g[q] = n; T_g[q] = T; }
+  }
+  if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned long long)n_admit); atomicAdd(&stats[1], (unsigned long long)n_demand); atomicAdd(&stats[2], (unsigned long long)n_dense); }
+}
+
 // Replay over the packed-plane scan that also left the other two counters of every pair (scan2_extras: `ext`), default mode.
 // The same machine as replay2_kernel -- one wave per query, the tile bounds walked 64 at a time, only tiles that can admit under the
 // present state are opened, in stream order -- rebuilt around two facts about a handful of queries:
