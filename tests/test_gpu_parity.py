@@ -46,6 +46,9 @@ def synth():
 @pytest.mark.parametrize("acgt", [False, True])
 @pytest.mark.parametrize("trim", [0, 230])
 def test_allpairs_counts_synthetic(synth, acgt, trim):
+    """40 queries x 300 references, untruncated counts of the FOUR-counter kernels (scan_iupac_kernel / scan_acgt_kernel): outside the wide path
+    uvaia_gpu_last_batch_scores recounts the batch with launch_scan, it does not read what scan3_kernel or scan2_*_kernel wrote (their
+    counters: tests/test_scan_edges_gpu.py)."""
     refs, qs = synth
     q = O.Query(qs, _names(len(qs), "q"), trim=trim, acgt=acgt)
     want = q.allpairs(refs[:300])
@@ -57,7 +60,8 @@ def test_allpairs_counts_synthetic(synth, acgt, trim):
 
 @pytest.mark.parametrize("acgt", [False, True])
 def test_allpairs_counts_bundled(bundled_db, acgt):
-    """16 queries x 512 references of the reference's own alignment, untruncated counts, trim 0 and 230."""
+    """16 queries x 512 references of the reference's own alignment, untruncated counts, trim 0 and 230: the four-counter kernels
+    (scan_iupac_kernel / scan_acgt_kernel), by the recount of uvaia_gpu_last_batch_scores -- not the two-counter scans of the search itself."""
     names, seqs = bundled_db
     by = dict(zip(names, seqs))
     qn = F.sample_names_1k()[:16]
