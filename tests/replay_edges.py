@@ -8,7 +8,7 @@ Deterministic and seeded; no GPU code here.  tests/test_replay_edges_cpu.py show
 tests/test_replay_edges_gpu.py runs the inputs on the device.
 
 The edge table: which line each group is aimed at (kernels_replay.inc unless another file is named).
-  R  rounds of tile bounds, the ring   replay2_kernel / replay2_lean_kernel: `nbq[i] = tmrow[i * 64 + lane];`  `for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];`
+  R  rounds of tile bounds, the ring   replay2_kernel / replay2_lean_kernel (replay_bounds_start, replay_bounds_next): `nbq[i] = tmrow[i * 64 + lane];`  `for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];`
                                        `if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];`
                                        replay3_kernel: `lds_dma_dwordx4(src, bring_lds + (uint32_t)(r & (BR - 1)) * 1024u);`  `for (int r = 0; r < 9; r++) fetch_bounds(r);`
                                        `if ((rnd & 3) == 3) {`  `for (int r = rnd + 6; r < rnd + 10; r++) fetch_bounds(r);`  `const uint4 tbv = bring[(rnd & (BR - 1)) * 64 + lane];`
@@ -19,17 +19,18 @@ The edge table: which line each group is aimed at (kernels_replay.inc unless ano
                                        replay3_kernel: `if (!((have[b] >> tsel) & 1ull)) {`  `if (hb + 1 < NSUB) { have[b ^ 1] = needed(tbv) & (SUB0 << (HALF * (hb + 1)));`
                                        `if (admitted_here || T != T_used) P = needed(tbv) & half_mask & ~((2ull << tsel) - 1ull);`
   H  heap layout                       `static __device__ __forceinline__ int wave_minchild_init(` : `if (better) mcv = c + 1;`  wave_replace_root_mc: `if (D == d && ahead) D = d + 1;`
-                                       `if (lane == nd) mc = left_ahead ? cc + 1 : cc;`  `const bool use_mc = k <= 127;`  wave_replace_root: `p = b2 ? c + 1 : c;`
-                                       heap_sift_down (replay_kernel): `if (c + i <= n && entry_better(h + pick * HEAP_ENTRY, h + (c + i) * HEAP_ENTRY)) pick = c + i;`  wave_sift_up
+                                       `if (lane == nd) mc = left_ahead ? cc + 1 : cc;`  replay_heap_state: `const bool use_mc = k <= 127;`  wave_replace_root: `p = b2 ? c + 1 : c;`
+                                       heap_sift_down (replay_kernel): `if (c + i <= n && lex_better(h + pick * HEAP_ENTRY, h + (c + i) * HEAP_ENTRY)) pick = c + i;`  wave_sift_up
+                                       replay_admit (the other three kernels): `if (!(was_full && use_mc)) replay_worst_keys<LEAN>(h, W);`  `if (!was_full && use_mc) mc = wave_minchild_init(h, n, lane);`
   K  the key ladder                    `static __device__ __forceinline__ bool lex_better(`  replay2_kernel may_enter: `return K3[u] >= W[3];`  `return K0[u] >= W[0];`
-                                       `const bool accept = (mi < T) && (!full || lex_better(Si, W));`  `mask = __ballot(lane > i && may_enter());`  replay3_kernel: `return lex_better(S, W);`
+                                       replay_kernel, replay_exact_default: `const bool accept = (mi < T) && (!full || lex_better(Si, W));`  `mask = __ballot(lane > i && may_enter());`  replay3_kernel: `return lex_better(S, W);`
   T  the tolerance and the bounds      replay3_kernel needed: `for (int i = TB8_N - 2; i >= 0; i--) if (TB8_THR[i] >= T - 1) j = i;`  `return __ballot(e != 0u && (!full || (int)e > W[0]));`
                                        kernels_scan2.inc: `__device__ constexpr int TB8_THR[TB8_N - 1] = {0, 1, 2, 3, 5, 8, 14};`  tile_bounds8: `(in_batch && (j == TB8_N - 1 || mm <= TB8_THR[j]))`
                                        replay2_kernel needed: `return __ballot((tm < T || (CONS && snap < T)) && (!full || tk >= W[0]));`
   S  slow pairs                        wave_iupac_request: `if (nq <= AMB_CAP) {`  `} else if (lane < nq + AMB_CAP) {`  wave_iupac_finish: `dense = (nr > AMB_CAP || nq > AMB_CAP);`
                                        `const bool mine = lane < nq || (lane < nq + nr && !((qlisted[e.w >> 5] >> (e.w & 31)) & 1u));`  replay3_kernel: `const bool slow = cut || xraw == EXT_UNKNOWN;`
                                        `if (slow) return K0 >= W[0];`  `const bool cut = CONS && mc_true >= snap;`  kernels_scan2.inc: `ext[(size_t)q * ppad + r] = (r_known && aqn[i] <= AMB_CAP) ?`
-  F  range ends                        `e[6] = (int)(unsigned)(ord & 0xffffffffll); e[7] = (int)(ord >> 32);`  `if ((lane & 7) == 7) v = (int)(ord >> 32);`  `const long long ord = ord_base + (rl - r_begin);`
+  F  range ends                        replay_kernel: `e[6] = (int)(unsigned)(ord & 0xffffffffll); e[7] = (int)(ord >> 32);`  replay_admit: `if ((lane & 7) == 7) v = (int)(ord >> 32);`  `const long long ord = ord_base + (rl - r_begin);`
                                        `const bool valid = (base_u + lane >= r_begin) && (base_u + lane < r_end);`  host_open.inc: `if (c->nchar > 49000) c->fullscan = true;`
                                        `return !c ? -2 : c->fullscan ? -1 : c->scan_variant;`  host_launch.inc: `if (c->fullscan) {` of launch_replay, `bool lean = lean_replay_context(c) && L.prefetch == 2 && lq_words == 0;`
                                        host_open.inc: `c->use_ext = !c->fullscan && !c->acgt && tn.replay_extras != 1 && (c->scan_variant == 0 ||`  `c->replay_half = (want_half == 32 || want_half == 16 || want_half == 8) ? want_half : c->nq <= 8 ? 32 : c->nq <= 24 ? 16 : 8;`"""

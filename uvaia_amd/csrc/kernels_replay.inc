@@ -3,6 +3,14 @@
 // ------------------------------------------------------------------------------------------------------------
 // device: score assembly and the ordered gate / heap replay
 // ------------------------------------------------------------------------------------------------------------
+// probes of a -DREPLAY_TIMING build (replay2_kernel, replay3_kernel): wall-clock ticks of a stretch of code added to an accumulator
+#ifdef REPLAY_TIMING
+#define TT_START(x) const unsigned long long x = wall_clock64()
+#define TT_ADD(acc, x) acc += wall_clock64() - x
+#else
+#define TT_START(x)
+#define TT_ADD(acc, x)
+#endif
 // Assembles score[6] exactly as src/nearest.c:499-501 (default) or :464-469 (--acgt) from
 //   cnt = pair counters over all compared columns, rt = untruncated consensus counters over idx_c,
 //   rc  = the consensus counters the reference would hold in cq->res (possibly truncated), nn = cq->non_n.
@@ -38,17 +46,11 @@ static __device__ __forceinline__ bool lex_better(const int a[6], const int b[6]
   return false;
 }
 
-static __device__ __forceinline__ bool entry_better(const int *a, const int *b)
-{
-  for (int i = 0; i < 6; i++) { if (a[i] != b[i]) return a[i] > b[i]; }
-  return false;
-}
-
 static __device__ void heap_sift_down(int *h, int n, int p)
 { // heap_bubble_down, src/min_heap.c:119-133: root = worst; swap towards the worse child while p is better than it
   for (;;) {
     int c = 2 * p, pick = p;
-    for (int i = 0; i < 2; i++) if (c + i <= n && entry_better(h + pick * HEAP_ENTRY, h + (c + i) * HEAP_ENTRY)) pick = c + i;
+    for (int i = 0; i < 2; i++) if (c + i <= n && lex_better(h + pick * HEAP_ENTRY, h + (c + i) * HEAP_ENTRY)) pick = c + i;
     if (pick == p) return;
     for (int i = 0; i < HEAP_ENTRY; i++) { int tmp = h[p * HEAP_ENTRY + i]; h[p * HEAP_ENTRY + i] = h[pick * HEAP_ENTRY + i]; h[pick * HEAP_ENTRY + i] = tmp; }
     p = pick;
@@ -59,7 +61,7 @@ static __device__ void heap_sift_up(int *h, int i)
 { // heap_bubble_up, src/min_heap.c:135-147
   while (i > 1) {
     const int parent = i / 2;
-    if (!entry_better(h + parent * HEAP_ENTRY, h + i * HEAP_ENTRY)) return;
+    if (!lex_better(h + parent * HEAP_ENTRY, h + i * HEAP_ENTRY)) return;
     for (int k = 0; k < HEAP_ENTRY; k++) { int tmp = h[parent * HEAP_ENTRY + k]; h[parent * HEAP_ENTRY + k] = h[i * HEAP_ENTRY + k]; h[i * HEAP_ENTRY + k] = tmp; }
     i = parent;
   }
@@ -446,6 +448,135 @@ static __device__ int wave_dense_poly_mismatches(const uint4 *__restrict__ polyp
   return wave_sum_dpp(mp);
 }
 
+// ---- what replay2_kernel, replay2_lean_kernel and replay3_kernel share: the state of a query's heap around the walk, the exact
+// evaluation of a default-mode candidate and the admission.  One wave per block, uniform control flow; the barriers are counted in
+// the comments because each kernel keeps the ones it had.  LEAN (replay2_lean_kernel): what is uniform over the wave is forced into
+// scalars (v_readfirstlane), and the heap has at most 127 entries.
+template <bool LEAN> static __device__ __forceinline__ void replay_worst_keys(const int *h, int (&W)[6])
+{ // the keys of the root (the worst kept entry)
+#pragma unroll
+  for (int i = 0; i < 6; i++) W[i] = LEAN ? __builtin_amdgcn_readfirstlane(h[HEAP_ENTRY + i]) : h[HEAP_ENTRY + i];
+}
+
+// the heap of a query from memory into LDS, no barrier: the caller's next one publishes it.  Returns the clamped entry count.
+static __device__ __forceinline__ int replay_load_heap(int *h, const int *__restrict__ hg, int n_stored, int k, int lane)
+{
+  const int n = min(max(n_stored, 0), k);           // clamp: an imported state blob is external input
+  for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) h[i] = hg[i];
+  return n;
+}
+
+// full, W and mc of the heap in LDS (behind a barrier after replay_load_heap); returns use_mc
+template <bool LEAN> static __device__ __forceinline__ bool replay_heap_state(const int *h, int n, int k, int lane, bool &full, int (&W)[6], int &mc)
+{
+  const bool use_mc = k <= 127;                     // every inner node of the heap has a lane: root replacement along the worse-child path (wave_replace_root_mc)
+  full = (n == k);
+#pragma unroll
+  for (int i = 0; i < 6; i++) W[i] = 0;
+  mc = 0;
+  if (full) {
+    replay_worst_keys<LEAN>(h, W);
+    if (LEAN || use_mc) mc = wave_minchild_init(h, n, lane);
+  }
+  return LEAN || use_mc;
+}
+
+// The query's ambiguity-word list, one int per lane: how many words it lists (aq_n), lane l's listed word (aq_w), and the 32-word LDS
+// bitmap of the listed words.  Two barriers: the first one also publishes what the caller wrote to LDS before the call.
+template <bool LEAN> static __device__ __forceinline__ void replay_query_listed(const int *__restrict__ amb_q, int q, int lane, uint32_t *qlisted, int &aq_n, int &aq_w)
+{
+  const int aqv = (lane < AMB_STRIDE) ? amb_q[(size_t)q * AMB_STRIDE + lane] : 0;
+  aq_n = LEAN ? __builtin_amdgcn_readlane(aqv, 0) : __shfl(aqv, 0);
+  aq_w = __shfl(aqv, 1 + ((lane < aq_n && lane < AMB_CAP) ? lane : 0));
+  if (lane < 32) qlisted[lane] = 0u;
+  __syncthreads();
+  if (lane < aq_n && aq_n <= AMB_CAP) atomicOr(&qlisted[aq_w >> 5], 1u << (aq_w & 31));
+  __syncthreads();
+}
+
+// the end of a replay: heap, entry count and tolerance back to memory if an admission changed them (one barrier), the counters to `stats`
+static __device__ __forceinline__ void replay_store_state(const int *h, int *__restrict__ hg, int *__restrict__ n_g, int *__restrict__ T_g, int q, int n, int T, bool dirty,
+                                                          unsigned long long *__restrict__ stats, unsigned n_admit, unsigned n_demand, unsigned n_dense, int lane)
+{
+  if (dirty) {
+    __syncthreads();
+    for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) hg[i] = h[i];
+    if (lane == 0) { n_g[q] = n; T_g[q] = T; }
+  }
+  if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned long long)n_admit); atomicAdd(&stats[1], (unsigned long long)n_demand); atomicAdd(&stats[2], (unsigned long long)n_dense); }
+}
+
+// Bounds of the next 64-tile rounds, requested PD rounds ahead (replay2_kernel, replay2_lean_kernel): with few queries (a handful of
+// waves next to a scan that saturates HBM) the walk over the bounds is a chain of dependent loads, and most rounds need nothing but
+// their bounds.  Lane l holds tile l of each round: smallest mismatch count (.x), largest first key (.y).
+constexpr int PD = 4;
+static __device__ __forceinline__ void replay_bounds_start(int2 (&nbq)[PD], const int2 *__restrict__ tmrow, bool use_tmin, int n_slice_tiles, int lane)
+{
+#pragma unroll
+  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
+}
+
+// the bounds of round tb / 64 (0x7fffffff twice for a tile past the slice); the queue moves up and round tb / 64 + PD is requested
+static __device__ __forceinline__ int2 replay_bounds_next(int2 (&nbq)[PD], const int2 *__restrict__ tmrow, bool use_tmin, int n_slice_tiles, int tb, int lane)
+{
+  int2 b = make_int2(0x7fffffff, 0x7fffffff);
+  if (tb + lane < n_slice_tiles) b = nbq[0];
+#pragma unroll
+  for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];
+  if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];
+  return b;
+}
+
+// Exact evaluation of a default-mode candidate whose on-demand words were requested (`cur`): its other two counters, score[] as
+// src/nearest.c:499-501 assembles it, the test of src/nearest.c:488-496 + heap_insert (src/min_heap.c:93-117).  cx, cy: the pair's two scan
+// counters; ai, ri: its consensus counters, untruncated and as cq->res holds them; nni: the reference's valid sites.
+template <bool LEAN>
+static __device__ __forceinline__ bool replay_exact_default(const ExtraReq &cur, const uint4 *__restrict__ db, size_t tile_abs, int lane_r, int W4, const uint32_t *qw, const uint32_t *qlisted,
+                                                            int aq_n, int lane, int cx, int cy, const int4 ai, const int4 ri, int nni, int T, bool full, const int (&W)[6],
+                                                            int (&Si)[6], unsigned &n_dense)
+{
+  bool dense;
+  int2 d = wave_iupac_finish(cur, db, tile_abs, lane_r, W4, qw, qlisted, aq_n, lane, dense);
+  n_dense += dense;
+  if (LEAN) d = make_int2(__builtin_amdgcn_readfirstlane(d.x), __builtin_amdgcn_readfirstlane(d.y));
+  int mi;
+  assemble_scores<false>(make_int4(cx, cx + d.x, cx + d.x + d.y, cy), ai, ri, nni, Si, mi);
+  const bool accept = (mi < T) && (!full || lex_better(Si, W));
+  return accept;
+}
+
+// Admission of the accepted candidate `rl` (index relative to the first tile of the batch) with scores Si: the entry built in lanes 0-7
+// and 8-15, its entered flag, the heap update -- root replacement along the worse-child path (use_mc), level by level (larger heaps), or
+// append + sift-up while the heap fills: the comparisons and swaps of src/min_heap.c:93-147, hence its layout --, then (behind a barrier)
+// full, the worst kept keys W unless wave_replace_root_mc left them, the worse-child lanes on the first fill, and the tolerance.
+template <bool ACGT, bool LEAN>
+static __device__ __forceinline__ void replay_admit(int *h, int k, int &n, int &T, bool &full, int (&W)[6], int &mc, const bool use_mc, const int (&Si)[6],
+                                                    long long ord_base, int r_begin, int rl, uint8_t *__restrict__ entered, int lane)
+{
+  const long long ord = ord_base + (rl - r_begin);
+  int v = (int)(unsigned)(ord & 0xffffffffll);                   // lanes l and l + 8 hold int l of the new entry
+  if ((lane & 7) == 7) v = (int)(ord >> 32);
+#pragma unroll
+  for (int sidx = 0; sidx < 6; sidx++) if ((lane & 7) == sidx) v = Si[sidx];
+  if (lane == 0) entered[rl] = 1;
+  if (full && use_mc) wave_replace_root_mc(h, n, v, mc, lane, W, Si);      // (leaves the new root's keys in W)
+  else if (full) wave_replace_root(h, n, v, lane);
+  else {
+    if (lane < HEAP_ENTRY) h[(n + 1) * HEAP_ENTRY + lane] = v;
+    __syncthreads();
+    wave_sift_up(h, n + 1, lane);
+  }
+  const bool was_full = full;
+  if (!full) n++;
+  __syncthreads();
+  full = (n == k);
+  if (full) {
+    if (!(was_full && use_mc)) replay_worst_keys<LEAN>(h, W);
+    if (!was_full && use_mc) mc = wave_minchild_init(h, n, lane);
+    T = entry_mismatches<ACGT>(W) + 1;                             // src/nearest.c:506-508 / :474-475
+  }
+}
+
 // Replay over the two-counter scan.  One wave per query walks the batch in reference order, 256 references per
 // round.  Between two admissions the heap state is constant, so the exact tests of src/nearest.c:488-496 and
 // src/min_heap.c:95 are evaluated for 64 references at once (ballot); the first survivor in order gets its missing
@@ -467,19 +598,12 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
   if (prio_) __builtin_amdgcn_s_setprio(3);     // few latency-bound waves on the critical path: win issue arbitration against co-resident scan waves
   const int q = blockIdx.x + q_first, lane = threadIdx.x;
   int *hg = heap_g + (size_t)q * (k + 1) * HEAP_ENTRY;
-  int n = min(max(n_g[q], 0), k), T = T_g[q];       // clamp: an imported state blob is external input
+  int n = replay_load_heap(h, hg, n_g[q], k, lane), T = T_g[q];
   const int snap = *snap_ptr;
-  for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) h[i] = hg[i];
   __syncthreads();
-  bool full = (n == k);
-  int W[6] = {0, 0, 0, 0, 0, 0};
-  const bool use_mc = k <= 127;                     // every inner node of the heap has a lane: root replacement along the worse-child path (wave_replace_root_mc)
-  int mc = 0;
-  if (full) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) W[i] = h[HEAP_ENTRY + i];
-    if (use_mc) mc = wave_minchild_init(h, n, lane);
-  }
+  bool full;
+  int W[6], mc;
+  const bool use_mc = replay_heap_state<false>(h, n, k, lane, full, W, mc);
   const uint32_t *crow = cnt + (size_t)q * ppad;
   const uint32_t *qrow = qfull + (size_t)q * W4 * 4 * (ACGT ? 4 : 6);
   // default mode: keep the query's full planes in LDS (behind the heap) when they fit; the on-demand counters then need a
@@ -490,23 +614,13 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
     for (int i = lane; i < lq_words; i += 64) lq[i] = qrow[i];
     qw = lq;
   }
-  const int aqv = (lane < AMB_STRIDE) ? amb_q[(size_t)q * AMB_STRIDE + lane] : 0;      // the query's ambiguity-word list, one int per lane
-  const int aq_n = __shfl(aqv, 0);                                                      // how many words it lists
-  const int aq_w = __shfl(aqv, 1 + ((lane < aq_n && lane < AMB_CAP) ? lane : 0));       // lane l: the l-th listed word
   uint32_t *qlisted = reinterpret_cast<uint32_t *>(h + (k + 1) * HEAP_ENTRY) + lq_words;   // 32-word bitmap of the listed words
-  if (lane < 32) qlisted[lane] = 0u;
-  __syncthreads();
-  if (lane < aq_n && aq_n <= AMB_CAP) atomicOr(&qlisted[aq_w >> 5], 1u << (aq_w & 31));
-  __syncthreads();
+  int aq_n, aq_w;
+  replay_query_listed<false>(amb_q, q, lane, qlisted, aq_n, aq_w);
   bool dirty = false;
   unsigned n_admit = 0, n_demand = 0, n_dense = 0;
 #ifdef REPLAY_TIMING
   unsigned long long t2_fetch = 0, t2_finish = 0, t2_heap = 0, t2_group = 0, n_trise = 0, n_groups = 0; const unsigned long long t2_begin = wall_clock64();
-#define TT_START(x) const unsigned long long x = wall_clock64()
-#define TT_ADD(acc, x) acc += wall_clock64() - x
-#else
-#define TT_START(x)
-#define TT_ADD(acc, x)
 #endif
   // prefetch: the counters of round i+1 are requested before round i is processed (the kernel is latency bound:
   // one wave per query, a few hundred dependent rounds)
@@ -519,18 +633,11 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
   const int2 *tmrow = use_tmin ? tmin + (size_t)q * (ppad >> 6) : nullptr;
   const int n_slice_tiles = (r_end + 63) >> 6;
   constexpr int D = 8;      // tiles whose counters are in flight (16 and 32 for a handful of queries measured 1.7x and 2x SLOWER in round 3: the bookkeeping of the group, not the latency, bounds the wave)
-  // bounds of the next 64-tile rounds, requested PD rounds ahead: with few queries (a handful of waves next to a scan that saturates
-  // HBM) the walk over the bounds is a chain of dependent loads, and most rounds need nothing but their bounds
-  constexpr int PD = 4;
   int2 nbq[PD];
-#pragma unroll
-  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
+  replay_bounds_start(nbq, tmrow, use_tmin, n_slice_tiles, lane);
   for (int tb = 0; tb < n_slice_tiles; tb += 64) {
-    int tm = 0x7fffffff, tk = 0x7fffffff;            // tile bounds: smallest mismatch count, largest first key
-    if (tb + lane < n_slice_tiles) { tm = nbq[0].x; tk = nbq[0].y; }
-#pragma unroll
-    for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];
-    if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];
+    const int2 tbound = replay_bounds_next(nbq, tmrow, use_tmin, n_slice_tiles, tb, lane);
+    const int tm = tbound.x, tk = tbound.y;          // tile bounds: smallest mismatch count, largest first key
     // a tile can admit only if some reference passes the gate and (heap full) some reference's first key reaches the worst kept one
     // With consensus counters (CONS) a pre-score cut short at the snapshot lowers a pair's mismatch count, but never below the
     // snapshot, and never raises its first key: the bounds stay valid with "tm < T" widened to "tm < T or snapshot < T".
@@ -663,52 +770,23 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
           const int nni = (CONS || ACGT) ? __builtin_amdgcn_readlane(nn[u], i) : cur.nn;
           const size_t tile_abs = (size_t)tile_first + (size_t)(rl >> 6);
           if (CONS && ((__ballot(cut[u]) >> i) & 1ull)) ri = wave_truncated_consensus<ACGT>(db, tile_abs, rl & 63, W4, cp_cons, snap, lane);   // ... the ones the cut walk returns
-          int Si[6], mi;
+          int Si[6];
+          bool accept;
           n_demand++;
           if (ACGT) {
             // with the column-compressed scan the dense count on the polymorphic columns IS score[5] (src/nearest.c:469)
             // dist_unique (src/nearest.c:469): with the column-compressed scan from the gathered planes of the polymorphic and the rare columns
             int mp = qpl ? wave_dense_poly_mismatches(polyp, tile_abs, rl & 63, NPT, NP4, qpl + (size_t)q * NP4 * 16, lane) : wave_acgt_poly_mismatches(db, tile_abs, rl & 63, W4, qrow, lane);
             if (qpl && NR4 > 0) mp += wave_rare_mismatches(polyp, tile_abs, rl & 63, NPT, NP4, NR4, qrare + (size_t)q * NR4 * 12, lane);
+            int mi;
             assemble_scores<true>(make_int4(cx, cy, mp, 0), ai, ri, nni, Si, mi);
-          } else {
-            bool dense;
-            const int2 d = wave_iupac_finish(cur, db, tile_abs, rl & 63, W4, qw, qlisted, aq_n, lane, dense);
-            n_dense += dense;
-            assemble_scores<false>(make_int4(cx, cx + d.x, cx + d.x + d.y, cy), ai, ri, nni, Si, mi);
-          }
-          const bool accept = (mi < T) && (!full || lex_better(Si, W));   // src/nearest.c:488-496 + heap_insert :93-117
+            accept = (mi < T) && (!full || lex_better(Si, W));            // src/nearest.c:488-496 + heap_insert :93-117
+          } else accept = replay_exact_default<false>(cur, db, tile_abs, rl & 63, W4, qw, qlisted, aq_n, lane, cx, cy, ai, ri, nni, T, full, W, Si, n_dense);
           TT_ADD(t2_finish, tfin_);
           if (!accept) { mask &= mask - 1; continue; }
           TT_START(th_);
-          {
-            const long long ord = ord_base + (rl - r_begin);
-            int v = (int)(unsigned)(ord & 0xffffffffll);                   // lanes l and l + 8 hold int l of the new entry
-            if ((lane & 7) == 7) v = (int)(ord >> 32);
-#pragma unroll
-            for (int sidx = 0; sidx < 6; sidx++) if ((lane & 7) == sidx) v = Si[sidx];
-            if (lane == 0) entered[rl] = 1;
-            if (full && use_mc) wave_replace_root_mc(h, n, v, mc, lane, W, Si);      // (leaves the new root's keys in W)
-            else if (full) wave_replace_root(h, n, v, lane);
-            else {
-              if (lane < HEAP_ENTRY) h[(n + 1) * HEAP_ENTRY + lane] = v;
-              __syncthreads();
-              wave_sift_up(h, n + 1, lane);
-            }
-          }
-          const bool was_full = full;
-          if (!full) n++;
+          replay_admit<ACGT, false>(h, k, n, T, full, W, mc, use_mc, Si, ord_base, r_begin, rl, entered, lane);
           dirty = true; n_admit++;
-          __syncthreads();
-          full = (n == k);
-          if (full) {
-            if (!(was_full && use_mc)) {
-#pragma unroll
-              for (int sidx = 0; sidx < 6; sidx++) W[sidx] = h[HEAP_ENTRY + sidx];
-            }
-            if (!was_full && use_mc) mc = wave_minchild_init(h, n, lane);
-            T = entry_mismatches<ACGT>(W) + 1;                             // src/nearest.c:506-508 / :474-475
-          }
           TT_ADD(t2_heap, th_);
           mask = __ballot(lane > i && may_enter());
         }
@@ -731,18 +809,11 @@ __global__ __launch_bounds__(64) void replay2_kernel(const uint32_t *__restrict_
       }
     }
   }
-  if (dirty) {
-    __syncthreads();
-    for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) hg[i] = h[i];
-    if (lane == 0) { n_g[q] = n; T_g[q] = T; }
-  }
-  if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned long long)n_admit); atomicAdd(&stats[1], (unsigned long long)n_demand); atomicAdd(&stats[2], (unsigned long long)n_dense); }
+  replay_store_state(h, hg, n_g, T_g, q, n, T, dirty, stats, n_admit, n_demand, n_dense, lane);
 #ifdef REPLAY_TIMING
   if (stats && lane == 0) { atomicAdd(&stats[4], t2_fetch); atomicAdd(&stats[5], t2_finish); atomicAdd(&stats[6], t2_heap); atomicAdd(&stats[7], t2_group); atomicAdd(&stats[8], n_trise); atomicAdd(&stats[9], n_groups);
                             atomicAdd(&stats[10], wall_clock64() - t2_begin); atomicMax(&stats[11], wall_clock64() - t2_begin); }
 #endif
-#undef TT_START
-#undef TT_ADD
 }
 
 // replay2_kernel<false, false, 2> for heaps of at most 127 entries and the query's planes read from memory (no LDS copy): the regime of a
@@ -765,42 +836,27 @@ __global__ __launch_bounds__(64) void replay2_lean_kernel(const uint32_t *__rest
   if (prio_) __builtin_amdgcn_s_setprio(3);
   const int q = blockIdx.x + q_first, lane = threadIdx.x;
   int *hg = heap_g + (size_t)q * (k + 1) * HEAP_ENTRY;
-  int n = min(max(n_g[q], 0), k), T = T_g[q];       // clamp: an imported state blob is external input
-  for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) h[i] = hg[i];
+  int n = replay_load_heap(h, hg, n_g[q], k, lane), T = T_g[q];
   __syncthreads();
-  bool full = (n == k);
-  int W[6] = {0, 0, 0, 0, 0, 0};
-  int mc = 0;
-  if (full) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) W[i] = __builtin_amdgcn_readfirstlane(h[HEAP_ENTRY + i]);
-    mc = wave_minchild_init(h, n, lane);
-  }
+  bool full;
+  int W[6], mc;
+  replay_heap_state<true>(h, n, k, lane, full, W, mc);
   const uint32_t *crow = cnt + (size_t)q * ppad;
   const uint32_t *qw = qfull + (size_t)q * W4 * 4 * 6;
-  const int aqv = (lane < AMB_STRIDE) ? amb_q[(size_t)q * AMB_STRIDE + lane] : 0;      // the query's ambiguity-word list, one int per lane
-  const int aq_n = __builtin_amdgcn_readlane(aqv, 0);                                   // how many words it lists
-  const int aq_w = __shfl(aqv, 1 + ((lane < aq_n && lane < AMB_CAP) ? lane : 0));       // lane l: the l-th listed word
   uint32_t *qlisted = reinterpret_cast<uint32_t *>(h + (k + 1) * HEAP_ENTRY);           // 32-word bitmap of the listed words
-  if (lane < 32) qlisted[lane] = 0u;
-  __syncthreads();
-  if (lane < aq_n && aq_n <= AMB_CAP) atomicOr(&qlisted[aq_w >> 5], 1u << (aq_w & 31));
-  __syncthreads();
+  int aq_n, aq_w;
+  replay_query_listed<true>(amb_q, q, lane, qlisted, aq_n, aq_w);
   bool dirty = false;
   unsigned n_admit = 0, n_demand = 0, n_dense = 0;
   const bool use_tmin = tmin != nullptr;
   const int2 *tmrow = use_tmin ? tmin + (size_t)q * (ppad >> 6) : nullptr;
   const int n_slice_tiles = (r_end + 63) >> 6;
-  constexpr int D = 8, PD = 4;      // tiles in flight; rounds of bounds requested ahead (as replay2_kernel)
+  constexpr int D = 8;              // tiles in flight (as replay2_kernel)
   int2 nbq[PD];
-#pragma unroll
-  for (int i = 0; i < PD; i++) { nbq[i] = make_int2(-1, 0x7fffffff); if (use_tmin && i * 64 + lane < n_slice_tiles) nbq[i] = tmrow[i * 64 + lane]; }
+  replay_bounds_start(nbq, tmrow, use_tmin, n_slice_tiles, lane);
   for (int tb = 0; tb < n_slice_tiles; tb += 64) {
-    int tm = 0x7fffffff, tk = 0x7fffffff;            // tile bounds: smallest mismatch count, largest first key
-    if (tb + lane < n_slice_tiles) { tm = nbq[0].x; tk = nbq[0].y; }
-#pragma unroll
-    for (int i = 0; i + 1 < PD; i++) nbq[i] = nbq[i + 1];
-    if (use_tmin && tb + PD * 64 + lane < n_slice_tiles) nbq[PD - 1] = tmrow[tb + PD * 64 + lane];
+    const int2 tbound = replay_bounds_next(nbq, tmrow, use_tmin, n_slice_tiles, tb, lane);
+    const int tm = tbound.x, tk = tbound.y;          // tile bounds: smallest mismatch count, largest first key
     auto needed = [&]() -> unsigned long long { return __ballot(tm < T && (!full || tk >= W[0])); };
     unsigned long long P = needed();
     while (P) {
@@ -854,42 +910,13 @@ __global__ __launch_bounds__(64) void replay2_lean_kernel(const uint32_t *__rest
           const int rl = base_u + i;                                      // index relative to the first tile of the batch
           const int cx = __builtin_amdgcn_readlane(K0, i), cy = __builtin_amdgcn_readlane(K3, i);
           const size_t tile_abs = (size_t)tile_first + (size_t)(rl >> 6);
-          int Si[6], mi;
+          int Si[6];
           n_demand++;
-          bool dense;
-          const int2 d = wave_iupac_finish(cur, db, tile_abs, rl & 63, W4, qw, qlisted, aq_n, lane, dense);
-          n_dense += dense;
-          const int dx = __builtin_amdgcn_readfirstlane(d.x), dy = __builtin_amdgcn_readfirstlane(d.y);
-          assemble_scores<false>(make_int4(cx, cx + dx, cx + dx + dy, cy), make_int4(0, 0, 0, 0), make_int4(0, 0, 0, 0), __builtin_amdgcn_readfirstlane(cur.nn), Si, mi);
-          const bool accept = (mi < T) && (!full || lex_better(Si, W));   // src/nearest.c:488-496 + heap_insert :93-117
+          const int4 zero = make_int4(0, 0, 0, 0);                        // no consensus counters in this regime
+          const bool accept = replay_exact_default<true>(cur, db, tile_abs, rl & 63, W4, qw, qlisted, aq_n, lane, cx, cy, zero, zero, __builtin_amdgcn_readfirstlane(cur.nn), T, full, W, Si, n_dense);
           if (!accept) { mask = behind; continue; }
-          {
-            const long long ord = ord_base + (rl - r_begin);
-            int v = (int)(unsigned)(ord & 0xffffffffll);                   // lanes l and l + 8 hold int l of the new entry
-            if ((lane & 7) == 7) v = (int)(ord >> 32);
-#pragma unroll
-            for (int sidx = 0; sidx < 6; sidx++) if ((lane & 7) == sidx) v = Si[sidx];
-            if (lane == 0) entered[rl] = 1;
-            if (full) wave_replace_root_mc(h, n, v, mc, lane, W, Si);      // (leaves the new root's keys in W)
-            else {
-              if (lane < HEAP_ENTRY) h[(n + 1) * HEAP_ENTRY + lane] = v;
-              __syncthreads();
-              wave_sift_up(h, n + 1, lane);
-            }
-          }
-          const bool was_full = full;
-          if (!full) n++;
+          replay_admit<false, true>(h, k, n, T, full, W, mc, true, Si, ord_base, r_begin, rl, entered, lane);
           dirty = true; n_admit++;
-          __syncthreads();
-          full = (n == k);
-          if (full) {
-            if (!was_full) {
-#pragma unroll
-              for (int sidx = 0; sidx < 6; sidx++) W[sidx] = __builtin_amdgcn_readfirstlane(h[HEAP_ENTRY + sidx]);
-              mc = wave_minchild_init(h, n, lane);
-            }
-            T = entry_mismatches<false>(W) + 1;                            // src/nearest.c:506-508
-          }
           mask = __ballot(lane > i && may_enter());
         }
         P &= ~(1ull << t);                                                // this tile is done
@@ -904,12 +931,7 @@ __global__ __launch_bounds__(64) void replay2_lean_kernel(const uint32_t *__rest
       }
     }
   }
-  if (dirty) {
-    __syncthreads();
-    for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) hg[i] = h[i];
-    if (lane == 0) { n_g[q] = n; T_g[q] = T; }
-  }
-  if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned long long)n_admit); atomicAdd(&stats[1], (unsigned long long)n_demand); atomicAdd(&stats[2], (unsigned long long)n_dense); }
+  replay_store_state(h, hg, n_g, T_g, q, n, T, dirty, stats, n_admit, n_demand, n_dense, lane);
 }
 
 // Replay over the packed-plane scan that also left the other two counters of every pair (scan2_extras: `ext`), default mode.
@@ -960,41 +982,24 @@ __global__ __launch_bounds__(64) void replay3_kernel(const uint32_t *__restrict_
   if (prio_) __builtin_amdgcn_s_setprio(3);
   const int q = blockIdx.x + q_first, lane = threadIdx.x;
   int *hg = heap_g + (size_t)q * (k + 1) * HEAP_ENTRY;
-  int n = min(max(n_g[q], 0), k), T = T_g[q];
+  int n = replay_load_heap(h, hg, n_g[q], k, lane), T = T_g[q];     // (no barrier of its own: replay_query_listed's first one publishes the heap)
   const int snap = *snap_ptr;
-  for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) h[i] = hg[i];
   const uint32_t *crow = cnt + (size_t)q * ppad, *xrow = ext + (size_t)q * ppad;
   const uint32_t *qrow = qfull + (size_t)q * W4 * 4 * 6;
-  const int aqv = (lane < AMB_STRIDE) ? amb_q[(size_t)q * AMB_STRIDE + lane] : 0;
-  const int aq_n = __shfl(aqv, 0);
-  const int aq_w = __shfl(aqv, 1 + ((lane < aq_n && lane < AMB_CAP) ? lane : 0));
   uint32_t *qlisted = reinterpret_cast<uint32_t *>(h + (k + 1) * HEAP_ENTRY);           // bitmap of the words the query lists (slow pairs)
   constexpr int BR = 16;                                                                // rounds of bounds the LDS ring holds
   uint4 *bring = reinterpret_cast<uint4 *>(qlisted + 32);                               // [BR][64] uint4: the bounds of round x in slot x & 15
   uint32_t *stage = reinterpret_cast<uint32_t *>(bring + BR * 64);                      // [2][HALF][NA][64] dwords
   const uint32_t stage_lds = (uint32_t)(uintptr_t)(replay_lds_void *)stage, bring_lds = (uint32_t)(uintptr_t)(replay_lds_void *)bring;
-  if (lane < 32) qlisted[lane] = 0u;
-  __syncthreads();
-  if (lane < aq_n && aq_n <= AMB_CAP) atomicOr(&qlisted[aq_w >> 5], 1u << (aq_w & 31));
-  __syncthreads();
-  bool full = (n == k);
-  int W[6] = {0, 0, 0, 0, 0, 0};
-  const bool use_mc = k <= 127;                               // every inner node of the heap has a lane: root replacement along the worse-child path
-  int mc = 0;
-  if (full) {
-#pragma unroll
-    for (int i = 0; i < 6; i++) W[i] = h[HEAP_ENTRY + i];
-    if (use_mc) mc = wave_minchild_init(h, n, lane);
-  }
+  int aq_n, aq_w;
+  replay_query_listed<false>(amb_q, q, lane, qlisted, aq_n, aq_w);
+  bool full;
+  int W[6], mc;
+  const bool use_mc = replay_heap_state<false>(h, n, k, lane, full, W, mc);
   bool dirty = false;
   unsigned n_admit = 0, n_demand = 0, n_dense = 0, n_open = 0;
 #ifdef REPLAY_TIMING
   unsigned long long tt_wait = 0, tt_fetch = 0, tt_admit = 0, tt_tile = 0, tt_late = 0, n_late = 0; const unsigned long long tt_begin = tt_kernel, tt_prologue_end = wall_clock64();
-#define TT_START(x) const unsigned long long x = wall_clock64()
-#define TT_ADD(acc, x) acc += wall_clock64() - x
-#else
-#define TT_START(x)
-#define TT_ADD(acc, x)
 #endif
   const uint4 *tmrow = tb8 + (size_t)q * (ppad >> 6);
   const int n_slice_tiles = (r_end + 63) >> 6, n_rounds = (n_slice_tiles + 63) >> 6;
@@ -1109,45 +1114,14 @@ __global__ __launch_bounds__(64) void replay3_kernel(const uint32_t *__restrict_
             if (CONS && ((cut_mask >> i) & 1ull)) ri = wave_truncated_consensus<false>(db, tile_abs, rl & 63, W4, cp_cons, snap, lane);
             n_demand++;
             const ExtraReq cur = wave_iupac_request(db, tile_abs, rl & 63, W4, amb + (size_t)rl * AMB_ROW, aq_n, aq_w, lane);
-            bool dense;
-            const int2 d = wave_iupac_finish(cur, db, tile_abs, rl & 63, W4, qrow, qlisted, aq_n, lane, dense);
-            n_dense += dense;
-            int mi;
-            assemble_scores<false>(make_int4(cx, cx + d.x, cx + d.x + d.y, cy), ai, ri, __builtin_amdgcn_readlane(nn, i), Si, mi);
-            const bool accept = (mi < T) && (!full || lex_better(Si, W));
+            const bool accept = replay_exact_default<false>(cur, db, tile_abs, rl & 63, W4, qrow, qlisted, aq_n, lane, cx, cy, ai, ri, __builtin_amdgcn_readlane(nn, i), T, full, W, Si, n_dense);
             if (!accept) { mask &= mask - 1; continue; }
           } else {                                            // the ballot ran the exact test under the present state
 #pragma unroll
             for (int s_ = 0; s_ < 6; s_++) Si[s_] = __builtin_amdgcn_readlane(S[s_], i);
           }
-          {
-            const long long ord = ord_base + (rl - r_begin);
-            int v = (int)(unsigned)(ord & 0xffffffffll);
-            if ((lane & 7) == 7) v = (int)(ord >> 32);
-#pragma unroll
-            for (int sidx = 0; sidx < 6; sidx++) if ((lane & 7) == sidx) v = Si[sidx];
-            if (lane == 0) entered[rl] = 1;
-            if (full && use_mc) wave_replace_root_mc(h, n, v, mc, lane, W, Si);      // (leaves the new root's keys in W)
-            else if (full) wave_replace_root(h, n, v, lane);
-            else {
-              if (lane < HEAP_ENTRY) h[(n + 1) * HEAP_ENTRY + lane] = v;
-              __syncthreads();
-              wave_sift_up(h, n + 1, lane);
-            }
-          }
-          const bool was_full = full;
-          if (!full) n++;
+          replay_admit<false, false>(h, k, n, T, full, W, mc, use_mc, Si, ord_base, r_begin, rl, entered, lane);
           dirty = true; n_admit++; admitted_here = true;
-          __syncthreads();
-          full = (n == k);
-          if (full) {
-            if (!(was_full && use_mc)) {
-#pragma unroll
-              for (int sidx = 0; sidx < 6; sidx++) W[sidx] = h[HEAP_ENTRY + sidx];
-            }
-            if (!was_full && use_mc) mc = wave_minchild_init(h, n, lane);
-            T = W[3] - W[0] + 1;                              // src/nearest.c:506-508
-          }
           mask = __ballot(lane > i && may_enter());
         }
         // the tiles still to open in this half under the new state, after this one: a higher worst key only removes tiles, a higher
@@ -1163,14 +1137,8 @@ __global__ __launch_bounds__(64) void replay3_kernel(const uint32_t *__restrict_
   if (lane == 0) { atomicAdd(&stats[4], tt_wait); atomicAdd(&stats[5], tt_fetch); atomicAdd(&stats[6], tt_tile); atomicAdd(&stats[7], tt_admit); atomicAdd(&stats[8], tt_late); atomicAdd(&stats[9], n_late); atomicAdd(&stats[10], wall_clock64() - tt_begin);
                    atomicAdd(&stats[11], tt_prologue_end - tt_kernel); atomicAdd(&stats[12], 1ull); }
 #endif
-#undef TT_START
-#undef TT_ADD
-  if (dirty) {
-    __syncthreads();
-    for (int i = lane; i < (n + 1) * HEAP_ENTRY; i += 64) hg[i] = h[i];
-    if (lane == 0) { n_g[q] = n; T_g[q] = T; }
-  }
-  if (stats && lane == 0) { atomicAdd(&stats[0], (unsigned long long)n_admit); atomicAdd(&stats[1], (unsigned long long)n_demand); atomicAdd(&stats[2], (unsigned long long)n_dense); atomicAdd(&stats[3], (unsigned long long)n_open); }
+  replay_store_state(h, hg, n_g, T_g, q, n, T, dirty, stats, n_admit, n_demand, n_dense, lane);
+  if (stats && lane == 0) atomicAdd(&stats[3], (unsigned long long)n_open);
 }
 
 // Redundancy test of exclude_redundant_query_sequences() (src/fastaseq.c:806-808): a sequence and a query "agree" when the
