@@ -232,3 +232,15 @@ def test_wavefronts_wider_than_the_lds_ring_equal_oracle(opts):
               max_distance_threshold=opts.get("max_distance_threshold", d.max_distance_threshold))
     with align.Aligner(ref, **opts) as al:
         _check(ref, [q, ref[:7000]], al, **kw)
+
+
+def test_one_aligner_across_pools_that_grow_and_shrink():
+    """3 queries take the 256 per-query slots an aligner starts with, 330 need all six per-query arrays made again, 5 then run in the
+    larger arrays: every pool's scores and rows are the oracle's"""
+    ref = F.random_acgt(400, 31)
+    with align.Aligner(ref) as al:
+        for n, seed in ((3, 32), (330, 33), (5, 34)):
+            seqs = F.unaligned_queries(ref, n, seed)
+            gold_score, gold_rows = O.uvaialign_batch(ref, seqs)
+            score, rows = al.align(seqs)
+            assert np.array_equal(score, gold_score) and np.array_equal(rows, gold_rows), n

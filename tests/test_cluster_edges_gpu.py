@@ -141,3 +141,53 @@ def test_packed_run_shapes(cut, n_queues):
     for i, (a, b) in enumerate(zip(got[2], rows)):
         assert a == b, (i, E.run_specs()[i // 2], [k for k in range(len(a)) if a[k] != b[k]][:8])
     _same(got[:2], CL.rs_cluster(ref, rows, q, 0, 0, 1, n_queues))
+
+
+# ------------------------------------------------------ E: the medoid lists and the row arrays grow while three queues hold entries
+GROW_PUSH = 150
+
+
+@pytest.fixture(scope="module")
+def grow():
+    ref = F.random_acgt(64, 1)
+    distinct = [F.random_acgt(64, 1000 + k) for k in range(800)]
+    seqs = distinct + [distinct[(7 * k) % 800] for k in range(300)]
+    first = {}
+    for k, s in enumerate(distinct):
+        first.setdefault(s, k)
+    queues = [first[s] % 3 for s in seqs]
+    return ref, seqs, queues, CL.rs_cluster(ref, seqs, queues, 0, 0, 2, 3)
+
+
+def test_growth_input_crosses_the_first_capacities(grow):
+    """what makes the growth paths matter: every queue founds more than the 256 medoid slots its lists start with, the rows pass the 1 024
+    the row arrays start with, and the rows pushed after that join founders whose entries were made before the arrays grew"""
+    ref, seqs, queues, want = grow
+    assert len(seqs) == 1100 and len(want[0]) == 800
+    founders = [m for m, _ in want[0]]
+    assert sorted(founders) == list(range(800))
+    assert [sum(1 for m in founders if queues[m] == q) for q in range(3)] == [267, 267, 266]
+    joined = [(m, o) for m, members in want[0] for o in members]
+    assert len(joined) == 300 and all(o >= 800 for _, o in joined)
+    assert sum(1 for m, _ in joined if m < 768) == 290
+
+
+@pytest.mark.parametrize("mode", ["default", "keep", "packed"])
+def test_medoid_lists_and_rows_grow_with_contents(grow, mode):
+    ref, seqs, queues, want = grow
+    with cluster.Clusterer(ref, dist=0, trim=0, n_score=2, n_queues=3) as c:
+        if mode == "keep":
+            c.keep_medoids(4)
+        for a in range(0, len(seqs), GROW_PUSH):
+            b = min(a + GROW_PUSH, len(seqs))
+            if mode == "packed" and a >= 600:
+                pk = E.Packed(seqs[a:b])
+                c.push_packed(pk.planes, pk.n, pk.off, pk.exc, queues[a:b])
+            else:
+                c.push(seqs[a:b], queues[a:b])
+        c.finish()
+        r = c.result()
+        med = r.medoid.tolist()
+        rows = c.rows(med)
+    _same((r.clusters(), r.scores), want, mode)
+    assert rows == [seqs[m] for m in med], mode

@@ -1,5 +1,5 @@
-// host_ctx.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): what the host side owns -- device buffers, pinned
-// blocks, events and streams behind move-only handles -- the tile stores and counter buffers made of them, and the context.  Everything a
+// host_ctx.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): what the host side owns -- the tile stores and
+// counter buffers made of the move-only handles of host_owners.h (device buffers, pinned blocks, events, streams) -- and the context.  Everything a
 // context holds is released by its destructor: uvaia_gpu_close waits for the streams, unmaps what it mapped from other processes and deletes.
 
 struct uvaia_gpu_ctx;
@@ -12,65 +12,16 @@ int fail(uvaia_gpu_ctx *c, int code, const char *fmt, ...);
 
 // One check for every HIP call; what happens on failure is the caller's hook (the code maps out-of-memory to UVAIA_GPU_ENOMEM).
 #define HIP_TRY(call, on_fail) do { hipError_t e_ = (call); if (e_ != hipSuccess) { const int code_ = e_ == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP; (void)code_; on_fail; } } while (0)
-// inside an entry point that has a context (or none: the message goes where uvaia_gpu_last_error(NULL) finds it): message, return the code
-#define HIPCHK(c, call) HIP_TRY(call, return fail((c), code_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__))
+// what HIPCHK (host_owners.h) does on failure, in an entry point that has a context (or none: the message goes where
+// uvaia_gpu_last_error(NULL) finds it) and in the handles: message, return the code
+inline int hip_failed(uvaia_gpu_ctx *c, hipError_t e, const char *call, const char *file, int line)
+{ return fail(c, e == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line); }
 
-// Device memory of `cap` elements.  reserve() is the one grow step: nothing happens while the capacity suffices; otherwise what was held
-// goes (contents are not kept), and the capacity is recorded only once the new array exists -- a failure leaves the buffer empty.
-template <class T> struct DevBuf {
-  T *p = nullptr; size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-  DevBuf &operator=(DevBuf &&o) noexcept { if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; } return *this; }
-  ~DevBuf() { release(); }
-  void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
-  int reserve(uvaia_gpu_ctx *c, size_t n)
-  {
-    if (n <= cap) return 0;
-    release();
-    HIPCHK(c, hipMalloc(&p, n * sizeof(T)));
-    cap = n;
-    return 0;
-  }
-  operator T *() const { return p; }
-};
+}  // namespace
 
-// a pinned host block
-struct PinnedBuf {
-  uint8_t *p = nullptr;
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { if (p) hipHostFree(p); }
-  int alloc(uvaia_gpu_ctx *c, size_t bytes) { HIPCHK(c, hipHostMalloc(&p, bytes, hipHostMallocDefault)); return 0; }
-  operator uint8_t *() const { return p; }
-};
+#include "host_owners.h"
 
-// an event, made by the first make() (later ones do nothing): with timing by default, or with the flags given
-struct Event {
-  hipEvent_t e = nullptr;
-  Event() = default;
-  Event(const Event &) = delete; Event &operator=(const Event &) = delete;
-  Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-  Event &operator=(Event &&o) noexcept { if (this != &o) { if (e) hipEventDestroy(e); e = o.e; o.e = nullptr; } return *this; }
-  ~Event() { if (e) hipEventDestroy(e); }
-  int make(uvaia_gpu_ctx *c, unsigned flags = 0)
-  {
-    if (e) return 0;
-    if (flags) HIPCHK(c, hipEventCreateWithFlags(&e, flags)); else HIPCHK(c, hipEventCreate(&e));
-    return 0;
-  }
-  operator hipEvent_t() const { return e; }
-};
-
-// a stream the holder created (s is filled by the hipStreamCreate* call that suits it); the holder waits for it before it goes
-struct Stream {
-  hipStream_t s = nullptr;
-  Stream() = default;
-  Stream(const Stream &) = delete; Stream &operator=(const Stream &) = delete;
-  ~Stream() { if (s) hipStreamDestroy(s); }
-  operator hipStream_t() const { return s; }
-};
+namespace {
 
 struct ScanEvt { Event a, b; double bytes = 0; };
 

@@ -527,25 +527,37 @@ thread_local std::string g_align_open_error;
 
 }  // namespace
 
+// ---- host side.  Device memory, events and the stream are the move-only handles of host_owners.h; a failed HIP call goes through hip_failed.
+struct uvaia_aligner;
+namespace { int hip_failed(uvaia_aligner *a, hipError_t e, const char *call, const char *file, int line); }
+#include <memory>
+#include "host_owners.h"
+
+// Members are destroyed last to first: the stream comes first so that it outlives every buffer and event that work queued on it may still
+// name (uvaia_align_close has waited for it by then).
 struct uvaia_aligner {
+  Stream stream;
+  Event ev_a, ev_b;
   int device = 0;
-  hipStream_t stream = nullptr;
   int plen = 0;
   WfaParams P{};
-  uint8_t *d_ref = nullptr, *d_seqs = nullptr, *d_aln = nullptr;
-  long long *d_off = nullptr;
-  int *d_score = nullptr, *d_status = nullptr, *d_next = nullptr, *d_todo = nullptr, *d_order = nullptr;   // d_order: the pool's queries, the dearest first
-  unsigned long long *d_cells = nullptr;
-  uint32_t *d_pool = nullptr;               // wavefront memory: n_chunks chunks of 2^chunk_log2 words
-  PoolCtl *d_ctl = nullptr; int *d_stack = nullptr;
-  int n_chunks = 0, chunk_log2 = 0;
-  std::vector<int> h_stack;
-  size_t seqs_cap = 0, n_cap = 0, workspace_request = 0;
+  DevBuf<uint8_t> d_ref, d_seqs;
+  // per query of the pool, n_cap of each: offsets (one more), aligned rows, scores, status, the queries of a later pass, the pool's queries the dearest first
+  DevBuf<long long> d_off; DevBuf<uint8_t> d_aln; DevBuf<int> d_score, d_status, d_todo, d_order;
+  DevBuf<int> d_next;
+  DevBuf<unsigned long long> d_cells;
+  // wavefront memory: n_chunks chunks of 2^chunk_log2 words, the control block and the stack of free chunks.  n_chunks is set last and
+  // says that all of it is there: a workspace that could not be built is empty
+  struct Workspace {
+    DevBuf<uint32_t> pool; DevBuf<PoolCtl> ctl; DevBuf<int> stack;
+    int n_chunks = 0, chunk_log2 = 0;
+    std::vector<int> h_stack;
+  } ws;
+  size_t n_cap = 0, workspace_request = 0;
   int n = 0, max_blocks = 0, passes = 0;
   bool ran = false;
   unsigned long long cells = 0;
   double kernel_ms = 0;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
   std::vector<char> h_bytes; std::vector<long long> h_off;
   std::string err;
 };
@@ -560,27 +572,20 @@ int afail(uvaia_aligner *a, int code, const char *fmt, ...)
   return code;
 }
 
-#define ACHK(a, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) \
-  return afail((a), e_ == hipErrorOutOfMemory ? UVAIA_ALIGN_ENOMEM : UVAIA_ALIGN_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+// (a is null while uvaia_align_open builds the aligner: the message goes where uvaia_align_last_error(NULL) finds it)
+int hip_failed(uvaia_aligner *a, hipError_t e, const char *call, const char *file, int line)
+{ return afail(a, e == hipErrorOutOfMemory ? UVAIA_ALIGN_ENOMEM : UVAIA_ALIGN_EHIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line); }
 
+// room for a pool of n queries and `bytes` characters; the six per-query arrays grow as a group
 int ensure_pool(uvaia_aligner *a, size_t bytes, int n)
 {
-  if (bytes + 512 > a->seqs_cap) {
-    if (a->d_seqs) hipFree(a->d_seqs);
-    a->d_seqs = nullptr; a->seqs_cap = 0;
-    const size_t cap = std::max<size_t>(bytes + 512, 1u << 20) * 5 / 4;
-    ACHK(a, hipMalloc(&a->d_seqs, cap)); a->seqs_cap = cap;
-  }
+  if (bytes + 512 > a->d_seqs.cap) if (int rc = a->d_seqs.reserve(a, std::max<size_t>(bytes + 512, 1u << 20) * 5 / 4)) return rc;
   if ((size_t)n > a->n_cap) {
-    hipFree(a->d_off); hipFree(a->d_aln); hipFree(a->d_score); hipFree(a->d_status); hipFree(a->d_todo); hipFree(a->d_order);
-    a->d_off = nullptr; a->d_aln = nullptr; a->d_score = a->d_status = a->d_todo = a->d_order = nullptr; a->n_cap = 0;
     const size_t cap = std::max<size_t>((size_t)n * 5 / 4, 256);
-    ACHK(a, hipMalloc(&a->d_off, (cap + 1) * sizeof(long long)));
-    ACHK(a, hipMalloc(&a->d_aln, cap * ((size_t)a->plen + 1)));
-    ACHK(a, hipMalloc(&a->d_score, cap * sizeof(int)));
-    ACHK(a, hipMalloc(&a->d_status, cap * sizeof(int)));
-    ACHK(a, hipMalloc(&a->d_todo, cap * sizeof(int)));
-    ACHK(a, hipMalloc(&a->d_order, cap * sizeof(int)));
+    a->n_cap = 0;
+    int rc;
+    if ((rc = a->d_off.reserve(a, cap + 1)) || (rc = a->d_aln.reserve(a, cap * ((size_t)a->plen + 1))) || (rc = a->d_score.reserve(a, cap)) ||
+        (rc = a->d_status.reserve(a, cap)) || (rc = a->d_todo.reserve(a, cap)) || (rc = a->d_order.reserve(a, cap))) return rc;
     a->n_cap = cap;
   }
   return 0;
@@ -590,29 +595,30 @@ int ensure_pool(uvaia_aligner *a, size_t bytes, int n)
 // of four, up to three quarters of the free device memory, whenever a pass leaves queries that found the pool empty.
 int ensure_pool_memory(uvaia_aligner *a, bool grow, bool *grew)
 {
+  uvaia_aligner::Workspace &w = a->ws;
   if (grew) *grew = false;
-  if (a->d_pool && !grow) return 0;
+  if (w.n_chunks && !grow) return 0;
   // a chunk holds the ring of I and D wavefronts (e + 2 pairs of the widest wavefront, at most all plen + tlen + 1 diagonals of a
   // query of up to 1.5 reference lengths, src/align.c:199) and serves as the unit the queries' histories grow by
   const unsigned long long widest = (unsigned long long)a->plen * 5 / 2 + 64;
   int lg = 19;
   while ((1ull << lg) < (unsigned long long)(a->P.e + 2) * 2ull * widest) lg++;
   if (lg > 28) return afail(a, UVAIA_ALIGN_EINVAL, "reference of %d sites is too long for the wavefront workspace", a->plen);
-  const size_t chunk_bytes = (size_t)4 << lg, have = (size_t)a->n_chunks * chunk_bytes;
-  if (a->d_pool && a->workspace_request) return 0;                  // a workspace of a given size does not grow
+  const size_t chunk_bytes = (size_t)4 << lg, have = (size_t)w.n_chunks * chunk_bytes;
+  if (w.n_chunks && a->workspace_request) return 0;                 // a workspace of a given size does not grow
   size_t free_b = 0, total_b = 0;
-  ACHK(a, hipMemGetInfo(&free_b, &total_b));
+  HIPCHK(a, hipMemGetInfo(&free_b, &total_b));
   const size_t cap = std::min((free_b + have) / 4 * 3, (size_t)0xffffffffull * 64);   // array positions are kept in units of 64 bytes in 32 bits
-  size_t want = a->workspace_request ? std::min(a->workspace_request, (size_t)0xffffffffull * 64) : std::min(cap, a->d_pool ? have * 4 : std::max((size_t)4 << 30, 8 * chunk_bytes));
-  if (a->d_pool && want <= have) return 0;                          // already as large as it gets
+  size_t want = a->workspace_request ? std::min(a->workspace_request, (size_t)0xffffffffull * 64) : std::min(cap, w.n_chunks ? have * 4 : std::max((size_t)4 << 30, 8 * chunk_bytes));
+  if (w.n_chunks && want <= have) return 0;                         // already as large as it gets
   size_t n_chunks = want / chunk_bytes;
   if (n_chunks < 3) return afail(a, UVAIA_ALIGN_ENOMEM, "workspace of %zu bytes is below three chunks of %zu bytes", want, chunk_bytes);
-  if (a->d_pool) { ACHK(a, hipStreamSynchronize(a->stream)); hipFree(a->d_pool); hipFree(a->d_ctl); hipFree(a->d_stack); a->d_pool = nullptr; a->d_ctl = nullptr; a->d_stack = nullptr; a->n_chunks = 0; }
-  ACHK(a, hipMalloc(&a->d_pool, n_chunks * chunk_bytes));
-  ACHK(a, hipMalloc(&a->d_ctl, sizeof(PoolCtl)));
-  ACHK(a, hipMalloc(&a->d_stack, n_chunks * sizeof(int)));
-  a->n_chunks = (int)n_chunks; a->chunk_log2 = lg;
-  a->h_stack.resize(n_chunks);
+  if (w.n_chunks) HIPCHK(a, hipStreamSynchronize(a->stream));
+  w = uvaia_aligner::Workspace();                                   // the old one goes before the new one is asked for
+  int rc;
+  if ((rc = w.pool.reserve(a, n_chunks << lg)) || (rc = w.ctl.reserve(a, 1)) || (rc = w.stack.reserve(a, n_chunks))) { w = uvaia_aligner::Workspace(); return rc; }
+  w.h_stack.resize(n_chunks);
+  w.chunk_log2 = lg; w.n_chunks = (int)n_chunks;
   if (grew) *grew = true;
   return 0;
 }
@@ -621,29 +627,29 @@ int ensure_pool_memory(uvaia_aligner *a, bool grow, bool *grew)
 int run_passes(uvaia_aligner *a)
 {
   int n_todo = a->n;
-  int blocks = std::max(1, std::min(std::min(n_todo, a->max_blocks), a->n_chunks / 3));
+  int blocks = std::max(1, std::min(std::min(n_todo, a->max_blocks), a->ws.n_chunks / 3));
   const int *todo = a->d_order;                                       // the first launch: every query of the pool, the dearest first
   std::vector<int> status((size_t)a->n), list, todo_list;             // todo_list empty: all queries of the pool
   for (;;) {
     // every block keeps two chunks for the whole launch; the rest of the pool is what the queries in flight share
-    const PoolCtl ctl{0, a->n_chunks - 2 * blocks, a->n_chunks, a->chunk_log2};
-    for (int i = 0; i < ctl.top; i++) a->h_stack[(size_t)i] = 2 * blocks + i;
-    ACHK(a, hipMemcpyAsync(a->d_ctl, &ctl, sizeof ctl, hipMemcpyHostToDevice, a->stream));
-    if (ctl.top > 0) ACHK(a, hipMemcpyAsync(a->d_stack, a->h_stack.data(), (size_t)ctl.top * sizeof(int), hipMemcpyHostToDevice, a->stream));
-    ACHK(a, hipMemsetAsync(a->d_next, 0, sizeof(int), a->stream));
-    ACHK(a, hipStreamSynchronize(a->stream));                     // (ctl is on the stack of this function)
+    const PoolCtl ctl{0, a->ws.n_chunks - 2 * blocks, a->ws.n_chunks, a->ws.chunk_log2};
+    for (int i = 0; i < ctl.top; i++) a->ws.h_stack[(size_t)i] = 2 * blocks + i;
+    HIPCHK(a, hipMemcpyAsync(a->ws.ctl, &ctl, sizeof ctl, hipMemcpyHostToDevice, a->stream));
+    if (ctl.top > 0) HIPCHK(a, hipMemcpyAsync(a->ws.stack, a->ws.h_stack.data(), (size_t)ctl.top * sizeof(int), hipMemcpyHostToDevice, a->stream));
+    HIPCHK(a, hipMemsetAsync(a->d_next, 0, sizeof(int), a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));                     // (ctl is on the stack of this function)
     hipLaunchKernelGGL(wfa_align_kernel, dim3((unsigned)blocks), dim3(TPB), 0, a->stream, a->d_ref, a->plen, a->d_seqs, a->d_off, todo, n_todo, a->d_aln, (size_t)a->plen + 1,
-                       a->d_score, a->d_status, a->d_cells, a->d_pool, a->d_ctl, a->d_stack, a->d_next, a->P);
-    ACHK(a, hipGetLastError());
+                       a->d_score, a->d_status, a->d_cells, a->ws.pool, a->ws.ctl, a->ws.stack, a->d_next, a->P);
+    HIPCHK(a, hipGetLastError());
     a->passes++;
-    ACHK(a, hipMemcpyAsync(status.data(), a->d_status, (size_t)a->n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
-    ACHK(a, hipStreamSynchronize(a->stream));
+    HIPCHK(a, hipMemcpyAsync(status.data(), a->d_status, (size_t)a->n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
     list.clear();
     auto look = [&](int i) -> int {
       if (status[(size_t)i] == ST_OVERFLOW) list.push_back(i);
       else if (status[(size_t)i] == ST_MAXSCORE) return afail(a, UVAIA_ALIGN_EINVAL, "sequence %d: alignment score above %d, the size of the reference's score table", i, a->P.max_score);
       else if (status[(size_t)i] == ST_HDRPAGES) return afail(a, UVAIA_ALIGN_EINVAL, "sequence %d: alignment score above %d, the most this aligner keeps score headers for (%d pages of %d scores)", i, MAX_HDR_PAGES * HDR_PAGE_SCORES - 1, MAX_HDR_PAGES, HDR_PAGE_SCORES);
-      else if (status[(size_t)i] == ST_TOOWIDE) return afail(a, UVAIA_ALIGN_EINVAL, "sequence %d: a wavefront wider than the workspace's chunks hold (%zu bytes each)", i, (size_t)4 << a->chunk_log2);
+      else if (status[(size_t)i] == ST_TOOWIDE) return afail(a, UVAIA_ALIGN_EINVAL, "sequence %d: a wavefront wider than the workspace's chunks hold (%zu bytes each)", i, (size_t)4 << a->ws.chunk_log2);
       else if (status[(size_t)i] != ST_OK) return afail(a, UVAIA_ALIGN_ESTATE, "sequence %d: inconsistent backtrace", i);
       return 0;
     };
@@ -654,17 +660,19 @@ int run_passes(uvaia_aligner *a)
     bool grew = false;                                             // queries found the pool empty: a workspace of the library's choosing grows first, ...
     { const int rc = ensure_pool_memory(a, true, &grew); if (rc) return rc; }
     if (!grew) {                                                   // ... then fewer queries go in flight
-      if (blocks == 1) return afail(a, UVAIA_ALIGN_ENOMEM, "sequence %d needs more than the whole workspace (%zu bytes) for its wavefronts", list[0], ((size_t)a->n_chunks * 4) << a->chunk_log2);
+      if (blocks == 1) return afail(a, UVAIA_ALIGN_ENOMEM, "sequence %d needs more than the whole workspace (%zu bytes) for its wavefronts", list[0], ((size_t)a->ws.n_chunks * 4) << a->ws.chunk_log2);
       blocks = std::max(1, std::min((int)list.size(), blocks / 4));
     }
     todo_list = list;
-    ACHK(a, hipMemcpyAsync(a->d_todo, todo_list.data(), todo_list.size() * sizeof(int), hipMemcpyHostToDevice, a->stream));
-    ACHK(a, hipStreamSynchronize(a->stream));
+    HIPCHK(a, hipMemcpyAsync(a->d_todo, todo_list.data(), todo_list.size() * sizeof(int), hipMemcpyHostToDevice, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
     todo = a->d_todo; n_todo = (int)todo_list.size();
-    if (grew) blocks = std::max(1, std::min(std::min(n_todo, a->max_blocks), a->n_chunks / 3));
+    if (grew) blocks = std::max(1, std::min(std::min(n_todo, a->max_blocks), a->ws.n_chunks / 3));
   }
   return 0;
 }
+
+struct CloseAligner { void operator()(uvaia_aligner *a) const { uvaia_align_close(a); } };
 
 }  // namespace
 
@@ -685,11 +693,6 @@ void uvaia_align_close(uvaia_aligner *a)
   if (!a) return;
   hipSetDevice(a->device);
   if (a->stream) hipStreamSynchronize(a->stream);
-  hipFree(a->d_ref); hipFree(a->d_seqs); hipFree(a->d_aln); hipFree(a->d_off); hipFree(a->d_score); hipFree(a->d_status); hipFree(a->d_next);
-  hipFree(a->d_todo); hipFree(a->d_order); hipFree(a->d_cells); hipFree(a->d_pool); hipFree(a->d_ctl); hipFree(a->d_stack);
-  if (a->ev_a) hipEventDestroy(a->ev_a);
-  if (a->ev_b) hipEventDestroy(a->ev_b);
-  if (a->stream) hipStreamDestroy(a->stream);
   delete a;
 }
 
@@ -712,7 +715,7 @@ int uvaia_align_open(uvaia_aligner **out, const char *ref, int ref_len, int devi
   if (hipGetDevice(&caller_device) != hipSuccess) caller_device = -1;
   if (hipSetDevice(device) != hipSuccess) return afail(nullptr, UVAIA_ALIGN_ENODEV, "cannot select device %d", device);
   struct RestoreDevice { int d; ~RestoreDevice() { if (d >= 0) hipSetDevice(d); } } restore_{caller_device};   // every later call selects a->device itself
-  uvaia_aligner *a = new uvaia_aligner();
+  std::unique_ptr<uvaia_aligner, CloseAligner> a(new uvaia_aligner());   // a failure below closes the half-made aligner; its message goes to uvaia_align_last_error(NULL)
   a->device = device; a->plen = ref_len;
   a->P.x = opt.mismatch; a->P.oe = opt.gap_opening + opt.gap_extension; a->P.e = opt.gap_extension;
   a->P.min_wf_len = opt.min_wavefront_length; a->P.max_dist_thr = opt.max_distance_threshold;
@@ -726,15 +729,12 @@ int uvaia_align_open(uvaia_aligner **out, const char *ref, int ref_len, int devi
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wfa_align_kernel, TPB, 0) != hipSuccess || per_cu < 1) per_cu = 4;
     a->max_blocks = opt.max_blocks > 0 ? opt.max_blocks : prop.multiProcessorCount * per_cu;
   }
-#define OCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int rc_ = afail(nullptr, e_ == hipErrorOutOfMemory ? UVAIA_ALIGN_ENOMEM : UVAIA_ALIGN_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); uvaia_align_close(a); return rc_; } } while (0)
-  OCHK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-  OCHK(hipEventCreate(&a->ev_a)); OCHK(hipEventCreate(&a->ev_b));
-  OCHK(hipMalloc(&a->d_ref, (size_t)ref_len + 512));
-  OCHK(hipMemcpy(a->d_ref, ref, (size_t)ref_len, hipMemcpyHostToDevice));
-  OCHK(hipMalloc(&a->d_next, sizeof(int)));
-  OCHK(hipMalloc(&a->d_cells, sizeof(unsigned long long)));
-#undef OCHK
-  *out = a;
+  int rc;
+  HIPCHK(nullptr, hipStreamCreateWithFlags(&a->stream.s, hipStreamNonBlocking));
+  if ((rc = a->ev_a.make(nullptr)) || (rc = a->ev_b.make(nullptr)) || (rc = a->d_ref.reserve(nullptr, (size_t)ref_len + 512))) return rc;
+  HIPCHK(nullptr, hipMemcpy(a->d_ref, ref, (size_t)ref_len, hipMemcpyHostToDevice));
+  if ((rc = a->d_next.reserve(nullptr, 1)) || (rc = a->d_cells.reserve(nullptr, 1))) return rc;
+  *out = a.release();
   return 0;
 }
 
@@ -742,7 +742,7 @@ int uvaia_align_load_block(uvaia_aligner *a, const char *bytes, const int64_t *o
 {
   if (!a) return UVAIA_ALIGN_EINVAL;
   if (n < 0 || (n > 0 && (!bytes || !offsets))) return afail(a, UVAIA_ALIGN_EINVAL, "bad pool");
-  ACHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipSetDevice(a->device));
   a->n = 0; a->ran = false;
   if (n == 0) return 0;
   for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return afail(a, UVAIA_ALIGN_EINVAL, "bad length of sequence %d", i);
@@ -750,24 +750,24 @@ int uvaia_align_load_block(uvaia_aligner *a, const char *bytes, const int64_t *o
   int rc = ensure_pool(a, total, n); if (rc) return rc;
   a->h_off.resize((size_t)n + 1);
   for (int i = 0; i <= n; i++) a->h_off[(size_t)i] = (long long)(offsets[i] - offsets[0]);
-  ACHK(a, hipStreamSynchronize(a->stream));
-  if (total) ACHK(a, hipMemcpyAsync(a->d_seqs, bytes + offsets[0], total, hipMemcpyHostToDevice, a->stream));
-  ACHK(a, hipMemcpyAsync(a->d_off, a->h_off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, a->stream));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  if (total) HIPCHK(a, hipMemcpyAsync(a->d_seqs, bytes + offsets[0], total, hipMemcpyHostToDevice, a->stream));
+  HIPCHK(a, hipMemcpyAsync(a->d_off, a->h_off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, a->stream));
   {   // the order the queries are started in (d_status is free until the run: it takes the estimates)
     hipLaunchKernelGGL(expected_cost_kernel, dim3((unsigned)n), dim3(256), 0, a->stream, a->d_seqs, a->d_off, a->plen, n, a->d_status);
-    ACHK(a, hipGetLastError());
+    HIPCHK(a, hipGetLastError());
     std::vector<int> cost((size_t)n), order((size_t)n);
-    ACHK(a, hipMemcpyAsync(cost.data(), a->d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
-    ACHK(a, hipStreamSynchronize(a->stream));
+    HIPCHK(a, hipMemcpyAsync(cost.data(), a->d_status, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
     for (int i = 0; i < n; i++) order[(size_t)i] = i;
     std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return cost[(size_t)x] > cost[(size_t)y]; });
     // a pool of fewer than three rounds of blocks stays in descending order throughout (longest first: with so few queries per block
     // the order is most of the launch's length, and the dearest third of such a pool in flight at once is what the workspace of the
     // library's choosing holds: measured at 2 000 queries); a larger one would put only its very dearest in flight at once
     if (a->workspace_request != 0 || (long long)n * 4 > (long long)a->max_blocks * 11) std::sort(order.begin(), order.begin() + n / 2);
-    ACHK(a, hipMemcpyAsync(a->d_order, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, a->stream));
+    HIPCHK(a, hipMemcpyAsync(a->d_order, order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, a->stream));
   }
-  ACHK(a, hipStreamSynchronize(a->stream));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
   a->n = n;
   return 0;
 }
@@ -786,17 +786,17 @@ int uvaia_align_load(uvaia_aligner *a, const char *const *seq, const int *seq_le
 int uvaia_align_run(uvaia_aligner *a)
 {
   if (!a) return UVAIA_ALIGN_EINVAL;
-  ACHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipSetDevice(a->device));
   a->passes = 0; a->cells = 0; a->kernel_ms = 0; a->ran = false;
   if (a->n == 0) { a->ran = true; return 0; }
   int rc = ensure_pool_memory(a, false, nullptr); if (rc) return rc;
-  ACHK(a, hipMemsetAsync(a->d_cells, 0, sizeof(unsigned long long), a->stream));
-  ACHK(a, hipEventRecord(a->ev_a, a->stream));
+  HIPCHK(a, hipMemsetAsync(a->d_cells, 0, sizeof(unsigned long long), a->stream));
+  HIPCHK(a, hipEventRecord(a->ev_a, a->stream));
   rc = run_passes(a); if (rc) return rc;
-  ACHK(a, hipEventRecord(a->ev_b, a->stream));
-  ACHK(a, hipEventSynchronize(a->ev_b));
-  float ms = 0; ACHK(a, hipEventElapsedTime(&ms, a->ev_a, a->ev_b)); a->kernel_ms = ms;
-  ACHK(a, hipMemcpy(&a->cells, a->d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPCHK(a, hipEventRecord(a->ev_b, a->stream));
+  HIPCHK(a, hipEventSynchronize(a->ev_b));
+  float ms = 0; HIPCHK(a, hipEventElapsedTime(&ms, a->ev_a, a->ev_b)); a->kernel_ms = ms;
+  HIPCHK(a, hipMemcpy(&a->cells, a->d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost));
   a->ran = true;
   return 0;
 }
@@ -804,8 +804,8 @@ int uvaia_align_run(uvaia_aligner *a)
 int uvaia_align_sync(uvaia_aligner *a)
 {
   if (!a) return UVAIA_ALIGN_EINVAL;
-  ACHK(a, hipSetDevice(a->device));
-  ACHK(a, hipStreamSynchronize(a->stream));
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
   return 0;
 }
 
@@ -815,10 +815,10 @@ int uvaia_align_fetch(uvaia_aligner *a, char *aln, int *score)
   if (!a->ran) return afail(a, UVAIA_ALIGN_ESTATE, "fetch without a completed run");
   if (a->n == 0) return 0;
   if (!aln) return afail(a, UVAIA_ALIGN_EINVAL, "NULL row buffer");
-  ACHK(a, hipSetDevice(a->device));
-  ACHK(a, hipMemcpyAsync(aln, a->d_aln, (size_t)a->n * ((size_t)a->plen + 1), hipMemcpyDeviceToHost, a->stream));
-  if (score) ACHK(a, hipMemcpyAsync(score, a->d_score, (size_t)a->n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
-  ACHK(a, hipStreamSynchronize(a->stream));
+  HIPCHK(a, hipSetDevice(a->device));
+  HIPCHK(a, hipMemcpyAsync(aln, a->d_aln, (size_t)a->n * ((size_t)a->plen + 1), hipMemcpyDeviceToHost, a->stream));
+  if (score) HIPCHK(a, hipMemcpyAsync(score, a->d_score, (size_t)a->n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
   return 0;
 }
 
@@ -826,7 +826,7 @@ int uvaia_align_device_rows(uvaia_aligner *a, const void **d_rows, size_t *pitch
 {
   if (!a) return UVAIA_ALIGN_EINVAL;
   if (!a->ran) return afail(a, UVAIA_ALIGN_ESTATE, "no completed run whose rows could be handed out");
-  if (d_rows) *d_rows = a->n ? a->d_aln : nullptr;
+  if (d_rows) *d_rows = a->n ? a->d_aln.p : nullptr;
   if (pitch) *pitch = (size_t)a->plen + 1;
   if (n) *n = a->n;
   if (device) *device = a->device;

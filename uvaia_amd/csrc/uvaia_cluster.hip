@@ -451,27 +451,34 @@ thread_local std::string g_open_error;
 
 }  // namespace
 
+// ---- host side.  Device memory, events and the stream are the move-only handles of host_owners.h; a failed HIP call goes through hip_failed.
+struct uvaia_clust_ctx;
+namespace { int hip_failed(uvaia_clust_ctx *c, hipError_t e, const char *call, const char *file, int line); }
+#include <memory>
+#include "host_owners.h"
+
+// Members are destroyed last to first: the stream comes first so that it outlives every buffer and event that work queued on it may still
+// name (uvaia_clust_close has waited for it by then).
 struct uvaia_clust_ctx {
+  Stream stream;
+  Event ev_a, ev_b;
   int device = 0, nchar = 0, dist = 0, trim = 0, n_score = 0, n_queues = 0;
   size_t pitch = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
-  uint8_t *d_ref = nullptr, *d_rows = nullptr;
-  int *d_dist = nullptr, *d_p = nullptr, *d_join = nullptr, *d_bad = nullptr;
-  int *d_qoff = nullptr, *d_qlist = nullptr, *d_mcount = nullptr, *d_mord = nullptr, *d_mst = nullptr;
-  uint8_t *d_tiles = nullptr, *d_gather = nullptr;      // packed pushes: the tiles of a push; uvaia_clust_rows: the gathered rows
-  uint32_t *d_xoff = nullptr; uint2 *d_xrec = nullptr;  // packed pushes: record offsets per row of the push, and the records
-  int *d_gord = nullptr;
-  size_t rows_cap = 0, qlist_cap = 0, tiles_cap = 0, xoff_cap = 0, xrec_cap = 0, gather_cap = 0, gord_cap = 0;
+  DevBuf<uint8_t> d_ref, d_rows;
+  DevBuf<int> d_dist, d_p, d_join, d_bad;                  // d_rows (or d_slot), d_dist, d_p and d_join hold rows_cap rows
+  DevBuf<int> d_qoff, d_qlist, d_mcount, d_mord, d_mst;    // d_mord, d_mst (and d_mloc): m_cap slots per queue
+  DevBuf<uint8_t> d_tiles, d_gather;                       // packed pushes: the tiles of a push; uvaia_clust_rows: the gathered rows
+  DevBuf<uint32_t> d_xoff; DevBuf<uint2> d_xrec;           // packed pushes: record offsets per row of the push, and the records
+  DevBuf<int> d_gord;
+  size_t rows_cap = 0;
   int m_cap = 0;
   long long pushed = 0;
-  // keep medoids: the rows of the running push (d_stage), the founders in slabs (slabs / d_slabtab), and where they are
+  // keep medoids: the rows of the running push (d_stage, exactly as large as the largest push), the founders in slabs (slabs / d_slabtab), and where they are
   bool keep = false;
   int slab_rows = 0, slab_shift = 0;
-  std::vector<uint8_t *> slabs;
-  uint8_t **d_slabtab = nullptr, *d_stage = nullptr;
-  int *d_slot = nullptr, *d_mloc = nullptr, *d_blk = nullptr, *d_pq = nullptr;   // slot per push ordinal, location per medoid entry, prefix-sum scratch, queue per row of the push
-  size_t slabtab_cap = 0, stage_cap = 0, blk_cap = 0, pq_cap = 0;
+  std::vector<DevBuf<uint8_t>> slabs;
+  DevBuf<uint8_t *> d_slabtab; DevBuf<uint8_t> d_stage;
+  DevBuf<int> d_slot, d_mloc, d_blk, d_pq;   // slot per push ordinal, location per medoid entry, prefix-sum scratch, queue per row of the push
   long long kept = 0;                      // founders so far = slots in use
   std::vector<int> h_slot;                 // d_slot on the host: uvaia_clust_rows and uvaia_clust_gather_device check their ordinals against it
   size_t peak_row_bytes = 0;
@@ -497,78 +504,95 @@ int cfail(uvaia_clust_ctx *c, int code, const char *fmt, ...)
   return code;
 }
 
-#define CCHK(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (c)->broken = true; \
-  return cfail((c), e_ == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
-
-// grows a device array to `want` bytes (at least doubling), keeping its first `keep` bytes
-int grow(uvaia_clust_ctx *c, void **ptr, size_t keep, size_t want)
+// a failed HIP call leaves the context unusable (c is null while uvaia_clust_open builds it: the message goes where uvaia_clust_last_error(NULL) finds it)
+int hip_failed(uvaia_clust_ctx *c, hipError_t e, const char *call, const char *file, int line)
 {
-  void *np = nullptr;
-  CCHK(c, hipMalloc(&np, want));
-  if (keep) CCHK(c, hipMemcpyAsync(np, *ptr, keep, hipMemcpyDeviceToDevice, c->stream));
-  CCHK(c, hipStreamSynchronize(c->stream));
-  if (*ptr) hipFree(*ptr);
-  *ptr = np;
+  if (c) c->broken = true;
+  return cfail(c, e == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line);
+}
+
+// what every entry point that works on the device asks first
+int usable(uvaia_clust_ctx *c)
+{
+  return c->broken ? cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str()) : 0;
+}
+
+// a device scratch array of at least n elements whose contents are not kept: kernels queued on the stream may still read the old one, so
+// the host waits for the stream before it goes
+template <class T> int reserve_idle(uvaia_clust_ctx *c, DevBuf<T> &b, size_t n)
+{
+  if (n <= b.cap) return 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return b.reserve(c, n);
+}
+
+// One timed launch: launch() between the context's two events (timed_issue), the wait for the second, the time added to `acc` (timed_take).
+// The merge round queues its copy back between the two halves and waits for the stream once.
+template <class F> int timed_issue(uvaia_clust_ctx *c, F launch)
+{
+  HIPCHK(c, hipEventRecord(c->ev_a, c->stream));
+  launch();
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev_b, c->stream));
   return 0;
+}
+int timed_take(uvaia_clust_ctx *c, double &acc)
+{
+  float ms = 0;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  acc += ms;
+  return 0;
+}
+template <class F> int timed(uvaia_clust_ctx *c, double &acc, F launch)
+{
+  if (int rc = timed_issue(c, launch)) return rc;
+  HIPCHK(c, hipEventSynchronize(c->ev_b));
+  return timed_take(c, acc);
 }
 
 int ensure_rows(uvaia_clust_ctx *c, size_t need)
 {
   if (need <= c->rows_cap) return 0;
   const size_t cap = std::max(need, std::max<size_t>(c->rows_cap * 2, 1024));
-  const size_t old = (size_t)c->pushed;
+  const size_t old = (size_t)c->pushed, np = (size_t)std::max(c->n_score, 1);
   int rc;
   if (c->keep) {                       // the text of the rows is not kept: their slots are
-    if ((rc = grow(c, (void **)&c->d_slot, old * sizeof(int), cap * sizeof(int)))) return rc;
+    if ((rc = c->d_slot.grow_keeping(c, cap, old, c->stream))) return rc;
   } else {
-    c->peak_row_bytes = std::max(c->peak_row_bytes, (c->rows_cap + cap) * c->pitch);     // grow() holds the old and the new array at once
-    if ((rc = grow(c, (void **)&c->d_rows, old * c->pitch, cap * c->pitch))) return rc;
+    c->peak_row_bytes = std::max(c->peak_row_bytes, (c->rows_cap + cap) * c->pitch);     // grow_keeping holds the old and the new array at once
+    if ((rc = c->d_rows.grow_keeping(c, cap * c->pitch, old * c->pitch, c->stream))) return rc;
   }
-  if ((rc = grow(c, (void **)&c->d_dist, old * sizeof(int), cap * sizeof(int)))) return rc;
-  if ((rc = grow(c, (void **)&c->d_p, old * std::max(c->n_score, 1) * sizeof(int), cap * std::max(c->n_score, 1) * sizeof(int)))) return rc;
-  if ((rc = grow(c, (void **)&c->d_join, old * sizeof(int), cap * sizeof(int)))) return rc;
+  if ((rc = c->d_dist.grow_keeping(c, cap, old, c->stream))) return rc;
+  if ((rc = c->d_p.grow_keeping(c, cap * np, old * np, c->stream))) return rc;
+  if ((rc = c->d_join.grow_keeping(c, cap, old, c->stream))) return rc;
   c->rows_cap = cap;
   return 0;
 }
 
-// medoid slots per queue: at least as many as rows pushed to the busiest queue
+// medoid slots per queue: at least as many as rows pushed to the busiest queue.  A queue's row of m_ord, m_st and m_loc moves from m_cap to
+// cap ints apart; the new arrays join the context only once all of them exist and hold the old entries.
 int ensure_medoids(uvaia_clust_ctx *c, long long need)
 {
   if (need <= c->m_cap) return 0;
   if (need > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences in one queue", INT_MAX / 2);
   const int cap = (int)std::max<long long>(need, std::max(2LL * c->m_cap, 256LL));
-  int *no = nullptr, *ns = nullptr, *nl = nullptr;
-  CCHK(c, hipMalloc(&no, (size_t)c->n_queues * cap * sizeof(int)));
-  CCHK(c, hipMalloc(&ns, (size_t)c->n_queues * cap * sizeof(int)));
-  if (c->keep) CCHK(c, hipMalloc(&nl, (size_t)c->n_queues * cap * sizeof(int)));
-  if (c->m_cap) {
-    if (c->keep) CCHK(c, hipMemcpy2DAsync(nl, (size_t)cap * sizeof(int), c->d_mloc, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
-    CCHK(c, hipMemcpy2DAsync(no, (size_t)cap * sizeof(int), c->d_mord, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
-    CCHK(c, hipMemcpy2DAsync(ns, (size_t)cap * sizeof(int), c->d_mst, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
+  DevBuf<int> *const held[3] = {&c->d_mord, &c->d_mst, &c->d_mloc};
+  DevBuf<int> made[3];
+  for (int k = 0; k < (c->keep ? 3 : 2); k++) {
+    if (int rc = made[k].reserve(c, (size_t)c->n_queues * cap)) return rc;
+    if (c->m_cap) HIPCHK(c, hipMemcpy2DAsync(made[k].p, (size_t)cap * sizeof(int), held[k]->p, (size_t)c->m_cap * sizeof(int), (size_t)c->m_cap * sizeof(int), c->n_queues, hipMemcpyDeviceToDevice, c->stream));
   }
-  CCHK(c, hipStreamSynchronize(c->stream));
-  hipFree(c->d_mord); hipFree(c->d_mst); hipFree(c->d_mloc);
-  c->d_mord = no; c->d_mst = ns; c->d_mloc = nl; c->m_cap = cap;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 3; k++) *held[k] = std::move(made[k]);
+  c->m_cap = cap;
   return 0;
 }
 
 struct uvdb_like_exc { uint32_t pos, len_char; };   // an exception record as a packed database file holds it (host/uvdb.h)
 
-// a device scratch array of at least `want` bytes; its contents are not kept
-int ensure_bytes(uvaia_clust_ctx *c, void **ptr, size_t *cap, size_t want)
-{
-  if (want <= *cap) return 0;
-  CCHK(c, hipStreamSynchronize(c->stream));
-  if (*ptr) hipFree(*ptr);
-  *ptr = nullptr; *cap = 0;
-  CCHK(c, hipMalloc(ptr, want));
-  *cap = want;
-  return 0;
-}
-
 size_t row_bytes_now(const uvaia_clust_ctx *c)
 {
-  return c->keep ? c->slabs.size() * (size_t)c->slab_rows * c->pitch + c->stage_cap : c->rows_cap * c->pitch;
+  return c->keep ? c->slabs.size() * (size_t)c->slab_rows * c->pitch + c->d_stage.cap : c->rows_cap * c->pitch;
 }
 
 // keep medoids: slabs for `need` slots.  A new slab is a new allocation: nothing is copied, the table of base pointers is sent again.
@@ -577,17 +601,14 @@ int ensure_slabs(uvaia_clust_ctx *c, long long need)
   const size_t want = (size_t)((need + c->slab_rows - 1) >> c->slab_shift);
   if (want <= c->slabs.size()) return 0;
   while (c->slabs.size() < want) {
-    uint8_t *p = nullptr;
-    CCHK(c, hipMalloc(&p, (size_t)c->slab_rows * c->pitch));
-    c->slabs.push_back(p);
+    DevBuf<uint8_t> slab;
+    if (int rc = slab.reserve(c, (size_t)c->slab_rows * c->pitch)) return rc;
+    c->slabs.push_back(std::move(slab));
   }
-  if (want > c->slabtab_cap) {
-    size_t cap = 0;
-    if (int rc = ensure_bytes(c, (void **)&c->d_slabtab, &cap, std::max(want, 2 * c->slabtab_cap) * sizeof(uint8_t *))) { c->slabtab_cap = 0; return rc; }
-    c->slabtab_cap = cap / sizeof(uint8_t *);
-  }
-  CCHK(c, hipMemcpyAsync(c->d_slabtab, c->slabs.data(), c->slabs.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
-  CCHK(c, hipStreamSynchronize(c->stream));
+  if (want > c->d_slabtab.cap) if (int rc = reserve_idle(c, c->d_slabtab, std::max(want, 2 * c->d_slabtab.cap))) return rc;
+  std::vector<uint8_t *> tab(c->slabs.begin(), c->slabs.end());
+  HIPCHK(c, hipMemcpyAsync(c->d_slabtab, tab.data(), tab.size() * sizeof(uint8_t *), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   c->peak_row_bytes = std::max(c->peak_row_bytes, row_bytes_now(c));
   return 0;
 }
@@ -598,7 +619,7 @@ int push_rows_dst(uvaia_clust_ctx *c, long long first, int n, uint8_t **dst)
   int rc;
   if ((rc = ensure_rows(c, (size_t)first + n))) return rc;
   if (c->keep) {
-    if ((rc = ensure_bytes(c, (void **)&c->d_stage, &c->stage_cap, (size_t)n * c->pitch))) return rc;
+    if ((rc = reserve_idle(c, c->d_stage, (size_t)n * c->pitch))) return rc;
     *dst = c->d_stage;
   } else *dst = c->d_rows + (size_t)first * c->pitch;
   c->peak_row_bytes = std::max(c->peak_row_bytes, row_bytes_now(c));
@@ -610,10 +631,17 @@ SlabRows slab_rows_of(const uvaia_clust_ctx *c, long long first)
   return SlabRows{c->d_stage, c->d_slabtab, c->pitch, c->d_slot, c->d_mloc, first, c->slab_shift, c->slab_rows - 1};
 }
 
+// the row addressing of the context's residency mode, handed to f (a generic callable: the kernels take it as a template parameter);
+// first: the push ordinal of the first row in staging
+template <class F> void with_rows(const uvaia_clust_ctx *c, long long first, F f)
+{
+  if (c->keep) f(slab_rows_of(c, first)); else f(FlatRows{c->d_rows, c->pitch});
+}
+
 // what both kinds of push check first
 int push_check(uvaia_clust_ctx *c, int n, bool have_data, const int *queue)
 {
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "push after finish");
   if (n < 0 || (n && (!have_data || !queue))) return cfail(c, UVAIA_GPU_EINVAL, "bad push arguments");
   if (c->pushed + n > INT_MAX / 2) return cfail(c, UVAIA_GPU_EINVAL, "more than %d sequences", INT_MAX / 2);
@@ -626,7 +654,7 @@ int push_check(uvaia_clust_ctx *c, int n, bool have_data, const int *queue)
 int push_lists(uvaia_clust_ctx *c, long long first, int n, const int *queue)
 {
   const int big = INT_MAX;
-  CCHK(c, hipMemcpyAsync(c->d_bad, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_bad, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
   std::vector<int> qoff((size_t)c->n_queues + 1, 0), qlist((size_t)n);
   for (int i = 0; i < n; i++) qoff[(size_t)queue[i] + 1]++;
   for (int q = 0; q < c->n_queues; q++) qoff[(size_t)q + 1] += qoff[(size_t)q];
@@ -634,19 +662,16 @@ int push_lists(uvaia_clust_ctx *c, long long first, int n, const int *queue)
   long long busiest = 0;
   for (int i = 0; i < n; i++) busiest = std::max(busiest, ++c->per_queue[(size_t)queue[i]]);
   c->queue_of.insert(c->queue_of.end(), queue, queue + n);
-  if (int rc = ensure_medoids(c, busiest)) return rc;
-  if ((size_t)n > c->qlist_cap) {
-    hipFree(c->d_qlist); c->d_qlist = nullptr; c->qlist_cap = 0;
-    CCHK(c, hipMalloc(&c->d_qlist, (size_t)n * sizeof(int)));
-    c->qlist_cap = (size_t)n;
-  }
-  CCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  CCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  int rc;
+  if ((rc = ensure_medoids(c, busiest))) return rc;
+  if ((rc = c->d_qlist.reserve(c, (size_t)n))) return rc;   // (no wait: its one reader, the queue kernel of the push before, was waited for by that push)
+  HIPCHK(c, hipMemcpyAsync(c->d_qoff, qoff.data(), qoff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_qlist, qlist.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   if (c->keep) {
-    if (int rc = ensure_bytes(c, (void **)&c->d_pq, &c->pq_cap, (size_t)n * sizeof(int))) return rc;
-    CCHK(c, hipMemcpyAsync(c->d_pq, queue, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if ((rc = reserve_idle(c, c->d_pq, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_pq, queue, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   }
-  CCHK(c, hipStreamSynchronize(c->stream));            // qoff and qlist leave scope
+  HIPCHK(c, hipStreamSynchronize(c->stream));            // qoff and qlist leave scope
   return 0;
 }
 
@@ -655,26 +680,26 @@ int keep_founders(uvaia_clust_ctx *c, long long first, int n)
 {
   const int nb = (n + KTPB - 1) / KTPB;
   int rc, founders = 0;
-  if ((rc = ensure_bytes(c, (void **)&c->d_blk, &c->blk_cap, ((size_t)nb + 1) * sizeof(int)))) return rc;
+  if ((rc = reserve_idle(c, c->d_blk, (size_t)nb + 1))) return rc;
   hipLaunchKernelGGL(clust_founder_count_kernel, dim3((unsigned)nb), dim3(KTPB), 0, c->stream, c->d_join, first, n, c->d_blk);
-  CCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(clust_founder_offsets_kernel, dim3(1), dim3(KTPB), 0, c->stream, c->d_blk, nb);
-  CCHK(c, hipGetLastError());
-  CCHK(c, hipMemcpyAsync(&founders, c->d_blk + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  CCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&founders, c->d_blk + nb, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   if (founders < 0 || founders > n) { c->broken = true; return cfail(c, UVAIA_GPU_EHIP, "push of %d sequences: %d founders counted", n, founders); }
   if ((rc = ensure_slabs(c, c->kept + founders))) return rc;          // before anything is written to a slot
   hipLaunchKernelGGL(clust_founder_slots_kernel, dim3((unsigned)nb), dim3(KTPB), 0, c->stream, c->d_join, c->d_pq, first, n, c->d_blk, (int)c->kept, c->d_slot,
                      c->d_mloc, c->m_cap);
-  CCHK(c, hipGetLastError());
+  HIPCHK(c, hipGetLastError());
   if (founders) {
     hipLaunchKernelGGL(clust_keep_founders_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, c->d_stage, c->pitch, first, c->d_slot, c->d_slabtab, c->slab_shift,
                        c->slab_rows - 1);
-    CCHK(c, hipGetLastError());
+    HIPCHK(c, hipGetLastError());
   }
   c->h_slot.resize((size_t)first + n);
-  CCHK(c, hipMemcpyAsync(c->h_slot.data() + first, c->d_slot + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  CCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->h_slot.data() + first, c->d_slot + first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   c->kept += founders;
   return 0;
 }
@@ -684,19 +709,15 @@ int keep_founders(uvaia_clust_ctx *c, long long first, int n)
 int push_kernels(uvaia_clust_ctx *c, uint8_t *rows, long long first, int n, const char *const *seq)
 {
   const int big = INT_MAX;
-  float ms = 0;
+  int rc;
   // prep addresses row o at base + o * pitch: for staging the base is the address its row `first` would have, and only rows first .. are touched
   uint8_t *prep_base = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(rows) - (uintptr_t)((size_t)first * c->pitch));
-  CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, prep_base, c->pitch, first, n, c->d_ref,
-                     c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
-  CCHK(c, hipGetLastError());
-  CCHK(c, hipEventRecord(c->ev_b, c->stream));
-  CCHK(c, hipEventSynchronize(c->ev_b));
-  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->prep_ms += ms;
+  if ((rc = timed(c, c->prep_ms, [&] {
+        hipLaunchKernelGGL(clust_prep_kernel, dim3((unsigned)((n + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, prep_base, c->pitch, first, n, c->d_ref,
+                           c->nchar, c->trim, c->n_score, c->d_dist, c->d_p, c->d_bad);
+      }))) return rc;
   int bad = big;
-  CCHK(c, hipMemcpy(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(&bad, c->d_bad, sizeof(int), hipMemcpyDeviceToHost));
   if (bad != big) {
     c->broken = true;
     for (int k = 0; seq && k < c->nchar; k++) {
@@ -705,20 +726,13 @@ int push_kernels(uvaia_clust_ctx *c, uint8_t *rows, long long first, int n, cons
     }
     return cfail(c, UVAIA_GPU_EALPHABET, "sequence %lld (push ordinal) holds a byte 0 or >= 0x80", first + bad);
   }
-
-  CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  if (c->keep)
-    hipLaunchKernelGGL(clust_queue_kernel<SlabRows>, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, slab_rows_of(c, first), c->nchar, c->trim, c->dist,
-                       c->n_score, c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
-  else
-    hipLaunchKernelGGL(clust_queue_kernel<FlatRows>, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->nchar, c->trim, c->dist,
-                       c->n_score, c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
-  CCHK(c, hipGetLastError());
-  CCHK(c, hipEventRecord(c->ev_b, c->stream));
-  CCHK(c, hipEventSynchronize(c->ev_b));
-  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->queue_ms += ms;
-  if (c->keep) if (int rc = keep_founders(c, first, n)) return rc;
+  if ((rc = timed(c, c->queue_ms, [&] {
+        with_rows(c, first, [&](auto rows_at) {
+          hipLaunchKernelGGL(clust_queue_kernel<decltype(rows_at)>, dim3((unsigned)c->n_queues), dim3(QTPB), 0, c->stream, rows_at, c->nchar, c->trim, c->dist, c->n_score,
+                             c->d_dist, c->d_p, c->d_qoff, c->d_qlist, c->d_mcount, c->d_mord, c->d_mst, c->m_cap, c->d_join);
+        });
+      }))) return rc;
+  if (c->keep) if ((rc = keep_founders(c, first, n))) return rc;
   c->pushed += n;
   return 0;
 }
@@ -735,15 +749,14 @@ int gather_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n)
   }
   hipSetDevice(c->device);
   int rc;
-  if ((rc = ensure_bytes(c, (void **)&c->d_gord, &c->gord_cap, (size_t)n * sizeof(int)))) return rc;
-  if ((rc = ensure_bytes(c, (void **)&c->d_gather, &c->gather_cap, (size_t)n * c->pitch))) return rc;
-  CCHK(c, hipMemcpyAsync(c->d_gord, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (c->keep)
-    hipLaunchKernelGGL(clust_gather_rows_kernel<SlabRows>, dim3((unsigned)n), dim3(256), 0, c->stream, slab_rows_of(c, c->pushed), c->d_gord, c->d_gather);
-  else
-    hipLaunchKernelGGL(clust_gather_rows_kernel<FlatRows>, dim3((unsigned)n), dim3(256), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->d_gord, c->d_gather);
-  CCHK(c, hipGetLastError());
-  CCHK(c, hipStreamSynchronize(c->stream));        // ord leaves scope
+  if ((rc = reserve_idle(c, c->d_gord, (size_t)n))) return rc;
+  if ((rc = reserve_idle(c, c->d_gather, (size_t)n * c->pitch))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_gord, ord.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  with_rows(c, c->pushed, [&](auto rows_at) {
+    hipLaunchKernelGGL(clust_gather_rows_kernel<decltype(rows_at)>, dim3((unsigned)n), dim3(256), 0, c->stream, rows_at, c->d_gord, c->d_gather);
+  });
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));        // ord leaves scope
   return 0;
 }
 
@@ -764,6 +777,129 @@ struct ScoreOrder {
   }
 };
 
+// ---- uvaia_clust_finish, step by step.  L[q]: the cluster list queue q holds now.
+
+// the queues' medoid lists as phase 2 left them, the members attached; p: the score positions of every row
+int read_lists(uvaia_clust_ctx *c, std::vector<std::vector<Clust>> &L, std::vector<int> &p)
+{
+  const int Q = c->n_queues, ns = c->n_score;
+  const size_t N = (size_t)c->pushed;
+  std::vector<int> mcount((size_t)Q), join(N), mord((size_t)Q * c->m_cap), mst((size_t)Q * c->m_cap);
+  p.resize(N * (size_t)ns);
+  HIPCHK(c, hipMemcpy(mcount.data(), c->d_mcount, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost));
+  if (N) HIPCHK(c, hipMemcpy(join.data(), c->d_join, N * sizeof(int), hipMemcpyDeviceToHost));
+  if (N && ns) HIPCHK(c, hipMemcpy(p.data(), c->d_p, N * ns * sizeof(int), hipMemcpyDeviceToHost));
+  if (c->m_cap) {
+    HIPCHK(c, hipMemcpy(mord.data(), c->d_mord, mord.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(mst.data(), c->d_mst, mst.size() * sizeof(int), hipMemcpyDeviceToHost));
+  }
+  L.assign((size_t)Q, {});
+  for (int q = 0; q < Q; q++) {
+    L[(size_t)q].resize((size_t)mcount[(size_t)q]);
+    for (int s = 0; s < mcount[(size_t)q]; s++) {
+      Clust &k = L[(size_t)q][(size_t)s];
+      k.ord = mord[(size_t)q * c->m_cap + s]; k.stored = mst[(size_t)q * c->m_cap + s];
+    }
+  }
+  // members in push order, which is queue order: join[o] is a slot of o's own queue
+  for (size_t o = 0; o < N; o++) if (join[o] >= 0) L[(size_t)c->queue_of[o]][(size_t)join[o]].members.push_back((long long)o);
+  return 0;
+}
+
+// One round of the merge tree over cc lists: list j absorbs list j + cc / 2 + cc % 2.  An item is an absorbed cluster with its window
+// [lo, hi) of `list`, the absorbing lists laid end to end; target: the entry of `list` it joins, or -1.
+struct MergeRound {
+  int cc;
+  std::vector<int> item_ord, item_lo, item_hi, list, target;
+  std::vector<int> pair_item0, pair_list0;     // per pair: its first item, the start of its absorbing list
+  int absorbed(int j) const { return j + cc / 2 + cc % 2; }
+};
+struct MergeBufs { DevBuf<int> item_ord, item_lo, item_hi, list, target; };
+
+MergeRound build_round(const uvaia_clust_ctx *c, std::vector<std::vector<Clust>> &L, int cc, const ScoreOrder &by_score)
+{
+  MergeRound r; r.cc = cc;
+  for (int j = 0; j < cc / 2; j++) {
+    std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)r.absorbed(j)];
+    r.pair_item0.push_back((int)r.item_ord.size()); r.pair_list0.push_back((int)r.list.size());
+    if (B.empty()) continue;                                  // an empty absorbed queue: no-op
+    std::stable_sort(A.begin(), A.end(), by_score);
+    std::stable_sort(B.begin(), B.end(), by_score);
+    if (A.empty()) continue;                                  // spliced below: A takes B as it is sorted
+    const int base = (int)r.list.size();
+    for (const Clust &k : A) r.list.push_back(k.ord);
+    for (const Clust &k : B) {
+      // A is sorted by stored distance descending: the ring |stored - k.stored| <= d is one window
+      auto lo = std::partition_point(A.begin(), A.end(), [&](const Clust &x) { return x.stored > k.stored + c->dist; });
+      auto hi = std::partition_point(lo, A.end(), [&](const Clust &x) { return x.stored >= k.stored - c->dist; });
+      r.item_ord.push_back(k.ord); r.item_lo.push_back(base + (int)(lo - A.begin())); r.item_hi.push_back(base + (int)(hi - A.begin()));
+    }
+  }
+  r.target.assign(r.item_ord.size(), -1);
+  return r;
+}
+
+// the round on the device: items and lists up, one wave per item, the targets back; one wait for the stream
+int run_round(uvaia_clust_ctx *c, MergeRound &r, MergeBufs &d)
+{
+  const int n_items = (int)r.item_ord.size();
+  if (!n_items) return 0;
+  int rc;
+  // (no wait before these grow: the round before ended with a wait for the stream)
+  for (DevBuf<int> *b : {&d.item_ord, &d.item_lo, &d.item_hi, &d.target}) if ((rc = b->reserve(c, (size_t)n_items))) return rc;
+  if ((rc = d.list.reserve(c, r.list.size()))) return rc;
+  auto up = [&](int *dst, const std::vector<int> &v) { return hipMemcpyAsync(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, c->stream); };
+  HIPCHK(c, up(d.item_ord, r.item_ord)); HIPCHK(c, up(d.item_lo, r.item_lo)); HIPCHK(c, up(d.item_hi, r.item_hi)); HIPCHK(c, up(d.list, r.list));
+  if ((rc = timed_issue(c, [&] {
+        with_rows(c, c->pushed, [&](auto rows_at) {
+          hipLaunchKernelGGL(clust_merge_kernel<decltype(rows_at)>, dim3((unsigned)((n_items + PTPB / 64 - 1) / (PTPB / 64))), dim3(PTPB), 0, c->stream, rows_at, c->nchar,
+                             c->trim, c->dist, d.item_ord, d.item_lo, d.item_hi, d.list, n_items, d.target);
+        });
+      }))) return rc;
+  HIPCHK(c, hipMemcpyAsync(r.target.data(), d.target, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return timed_take(c, c->merge_ms);
+}
+
+// splice, in the absorbed list's sorted order (src/fastaseq.c:228-253)
+void splice_round(std::vector<std::vector<Clust>> &L, const MergeRound &r)
+{
+  for (int j = 0; j < r.cc / 2; j++) {
+    std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)r.absorbed(j)];
+    if (B.empty()) continue;
+    if (A.empty()) { A.swap(B); continue; }
+    int it = r.pair_item0[(size_t)j];
+    const int base = r.pair_list0[(size_t)j];
+    for (Clust &k : B) {
+      const int t = r.target[(size_t)it++];
+      if (t >= 0) {
+        Clust &to = A[(size_t)(t - base)];
+        to.members.push_back(k.ord);
+        to.members.insert(to.members.end(), k.members.begin(), k.members.end());
+      } else A.push_back(std::move(k));
+    }
+    B.clear();
+  }
+}
+
+// final order (src/cluster.c:233, compare_fastaseq src/fastaseq.c:23-29): more members first, then the score vectors; the result arrays
+void emit_result(uvaia_clust_ctx *c, std::vector<Clust> &F, const ScoreOrder &by_score)
+{
+  std::stable_sort(F.begin(), F.end(), [&](const Clust &a, const Clust &b) {
+    if (a.members.size() != b.members.size()) return a.members.size() > b.members.size();
+    return by_score(a, b);
+  });
+  c->r_medoid.clear(); c->r_offsets.assign(1, 0); c->r_members.clear(); c->r_scores.clear();
+  for (const Clust &k : F) {
+    c->r_medoid.push_back(k.ord);
+    c->r_members.insert(c->r_members.end(), k.members.begin(), k.members.end());
+    c->r_offsets.push_back((long long)c->r_members.size());
+    for (int s = 0; s < c->n_score + 2; s++) c->r_scores.push_back(by_score.key(k, s));
+  }
+}
+
+struct CloseClust { void operator()(uvaia_clust_ctx *c) const { uvaia_clust_close(c); } };
+
 }  // namespace
 
 extern "C" {
@@ -775,14 +911,6 @@ void uvaia_clust_close(uvaia_clust_ctx *c)
   if (!c) return;
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
-  hipFree(c->d_ref); hipFree(c->d_rows); hipFree(c->d_dist); hipFree(c->d_p); hipFree(c->d_join); hipFree(c->d_bad);
-  hipFree(c->d_qoff); hipFree(c->d_qlist); hipFree(c->d_mcount); hipFree(c->d_mord); hipFree(c->d_mst);
-  hipFree(c->d_tiles); hipFree(c->d_gather); hipFree(c->d_xoff); hipFree(c->d_xrec); hipFree(c->d_gord);
-  hipFree(c->d_slabtab); hipFree(c->d_stage); hipFree(c->d_slot); hipFree(c->d_mloc); hipFree(c->d_blk); hipFree(c->d_pq);
-  for (uint8_t *p : c->slabs) hipFree(p);
-  if (c->ev_a) hipEventDestroy(c->ev_a);
-  if (c->ev_b) hipEventDestroy(c->ev_b);
-  if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
 
@@ -804,23 +932,20 @@ int uvaia_clust_open(uvaia_clust_ctx **out, int device, const char *reference, i
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) return cfail(nullptr, UVAIA_GPU_ENODEV, "cannot query device %d", device);
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return cfail(nullptr, UVAIA_GPU_ENODEV, "device %d is %s: this library is built for gfx950 only", device, prop.gcnArchName);
   if (hipSetDevice(device) != hipSuccess) return cfail(nullptr, UVAIA_GPU_ENODEV, "cannot select device %d", device);
-  uvaia_clust_ctx *c = new uvaia_clust_ctx();
+  std::unique_ptr<uvaia_clust_ctx, CloseClust> c(new uvaia_clust_ctx());   // a failure below closes the half-made context; its message goes to uvaia_clust_last_error(NULL)
   c->device = device; c->nchar = nchar; c->dist = dist; c->trim = trim; c->n_score = n_score; c->n_queues = n_queues;
   c->pitch = ((size_t)nchar + 63) & ~(size_t)63;
   c->per_queue.assign((size_t)n_queues, 0);
   std::vector<uint8_t> ref(c->pitch, 0);
   for (int i = 0; i < nchar; i++) { const uint8_t b = (uint8_t)reference[i]; ref[(size_t)i] = (b >= 'a' && b <= 'z') ? b - 32 : b; }
-#define OCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { int rc_ = cfail(nullptr, e_ == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s", #call, hipGetErrorString(e_)); uvaia_clust_close(c); return rc_; } } while (0)
-  OCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  OCHK(hipEventCreate(&c->ev_a)); OCHK(hipEventCreate(&c->ev_b));
-  OCHK(hipMalloc(&c->d_ref, c->pitch));
-  OCHK(hipMemcpy(c->d_ref, ref.data(), c->pitch, hipMemcpyHostToDevice));
-  OCHK(hipMalloc(&c->d_bad, sizeof(int)));
-  OCHK(hipMalloc(&c->d_qoff, ((size_t)n_queues + 1) * sizeof(int)));
-  OCHK(hipMalloc(&c->d_mcount, (size_t)n_queues * sizeof(int)));
-  OCHK(hipMemset(c->d_mcount, 0, (size_t)n_queues * sizeof(int)));
-#undef OCHK
-  *out = c;
+  int rc;
+  HIPCHK(nullptr, hipStreamCreateWithFlags(&c->stream.s, hipStreamNonBlocking));
+  if ((rc = c->ev_a.make(nullptr)) || (rc = c->ev_b.make(nullptr))) return rc;
+  if ((rc = c->d_ref.reserve(nullptr, c->pitch))) return rc;
+  HIPCHK(nullptr, hipMemcpy(c->d_ref, ref.data(), c->pitch, hipMemcpyHostToDevice));
+  if ((rc = c->d_bad.reserve(nullptr, 1)) || (rc = c->d_qoff.reserve(nullptr, (size_t)n_queues + 1)) || (rc = c->d_mcount.reserve(nullptr, (size_t)n_queues))) return rc;
+  HIPCHK(nullptr, hipMemset(c->d_mcount, 0, (size_t)n_queues * sizeof(int)));
+  *out = c.release();
   return 0;
 }
 
@@ -838,7 +963,7 @@ int uvaia_clust_push(uvaia_clust_ctx *c, int n, const char *const *seq, const in
   // rows, padded with zero bytes to the pitch
   c->h_rows.assign((size_t)n * c->pitch, 0);
   for (int i = 0; i < n; i++) memcpy(c->h_rows.data() + (size_t)i * c->pitch, seq[i], (size_t)c->nchar);
-  CCHK(c, hipMemcpyAsync(dst, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(dst, c->h_rows.data(), c->h_rows.size(), hipMemcpyHostToDevice, c->stream));
   if ((rc = push_lists(c, first, n, queue))) return rc;
   return push_kernels(c, dst, first, n, seq);
 }
@@ -876,35 +1001,24 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
   if ((rc = push_rows_dst(c, first, n, &dst))) return rc;
   const int W4 = ((c->nchar + 31) / 32 + 3) / 4, n_tiles = (n + 63) / 64;
   const size_t tile_bytes = (size_t)W4 * 4 * 64 * 16, n_rec = (size_t)(x1 - x0);
-  if ((rc = ensure_bytes(c, (void **)&c->d_tiles, &c->tiles_cap, (size_t)n_tiles * tile_bytes))) return rc;
-  if ((rc = ensure_bytes(c, (void **)&c->d_xoff, &c->xoff_cap, ((size_t)n + 1) * sizeof(uint32_t)))) return rc;
-  if (n_rec && (rc = ensure_bytes(c, (void **)&c->d_xrec, &c->xrec_cap, n_rec * sizeof(uint2)))) return rc;
-  CCHK(c, hipMemcpyAsync(c->d_tiles, planes, (size_t)n_tiles * tile_bytes, hipMemcpyHostToDevice, c->stream));
+  if ((rc = reserve_idle(c, c->d_tiles, (size_t)n_tiles * tile_bytes))) return rc;
+  if ((rc = reserve_idle(c, c->d_xoff, (size_t)n + 1))) return rc;
+  if (n_rec && (rc = reserve_idle(c, c->d_xrec, n_rec))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->d_tiles, planes, (size_t)n_tiles * tile_bytes, hipMemcpyHostToDevice, c->stream));
   if (n_rec) {
     c->h_xoff.resize((size_t)n + 1);
     for (int i = 0; i <= n; i++) c->h_xoff[(size_t)i] = (uint32_t)(exc_offsets[i] - x0);
-    CCHK(c, hipMemcpyAsync(c->d_xoff, c->h_xoff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    CCHK(c, hipMemcpyAsync(c->d_xrec, rec + x0, n_rec * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_xoff, c->h_xoff.data(), ((size_t)n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_xrec, rec + x0, n_rec * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
   }
   const int units = (W4 + UGROUPS - 1) / UGROUPS;
-  float ms = 0;
-  CCHK(c, hipEventRecord(c->ev_a, c->stream));
-  hipLaunchKernelGGL(clust_unpack_tiles_kernel, dim3((unsigned)(n_tiles * units)), dim3(UTPB), 0, c->stream, reinterpret_cast<const uint4 *>(c->d_tiles), W4, c->nchar, n, dst,
-                     c->pitch, units);
-  CCHK(c, hipGetLastError());
-  CCHK(c, hipEventRecord(c->ev_b, c->stream));
-  CCHK(c, hipEventSynchronize(c->ev_b));
-  CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->decode_ms += ms;
-  if (n_rec) {
-    CCHK(c, hipEventRecord(c->ev_a, c->stream));
-    hipLaunchKernelGGL(clust_overlay_runs_kernel, dim3((unsigned)n), dim3(OTPB), 0, c->stream, dst, c->pitch, c->d_xoff, c->d_xrec);
-    CCHK(c, hipGetLastError());
-    CCHK(c, hipEventRecord(c->ev_b, c->stream));
-    CCHK(c, hipEventSynchronize(c->ev_b));
-    CCHK(c, hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-    c->overlay_ms += ms;
-  }
+  if ((rc = timed(c, c->decode_ms, [&] {
+        hipLaunchKernelGGL(clust_unpack_tiles_kernel, dim3((unsigned)(n_tiles * units)), dim3(UTPB), 0, c->stream, reinterpret_cast<const uint4 *>(c->d_tiles.p), W4, c->nchar, n,
+                           dst, c->pitch, units);
+      }))) return rc;
+  if (n_rec && (rc = timed(c, c->overlay_ms, [&] {
+        hipLaunchKernelGGL(clust_overlay_runs_kernel, dim3((unsigned)n), dim3(OTPB), 0, c->stream, dst, c->pitch, c->d_xoff, c->d_xrec);
+      }))) return rc;
   if ((rc = push_lists(c, first, n, queue))) return rc;
   return push_kernels(c, dst, first, n, nullptr);
 }
@@ -912,26 +1026,26 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
 int uvaia_clust_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (n < 0 || (n && (!ordinal || !rows))) return cfail(c, UVAIA_GPU_EINVAL, "bad arguments");
   if (n && pitch < (size_t)c->nchar) return cfail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
   if (!n) return 0;
   if (int rc = gather_rows(c, ordinal, n)) return rc;
-  CCHK(c, hipMemcpy2DAsync(rows, pitch, c->d_gather, c->pitch, (size_t)c->nchar, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-  CCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(rows, pitch, c->d_gather, c->pitch, (size_t)c->nchar, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int uvaia_clust_gather_device(uvaia_clust_ctx *c, const int64_t *ordinal, int n, const void **d_rows, size_t *pitch)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (n < 0 || (n && !ordinal)) return cfail(c, UVAIA_GPU_EINVAL, "bad arguments");
   if (n) {
     if (int rc = gather_rows(c, ordinal, n)) return rc;
-    CCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  if (d_rows) *d_rows = n ? c->d_gather : nullptr;
+  if (d_rows) *d_rows = n ? c->d_gather.p : nullptr;
   if (pitch) *pitch = c->pitch;
   return 0;
 }
@@ -939,7 +1053,7 @@ int uvaia_clust_gather_device(uvaia_clust_ctx *c, const int64_t *ordinal, int n,
 int uvaia_clust_device_rows(uvaia_clust_ctx *c, const void **d_rows, size_t *pitch)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (c->keep) return cfail(c, UVAIA_GPU_ESTATE, "this context keeps medoid rows only, in slabs: there is no row store to hand out; uvaia_clust_gather_device gives the rows of medoids");
   if (d_rows) *d_rows = c->d_rows;
   if (pitch) *pitch = c->pitch;
@@ -949,7 +1063,7 @@ int uvaia_clust_device_rows(uvaia_clust_ctx *c, const void **d_rows, size_t *pit
 int uvaia_clust_keep_medoids(uvaia_clust_ctx *c, int slab_rows)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (c->pushed || c->finished) return cfail(c, UVAIA_GPU_ESTATE, "uvaia_clust_keep_medoids after a push: the mode is chosen before the first one");
   if (slab_rows < 0 || (slab_rows & (slab_rows - 1))) return cfail(c, UVAIA_GPU_EINVAL, "slab_rows %d is not a power of two", slab_rows);
   c->keep = true;
@@ -976,130 +1090,20 @@ int uvaia_clust_memory(uvaia_clust_ctx *c, size_t *row_bytes, size_t *peak_row_b
 int uvaia_clust_finish(uvaia_clust_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
-  if (c->broken) return cfail(c, UVAIA_GPU_ESTATE, "context unusable after an earlier error: %s", c->err.c_str());
+  if (int rc = usable(c)) return rc;
   if (c->finished) return cfail(c, UVAIA_GPU_ESTATE, "finish called twice");
   hipSetDevice(c->device);
-  const int Q = c->n_queues, ns = c->n_score;
-  const size_t N = (size_t)c->pushed;
-  std::vector<int> mcount((size_t)Q), join(N), p(N * (size_t)ns);
-  CCHK(c, hipMemcpy(mcount.data(), c->d_mcount, (size_t)Q * sizeof(int), hipMemcpyDeviceToHost));
-  if (N) CCHK(c, hipMemcpy(join.data(), c->d_join, N * sizeof(int), hipMemcpyDeviceToHost));
-  if (N && ns) CCHK(c, hipMemcpy(p.data(), c->d_p, N * ns * sizeof(int), hipMemcpyDeviceToHost));
-  std::vector<std::vector<Clust>> L((size_t)Q);
-  {
-    std::vector<int> mord, mst;
-    if (c->m_cap) {
-      mord.resize((size_t)Q * c->m_cap); mst.resize((size_t)Q * c->m_cap);
-      CCHK(c, hipMemcpy(mord.data(), c->d_mord, mord.size() * sizeof(int), hipMemcpyDeviceToHost));
-      CCHK(c, hipMemcpy(mst.data(), c->d_mst, mst.size() * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    for (int q = 0; q < Q; q++) {
-      L[(size_t)q].resize((size_t)mcount[(size_t)q]);
-      for (int s = 0; s < mcount[(size_t)q]; s++) {
-        Clust &k = L[(size_t)q][(size_t)s];
-        k.ord = mord[(size_t)q * c->m_cap + s]; k.stored = mst[(size_t)q * c->m_cap + s];
-      }
-    }
-    // members in push order, which is queue order: join[o] is a slot of o's own queue
-    for (size_t o = 0; o < N; o++) if (join[o] >= 0) L[(size_t)c->queue_of[o]][(size_t)join[o]].members.push_back((long long)o);
+  std::vector<std::vector<Clust>> L;
+  std::vector<int> p;
+  if (int rc = read_lists(c, L, p)) return rc;
+  const ScoreOrder by_score{&p, c->n_score, c->nchar};
+  MergeBufs bufs;
+  for (int cc = c->n_queues; cc > 1; cc = cc / 2 + cc % 2) {
+    MergeRound r = build_round(c, L, cc, by_score);
+    if (int rc = run_round(c, r, bufs)) return rc;
+    splice_round(L, r);
   }
-  ScoreOrder by_score{&p, ns, c->nchar};
-  float ms = 0;
-  int *d_item_ord = nullptr, *d_item_lo = nullptr, *d_item_hi = nullptr, *d_list = nullptr, *d_target = nullptr;
-  size_t items_cap = 0, list_cap = 0;
-  auto free_merge = [&]() { hipFree(d_item_ord); hipFree(d_item_lo); hipFree(d_item_hi); hipFree(d_list); hipFree(d_target); };
-  for (int cc = Q; cc > 1; cc = cc / 2 + cc % 2) {
-    std::vector<int> item_ord, item_lo, item_hi, list;
-    std::vector<int> pair_item0, pair_list0;
-    for (int j = 0; j < cc / 2; j++) {
-      const int i = j + cc / 2 + cc % 2;
-      std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)i];
-      pair_item0.push_back((int)item_ord.size()); pair_list0.push_back((int)list.size());
-      if (B.empty()) continue;                                  // an empty absorbed queue: no-op
-      std::stable_sort(A.begin(), A.end(), by_score);
-      std::stable_sort(B.begin(), B.end(), by_score);
-      if (A.empty()) continue;                                  // spliced below: A takes B as it is sorted
-      const int base = (int)list.size();
-      for (const Clust &k : A) list.push_back(k.ord);
-      for (const Clust &k : B) {
-        // A is sorted by stored distance descending: the ring |stored - k.stored| <= d is one window
-        auto lo = std::partition_point(A.begin(), A.end(), [&](const Clust &x) { return x.stored > k.stored + c->dist; });
-        auto hi = std::partition_point(lo, A.end(), [&](const Clust &x) { return x.stored >= k.stored - c->dist; });
-        item_ord.push_back(k.ord); item_lo.push_back(base + (int)(lo - A.begin())); item_hi.push_back(base + (int)(hi - A.begin()));
-      }
-    }
-    const int n_items = (int)item_ord.size();
-    std::vector<int> target((size_t)n_items, -1);
-    if (n_items) {
-      if ((size_t)n_items > items_cap) {
-        hipFree(d_item_ord); hipFree(d_item_lo); hipFree(d_item_hi); hipFree(d_target);
-        d_item_ord = d_item_lo = d_item_hi = d_target = nullptr;
-        if (hipMalloc(&d_item_ord, n_items * sizeof(int)) != hipSuccess || hipMalloc(&d_item_lo, n_items * sizeof(int)) != hipSuccess ||
-            hipMalloc(&d_item_hi, n_items * sizeof(int)) != hipSuccess || hipMalloc(&d_target, n_items * sizeof(int)) != hipSuccess) {
-          free_merge(); c->broken = true;
-          return cfail(c, UVAIA_GPU_ENOMEM, "merge round of %d items: device allocation failed", n_items);
-        }
-        items_cap = (size_t)n_items;
-      }
-      if (list.size() > list_cap) {
-        hipFree(d_list); d_list = nullptr;
-        if (hipMalloc(&d_list, list.size() * sizeof(int)) != hipSuccess) { free_merge(); c->broken = true; return cfail(c, UVAIA_GPU_ENOMEM, "merge lists: device allocation failed"); }
-        list_cap = list.size();
-      }
-      hipError_t e = hipSuccess;
-      auto up = [&](int *dst, const std::vector<int> &v) { if (e == hipSuccess) e = hipMemcpyAsync(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, c->stream); };
-      up(d_item_ord, item_ord); up(d_item_lo, item_lo); up(d_item_hi, item_hi); up(d_list, list);
-      if (e == hipSuccess) e = hipEventRecord(c->ev_a, c->stream);
-      if (e == hipSuccess) {
-        const dim3 grid((unsigned)((n_items + PTPB / 64 - 1) / (PTPB / 64)));
-        if (c->keep)
-          hipLaunchKernelGGL(clust_merge_kernel<SlabRows>, grid, dim3(PTPB), 0, c->stream, slab_rows_of(c, c->pushed), c->nchar, c->trim, c->dist, d_item_ord, d_item_lo,
-                             d_item_hi, d_list, n_items, d_target);
-        else
-          hipLaunchKernelGGL(clust_merge_kernel<FlatRows>, grid, dim3(PTPB), 0, c->stream, FlatRows{c->d_rows, c->pitch}, c->nchar, c->trim, c->dist, d_item_ord, d_item_lo,
-                             d_item_hi, d_list, n_items, d_target);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipEventRecord(c->ev_b, c->stream);
-      if (e == hipSuccess) e = hipMemcpyAsync(target.data(), d_target, (size_t)n_items * sizeof(int), hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev_a, c->ev_b);
-      if (e != hipSuccess) { free_merge(); c->broken = true; return cfail(c, UVAIA_GPU_EHIP, "merge round: %s", hipGetErrorString(e)); }
-      c->merge_ms += ms;
-    }
-    // splice, in the absorbed list's sorted order (src/fastaseq.c:228-253)
-    for (int j = 0; j < cc / 2; j++) {
-      const int i = j + cc / 2 + cc % 2;
-      std::vector<Clust> &A = L[(size_t)j], &B = L[(size_t)i];
-      if (B.empty()) continue;
-      if (A.empty()) { A.swap(B); continue; }
-      int it = pair_item0[(size_t)j];
-      const int base = pair_list0[(size_t)j];
-      for (Clust &k : B) {
-        const int t = target[(size_t)it++];
-        if (t >= 0) {
-          Clust &to = A[(size_t)(t - base)];
-          to.members.push_back(k.ord);
-          to.members.insert(to.members.end(), k.members.begin(), k.members.end());
-        } else A.push_back(std::move(k));
-      }
-      B.clear();
-    }
-  }
-  free_merge();
-  // final order (src/cluster.c:233, compare_fastaseq src/fastaseq.c:23-29): more members first, then the score vectors
-  std::vector<Clust> &F = L[0];
-  std::stable_sort(F.begin(), F.end(), [&](const Clust &a, const Clust &b) {
-    if (a.members.size() != b.members.size()) return a.members.size() > b.members.size();
-    return by_score(a, b);
-  });
-  c->r_medoid.clear(); c->r_offsets.assign(1, 0); c->r_members.clear(); c->r_scores.clear();
-  for (const Clust &k : F) {
-    c->r_medoid.push_back(k.ord);
-    c->r_members.insert(c->r_members.end(), k.members.begin(), k.members.end());
-    c->r_offsets.push_back((long long)c->r_members.size());
-    for (int s = 0; s < ns + 2; s++) c->r_scores.push_back(by_score.key(k, s));
-  }
+  emit_result(c, L[0], by_score);
   c->finished = true;
   return 0;
 }
