@@ -417,6 +417,26 @@ int uvaia_gpu_db_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char 
 void uvaia_gpu_window_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 size_t uvaia_gpu_free_bytes (uvaia_gpu_ctx *ctx);
 
+/* ---- resident tiles written in the compact form of a packed database (version 2 of uvaia_amd/csrc/host/uvdb.h), the inverse of
+ * stage_compact_at: per lane the 32-site words that differ from a base row, as the canonical fill and literal heads the host writer
+ * (uvdb_create_compact) gives the same rows.  About a twelfth of what uvaia_gpu_db_export copies leaves the device.  Two steps, because the
+ * sizes of the records are only known after the first:
+ *   db_encode_compact   base: one reference's worth of planes in the file's [word group][plane A,C,G,T] order (16-byte words), any base --
+ *                  correctness does not depend on it.  Counts the records of resident tiles first_tile .. first_tile + n_tiles - 1 and
+ *                  fills head_idx and lit_idx (n_tiles * 64 + 1 offsets each, from 0; literal offsets in words of 16 bytes) and non_n
+ *                  (n_tiles * 64 counts, as uvaia_gpu_db_export gives them).  Lanes at and past the last resident reference are encoded as
+ *                  all-zero rows, which is what the index sections of a file hold for them.  The plan stays in the context.
+ *   db_encoded_records  the records of the plan: head_idx[last] dwords to heads, 4 * lit_idx[last] dwords to lits (planes A, C, G, T of every
+ *                  literal word).  Every store on the device is bounded by the extent the plan gives its lane.
+ *   Refusals, all leaving the context usable: those of uvaia_gpu_db_export (an --acgt context, a context of a reference shard: UVAIA_GPU_ESTATE;
+ *   tiles outside the database: UVAIA_GPU_EINVAL); an alignment of more than UVAIA_GPU_COMPACT_MAX_NCHAR sites, db_encoded_records without a
+ *   plan or after any call that changed the database (appends, loads, db_skip, db_clear, db_drop_tiles): UVAIA_GPU_ESTATE.
+ *   encode_ms      device time in ms since the last reset of [0] the count and prefix passes, [1] the emit pass */
+#define UVAIA_GPU_COMPACT_MAX_NCHAR 2097152
+int uvaia_gpu_db_encode_compact (uvaia_gpu_ctx *ctx, size_t first_tile, size_t n_tiles, const void *base, uint64_t *head_idx, uint64_t *lit_idx, int *non_n);
+int uvaia_gpu_db_encoded_records (uvaia_gpu_ctx *ctx, uint32_t *heads, void *lits);
+void uvaia_gpu_encode_ms (uvaia_gpu_ctx *ctx, double out[2], int reset);
+
 /* ---- rows that are already in device memory (what the aligner leaves behind, include/uvaia_align.h; a tensor of the caller): into the
  * resident database and a packed database file without a round trip of their text.  A block is n rows of nchar bytes, `pitch` bytes apart
  * (pitch >= nchar; neither the pitch nor the first row need any alignment).  Every d_rows below must be memory of the context's device: the

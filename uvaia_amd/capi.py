@@ -31,6 +31,7 @@ SYMBOLS = [
     "uvaia_gpu_rows_census", "uvaia_gpu_db_append_device", "uvaia_gpu_rows_exceptions", "uvaia_gpu_db_drop_tiles", "uvaia_gpu_rows_kernel_ms", "uvaia_gpu_rows_set_run_cut",
     "uvaia_gpu_db_stage_reserve", "uvaia_gpu_db_stage_packed", "uvaia_gpu_db_load_staged", "uvaia_gpu_db_unpack_rows", "uvaia_gpu_window_ms", "uvaia_gpu_free_bytes",
     "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged", "uvaia_gpu_db_stage_compact_at", "uvaia_gpu_compact_ms",
+    "uvaia_gpu_db_encode_compact", "uvaia_gpu_db_encoded_records", "uvaia_gpu_encode_ms",
 ]
 
 
@@ -196,6 +197,9 @@ def load_library():
         "uvaia_gpu_db_append_staged": (C.c_int, [vp, C.c_int, pi, C.c_int]),
         "uvaia_gpu_db_stage_compact_at": (C.c_int, [vp, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, pi, C.c_int]),
         "uvaia_gpu_compact_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_db_encode_compact": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, pi]),
+        "uvaia_gpu_db_encoded_records": (C.c_int, [vp, C.c_void_p, C.c_void_p]),
+        "uvaia_gpu_encode_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_db_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_window_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
@@ -642,6 +646,39 @@ class Engine:
         """Device ms since the last reset of (expand_tiles_kernel, the side-row pass after it)."""
         out = (C.c_double * 2)()
         self.L.uvaia_gpu_compact_ms(self.ctx, out, int(reset))
+        return tuple(out)
+
+    def db_encode_compact(self, base, first_tile=0, n_tiles=None):
+        """Count pass of the compact form of resident tiles against `base` (uint32, one reference's worth of planes in the file's
+        [word group][plane][4] order): (head_idx uint64 [n_tiles*64 + 1], lit_idx uint64 [n_tiles*64 + 1], non_n int32 [n_tiles*64]).
+        The offsets start at 0, literal offsets count words of 16 bytes; db_encoded_records() then gives the records."""
+        if n_tiles is None:
+            n_tiles = (self.db_size() + 63) // 64 - first_tile
+        base = np.ascontiguousarray(base, dtype=np.uint32)
+        if base.size * 4 * 64 != self.L.uvaia_gpu_db_tile_bytes(self.ctx):
+            raise ValueError("the base is not one reference's worth of planes")
+        lanes = int(n_tiles) * 64
+        head_idx = np.zeros(lanes + 1, dtype=np.uint64)
+        lit_idx = np.zeros(lanes + 1, dtype=np.uint64)
+        non_n = np.zeros(max(lanes, 1), dtype=np.int32)
+        self._encode_sizes = None
+        self._chk(self.L.uvaia_gpu_db_encode_compact(self.ctx, int(first_tile), int(n_tiles), base.ctypes.data, head_idx.ctypes.data, lit_idx.ctypes.data,
+                                                     non_n.ctypes.data_as(C.POINTER(C.c_int))))
+        self._encode_sizes = (int(head_idx[lanes]), int(lit_idx[lanes]))
+        return head_idx, lit_idx, non_n[:lanes]
+
+    def db_encoded_records(self):
+        """Emit pass of the plan db_encode_compact left: (heads uint32 [head_idx[-1]], lits uint32 [lit_idx[-1], 4])."""
+        nh, nl = getattr(self, "_encode_sizes", None) or (0, 0)
+        heads = np.zeros(nh, dtype=np.uint32)
+        lits = np.zeros((nl, 4), dtype=np.uint32)
+        self._chk(self.L.uvaia_gpu_db_encoded_records(self.ctx, heads.ctypes.data if nh else None, lits.ctypes.data if nl else None))
+        return heads, lits
+
+    def encode_ms(self, reset=False):
+        """Device ms since the last reset of (count + prefix passes, emit pass) of the compact encoder."""
+        out = (C.c_double * 2)()
+        self.L.uvaia_gpu_encode_ms(self.ctx, out, int(reset))
         return tuple(out)
 
     def db_append_staged(self, slot, sel, n_ref):

@@ -34,7 +34,7 @@ packer_add_pool (struct uvdb_packer *p, uvaia_aligner *al, char **name, int fill
 int
 main (int argc, char **argv)
 {
-  int help = 0, version = 0, to_screen = 0, pool = 256 * omp_get_max_threads (), device = 0, errors = 0, n_fasta = 0, ch;   /* src/align.c:59-63 */
+  int help = 0, version = 0, to_screen = 0, pool = 256 * omp_get_max_threads (), device = 0, errors = 0, n_fasta = 0, compact = 0, ch;   /* src/align.c:59-63 */
   int devices[64], n_devices = 0;
   double ambig = 0.5, ambig_r = 0.5;
   const char *out = NULL, *ref_file = NULL, *packed = NULL;
@@ -42,7 +42,7 @@ main (int argc, char **argv)
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"stdout", no_argument, 0, 1000}, {"ambiguity", required_argument, 0, 'a'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002},
-    {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {0, 0, 0, 0}};
+    {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"compact", no_argument, 0, 1004}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -55,15 +55,20 @@ main (int argc, char **argv)
     case 1001: device = atoi (optarg); break;
     case 1002: n_devices = uvaia_parse_device_list (optarg, devices, 64); if (!n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); exit (EXIT_FAILURE); } break;
     case 1003: packed = optarg; break;
+    case 1004: compact = 1; break;
     case 'A': ambig_r = atof (optarg); break;
     default: errors++;
   }
   const char **fasta = (const char **) argv + optind;
   n_fasta = argc - optind;
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
+  if (!help && !errors && compact && !packed) {
+    fprintf (stderr, "--compact chooses the form of the packed database: it needs --packed <out.uvdb>\n");
+    errors++;
+  }
   if (help || errors || !ref_file || n_fasta < 1 || pool < 1) {
     printf ("%s \nAlign query sequences against a reference\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb>] [-A <double>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  --stdout                         print alignment to stdout (to redirect/pipe) instead of compress to file; much faster but may generate a big output\n");
     printf ("  -p, --pool=<int>                 How many query sequences are read in batch, to be aligned in parallel (defaults to 256 per thread)\n");
@@ -76,6 +81,8 @@ main (int argc, char **argv)
     printf ("  --devices=<list>                 several GPUs, e.g. 0-7 or 0,2,3: every pool of queries is cut among them (same rows as one GPU)\n");
     printf ("  --packed=<out.uvdb>              write the aligned sequences straight into a packed database, the file `uvaiapack` makes of the text output;\n");
     printf ("                                   the text itself is then written only if -o or --stdout is given as well (one GPU only)\n");
+    printf ("  --compact                        with --packed: write the compact form of the database, the file `uvaiapack --compact` makes of the text output\n");
+    printf ("                                   (several times smaller; encoded on the GPU once its base row is fixed, after 4096 sequences)\n");
     printf ("  -A, --ref_ambiguity=<double>     with --packed: maximum allowed ambiguity for an ALIGNED sequence to be kept in the database (default=0.5), as in `uvaiapack`\n");
     if (help) {
       printf ("Based on the wavefront algorithm (WFA, https://github.com/smarco/WFA), computed on the GPU.\n");
@@ -116,6 +123,7 @@ main (int argc, char **argv)
   const size_t aln_length = rfas->seqlength;
   del_readfasta (rfas);
   if (aln_length > 0x3fffffff) biomcmc_error ("reference sequence of %zu sites is too long", aln_length);
+  if (compact && aln_length > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%zu sites)", UVDB_COMPACT_MAX_NCHAR, aln_length);
   /* alignments of different queries do not depend on each other: with several GPUs every pool is cut into contiguous shares, one
      aligner and one host thread per GPU (replicas of src/align.c's per-thread aligners, no exchange) */
   if (!n_devices) { n_devices = 1; devices[0] = device; }
@@ -127,7 +135,7 @@ main (int argc, char **argv)
   struct uvdb_packer pk;
   double align_ms = 0.;
   if (packed) {
-    if (uvdb_packer_open (&pk, packed, (int) aln_length, ambig_r, devices[0], pool)) biomcmc_error ("%s", pk.err);
+    if (uvdb_packer_open (&pk, packed, (int) aln_length, ambig_r, devices[0], pool, compact)) biomcmc_error ("%s", pk.err);
     fprintf (stderr, "Aligned sequences with at least %d valid sites will be packed into %s.\n", pk.non_n_ref, packed);
   }
   file_compress_t outstream = (to_screen || !write_text) ? NULL : biomcmc_open_compress (outfilename, "w");
@@ -225,6 +233,7 @@ main (int argc, char **argv)
     if (uvdb_packer_close (&pk)) biomcmc_error ("%s", pk.err);
     fprintf (stderr, "Packed %ld of %d aligned sequences (%zu sites) into %s; %ld too ambiguous.\n", kept, n_output, aln_length, packed, dropped);
     fprintf (stderr, "Device time: alignment %.3lf ms; census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n", align_ms, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
+    if (compact) fprintf (stderr, "Compact tiles: %ld encoded on the device (count and prefix %.3lf ms, emit %.3lf ms), %ld on the host.\n", pk.tiles_device, pk.encode_ms[0], pk.encode_ms[1], pk.tiles_host);
   }
   if (to_screen) fprintf (stderr, "Output %d aligned sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
   else if (!write_text) fprintf (stderr, "Aligned %d sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));

@@ -130,16 +130,17 @@ packer_report (const struct uvdb_packer *pk, const char *path, int n_out, int nc
 {
   fprintf (stderr, "Packed %ld of %d medoids (%d sites) into %s; %ld too ambiguous. Device time: census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n",
            kept, n_out, nchar, path, dropped, pk->rows_ms[0], pk->rows_ms[1], pk->rows_ms[2]);
+  if (pk->compact) fprintf (stderr, "Compact tiles: %ld encoded on the device (count and prefix %.3lf ms, emit %.3lf ms), %ld on the host.\n", pk->tiles_device, pk->encode_ms[0], pk->encode_ms[1], pk->tiles_host);
 }
 
 /* --packed-out with --keep-medoids: there is no row store to read in place, so each batch of medoids, in the final order, is gathered into
    consecutive rows of device memory (uvaia_clust_gather_device) and goes to the packer as a block: census, filter and append as below */
 static void
-write_packed_out_gathered (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, const int64_t *medoid, int n_out,
+write_packed_out_gathered (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, int compact, const int64_t *medoid, int n_out,
                            const char *(*name_of) (void *, int64_t), void *name_arg)
 {
   struct uvdb_packer pk;
-  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH)) biomcmc_error ("%s", pk.err);
+  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH, compact)) biomcmc_error ("%s", pk.err);
   char **name = (char **) biomcmc_malloc (UVDB_PACK_BATCH * sizeof (char *));
   for (int a = 0; a < n_out; a += UVDB_PACK_BATCH) {
     const int m = n_out - a < UVDB_PACK_BATCH ? n_out - a : UVDB_PACK_BATCH;
@@ -161,13 +162,13 @@ write_packed_out_gathered (const char *path, uvaia_clust_ctx *ctx, int device, i
 
 /* --packed-out: the medoids in their final order into a packed database, from the rows in the clusterer's device memory */
 static void
-write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, int64_t count, const int64_t *medoid, int n_out,
+write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar, double ambig_r, int compact, int64_t count, const int64_t *medoid, int n_out,
                   const char *(*name_of) (void *, int64_t), void *name_arg)
 {
   const void *d_rows = NULL; size_t pitch = 0;
   if (uvaia_clust_device_rows (ctx, &d_rows, &pitch)) biomcmc_error ("%s", uvaia_clust_last_error (ctx));
   struct uvdb_packer pk;
-  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH)) biomcmc_error ("%s", pk.err);
+  if (uvdb_packer_open (&pk, path, nchar, ambig_r, device, UVDB_PACK_BATCH, compact)) biomcmc_error ("%s", pk.err);
   /* the census takes consecutive rows: the whole store in blocks, the counts of the medoids are kept */
   int *slot = (int *) biomcmc_malloc ((size_t) (count + 1) * sizeof (int));
   int *m_nn = (int *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int)), *m_exc = (int *) biomcmc_malloc ((size_t) (n_out + 1) * sizeof (int));
@@ -207,7 +208,7 @@ static const char *name_from_db (void *v, int64_t i) { return uvdb_set_name ((uv
 int
 main (int argc, char **argv)
 {
-  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, ch;   /* src/cluster.c:57-64 */
+  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, compact = 0, ch;   /* src/cluster.c:57-64 */
   double ambig_r = -1.;
   const char *out = "cluster_uvaia", *ref_file = NULL, *packed = NULL, *packed_out = NULL;
   const char **packed_files = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *)); int n_packed = 0;
@@ -215,7 +216,7 @@ main (int argc, char **argv)
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
     {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"packed", required_argument, 0, 1002},
-    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"keep-medoids", no_argument, 0, 1004}, {0, 0, 0, 0}};
+    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"keep-medoids", no_argument, 0, 1004}, {"compact", no_argument, 0, 1005}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -229,6 +230,7 @@ main (int argc, char **argv)
     case 1002: if (!packed) packed = optarg; packed_files[n_packed++] = optarg; break;
     case 1003: if (packed_out) errors++; packed_out = optarg; break;
     case 1004: keep_medoids = 1; break;
+    case 1005: compact = 1; break;
     case 'A': ambig_r = atof (optarg); if (ambig_r < 0.) ambig_r = 0.; break;
     default: errors++;
   }
@@ -239,9 +241,13 @@ main (int argc, char **argv)
     fprintf (stderr, "--packed %s takes the place of the alignment files: give one or the other, not both (%s was given as well)\n", packed, fasta[0]);
     errors++;
   }
+  if (!help && !errors && compact && !packed_out) {
+    fprintf (stderr, "--compact chooses the form of the packed database of medoids: it needs --packed-out <out.uvdb>\n");
+    errors++;
+  }
   if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024 || n_packed > UVDB_SET_MAX_FILES) {
     printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb>] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb> [--packed <in.uvdb>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb> [--compact]] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb> [--packed <in.uvdb>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
     printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
@@ -255,6 +261,8 @@ main (int argc, char **argv)
     printf ("                                   its tiles are decoded on the GPU, no text is parsed or held; same output files as from the same sequences as text;\n");
     printf ("                                   can be several files, clustered in the order given like several alignment files\n");
     printf ("  --packed-out=<out.uvdb>          also write the medoids as a packed database, the file `uvaiapack` makes of <prefix>.aln.xz (with either kind of input)\n");
+    printf ("  --compact                        with --packed-out: write the compact form of that database, the file `uvaiapack --compact` makes of <prefix>.aln.xz\n");
+    printf ("                                   (several times smaller; encoded on the GPU once its base row is fixed, after 4096 medoids)\n");
     printf ("  -A, --ref_ambiguity=<double>     with --packed-out: maximum allowed ambiguity for a medoid to be kept in that database, as in `uvaiapack`\n");
     printf ("                                   (default: the value recorded in the --packed database, 0.5 for alignment files)\n");
     printf ("  --keep-medoids                   keep only the sequences that found a cluster in GPU memory, not every sequence: memory follows the number of\n");
@@ -295,6 +303,7 @@ main (int argc, char **argv)
   if (ref_file) refseq = read_reference (ref_file, 1, &nchar);
   else if (db) { refseq = read_reference_packed (db, packed, 1024); nchar = (int) db->h.nchar; }
   else refseq = read_reference (fasta[0], 1024, &nchar);
+  if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);
   if (db && (uint32_t) nchar != db->h.nchar)
     biomcmc_error ("%s cannot work with unaligned sequences; the sequences of %s have %u sites while reference has %d.", UVAIA_PACKAGE_STRING, packed, db->h.nchar, nchar);
   if (trim < 0) trim = 0;                                                  /* new_cqueue, src/cluster.c:287-289 */
@@ -409,8 +418,8 @@ main (int argc, char **argv)
     free (text);
   } else for (int c = 0; c < n_out; c++) write_fasta_record (aln, names.v[medoid[c]], seqs.v[medoid[c]]);
   biomcmc_close_compress (aln);
-  if (packed_out && keep_medoids) write_packed_out_gathered (packed_out, ctx, device, nchar, ambig_r, medoid, n_out, name_of, name_arg);
-  else if (packed_out) write_packed_out (packed_out, ctx, device, nchar, ambig_r, count, medoid, n_out, name_of, name_arg);
+  if (packed_out && keep_medoids) write_packed_out_gathered (packed_out, ctx, device, nchar, ambig_r, compact, medoid, n_out, name_of, name_arg);
+  else if (packed_out) write_packed_out (packed_out, ctx, device, nchar, ambig_r, compact, count, medoid, n_out, name_of, name_arg);
   uvaia_clust_close (ctx);
   fprintf (stderr, "GPU memory for sequence rows: %zu bytes at the peak (%s)\n", peak_row_bytes, keep_medoids ? "medoid rows in slabs and one push" : "every row kept");
   fprintf (stderr, "%d clusters from %ld sequences; GPU kernels: prep %.3lf ms, queues %.3lf ms, merge %.3lf ms, decode %.3lf ms, overlay %.3lf ms\n", n_out, (long) count,

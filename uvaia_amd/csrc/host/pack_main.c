@@ -2,7 +2,7 @@
  * pack_main.c -- `uvaiapack`: aligned reference FASTA (raw/gz/xz/bz2, several files) -> packed database (uvdb.h).
  * No counterpart in the reference.  The filters of the reference's slot-filling loop that do not depend on
  * the queries are applied here once: the length check and the -A ambiguity filter (src/nearest.c:263-268).  The packing itself
- * runs on the GPU (uvaia_gpu_db_append + uvaia_gpu_db_export): the file holds exactly what the engine keeps resident.  Own code.
+ * runs on the GPU (uvaia_gpu_db_append + uvdb_export_tiles, uvdb_packer.h): the file holds exactly what the engine keeps resident.  Own code.
  *
  * `uvaiapack --merge`: packed databases -> one packed database, without their text: the file the same command without --merge writes from
  * the texts the inputs were packed from, byte for byte.  The tiles of an input are staged as the file holds them and its references
@@ -11,7 +11,8 @@
  *
  * `uvaiapack --compact` writes version 2 of the format (uvdb.h: a base row and per-reference differences, expanded on the GPU by
  * `uvaia --packed`), from texts or, with --merge, from packed inputs of either version; --merge without it reads both versions and
- * writes version 1, the way back to the dense file.
+ * writes version 1, the way back to the dense file.  Once the base row is fixed (the first 4 096 references) the tiles are encoded on the
+ * GPU and only their records cross the bus (uvdb_export_tiles).
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -21,6 +22,7 @@
 #include "fastaseq.h"
 #include "uvdb.h"
 #include "uvdb_set.h"
+#include "uvdb_packer.h"
 #include "../../../include/uvaia_gpu.h"
 
 #define PACK_BATCH 4096      /* references per engine round trip (a multiple of 64) */
@@ -78,8 +80,8 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
   if (set->tile_bytes != tb || set->side_row_ints != (uint32_t) row) biomcmc_error ("packed database %s does not match this engine's tile layout", in[0]);
   /* resident: what a round leaves behind (below MERGE_BATCH) and one chunk on top of it */
   if (uvaia_gpu_db_reserve (gpu, 2 * MERGE_BATCH) || uvaia_gpu_db_stage_reserve (gpu, CHUNK_TILES)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-  void *planes = biomcmc_malloc ((size_t) (2 * CHUNK_TILES) * tb);
-  int *tile_nonn = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * sizeof (int)), *side = (int *) biomcmc_malloc ((size_t) 2 * MERGE_BATCH * row * sizeof (int));
+  struct uvdb_export exp;
+  memset (&exp, 0, sizeof exp);
   int *sel = (int *) biomcmc_malloc (MERGE_BATCH * sizeof (int));
   uvdb_writer w = compact ? uvdb_create_compact (out, nchar, tb, (int) row, ambig_r) : uvdb_create (out, nchar, tb, (int) row, ambig_r);
   if (!w) biomcmc_error ("cannot create %s", out);
@@ -106,22 +108,24 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
       slot ^= 1;
       const size_t whole = uvaia_gpu_db_size (gpu) / 64;
       if (uvaia_gpu_db_size (gpu) >= MERGE_BATCH) {
-        if (uvaia_gpu_db_export (gpu, 0, whole, planes, tile_nonn, side) || uvaia_gpu_db_drop_tiles (gpu, whole)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-        if (uvdb_add_tiles (w, whole, planes, tile_nonn, side)) biomcmc_error ("cannot write to %s", out);
+        if (uvdb_export_tiles (&exp, gpu, w, 0, whole)) biomcmc_error ("%s: %s", out, exp.err);
+        if (uvaia_gpu_db_drop_tiles (gpu, whole)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
       }
     }
     if (db) fprintf (stderr, "Finished merging file %s in %.3lf secs; %ld sequences so far, %ld kept.\n", in[f], biomcmc_update_elapsed_time (time0), count, kept);
     else if (uvaia_gpu_db_size (gpu)) {                  /* the tail after the last input */
       const size_t nt = (uvaia_gpu_db_size (gpu) + 63) / 64;
-      if (uvaia_gpu_db_export (gpu, 0, nt, planes, tile_nonn, side)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-      if (uvdb_add_tiles (w, nt, planes, tile_nonn, side)) biomcmc_error ("cannot write to %s", out);
+      if (uvdb_export_tiles (&exp, gpu, w, 0, nt)) biomcmc_error ("%s: %s", out, exp.err);
     }
   }
   if (uvdb_close (w)) biomcmc_error ("problem writing %s", out);
-  fprintf (stderr, "Merged %ld of %ld sequences (%d sites, -A %g) from %d packed databases into %s\n", kept, count, nchar, ambig_r, n_in, out);
+  fprintf (stderr, "Merged %ld of %ld sequences (%d sites, -A %g) from %d packed databases into %s", kept, count, nchar, ambig_r, n_in, out);
+  if (compact) fprintf (stderr, "; compact tiles: %ld encoded on the device, %ld on the host", exp.tiles_device, exp.tiles_host);
+  fprintf (stderr, "\n");
   uvaia_gpu_close (gpu);
   uvdb_set_close (set);
-  free (planes); free (tile_nonn); free (side); free (sel);
+  uvdb_export_free (&exp);
+  free (sel);
   return EXIT_SUCCESS;
 }
 
@@ -154,7 +158,8 @@ main (int argc, char **argv)
   uvdb_writer w = NULL;
   char **seq = (char **) biomcmc_malloc (PACK_BATCH * sizeof (char *));
   int *non_n = (int *) biomcmc_malloc (PACK_BATCH * sizeof (int));
-  void *planes = NULL; int *tile_nonn = NULL, *side = NULL;
+  struct uvdb_export exp;
+  memset (&exp, 0, sizeof exp);
   int nchar = 0, non_n_ref = 0, fill = 0;
   long count = 0, kept = 0, n_invalid = 0;
 
@@ -178,9 +183,6 @@ main (int argc, char **argv)
           free (dummy);
           if (uvaia_gpu_db_reserve (gpu, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
           const size_t tb = uvaia_gpu_db_tile_bytes (gpu);
-          planes = biomcmc_malloc ((PACK_BATCH / 64) * tb);
-          tile_nonn = (int *) biomcmc_malloc (PACK_BATCH * sizeof (int));
-          side = (int *) biomcmc_malloc ((size_t) PACK_BATCH * (size_t) uvaia_gpu_db_side_row_ints () * sizeof (int));
           if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);
           w = compact ? uvdb_create_compact (out, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r) : uvdb_create (out, nchar, tb, uvaia_gpu_db_side_row_ints (), ambig_r);
           if (!w) biomcmc_error ("cannot create %s", out);
@@ -199,9 +201,9 @@ main (int argc, char **argv)
       }
       if (fill == PACK_BATCH || (!have && j == argc && fill)) {     /* a full batch, or the tail after the last file */
         const size_t nt = ((size_t) fill + 63) / 64;
-        if (uvaia_gpu_db_append (gpu, (const char *const *) seq, non_n, fill) || uvaia_gpu_db_export (gpu, 0, nt, planes, tile_nonn, side) ||
-            uvaia_gpu_db_clear (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-        if (uvdb_add_tiles (w, nt, planes, tile_nonn, side)) biomcmc_error ("cannot write to %s", out);
+        if (uvaia_gpu_db_append (gpu, (const char *const *) seq, non_n, fill)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+        if (uvdb_export_tiles (&exp, gpu, w, 0, nt)) biomcmc_error ("%s: %s", out, exp.err);
+        if (uvaia_gpu_db_clear (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
         for (int c = 0; c < fill; c++) free (seq[c]);
         fill = 0;
       }
@@ -214,8 +216,11 @@ main (int argc, char **argv)
   }
   if (!w) biomcmc_error ("no sequence found");
   if (uvdb_close (w)) biomcmc_error ("problem writing %s", out);
-  fprintf (stderr, "Packed %ld of %ld sequences (%d sites) into %s\n", kept, count, nchar, out);
+  fprintf (stderr, "Packed %ld of %ld sequences (%d sites) into %s", kept, count, nchar, out);
+  if (compact) fprintf (stderr, "; compact tiles: %ld encoded on the device, %ld on the host", exp.tiles_device, exp.tiles_host);
+  fprintf (stderr, "\n");
   uvaia_gpu_close (gpu);
-  free (seq); free (non_n); free (planes); free (tile_nonn); free (side);
+  uvdb_export_free (&exp);
+  free (seq); free (non_n);
   return EXIT_SUCCESS;
 }

@@ -102,20 +102,27 @@ compact_fix_base (uvdb_writer w, uint64_t m)
   w->base_fixed = 1;
 }
 
+/* room for n_lanes more offsets in both index arrays of a version 2 writer */
+static int
+compact_index_room (uvdb_writer w, size_t n_lanes)
+{
+  if (w->lanes + n_lanes + 1 <= w->lane_cap) return 0;
+  size_t ncap = w->lane_cap * 2 > 4096 ? w->lane_cap * 2 : 4096;
+  while (ncap < w->lanes + n_lanes + 1) ncap *= 2;
+  w->head_idx = (uint64_t *) realloc (w->head_idx, ncap * sizeof (uint64_t));
+  w->lit_idx = (uint64_t *) realloc (w->lit_idx, ncap * sizeof (uint64_t));
+  if (!w->head_idx || !w->lit_idx) return -1;
+  w->lane_cap = ncap;
+  return 0;
+}
+
 /* heads and literals of every lane of n_tiles dense tiles, in the canonical encoding (uvdb.h) */
 static int
 compact_encode_tiles (uvdb_writer w, size_t n_tiles, const void *planes)
 {
   const uint32_t W4 = w->h.W4, n_real = (w->h.nchar + 31) / 32;       /* the padding words behind them never differ from the base */
   const size_t tile_dwords = (size_t) W4 * 4 * 64 * 4;
-  if (w->lanes + n_tiles * 64 + 1 > w->lane_cap) {
-    size_t ncap = w->lane_cap * 2 > 4096 ? w->lane_cap * 2 : 4096;
-    while (ncap < w->lanes + n_tiles * 64 + 1) ncap *= 2;
-    w->head_idx = (uint64_t *) realloc (w->head_idx, ncap * sizeof (uint64_t));
-    w->lit_idx = (uint64_t *) realloc (w->lit_idx, ncap * sizeof (uint64_t));
-    if (!w->head_idx || !w->lit_idx) return -1;
-    w->lane_cap = ncap;
-  }
+  if (compact_index_room (w, n_tiles * 64)) return -1;
   for (size_t t = 0; t < n_tiles; t++) for (uint32_t lane = 0; lane < 64; lane++) {
     const uint32_t *t32 = (const uint32_t *) planes + t * tile_dwords + (size_t) lane * 4;
     uint32_t nh = 0, nl = 0, kind = 0, code = 0, first = 0, run = 0;      /* the open head: kind 1 = fill, 2 = literal */
@@ -170,6 +177,60 @@ compact_add_tiles (uvdb_writer w, size_t n_tiles, const void *planes)
   w->pend_tiles += n_tiles;
   /* the sample is complete once that many references have been named and their tiles are here */
   if (w->pend_tiles * 64 >= UVDB_BASE_SAMPLE && w->h.n_ref >= UVDB_BASE_SAMPLE) return compact_flush_pending (w);
+  return 0;
+}
+
+const uint32_t *
+uvdb_compact_base (uvdb_writer w)
+{
+  return w && w->compact && w->base_fixed ? w->base : NULL;
+}
+
+int
+uvdb_add_tiles_encoded (uvdb_writer w, size_t n_tiles, const int *non_n, const uint64_t *head_idx, const uint32_t *heads, const uint64_t *lit_idx, const uint32_t *lits)
+{
+  if (!w || !w->compact || !w->base_fixed) return -1;
+  if (!n_tiles) return 0;
+  if (!non_n || !head_idx || !lit_idx) return -1;
+  const size_t lanes = n_tiles * 64;
+  const uint32_t n_words = w->h.W4 * 4;
+  const uint64_t h0 = head_idx[0], l0 = lit_idx[0];
+  if (head_idx[lanes] < h0 || lit_idx[lanes] < l0 || (head_idx[lanes] > h0 && !heads) || (lit_idx[lanes] > l0 && !lits)) return -1;
+  /* what compact_check_heads asks of a file, before anything is appended */
+  int bad = 0;
+#pragma omp parallel for schedule(static) reduction(|:bad)
+  for (size_t g = 0; g < lanes; g++) {
+    const uint64_t hb = head_idx[g], he = head_idx[g + 1], lb = lit_idx[g], le = lit_idx[g + 1];
+    if (hb > he || hb < h0 || he > head_idx[lanes] || lb > le || lb < l0 || le > lit_idx[lanes]) { bad |= 1; continue; }
+    uint64_t lit = 0;
+    uint32_t end = 0;
+    for (uint64_t k = hb; k < he; k++) {
+      const uint32_t head = heads[k], first = UVDB_HEAD_FIRST (head), nw = UVDB_HEAD_WORDS (head);
+      if (!nw || first < end || first + nw > n_words) { bad |= 2; break; }
+      end = first + nw;
+      if (UVDB_HEAD_LITERAL (head)) lit += nw;
+    }
+    if (lit != le - lb) bad |= 2;
+  }
+  if (bad) return -1;
+  if ((w->tiles_written + n_tiles) * 64 > w->nonn_cap) {
+    size_t ncap = w->nonn_cap ? w->nonn_cap * 2 : (1u << 16);
+    while (ncap < (w->tiles_written + n_tiles) * 64) ncap *= 2;
+    int32_t *nn = (int32_t *) realloc (w->non_n, ncap * sizeof (int32_t));
+    if (!nn) return -1;
+    w->non_n = nn; w->nonn_cap = ncap;
+  }
+  if (compact_index_room (w, lanes)) return -1;
+  const uint64_t nh = head_idx[lanes] - h0, nl = lit_idx[lanes] - l0;
+  if ((nh && fwrite (heads + h0, sizeof (uint32_t), (size_t) nh, w->heads_tmp) != nh) || (nl && fwrite (lits + l0 * 4, 16, (size_t) nl, w->lits_tmp) != nl)) return -1;
+  memcpy (w->non_n + w->tiles_written * 64, non_n, lanes * sizeof (int32_t));
+  const uint64_t hbase = w->head_idx[w->lanes], lbase = w->lit_idx[w->lanes];      /* the file's running totals */
+  for (size_t g = 1; g <= lanes; g++) {
+    w->head_idx[w->lanes + g] = hbase + (head_idx[g] - h0);
+    w->lit_idx[w->lanes + g] = lbase + (lit_idx[g] - l0);
+  }
+  w->lanes += lanes;
+  w->tiles_written += n_tiles;
   return 0;
 }
 

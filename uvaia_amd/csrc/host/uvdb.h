@@ -89,9 +89,19 @@ int uvdb_add_reference_runs (uvdb_writer w, const char *name, const uvdb_exc *ru
 int uvdb_add_tiles (uvdb_writer w, size_t n_tiles, const void *planes, const int *non_n, const int *side_rows);
 int uvdb_close (uvdb_writer w);       /* 0 on success */
 /* a version 2 file: the same calls follow.  The writer ignores side rows (NULL will do); it keeps the tiles until it has UVDB_BASE_SAMPLE
- * references or is closed, then fixes the base and encodes that chunk and all later ones on the host.  NULL also for
- * nchar > UVDB_COMPACT_MAX_NCHAR. */
+ * references or is closed, then fixes the base and encodes that chunk on the host; later ones it encodes on the host as well
+ * (uvdb_add_tiles) or takes as records (uvdb_add_tiles_encoded).  NULL also for nchar > UVDB_COMPACT_MAX_NCHAR. */
 uvdb_writer uvdb_create_compact (const char *filename, int nchar, size_t tile_bytes, int side_row_ints, double ref_ambiguity);
+/* the base of a version 2 writer, [word group][plane A,C,G,T] 16-byte words, once it is fixed (the rule above: from the pending dense tiles, when
+ * the sample is complete); NULL before that and for a version 1 writer */
+const uint32_t *uvdb_compact_base (uvdb_writer w);
+/* the next n_tiles tiles of a version 2 writer whose base is fixed, as records somebody else encoded against that base (the engine:
+ * uvaia_gpu_db_encode_compact + uvaia_gpu_db_encoded_records, include/uvaia_gpu.h): non_n n_tiles * 64 counts; head_idx / lit_idx
+ * n_tiles * 64 + 1 offsets each, from any start -- they are rebased onto the file's running totals; heads / lits: the arrays the offsets
+ * count from (lits in words of 16 bytes).  The records are checked as uvdb_open checks a file's -- no empty head, none leaving the
+ * alignment, ascending without overlap, the literal heads of a lane adding up to its extent of lits -- and -1 is returned with nothing
+ * appended instead of writing a file uvdb_open would refuse.  -1 also before the base is fixed and for a version 1 writer. */
+int uvdb_add_tiles_encoded (uvdb_writer w, size_t n_tiles, const int *non_n, const uint64_t *head_idx, const uint32_t *heads, const uint64_t *lit_idx, const uint32_t *lits);
 
 /* ---- reader: the file is mapped read-only; every pointer below points into the mapping */
 typedef struct uvdb_reader_struct {

@@ -185,6 +185,14 @@ struct uvaia_gpu_ctx {
   // ---- resident database
   TileStore db;
   size_t db_cap = 0, db_n = 0, db_local_tiles = 0;   // (db_n counts the stream; a context of a reference shard keeps db_local_tiles tiles of it)
+  unsigned long long db_gen = 0;                     // counts the calls that changed the resident database (appends, loads, skips, clears, dropped tiles)
+  // ---- resident tiles written in the compact form (host_encode.inc): the base, per lane the counts and the offsets they sum to, the records;
+  // the plan uvaia_gpu_db_encode_compact leaves for uvaia_gpu_db_encoded_records holds while db_gen is the one it was made at
+  struct Encode {
+    DevBuf<uint4> base, lits; DevBuf<uint32_t> cnt_h, cnt_l, heads; DevBuf<unsigned long long> hidx, lidx;
+    Event ev[4]; double ms[2] = {0., 0.};              // device time of count + prefix, of emit
+    bool plan = false; size_t first_tile = 0, n_tiles = 0; unsigned long long db_gen = 0, n_heads = 0, n_lits = 0;
+  } enc;
   // last batch (introspection)
   struct { const TileStore *store = nullptr; long long tile_first = 0; int n_tiles = 0, n = 0, rbegin = 0, ppad = 0; const int4 *rt = nullptr; } last;
   // ---- statistics

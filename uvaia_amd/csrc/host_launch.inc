@@ -531,7 +531,7 @@ int win_image_room(uvaia_gpu_ctx *c, size_t tiles, bool *grown)
 
 // the end of an entry: the references the stream holds now, and those of them a four-plane image covers (0: rows that did not come through
 // the staged calls, no image covers them)
-void db_commit(uvaia_gpu_ctx *c, size_t db_n, int win_n) { c->db_n = db_n; c->win.n = win_n; }
+void db_commit(uvaia_gpu_ctx *c, size_t db_n, int win_n) { c->db_n = db_n; c->win.n = win_n; c->db_gen++; }
 
 // stage + pack n_ref rows (either scattered pointers or one pitched block) into the store starting at slot0
 int pack_rows(uvaia_gpu_ctx *c, const char *const *seq, const char *rows, size_t rows_pitch, const int *non_n, int n_ref, const TileStore &s, long long slot0)

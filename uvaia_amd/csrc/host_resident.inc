@@ -52,7 +52,7 @@ int uvaia_gpu_db_skip(uvaia_gpu_ctx *c, size_t n_ref)
   if (c->db_n + n_ref > c->db_cap) return db_refuse_full(c);
   for (size_t a = c->db_n; a < c->db_n + n_ref; a = (a / 64 + 1) * 64)
     if (owns_tile(c, (long long)(a / 64))) return fail(c, UVAIA_GPU_EINVAL, "reference %zu belongs to a piece of this context: it cannot be skipped", a);
-  c->db_n += n_ref;
+  c->db_n += n_ref; c->db_gen++;
   return 0;
 }
 
@@ -71,6 +71,7 @@ int uvaia_gpu_db_clear(uvaia_gpu_ctx *c)
 {
   if (!c) return UVAIA_GPU_EINVAL;
   c->win.n = 0;                                        // the four-plane image of a loaded window goes with the rows
+  c->db_gen++;
   if (!c->db.planes || !c->db_n) { c->db_n = 0; return 0; }
   { int rc = settle_derive(c); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->st.stream));

@@ -181,7 +181,7 @@ int uvaia_gpu_db_drop_tiles(uvaia_gpu_ctx *c, size_t n_tiles)
   HIPCHK(c, hipMemsetAsync(c->db.tot + rest_tiles * 64, 0, z * 64 * sizeof(int), c->st.stream));
   HIPCHK(c, hipMemsetAsync(c->db.amb + rest_tiles * 64 * AMB_ROW, 0, z * 64 * AMB_ROW * sizeof(int), c->st.stream));
   if (c->state.d_entered) HIPCHK(c, hipMemsetAsync(c->state.d_entered, 0, std::min(c->state.d_entered.cap, have * 64), c->st.stream));
-  c->db_n = rest;
+  c->db_n = rest; c->db_gen++;
   c->win.n = 0;                                        // the four-plane image of a window is not moved with the tiles
   { int rc = derive_rows(c, c->db, 0, (int)rest); if (rc) return rc; }
   HIPCHK(c, hipStreamSynchronize(c->st.stream));

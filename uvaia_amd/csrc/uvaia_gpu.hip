@@ -81,6 +81,7 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "kernels_ball.inc"
 #include "kernels_qprep.inc"
 #include "kernels_expand.inc"
+#include "kernels_encode.inc"
 
 // ------------------------------------------------------------------------------------------------------------
 // host side, in sections (one translation unit: the kernels above are templates the sections instantiate); the context and everything
@@ -97,3 +98,4 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "host_shards.inc"
 #include "host_ball.inc"
 #include "host_window.inc"
+#include "host_encode.inc"
