@@ -404,6 +404,15 @@ int    uvaia_gpu_db_append_packed (uvaia_gpu_ctx *ctx, const void *planes, const
  *                  every access all the same.  The host arrays must stay as they are until the slot has been loaded.
  *   compact_ms     device time in ms since the last reset of [0] expand_tiles_kernel, [1] the side-row pass (waits for the last expansion)
  *   window_ms      device time in ms since the last reset of [0] the selection, [1] totals, checks and derived planes after it, [2] the decode
+ *   stage_unpack_rows  the contract of uvaia_gpu_unpack_rows (any order, repeats, N for the empty and the full set, exception characters are
+ *                  the caller's business, pitch >= nchar) for positions within staging slot `slot` -- the positions sel of load_staged
+ *                  uses -- whatever stage_packed[_at] or stage_compact_at last put there: the text of a few references of a packed file
+ *                  without loading them.  Waits for the slot's copy, decodes the slot's four planes where they lie (default-mode and --acgt
+ *                  contexts alike: a slot holds the file's planes) and lets the next stage into the slot wait for the decode.  The resident
+ *                  database, the loaded window, the derived planes, the heaps and the tolerances are not touched.  Refused, with the
+ *                  context as usable as before: an index at or beyond 64 * (tiles filled in the slot) and a pitch below nchar
+ *                  (UVAIA_GPU_EINVAL), a slot never staged and a context of a reference shard (UVAIA_GPU_ESTATE).
+ *   stage_unpack_ms  device time in ms of stage_unpack_rows' kernel since the last reset
  *   free_bytes     free memory of the context's device as the runtime reports it (0: the runtime could not tell) */
 int uvaia_gpu_db_stage_reserve (uvaia_gpu_ctx *ctx, size_t n_tiles);
 int uvaia_gpu_db_stage_packed (uvaia_gpu_ctx *ctx, int slot, const void *planes, const int *non_n, const int *side_rows, int n_tiles);
@@ -415,6 +424,8 @@ int uvaia_gpu_db_stage_compact_at (uvaia_gpu_ctx *ctx, int slot, size_t tile_off
 void uvaia_gpu_compact_ms (uvaia_gpu_ctx *ctx, double out[2], int reset);
 int uvaia_gpu_db_unpack_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
 void uvaia_gpu_window_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
+int uvaia_gpu_db_stage_unpack_rows (uvaia_gpu_ctx *ctx, int slot, const int *index, int n, char *rows, size_t pitch);
+double uvaia_gpu_stage_unpack_ms (uvaia_gpu_ctx *ctx, int reset);
 size_t uvaia_gpu_free_bytes (uvaia_gpu_ctx *ctx);
 
 /* ---- resident tiles written in the compact form of a packed database (version 2 of uvaia_amd/csrc/host/uvdb.h), the inverse of

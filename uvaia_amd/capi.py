@@ -32,6 +32,7 @@ SYMBOLS = [
     "uvaia_gpu_db_stage_reserve", "uvaia_gpu_db_stage_packed", "uvaia_gpu_db_load_staged", "uvaia_gpu_db_unpack_rows", "uvaia_gpu_window_ms", "uvaia_gpu_free_bytes",
     "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged", "uvaia_gpu_db_stage_compact_at", "uvaia_gpu_compact_ms",
     "uvaia_gpu_db_encode_compact", "uvaia_gpu_db_encoded_records", "uvaia_gpu_encode_ms",
+    "uvaia_gpu_db_stage_unpack_rows", "uvaia_gpu_stage_unpack_ms",
 ]
 
 
@@ -202,6 +203,8 @@ def load_library():
         "uvaia_gpu_encode_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_db_unpack_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_window_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_db_stage_unpack_rows": (C.c_int, [vp, C.c_int, pi, C.c_int, C.c_void_p, C.c_size_t]),
+        "uvaia_gpu_stage_unpack_ms": (C.c_double, [vp, C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
     }
     for name, (res, args) in sig.items():
@@ -693,6 +696,19 @@ class Engine:
         rows = np.zeros((max(len(idx), 1), pitch), dtype=np.uint8)
         self._chk(self.L.uvaia_gpu_db_unpack_rows(self.ctx, idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
         return [rows[k, :self.nchar].tobytes() for k in range(len(idx))]
+
+    def db_stage_unpack_rows(self, slot, index, pitch=None):
+        """Upper-case text of lanes index[] of staging slot 0 or 1 (positions within the slot, as sel of db_load_staged), as a list of
+        bytes (exception runs not applied); the resident database and the search state are not touched."""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        pitch = (self.nchar + 15) // 16 * 16 if pitch is None else int(pitch)
+        rows = np.zeros((max(len(idx), 1), max(pitch, 1)), dtype=np.uint8)
+        self._chk(self.L.uvaia_gpu_db_stage_unpack_rows(self.ctx, int(slot), idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
+        return [rows[k, :self.nchar].tobytes() for k in range(len(idx))]
+
+    def stage_unpack_ms(self, reset=False):
+        """Device ms since the last reset of the decode kernel of db_stage_unpack_rows."""
+        return float(self.L.uvaia_gpu_stage_unpack_ms(self.ctx, int(reset)))
 
     def window_ms(self, reset=False):
         """Device ms since the last reset of (selection, totals + checks + derived planes after it, decode)."""

@@ -15,10 +15,12 @@
 #include "uvdb.h"
 #include "uvdb_window.h"
 #include "uvdb_set.h"
+#include "uvdb_extract.h"
 
 typedef struct {
   int help, version, acgt, keep_resolved, exclude_self, nbest, trim, pool, threads, threads_given, device, devices[64], n_devices;
   long long window; int window_given, window_report;
+  int final_aln, final_rank, final_rank_given, final_only;
   double ambig_q, ambig_r;
   const char *out, *query;
   const char **ref; int n_ref;
@@ -46,6 +48,9 @@ usage (const char *prog, int long_help)
   printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): loaded as it is, no text parsing; can be several\n                                   files, searched in the order given as one database (all packed with the same -A: see `uvaiapack --merge -A`).\n                                   Compact files (`uvaiapack --compact`) are expanded on the GPU, on one device (not with a --devices list of several)\n");
   printf ("  --window=<refs>                  with --packed: keep only this many references on the GPU at a time (rounded up to whole pools and tiles\n                                   of 64), for a database larger than GPU memory; chosen automatically when the database does not fit\n");
   printf ("  --window-report                  with --packed: one line on stderr with the GPU's free memory before and after and the time of the window steps\n");
+  printf ("  --final-aln                      with --packed: also write <prefix>.final.aln.xz, the alignment of exactly the references of the table (each once, in\n                                   stream order, chosen by position in the database and not by name), read back from the packed files on the GPU\n");
+  printf ("  --final-rank=<int>               with --final-aln: only the references of rank <int> or better in some query's list (default: all, i.e. -n)\n");
+  printf ("  --final-only                     with --final-aln: do not write <prefix>.aln.xz, the larger alignment of every reference that was a neighbour at\n                                   some moment of the search; the table is the same\n");
   printf ("  <seqs.fa(.gz,.xz)>               aligned query sequences\n");
   printf ("  -t, --nthreads=<int>             suggested number of host threads (only sets the default pool size here)\n");
   printf ("  -o, --output=<without suffix>    prefix of xzipped output alignment and table with nearest neighbour sequences\n");
@@ -76,7 +81,8 @@ parse_options (int argc, char **argv)
     {"trim", required_argument, 0, 1001}, {"query_ambiguity", required_argument, 0, 'a'}, {"ref_ambiguity", required_argument, 0, 'A'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"packed", required_argument, 0, 1003}, {"devices", required_argument, 0, 1004},
-    {"window", required_argument, 0, 1005}, {"window-report", no_argument, 0, 1006}, {0, 0, 0, 0}};
+    {"window", required_argument, 0, 1005}, {"window-report", no_argument, 0, 1006},
+    {"final-aln", no_argument, 0, 1007}, {"final-rank", required_argument, 0, 1008}, {"final-only", no_argument, 0, 1009}, {0, 0, 0, 0}};
   int ch, errors = 0;
   while ((ch = getopt_long (argc, argv, "hvkxn:a:A:p:r:t:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': o.help = 1; break;
@@ -97,6 +103,9 @@ parse_options (int argc, char **argv)
     case 1003: o.packed_files[o.n_packed++] = optarg; break;
     case 1005: o.window = atoll (optarg); o.window_given = 1; break;
     case 1006: o.window_report = 1; break;
+    case 1007: o.final_aln = 1; break;
+    case 1008: o.final_rank = atoi (optarg); o.final_rank_given = 1; break;
+    case 1009: o.final_only = 1; break;
     default: errors++;
   }
   if (optind < argc) o.query = argv[optind++];
@@ -113,6 +122,15 @@ parse_options (int argc, char **argv)
   if (o.window_given && o.window < 1) { fprintf (stderr, "--window: expected a positive number of references\n"); exit (EXIT_FAILURE); }
   if (o.n_packed > UVDB_SET_MAX_FILES) { fprintf (stderr, "--packed: at most %d files\n", UVDB_SET_MAX_FILES); exit (EXIT_FAILURE); }
   if (o.window_given && o.n_devices > 1) { fprintf (stderr, "--window works on one GPU: give --device, not a --devices list of several\n"); exit (EXIT_FAILURE); }
+  /* --final-aln: refused here as well */
+  if (o.final_aln && !o.n_packed) {
+    fprintf (stderr, "--final-aln needs --packed: a reference read as text (-r) is gone once the search has passed it, only a packed database gives a second look at a row; pack the references with `uvaiapack`\n");
+    exit (EXIT_FAILURE);
+  }
+  if (o.final_rank_given && !o.final_aln) { fprintf (stderr, "--final-rank needs --final-aln: it chooses what that file holds\n"); exit (EXIT_FAILURE); }
+  if (o.final_only && !o.final_aln) { fprintf (stderr, "--final-only needs --final-aln: without it no alignment would be written at all\n"); exit (EXIT_FAILURE); }
+  if (o.final_rank_given && o.final_rank < 1) { fprintf (stderr, "--final-rank: expected a rank of 1 or more\n"); exit (EXIT_FAILURE); }
+  if (o.final_aln && o.n_devices > 1) { fprintf (stderr, "--final-aln works on one GPU: give --device, not a --devices list of several (the rows are read back through the staging slots of a plain context)\n"); exit (EXIT_FAILURE); }
   /* a compact file is expanded in a staging slot of one GPU; a group of devices gathers lanes on the host from the dense tiles of the mapping */
   for (int f = 0; o.n_devices > 1 && f < o.n_packed; f++) if (uvdb_file_version (o.packed_files[f]) == 2) {
     fprintf (stderr, "--devices with several GPUs: %s is a compact packed database (`uvaiapack --compact`), which is searched on one GPU only; convert it with `uvaiapack --merge -o dense.uvdb %s`\n", o.packed_files[f], o.packed_files[f]);
@@ -134,23 +152,15 @@ wall_ms (void)
  * file rarely ends on a tile boundary, -x leaves holes): appended behind what is resident (resident search), or as the next window
  * (windowed search). */
 
-/* kept positions [a, b) into staging slot `slot`; sel (b - a entries) receives their positions within it.  Returns whether these are
- * 0, 1, 2, ... for certain: no keep list, one piece, the first at lane 0 */
+/* uvdb_stage_range (uvdb_extract.h) for the two searches: kept positions [a, b) into staging slot `slot`; returns whether sel is 0, 1, 2, ... */
 static int
 stage_range (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_t a, uint64_t b, int slot, uvdb_set_piece *pieces, int *sel)
 {
-  int np = 0;
-  uint64_t st = 0;
-  if (uvdb_set_span (set, keep, a, b, pieces, UVDB_SET_MAX_FILES, &np, &st, sel)) biomcmc_error ("--packed: the references from %llu on span more file tiles than the engine counts", (unsigned long long) a);
-  for (int p = 0; p < np; p++) {
-    uvdb_reader db = set->db[pieces[p].file];
-    const uint64_t t0 = pieces[p].first_tile;
-    const int rc = db->h.version == 2     /* a compact file's tiles are expanded in the slot, a set may mix both kinds */
-      ? uvaia_gpu_db_stage_compact_at (gpu, slot, (size_t) pieces[p].slot_tile, db->base, db->head_idx + t0 * 64, db->heads, db->lit_idx + t0 * 64, db->lits, db->non_n + t0 * 64, (int) pieces[p].n_tiles)
-      : uvaia_gpu_db_stage_packed_at (gpu, slot, (size_t) pieces[p].slot_tile, uvdb_tile_planes (db, t0), db->non_n + t0 * 64, uvdb_tile_side_rows (db, t0), (int) pieces[p].n_tiles);
-    if (rc) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
-  }
-  return !keep && np == 1 && sel[0] == 0;
+  int identity = 0;
+  const int rc = uvdb_stage_range (gpu, set, keep, a, b, slot, pieces, sel, &identity);
+  if (rc == UVDB_STAGE_ESPAN) biomcmc_error ("--packed: the references from %llu on span more file tiles than the engine counts", (unsigned long long) a);
+  if (rc) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  return identity;
 }
 
 /* the largest staging slot the ranges [w * step, (w + 1) * step) of n kept references need, in tiles (0: none is staged); resident: the
@@ -204,6 +214,7 @@ search_windowed (uvaia_gpu_ctx *gpu, uvdb_set set, const uint64_t *keep, uint64_
       upload_ms[0] += up;
       if (wall_ms () - t < 0.01 * up) upload_ms[1] += up;   /* the search had ended before the upload: counted as not hidden at all */
     } else if (uvaia_gpu_sync (gpu)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    if (!outstream) continue;                             /* --final-only: nothing is decoded during the search */
     if (uvaia_gpu_entered_flags (gpu, ent, 0)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
     for (uint64_t k = 0; k < b - a;) {                    /* dump every sequence that entered some heap, in stream order */
       int m = 0;
@@ -274,9 +285,15 @@ load_resident (uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, int n_devices, uvdb_set
   free (planes); free (nn); free (side); free (sel); free (pieces);
 }
 
-/* the search over o->packed_files: replaces the read/filter/fill loop of main (src/nearest.c:251-286); returns the number of sequences written */
+/* the packed files as the search saw them: position i of the kept stream is reference keep[i] of the set (keep NULL: i itself), n of them */
+typedef struct { uvdb_set set; uint64_t *keep; uint64_t n; } packed_stream;
+
+/* the search over o->packed_files: replaces the read/filter/fill loop of main (src/nearest.c:251-286); returns the number of sequences written.
+ * outstream NULL (--final-only): no sequence is decoded or written.  stream not NULL (--final-aln): the set and the keep list (NULL: every
+ * reference is kept) stay with the caller, whose table and final alignment name references by their position in the kept stream. */
 static int
-search_packed (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, file_compress_t outstream, name_table *names, int *count, int *same_name, int64_t *time0)
+search_packed (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, file_compress_t outstream, name_table *names, int *count, int *same_name, int64_t *time0,
+               packed_stream *stream)
 {
   char msg[1024];
   const char *first = o->packed_files[0];
@@ -333,10 +350,11 @@ search_packed (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_
                (unsigned long long) window, (unsigned long long) n_windows, mem_before, uvaia_gpu_free_bytes (gpu), part_ms[0], part_ms[1], part_ms[2], upload_ms[0], upload_ms[2]);
     }
   } else {
-    uint8_t *ent = (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1));
+    uint8_t *ent = outstream ? (uint8_t *) biomcmc_malloc ((size_t) (n ? n : 1)) : NULL;
     if (n && uvaia_gpu_group_search_resident (grp, (size_t) o->pool, 0, ent)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+    if (!ent && uvaia_gpu_group_sync (grp)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));   /* (a search that hands no flags back does not wait) */
     char *text = (char *) biomcmc_malloc ((size_t) nchar + 1);
-    for (uint64_t i = 0; i < n; i++) if (ent[i]) {     /* dump every sequence that entered some heap, in stream order */
+    for (uint64_t i = 0; outstream && i < n; i++) if (ent[i]) {     /* dump every sequence that entered some heap, in stream order */
       const uint64_t r = keep ? keep[i] : i;
       n_output++;
       uvdb_set_unpack_reference (set, r, text);
@@ -346,9 +364,75 @@ search_packed (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_
     free (text); free (ent);
     if (o->window_report) fprintf (stderr, "window report: {\"window\": 0, \"n_windows\": 0, \"free_before\": %zu, \"free_after\": %zu}\n", mem_before, uvaia_gpu_free_bytes (gpu));
   }
-  free (keep);
-  uvdb_set_close (set);
+  /* Without --final-aln (stream NULL) the set goes here, as it always did: the caller is about to wait for xz to finish the dump, and unmapping
+     files the runtime has copied straight out of (over a second for 1.5 GB) is hidden behind that wait; at the end of main it would be exposed. */
+  if (stream) { stream->set = set; stream->keep = keep; stream->n = n; }
+  else { free (keep); uvdb_set_close (set); }
   return n_output;
+}
+
+/* name of a reference by its ordinal, straight from the set: what the dump loop otherwise leaves in the name table (--final-only) */
+static const char *
+packed_stream_name (int64_t ordinal, void *user)
+{
+  const packed_stream *ps = (const packed_stream *) user;
+  if (ordinal < 0 || (uint64_t) ordinal >= ps->n) return NULL;
+  return uvdb_set_name (ps->set, ps->keep ? ps->keep[ordinal] : (uint64_t) ordinal);
+}
+
+/* --final-aln.  Membership is by ordinal: the heaps are collected once more with the ordinal in place of the name and put in the table's
+ * order by the same heap_finalise_heap_qsort, so rank j here is rank j there, also among references that share a name. */
+static const char *
+ordinal_as_name (int64_t ordinal, void *user)
+{
+  snprintf ((char *) user, 24, "%lld", (long long) ordinal);
+  return (const char *) user;
+}
+
+static int
+compare_positions (const void *a, const void *b)
+{
+  const uint64_t x = *(const uint64_t *) a, y = *(const uint64_t *) b;
+  return (x > y) - (x < y);
+}
+
+static int
+write_final_record (void *user, uint64_t k, uint64_t stream, const char *name, const char *row)
+{
+  write_fasta_record ((file_compress_t) user, name, row);
+  return 0;
+}
+
+/* <prefix>.final.aln.xz: every reference of rank `rank` or better in some query's list, once, in stream order, as the regular dump writes
+ * it; the rows come back from the packed files through the search's own context (uvdb_extract.h).  Returns their number. */
+static uint64_t
+save_final_alignment (const options *o, query_t query, uvaia_gpu_group *grp, uvaia_gpu_ctx *gpu, packed_stream *ps, const char *filename, uvdb_extract_stats *stats)
+{
+  const int nq = query->aln->ntax, rank = (o->final_rank_given && o->final_rank < o->nbest) ? o->final_rank : o->nbest;
+  char text[24], msg[1024];
+  heap_t *heap = (heap_t *) biomcmc_malloc ((size_t) nq * sizeof (heap_t));
+  for (int i = 0; i < nq; i++) heap[i] = new_heap_t (o->nbest);
+  if (uvaia_gpu_group_collect_heaps (grp, heap, ordinal_as_name, text)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+  uint64_t *pos = (uint64_t *) biomcmc_malloc (((size_t) nq * (size_t) rank + 1) * sizeof (uint64_t)), m = 0, u = 0;
+  for (int i = 0; i < nq; i++) {
+    heap_finalise_heap_qsort (heap[i]);
+    for (int j = 0; j < heap[i]->n && j < rank; j++) {
+      const long long ord = heap[i]->seq[j].name ? atoll (heap[i]->seq[j].name) : -1;
+      if (ord < 0 || (uint64_t) ord >= ps->n) biomcmc_error ("--final-aln: a neighbour of query %s lies outside the %llu references searched", query->aln->taxlabel->string[i], (unsigned long long) ps->n);
+      pos[m++] = ps->keep ? ps->keep[ord] : (uint64_t) ord;
+    }
+    del_heap_t (heap[i]);
+  }
+  free (heap);
+  qsort (pos, (size_t) m, sizeof (uint64_t), compare_positions);
+  for (uint64_t k = 0; k < m; k++) if (!u || pos[u - 1] != pos[k]) pos[u++] = pos[k];
+  file_compress_t out = biomcmc_open_compress (filename, "w");
+  if (uvdb_extract (ps->set, gpu, pos, u, write_final_record, out, stats, msg, sizeof msg)) biomcmc_error ("--final-aln: %s", msg);
+  free (ps->keep); uvdb_set_close (ps->set);           /* the set has done its work: unmapped while xz finishes the file (see search_packed) */
+  ps->keep = NULL; ps->set = NULL; ps->n = 0;
+  biomcmc_close_compress (out);
+  free (pos);
+  return u;
 }
 
 static void
@@ -430,7 +514,8 @@ main (int argc, char **argv)
   int *non_n = (int *) biomcmc_malloc ((size_t) o.pool * sizeof (int));
   uint8_t *entered = (uint8_t *) biomcmc_malloc ((size_t) o.pool);
   name_table names = {NULL, 0};
-  file_compress_t outstream = biomcmc_open_compress (outfilename, "w");
+  file_compress_t outstream = o.final_only ? NULL : biomcmc_open_compress (outfilename, "w");     /* --final-only: <prefix>.aln.xz is not even created */
+  packed_stream packed = {NULL, NULL, 0};
   const int non_n_ref = (int) (query->aln->nchar * (1. - o.ambig_r));
   const int print_interval = 10000;
   int count = 0, n_invalid = 0, same_name = 0, n_output = 0;
@@ -441,8 +526,9 @@ main (int argc, char **argv)
   fprintf (stderr, "\n The next step is main comparison, which may take a while\n\n");
 
   if (o.n_packed) {     /* packed databases, one stream */
-    n_output = search_packed (&o, query, grp, gpu, outstream, &names, &count, &same_name, time0);
-    fprintf (stderr, "Total of %d sequences searched; %d saved sequences include closest neighbours and intermediate. %.3lf secs elapsed. \n", count, n_output, biomcmc_update_elapsed_time (time1));
+    n_output = search_packed (&o, query, grp, gpu, outstream, &names, &count, &same_name, time0, o.final_aln ? &packed : NULL);
+    if (outstream) fprintf (stderr, "Total of %d sequences searched; %d saved sequences include closest neighbours and intermediate. %.3lf secs elapsed. \n", count, n_output, biomcmc_update_elapsed_time (time1));
+    else           fprintf (stderr, "Total of %d sequences searched; none saved during the search (--final-only). %.3lf secs elapsed. \n", count, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
   }
   for (int j = 0; j < o.n_ref; j++) {
@@ -495,16 +581,31 @@ main (int argc, char **argv)
              count, n_output, n_invalid, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
   }
-  biomcmc_close_compress (outstream);
-  fprintf (stderr, "Saved %d sequences to file %s , %.3lf secs elapsed.\n", n_output, outfilename, biomcmc_update_elapsed_time (time0));
+  if (outstream) {
+    biomcmc_close_compress (outstream);
+    fprintf (stderr, "Saved %d sequences to file %s , %.3lf secs elapsed.\n", n_output, outfilename, biomcmc_update_elapsed_time (time0));
+  }
 
   /* 3. heaps back to the host, table */
   heap_t *heap = (heap_t *) biomcmc_malloc ((size_t) query->aln->ntax * sizeof (heap_t));
   for (int i = 0; i < query->aln->ntax; i++) heap[i] = new_heap_t (o.nbest);
-  if (uvaia_gpu_group_collect_heaps (grp, heap, name_table_get, &names)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+  /* (--final-only: the dump loop did not run, the names come from the set) */
+  if (o.final_only ? uvaia_gpu_group_collect_heaps (grp, heap, packed_stream_name, &packed) : uvaia_gpu_group_collect_heaps (grp, heap, name_table_get, &names)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
   strcpy (outfilename + outlength, ".csv.xz");
   save_distance_table (heap, query, outfilename);
   fprintf (stderr, "Saved distance table to file %s , %.3lf secs elapsed.\n", outfilename, biomcmc_update_elapsed_time (time0));
+  if (o.final_aln) {
+    uvdb_extract_stats st;
+    memset (&st, 0, sizeof st);
+    strcpy (outfilename + outlength, ".final.aln.xz");
+    const uint64_t n_final = save_final_alignment (&o, query, grp, gpu, &packed, outfilename, &st);
+    fprintf (stderr, "Saved %llu sequences of the final neighbour lists to file %s , %.3lf secs elapsed.\n", (unsigned long long) n_final, outfilename, biomcmc_update_elapsed_time (time0));
+    if (o.window_report)
+      fprintf (stderr, "final report: {\"n_final\": %llu, \"n_dumped\": %d, \"chunks\": %llu, \"stage_calls\": %llu, \"tiles_staged\": %llu, \"stage_ms\": %.3f, \"decode_ms\": %.3f, \"decode_kernel_ms\": %.3f, \"exceptions_ms\": %.3f, \"write_ms\": %.3f}\n",
+               (unsigned long long) n_final, n_output, (unsigned long long) st.n_chunks, (unsigned long long) st.n_pieces, (unsigned long long) st.n_tiles, st.stage_ms, st.decode_ms, st.kernel_ms, st.exceptions_ms, st.write_ms);
+  }
+  free (packed.keep);
+  uvdb_set_close (packed.set);
 
   for (int i = 0; i < query->aln->ntax; i++) del_heap_t (heap[i]);
   free (heap); free (seq); free (name); free (non_n); free (entered); free (o.ref); free (o.packed_files);

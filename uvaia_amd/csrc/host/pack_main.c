@@ -13,6 +13,9 @@
  * `uvaia --packed`), from texts or, with --merge, from packed inputs of either version; --merge without it reads both versions and
  * writes version 1, the way back to the dense file.  Once the base row is fixed (the first 4 096 references) the tiles are encoded on the
  * GPU and only their records cross the bus (uvdb_export_tiles).
+ *
+ * `uvaiapack --unpack` is the way back: the references of packed databases of either version as FASTA, decoded on the GPU out of the
+ * staging slots (uvdb_extract.h), all of them or those a list of names asks for.  `uvaiapack --list` prints the stored names and needs no GPU.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -23,6 +26,7 @@
 #include "uvdb.h"
 #include "uvdb_set.h"
 #include "uvdb_packer.h"
+#include "uvdb_extract.h"
 #include "../../../include/uvaia_gpu.h"
 
 #define PACK_BATCH 4096      /* references per engine round trip (a multiple of 64) */
@@ -33,7 +37,9 @@ usage (const char *prog)
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("Packs an aligned reference FASTA into the bit-plane database the MI355X engine searches without parsing text.\n\n");
   printf (" %s [-hv] [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
-  printf (" %s --merge [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n\n", prog);
+  printf (" %s --merge [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n", prog);
+  printf (" %s --unpack (-o <without suffix> | --stdout) [--names <file>] [--device=<int>] <a.uvdb> [<b.uvdb>]...\n", prog);
+  printf (" %s --list <a.uvdb> [<b.uvdb>]...\n\n", prog);
   printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` is run with the value of its file\n");
   printf ("  --merge                          the inputs are packed databases: joins them, in order, into the file that packing their texts together gives.\n");
   printf ("                                   -A then defaults to the inputs' common value; a smaller one drops the rows it excludes, a larger one than\n");
@@ -41,9 +47,106 @@ usage (const char *prog)
   printf ("  --compact                        write the compact form: one base row and, per reference, the 32-site words that differ from it; several times\n");
   printf ("                                   smaller for genomes of one pathogen.  `uvaia --packed` expands it on the GPU (one device); `uvaiaball` and\n");
   printf ("                                   `uvaiaclust` need the dense file, which `--merge -o dense.uvdb compact.uvdb` writes.  --merge reads both forms\n");
-  printf ("  -o, --output=<file>              packed database to write\n");
+  printf ("  --unpack                         the inputs are packed databases (dense or compact, filtered with any -A): writes their references, in order, as\n");
+  printf ("                                   FASTA -- the stored name, the upper-case text with - ? X O . where the input had them -- to <prefix>.aln.xz (-o)\n");
+  printf ("                                   or uncompressed to standard output (--stdout); decoded on the GPU.  Not with --merge, --compact or -A\n");
+  printf ("  --stdout                         with --unpack: uncompressed FASTA on standard output instead of -o\n");
+  printf ("  --names=<file>                   with --unpack: only the references whose name is a line of <file>, every reference that carries such a name, in\n");
+  printf ("                                   stream order; names that match nothing are listed on stderr\n");
+  printf ("  --list                           prints the stored names of the packed databases given, one per line, in stream order (no GPU, no other option)\n");
+  printf ("  -o, --output=<file>              packed database to write (--unpack: prefix of the xzipped alignment)\n");
   printf ("  --device=<int>                   GPU to use (default: current device)\n");
   printf ("Sequences that still have to be aligned: `uvaialign --packed <out.uvdb>` writes the same file straight from the aligner, without the text in between.\n");
+}
+
+/* the engine needs some query to exist: a plain ACGT string of the alignment's length */
+static uvaia_gpu_ctx *
+open_engine (int nchar, int device)
+{
+  uvaia_gpu_ctx *gpu = NULL;
+  char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);
+  for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
+  dummy[nchar] = '\0';
+  const char *one[1] = {dummy};
+  uvaia_gpu_query q;
+  memset (&q, 0, sizeof q);
+  q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
+  if (uvaia_gpu_open (&gpu, &q, 1, device, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));
+  free (dummy);
+  return gpu;
+}
+
+/* `uvaiapack --list` */
+static int
+list_main (int n_in, char **in)
+{
+  char msg[1024];
+  if (n_in > UVDB_SET_MAX_FILES) biomcmc_error ("--list: at most %d packed databases", UVDB_SET_MAX_FILES);
+  uvdb_set set = uvdb_set_open ((const char *const *) in, n_in, UVDB_SET_ANY_AMBIGUITY, msg, sizeof msg);
+  if (!set) biomcmc_error ("%s", msg);
+  for (uint64_t i = 0; i < set->n_ref; i++) printf ("%s\n", uvdb_set_name (set, i));
+  uvdb_set_close (set);
+  return EXIT_SUCCESS;
+}
+
+/* `uvaiapack --unpack` */
+typedef struct { file_compress_t xz; int errors; } unpack_out;
+
+static int
+unpack_record (void *user, uint64_t k, uint64_t stream, const char *name, const char *row)
+{
+  unpack_out *u = (unpack_out *) user;
+  if (u->xz) { write_fasta_record (u->xz, name, row); return 0; }
+  if (printf (">%s\n%s\n", name, row) < 0) u->errors++;
+  return u->errors;
+}
+
+static int
+unpack_main (int n_in, char **in, const char *prefix, const char *names_file, int device)
+{
+  char msg[1024];
+  int64_t time0[2];
+  biomcmc_get_time (time0);
+  if (n_in > UVDB_SET_MAX_FILES) biomcmc_error ("--unpack: at most %d packed databases", UVDB_SET_MAX_FILES);
+  uvdb_name_list names = NULL;
+  if (names_file && !(names = uvdb_name_list_read (names_file, msg, sizeof msg))) biomcmc_error ("%s", msg);
+  uvdb_set set = uvdb_set_open ((const char *const *) in, n_in, UVDB_SET_ANY_AMBIGUITY, msg, sizeof msg);
+  if (!set) biomcmc_error ("%s", msg);
+  /* --names: every reference that carries a listed name, by position */
+  uint64_t *pos = NULL, n = set->n_ref;
+  if (names) {
+    pos = (uint64_t *) biomcmc_malloc ((size_t) (set->n_ref ? set->n_ref : 1) * sizeof (uint64_t));
+    n = 0;
+    for (uint64_t i = 0; i < set->n_ref; i++) if (uvdb_name_list_find (names, uvdb_set_name (set, i)) >= 0) pos[n++] = i;
+  }
+  size_t outlength = 0;
+  char *outfilename = prefix ? outfile_from_prefix (prefix, &outlength) : NULL;
+  /* the engine and the tile layout first: a command that cannot run leaves no output file behind */
+  uvaia_gpu_ctx *gpu = n ? open_engine ((int) set->nchar, device) : NULL;
+  if (gpu && (set->side_row_ints != (uint32_t) uvaia_gpu_db_side_row_ints () || set->tile_bytes != uvaia_gpu_db_tile_bytes (gpu))) biomcmc_error ("packed database %s does not match this engine's tile layout", in[0]);
+  unpack_out out = {prefix ? biomcmc_open_compress (outfilename, "w") : NULL, 0};
+  uvdb_extract_stats st;
+  memset (&st, 0, sizeof st);
+  if (n) {
+    if (uvdb_extract (set, gpu, pos, n, unpack_record, &out, &st, msg, sizeof msg)) biomcmc_error ("--unpack: %s", msg);
+    uvaia_gpu_close (gpu);
+  }
+  if (out.xz) biomcmc_close_compress (out.xz);
+  else if (fflush (stdout)) biomcmc_error ("--unpack: problem writing to standard output");
+  fprintf (stderr, "Unpacked %llu of %llu sequences (%u sites) from %d packed database%s to %s in %.3lf secs.\n", (unsigned long long) n, (unsigned long long) set->n_ref, set->nchar, n_in,
+           n_in > 1 ? "s" : "", prefix ? outfilename : "standard output", biomcmc_update_elapsed_time (time0));
+  fprintf (stderr, "unpack report: {\"rows\": %llu, \"chunks\": %llu, \"stage_calls\": %llu, \"tiles_staged\": %llu, \"stage_ms\": %.3f, \"decode_ms\": %.3f, \"decode_kernel_ms\": %.3f, \"exceptions_ms\": %.3f, \"write_ms\": %.3f}\n",
+           (unsigned long long) st.n_rows, (unsigned long long) st.n_chunks, (unsigned long long) st.n_pieces, (unsigned long long) st.n_tiles, st.stage_ms, st.decode_ms, st.kernel_ms, st.exceptions_ms, st.write_ms);
+  if (names) {
+    size_t absent = 0;
+    for (size_t k = 0; k < names->n; k++) if (!names->hits[k]) absent++;
+    if (absent) fprintf (stderr, "%zu of the %zu names in %s match no reference:\n", absent, names->n, names_file);
+    for (size_t k = 0; k < names->n; k++) if (!names->hits[k]) fprintf (stderr, "  %s\n", names->name[k]);
+  }
+  uvdb_name_list_free (names);
+  uvdb_set_close (set);
+  free (pos); free (outfilename);
+  return EXIT_SUCCESS;
 }
 
 /* `uvaiapack --merge`.  Whole tiles are exported once MERGE_BATCH references are resident and dropped from the front of the resident
@@ -64,18 +167,7 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
   const int nchar = (int) set->nchar, non_n_ref = (int) (nchar * (1. - ambig_r));      /* the threshold of the text path below */
   if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);
 
-  uvaia_gpu_ctx *gpu = NULL;
-  {
-    char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);
-    for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
-    dummy[nchar] = '\0';
-    const char *one[1] = {dummy};
-    uvaia_gpu_query q;
-    memset (&q, 0, sizeof q);
-    q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
-    if (uvaia_gpu_open (&gpu, &q, 1, device, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));
-    free (dummy);
-  }
+  uvaia_gpu_ctx *gpu = open_engine (nchar, device);
   const size_t tb = uvaia_gpu_db_tile_bytes (gpu), row = (size_t) uvaia_gpu_db_side_row_ints ();
   if (set->tile_bytes != tb || set->side_row_ints != (uint32_t) row) biomcmc_error ("packed database %s does not match this engine's tile layout", in[0]);
   /* resident: what a round leaves behind (below MERGE_BATCH) and one chunk on top of it */
@@ -102,8 +194,8 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
       }
       kept += m;
       if (!m) continue;
-      if ((db->h.version == 2 ? uvaia_gpu_db_stage_compact_at (gpu, slot, 0, db->base, db->head_idx + r0, db->heads, db->lit_idx + r0, db->lits, db->non_n + r0, (int) nt)
-                              : uvaia_gpu_db_stage_packed (gpu, slot, uvdb_tile_planes (db, t), db->non_n + r0, uvdb_tile_side_rows (db, t), (int) nt)) ||
+      const uvdb_set_piece piece = {f, t, nt, 0};          /* the chunk's tiles as one piece at the start of the slot, dense or compact */
+      if (uvdb_stage_pieces (gpu, set, slot, &piece, 1) ||
           uvaia_gpu_db_append_staged (gpu, slot, (uint64_t) m == r1 - r0 ? NULL : sel, m)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
       slot ^= 1;
       const size_t whole = uvaia_gpu_db_size (gpu) / 64;
@@ -133,10 +225,11 @@ int
 main (int argc, char **argv)
 {
   double ambig_r = 0.5;
-  const char *out = NULL;
-  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0, compact = 0;
+  const char *out = NULL, *names_file = NULL;
+  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0, compact = 0, unpack = 0, to_stdout = 0, list = 0;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
-    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {"compact", no_argument, 0, 1004}, {0, 0, 0, 0}};
+    {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {"compact", no_argument, 0, 1004},
+    {"unpack", no_argument, 0, 1005}, {"stdout", no_argument, 0, 1006}, {"names", required_argument, 0, 1007}, {"list", no_argument, 0, 1008}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
@@ -145,8 +238,21 @@ main (int argc, char **argv)
     case 1002: device = atoi (optarg); break;
     case 1003: merge = 1; break;
     case 1004: compact = 1; break;
+    case 1005: unpack = 1; break;
+    case 1006: to_stdout = 1; break;
+    case 1007: names_file = optarg; break;
+    case 1008: list = 1; break;
     default: errors++;
   }
+  /* what does not go together is refused here, before a file is opened or a GPU touched */
+  if (list && (unpack || merge || compact || have_ambig || out || to_stdout || names_file)) { fprintf (stderr, "--list prints the stored names and takes no other option\n"); return EXIT_FAILURE; }
+  if (unpack && (merge || compact || have_ambig)) { fprintf (stderr, "--unpack writes the references as they are stored: it does not go with --merge, --compact or -A\n"); return EXIT_FAILURE; }
+  if (unpack && !errors && (!out) == (!to_stdout)) { fprintf (stderr, "--unpack needs exactly one of -o <prefix> and --stdout\n"); return EXIT_FAILURE; }
+  if (names_file && !unpack) { fprintf (stderr, "--names needs --unpack: it chooses the references that are written\n"); return EXIT_FAILURE; }
+  if (to_stdout && !unpack) { fprintf (stderr, "--stdout needs --unpack\n"); return EXIT_FAILURE; }
+  if (!errors && optind < argc && list) return list_main (argc - optind, argv + optind);
+  if (!errors && optind < argc && unpack) return unpack_main (argc - optind, argv + optind, out, names_file, device);
+  if (list || unpack) out = NULL;                      /* (no input given: the usage below) */
   if (errors || !out || optind >= argc) { printf ("Error when reading arguments from command line:\n"); usage (basename (argv[0])); return EXIT_FAILURE; }
   if (ambig_r < 0.001) ambig_r = 0.001;
   if (ambig_r > 1.) ambig_r = 1.;
@@ -169,18 +275,10 @@ main (int argc, char **argv)
       const int have = rfas ? (readfasta_next (rfas) >= 0) : 0;
       if (have) {
         count++;
-        if (!gpu) {       /* the first record fixes the alignment length; the engine needs some query to exist: a plain ACGT string */
+        if (!gpu) {       /* the first record fixes the alignment length */
           nchar = (int) rfas->seqlength;
           non_n_ref = (int) (nchar * (1. - ambig_r));
-          char *dummy = (char *) biomcmc_malloc ((size_t) nchar + 1);
-          for (int s = 0; s < nchar; s++) dummy[s] = "ACGT"[s & 3];
-          dummy[nchar] = '\0';
-          const char *one[1] = {dummy};
-          uvaia_gpu_query q;
-          memset (&q, 0, sizeof q);
-          q.n_query = 1; q.nchar = nchar; q.seq = one; q.consensus = dummy;
-          if (uvaia_gpu_open (&gpu, &q, 1, device, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (NULL));
-          free (dummy);
+          gpu = open_engine (nchar, device);
           if (uvaia_gpu_db_reserve (gpu, PACK_BATCH)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
           const size_t tb = uvaia_gpu_db_tile_bytes (gpu);
           if (compact && nchar > UVDB_COMPACT_MAX_NCHAR) biomcmc_error ("--compact: alignments of more than %d sites have no compact form (%d sites)", UVDB_COMPACT_MAX_NCHAR, nchar);

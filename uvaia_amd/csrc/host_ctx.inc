@@ -165,6 +165,7 @@ struct uvaia_gpu_ctx {
     DevBuf<int> d_sel;
     DevBuf<uint4> d_four; int n = 0;      // n: references of the window loaded last (0: none)
     Event ev[5]; double ms[3] = {0., 0., 0.};            // device time of selection, import + derive, decode
+    Event slot_ev[2]; double slot_ms = 0.;               // device time of the decode straight out of a slot (uvaia_gpu_db_stage_unpack_rows)
     // uvaia_gpu_db_stage_compact_at: what a compact piece is expanded from -- the base row, the piece's index entries, heads and literals -- on
     // the copy stream's order, so one set serves both slots; device time of the expansion and of the side-row pass
     struct Compact { DevBuf<uint4> base; DevBuf<unsigned long long> hidx, lidx; DevBuf<uint32_t> heads, lits; Event ev[3]; bool timed = false; double ms[2] = {0., 0.}; } compact;

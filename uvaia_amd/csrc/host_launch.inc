@@ -120,6 +120,9 @@ int store_alloc(uvaia_gpu_ctx *c, TileStore &s, size_t tiles)
   HIPCHK(c, hipMemset(s.amb, 0, refs * AMB_ROW * sizeof(int)));
   if (int rc = planes.reserve(c, tiles * tile_u4)) return rc;
   HIPCHK(c, hipMemset(planes, 0, tiles * tile_u4 * sizeof(uint4)));
+  // hipMemset of device memory returns before it has run, on the null stream, which the context's own (non-blocking) streams do not wait
+  // for: without this wait a pack kernel queued right behind the allocation can be overtaken by the zeroing of the planes it wrote
+  HIPCHK(c, hipStreamSynchronize(nullptr));
   s.planes = std::move(planes);                           // last: its presence says all of them are there
   return 0;
 }

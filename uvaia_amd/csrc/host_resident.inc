@@ -18,6 +18,7 @@ int uvaia_gpu_db_reserve(uvaia_gpu_ctx *c, size_t cap)
   c->state.entered_clean = 0;
   if (int rc = c->state.d_entered.reserve(c, tiles * 64)) return rc;
   HIPCHK(c, hipMemset(c->state.d_entered, 0, c->state.d_entered.cap));
+  HIPCHK(c, hipStreamSynchronize(nullptr));             // (as in store_alloc: the flags are zero before a search on another stream sets them)
   return 0;
 }
 

@@ -258,6 +258,36 @@ int uvaia_gpu_db_unpack_rows(uvaia_gpu_ctx *c, const int *index, int n, char *ro
   return unpack_rows_from(c, c->acgt ? c->win.d_four : c->db.planes, count, "loaded window", "uvaia_gpu_db_load_staged", index, n, rows, pitch, c->win.ev + 3, &c->win.ms[2]);
 }
 
+// text of lanes index[0..n) of staging slot `slot` (positions within the slot, as sel of load_staged), decoded where the slot lies: the
+// resident database, the loaded window and the search state are not touched
+int uvaia_gpu_db_stage_unpack_rows(uvaia_gpu_ctx *c, int slot, const int *index, int n, char *rows, size_t pitch)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (c->shard.world > 1) return fail(c, UVAIA_GPU_ESTATE, "a context of a reference shard keeps its own pieces only: staged windows need a plain context");
+  if (slot < 0 || slot > 1) return fail(c, UVAIA_GPU_EINVAL, "staging slot %d: there are slots 0 and 1", slot);
+  auto &sl = c->win.stage[slot];
+  const int count = sl.n_tiles * 64;                       // (stage_reserve bounds a slot by what an int counts)
+  if (count) {
+    HIPCHK(c, hipSetDevice(c->device));
+    for (Event &e : c->win.slot_ev) if (int rc = e.make(c)) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->st.stream, sl.copied, 0));
+  }
+  char what[32];
+  snprintf(what, sizeof what, "staging slot %d", slot);
+  const int rc = unpack_rows_from(c, sl.planes, count, what, "uvaia_gpu_db_stage_packed", index, n, rows, pitch, c->win.slot_ev, &c->win.slot_ms);
+  if (rc || n == 0) return rc;
+  HIPCHK(c, hipEventRecord(sl.read, c->st.stream)); sl.read_recorded = true;      // the next stage into the slot waits for the decode
+  return 0;
+}
+
+double uvaia_gpu_stage_unpack_ms(uvaia_gpu_ctx *c, int reset)
+{
+  if (!c) return 0.;
+  const double v = c->win.slot_ms;
+  if (reset) c->win.slot_ms = 0.;
+  return v;
+}
+
 void uvaia_gpu_window_ms(uvaia_gpu_ctx *c, double out[3], int reset)
 {
   if (!c) return;
