@@ -235,6 +235,13 @@ int uvaia_gpu_replay_tiles_opened (uvaia_gpu_ctx *ctx, unsigned long long *out, 
  * [0] waits for on-demand words, [1] exact comparisons, [2] heap updates, [3] waits for a group's counters, [4] tolerance rises, [5] groups,
  * [6] whole waves, [7] the slowest wave.) */
 int uvaia_gpu_replay_timing (uvaia_gpu_ctx *ctx, unsigned long long out[12], int reset);
+/* The slices a resident search cuts references [first, first + n) into when it runs them in batches of `pool` (uvaia_gpu_search_resident
+ * is first = 0, n = db_size; uvaia_gpu_db_rederive rebuilds along first = 0, n = db_size, pool = max_pool): slice i covers
+ * [slice_first[i], slice_first[i] + slice_n[i]) and takes the batch snapshot first where pool_start[i] != 0.  Returns the number of
+ * slices and writes the first `cap` of them (the arrays may be NULL with cap = 0), or a negative code: pool < 1 or pool > max_pool is
+ * refused as uvaia_gpu_search_resident refuses it.  Host arithmetic only: the database is not looked at, nothing is allocated, the device
+ * is not touched. */
+int uvaia_gpu_search_plan (uvaia_gpu_ctx *ctx, size_t first, size_t n, size_t pool, size_t *slice_first, size_t *slice_n, unsigned char *pool_start, int cap);
 /* tuning knob: queries held per pass of the packed-plane and four-counter scans (8, 16 or 32); 0 = default */
 int uvaia_gpu_set_query_tile (uvaia_gpu_ctx *ctx, int qt);
 /* ---- query shards: several GPUs, each holding the whole database and the heaps of a contiguous range of the queries.  The

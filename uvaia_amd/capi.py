@@ -33,6 +33,7 @@ SYMBOLS = [
     "uvaia_gpu_db_stage_packed_at", "uvaia_gpu_db_append_staged", "uvaia_gpu_db_stage_compact_at", "uvaia_gpu_compact_ms",
     "uvaia_gpu_db_encode_compact", "uvaia_gpu_db_encoded_records", "uvaia_gpu_encode_ms",
     "uvaia_gpu_db_stage_unpack_rows", "uvaia_gpu_stage_unpack_ms",
+    "uvaia_gpu_search_plan",
 ]
 
 
@@ -206,6 +207,7 @@ def load_library():
         "uvaia_gpu_db_stage_unpack_rows": (C.c_int, [vp, C.c_int, pi, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_stage_unpack_ms": (C.c_double, [vp, C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
+        "uvaia_gpu_search_plan": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -474,6 +476,19 @@ class Engine:
             p = ent.ctypes.data_as(C.POINTER(C.c_uint8))
         self._chk(self.L.uvaia_gpu_search_resident(self.ctx, int(pool), int(ordinal0), p))
         return ent
+
+    def search_plan(self, first, n, pool):
+        """uvaia_gpu_search_plan: (first uint64 [slices], length uint64 [slices], opens a pool uint8 [slices]) of the slices a resident
+        search cuts references [first, first + n) into when it runs them in batches of pool; host arithmetic only"""
+        ns = self.L.uvaia_gpu_search_plan(self.ctx, int(first), int(n), int(pool), None, None, None, 0)
+        if ns < 0:
+            self._chk(ns)
+        sf, sn, ps = np.zeros(ns, dtype=np.uint64), np.zeros(ns, dtype=np.uint64), np.zeros(ns, dtype=np.uint8)
+        if ns:
+            got = self.L.uvaia_gpu_search_plan(self.ctx, int(first), int(n), int(pool), sf.ctypes.data, sn.ctypes.data, ps.ctypes.data, ns)
+            if got != ns:
+                self._chk(got if got < 0 else -1)
+        return sf, sn, ps
 
     def sync(self):
         self._chk(self.L.uvaia_gpu_sync(self.ctx))

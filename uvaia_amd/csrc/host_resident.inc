@@ -232,6 +232,16 @@ static std::vector<SubSlice> plan_subslices(const uvaia_gpu_ctx *c, size_t first
   return subs;
 }
 
+int uvaia_gpu_search_plan(uvaia_gpu_ctx *c, size_t first, size_t n, size_t pool, size_t *slice_first, size_t *slice_n, unsigned char *pool_start, int cap)
+{ // introspection: plan_subslices as the searches and the rebuild call it
+  if (!c || cap < 0 || (cap > 0 && (!slice_first || !slice_n || !pool_start))) return UVAIA_GPU_EINVAL;
+  if (pool < 1 || pool > c->max_pool) return fail(c, UVAIA_GPU_EINVAL, "pool must be in [1, max_pool=%zu]", c->max_pool);
+  const std::vector<SubSlice> plan = plan_subslices(c, first, n, pool);
+  if (plan.size() > (size_t)0x7fffffff) return fail(c, UVAIA_GPU_EINVAL, "a plan of %zu slices", plan.size());
+  for (size_t i = 0; i < plan.size() && i < (size_t)cap; i++) { slice_first[i] = plan[i].first; slice_n[i] = plan[i].n; pool_start[i] = plan[i].pool_start ? 1 : 0; }
+  return (int)plan.size();
+}
+
 int uvaia_gpu_db_rederive(uvaia_gpu_ctx *c)
 { // the reference-side work a query set costs on a database that is already resident: E/V/grp planes and gathered columns of
   // every tile for the open query set.  Appends do this for the rows they add; a caller that times "one search of a resident
