@@ -484,6 +484,57 @@ void uvaia_gpu_rows_kernel_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 /* diagnostics: the length exception runs are cut at (0 = the file format's 0xFFFFFF), so that tests reach the cut with short rows */
 int uvaia_gpu_rows_set_run_cut (uvaia_gpu_ctx *ctx, unsigned cut);
 
+/* ---- FASTA text split into rows on the device (`uvaiapack --device-parse`).  Replaces, for a block of decompressed text, the line loop of
+ * readfasta_next (uvaia_amd/csrc/host/seq_query.c:54-80: getline, realloc, the cleaning pass), quick_count_sequence_non_N and the copy of
+ * every row into pinned memory: the rows are made where uvaia_gpu_rows_census and uvaia_gpu_db_append_device read them.  The rules of a
+ * regular stream and what counts as irregular are stated in uvaia_amd/csrc/kernels_fasta.inc and restated in plain C by fasta_scan_host
+ * (uvaia_amd/csrc/host/fasta_blocks.h).  A handle of its own: the parser runs before the alignment length, and with it any uvaia_gpu_ctx,
+ * exists.  Offsets are positions in the text handed to the last scan.
+ *
+ * fasta_open:    device (-1 = the current one); block_bytes = the most text one scan takes (up to 1 GiB); max_records = the most records one
+ *                scan returns.
+ * fasta_scan:    pass 1 over text[0 .. n_bytes), host memory (pinned or not, any alignment; the copy keeps the alignment modulo 16).  final:
+ *                the text ends the stream, so its last record is complete; otherwise a record is complete once a later header line begins
+ *                in the text.  n_records = the complete records found, at most max_records; consumed = where the header line of the first
+ *                record not returned begins (n_bytes when everything was taken).  n_records == 0 with consumed == 0 on text that is not
+ *                final: its first record does not fit.  Irregular input among what would be returned -- a NUL byte, a line that is not
+ *                blank before the first header line, a record without one sequence byte -- fails with UVAIA_GPU_EINVAL, the message naming
+ *                the kind and the byte offset; nothing is returned or consumed and the handle stays usable.
+ * fasta_bad:     what the last scan refused: the kind (UVAIA_GPU_FASTA_NUL, _EMPTY or _TEXT; 0 when it refused nothing of the text) and, in
+ *                *offset, the byte of the text the message names.
+ * fasta_records: the table of the last scan, n_records entries.
+ * fasta_rows:    pass 2: the cleaned sequences of the records of the last scan whose length is nchar, in record order, at d_rows + k * pitch
+ *                in device memory (pitch = nchar rounded up to 16; valid until the next scan).  row_of_record[i] = the row of record i, or
+ *                -1 for a record of another length (may be NULL).
+ * fasta_rows_host: diagnostics: the rows of the last fasta_rows, n_rows * pitch bytes, copied to host memory.
+ * fasta_kernel_ms: device time in ms since the last reset of [0] pass 1, [1] pass 2. */
+typedef struct uvaia_gpu_fasta uvaia_gpu_fasta;
+typedef struct {
+  uint32_t name_off, name_len;   /* the bytes after the first '>' of the header line up to the end of that line */
+  uint32_t body_off, body_len;   /* from behind the header line to where the next header line begins (or the text ends) */
+  uint32_t seq_len;              /* bytes of the body that are no white space */
+  int32_t non_n;                 /* of those, the valid sites (quick_count_sequence_non_N) */
+  uint32_t flags;                /* UVAIA_GPU_FASTA_*: 0 in every record a successful scan returns */
+  uint32_t bad_off;              /* UVAIA_GPU_FASTA_NUL: where the first NUL of the record is */
+} uvaia_gpu_fasta_record;
+#define UVAIA_GPU_FASTA_NUL   1u   /* the record holds a NUL byte */
+#define UVAIA_GPU_FASTA_EMPTY 2u   /* the record has no sequence byte */
+#define UVAIA_GPU_FASTA_TEXT  4u   /* (the text before the first header line only) a line that is not blank */
+int uvaia_gpu_fasta_open (uvaia_gpu_fasta **out, int device, size_t block_bytes, int max_records);
+void uvaia_gpu_fasta_close (uvaia_gpu_fasta *fasta);
+const char *uvaia_gpu_fasta_last_error (const uvaia_gpu_fasta *fasta);   /* fasta may be NULL: error of the last failed open */
+int uvaia_gpu_fasta_scan (uvaia_gpu_fasta *fasta, const void *text, size_t n_bytes, int final, int *n_records, size_t *consumed);
+unsigned uvaia_gpu_fasta_bad (const uvaia_gpu_fasta *fasta, size_t *offset);
+int uvaia_gpu_fasta_records (uvaia_gpu_fasta *fasta, uvaia_gpu_fasta_record *out);
+int uvaia_gpu_fasta_rows (uvaia_gpu_fasta *fasta, int nchar, const void **d_rows, size_t *pitch, int *n_rows, int *row_of_record);
+int uvaia_gpu_fasta_rows_host (uvaia_gpu_fasta *fasta, void *out);
+void uvaia_gpu_fasta_kernel_ms (uvaia_gpu_fasta *fasta, double out[2], int reset);
+/* the bytes of text one block of pass 1 covers (tests place line ends and headers around its multiples) */
+size_t uvaia_gpu_fasta_chunk_bytes (void);
+/* page-locked host memory for the text blocks (NULL when there is none to be had), and its release */
+void *uvaia_gpu_fasta_pinned_alloc (size_t bytes);
+void uvaia_gpu_fasta_pinned_free (void *p);
+
 /* bytes the pair scan reads per reference (the default scan reads planes derived from the packed record for this query set) */
 size_t uvaia_gpu_scan_bytes_per_ref (const uvaia_gpu_ctx *ctx);
 /* the pair scan of this context: 2 = column-compressed scan over planes derived for the query set (default above 32 queries),

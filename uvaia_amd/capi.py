@@ -34,6 +34,8 @@ SYMBOLS = [
     "uvaia_gpu_db_encode_compact", "uvaia_gpu_db_encoded_records", "uvaia_gpu_encode_ms",
     "uvaia_gpu_db_stage_unpack_rows", "uvaia_gpu_stage_unpack_ms",
     "uvaia_gpu_search_plan",
+    "uvaia_gpu_fasta_open", "uvaia_gpu_fasta_close", "uvaia_gpu_fasta_last_error", "uvaia_gpu_fasta_scan", "uvaia_gpu_fasta_bad", "uvaia_gpu_fasta_records", "uvaia_gpu_fasta_rows", "uvaia_gpu_fasta_rows_host",
+    "uvaia_gpu_fasta_kernel_ms", "uvaia_gpu_fasta_chunk_bytes", "uvaia_gpu_fasta_pinned_alloc", "uvaia_gpu_fasta_pinned_free",
 ]
 
 
@@ -208,6 +210,18 @@ def load_library():
         "uvaia_gpu_stage_unpack_ms": (C.c_double, [vp, C.c_int]),
         "uvaia_gpu_free_bytes": (C.c_size_t, [vp]),
         "uvaia_gpu_search_plan": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+        "uvaia_gpu_fasta_open": (C.c_int, [C.POINTER(vp), C.c_int, C.c_size_t, C.c_int]),
+        "uvaia_gpu_fasta_close": (None, [vp]),
+        "uvaia_gpu_fasta_last_error": (C.c_char_p, [vp]),
+        "uvaia_gpu_fasta_scan": (C.c_int, [vp, C.c_void_p, C.c_size_t, C.c_int, pi, C.POINTER(C.c_size_t)]),
+        "uvaia_gpu_fasta_bad": (C.c_uint, [vp, C.POINTER(C.c_size_t)]),
+        "uvaia_gpu_fasta_records": (C.c_int, [vp, C.c_void_p]),
+        "uvaia_gpu_fasta_rows": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), pi, pi]),
+        "uvaia_gpu_fasta_rows_host": (C.c_int, [vp, C.c_void_p]),
+        "uvaia_gpu_fasta_kernel_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_fasta_chunk_bytes": (C.c_size_t, []),
+        "uvaia_gpu_fasta_pinned_alloc": (vp, [C.c_size_t]),
+        "uvaia_gpu_fasta_pinned_free": (None, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -763,6 +777,84 @@ class Engine:
         out = (C.c_double * 3)()
         self.L.uvaia_gpu_ball_kernel_ms(self.ctx, out, int(reset))
         return tuple(out)
+
+
+class FastaRecord(C.Structure):
+    """uvaia_gpu_fasta_record"""
+    _fields_ = [("name_off", C.c_uint32), ("name_len", C.c_uint32), ("body_off", C.c_uint32), ("body_len", C.c_uint32),
+                ("seq_len", C.c_uint32), ("non_n", C.c_int32), ("flags", C.c_uint32), ("bad_off", C.c_uint32)]
+
+    def astuple(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
+FASTA_RECORD_DTYPE = np.dtype([(f, np.int32 if f == "non_n" else np.uint32) for f, _ in FastaRecord._fields_])
+
+
+class Fasta:
+    """The FASTA parser's handle (uvaia_gpu_fasta): text in host memory split into records and rows on the device."""
+
+    def __init__(self, block_bytes, max_records, device=-1):
+        self.L = load_library()
+        self.h = C.c_void_p()
+        rc = self.L.uvaia_gpu_fasta_open(C.byref(self.h), int(device), int(block_bytes), int(max_records))
+        if rc != 0:
+            msg = self.L.uvaia_gpu_fasta_last_error(None)
+            self.h = None
+            raise GpuError(rc, msg.decode() if msg else "?")
+        self.n_records = 0
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise GpuError(rc, self.L.uvaia_gpu_fasta_last_error(self.h).decode())
+
+    def scan(self, text, final, offset=0):
+        """text: bytes-like or a uint8 array whose bytes from `offset` on are the block; (n_records, consumed)"""
+        arr = np.frombuffer(text, dtype=np.uint8) if not isinstance(text, np.ndarray) else text
+        n, cons = C.c_int(0), C.c_size_t(0)
+        self.n_records = 0
+        self._chk(self.L.uvaia_gpu_fasta_scan(self.h, arr.ctypes.data + int(offset), arr.size - int(offset), int(bool(final)), C.byref(n), C.byref(cons)))
+        self.n_records = n.value
+        return n.value, cons.value
+
+    def bad(self):
+        """(kind, offset) of what the last scan refused; kind 0: nothing of the text"""
+        off = C.c_size_t(0)
+        return int(self.L.uvaia_gpu_fasta_bad(self.h, C.byref(off))), off.value
+
+    def records(self):
+        """the table of the last scan as a structured array (FASTA_RECORD_DTYPE)"""
+        out = np.zeros(self.n_records, dtype=FASTA_RECORD_DTYPE)
+        self._chk(self.L.uvaia_gpu_fasta_records(self.h, out.ctypes.data))
+        return out
+
+    def rows(self, nchar):
+        """pass 2: (device pointer, pitch, n_rows, row_of_record)"""
+        p, pitch, n = C.c_void_p(), C.c_size_t(0), C.c_int(0)
+        row_of = np.full(max(self.n_records, 1), -2, dtype=np.int32)
+        self._chk(self.L.uvaia_gpu_fasta_rows(self.h, int(nchar), C.byref(p), C.byref(pitch), C.byref(n), row_of.ctypes.data_as(C.POINTER(C.c_int))))
+        return p.value, pitch.value, n.value, row_of[:self.n_records]
+
+    def rows_host(self, n_rows, pitch):
+        out = np.zeros((n_rows, pitch), dtype=np.uint8)
+        self._chk(self.L.uvaia_gpu_fasta_rows_host(self.h, out.ctypes.data))
+        return out
+
+    def kernel_ms(self, reset=False):
+        out = (C.c_double * 2)()
+        self.L.uvaia_gpu_fasta_kernel_ms(self.h, out, int(reset))
+        return list(out)
+
+    def close(self):
+        if self.h:
+            self.L.uvaia_gpu_fasta_close(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
 
 def finalise_heaps(n, scores, ordinals):

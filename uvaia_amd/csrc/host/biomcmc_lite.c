@@ -269,12 +269,36 @@ biomcmc_close_compress (file_compress_t fc)
 }
 
 int
+biomcmc_close_compress_status (file_compress_t fc)
+{ /* biomcmc_close_compress for a caller that has something to undo first: the same check, the verdict returned instead of the exit */
+  if (!fc) return 0;
+  int status = 0;
+  if (fc->fp) status = fc->from_popen ? pclose (fc->fp) : fclose (fc->fp);
+  const int bad = status != 0 && !fc->writing && fc->at_eof;
+  free (fc->filename); free (fc);
+  return bad ? -1 : 0;
+}
+
+int
 biomcmc_getline_compress (char **lineptr, size_t *n, file_compress_t fc)
 {
   ssize_t got = getline (lineptr, n, fc->fp);
   if (got < 0) { fc->at_eof = 1; return -1; }
   while (got > 0 && ((*lineptr)[got - 1] == '\n' || (*lineptr)[got - 1] == '\r')) (*lineptr)[--got] = '\0';   /* lines come back without their terminator */
   return (int) got;
+}
+
+size_t
+biomcmc_read_compress (file_compress_t fc, void *buf, size_t n)
+{ /* the raw sibling of biomcmc_getline_compress: fewer than n bytes only at end of data, which is noted as there, so that
+     biomcmc_close_compress tells a decompressor that failed mid-stream from the end of the file */
+  size_t have = 0;
+  while (have < n) {
+    size_t got = fread ((char *) buf + have, 1, n - have, fc->fp);
+    if (!got) { fc->at_eof = 1; break; }
+    have += got;
+  }
+  return have;
 }
 
 int

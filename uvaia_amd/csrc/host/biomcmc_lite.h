@@ -75,7 +75,9 @@ void biomcmc_count_sequence_acgt (const char *seq, size_t length, double result[
 /* possibly compressed text streams (xz, gz, bz2 by magic number / suffix, through the system tools) */
 file_compress_t biomcmc_open_compress (const char *path, const char *mode);
 void biomcmc_close_compress (file_compress_t fc);
+int biomcmc_close_compress_status (file_compress_t fc);                        /* for readers: -1 where biomcmc_close_compress would end the program */
 int biomcmc_getline_compress (char **lineptr, size_t *n, file_compress_t fc);   /* -1 at end of file */
+size_t biomcmc_read_compress (file_compress_t fc, void *buf, size_t n);         /* raw bytes; fewer than n at end of file only */
 int biomcmc_write_compress (file_compress_t fc, const char *str);              /* bytes written */
 
 #ifdef __cplusplus

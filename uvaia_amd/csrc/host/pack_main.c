@@ -16,6 +16,10 @@
  *
  * `uvaiapack --unpack` is the way back: the references of packed databases of either version as FASTA, decoded on the GPU out of the
  * staging slots (uvdb_extract.h), all of them or those a list of names asks for.  `uvaiapack --list` prints the stored names and needs no GPU.
+ *
+ * `uvaiapack --device-parse` (off by default) writes the same file from the same texts without the line reader: the decompressed bytes are
+ * read in blocks (fasta_blocks.h), split into records and rows on the GPU (uvaia_gpu_fasta_scan, uvaia_gpu_fasta_rows) and packed from the
+ * rows where they lie (uvdb_packer.h).  Only the names are taken from the host's copy of the text.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -27,6 +31,7 @@
 #include "uvdb_set.h"
 #include "uvdb_packer.h"
 #include "uvdb_extract.h"
+#include "fasta_blocks.h"
 #include "../../../include/uvaia_gpu.h"
 
 #define PACK_BATCH 4096      /* references per engine round trip (a multiple of 64) */
@@ -37,10 +42,14 @@ usage (const char *prog)
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("Packs an aligned reference FASTA into the bit-plane database the MI355X engine searches without parsing text.\n\n");
   printf (" %s [-hv] [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
+  printf (" %s --device-parse [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <ref.fa(.gz,.xz)> [<ref.fa(.gz,.xz)>]...\n", prog);
   printf (" %s --merge [-A <double>] [--compact] [--device=<int>] -o <out.uvdb> <a.uvdb> [<b.uvdb>]...\n", prog);
   printf (" %s --unpack (-o <without suffix> | --stdout) [--names <file>] [--device=<int>] <a.uvdb> [<b.uvdb>]...\n", prog);
   printf (" %s --list <a.uvdb> [<b.uvdb>]...\n\n", prog);
   printf ("  -A, --ref_ambiguity=<double>     maximum allowed ambiguity for a REFERENCE sequence to be kept (default=0.5); `uvaia --packed` is run with the value of its file\n");
+  printf ("  --device-parse                   split the text into sequences on the GPU instead of reading it line by line: the same file, from regular FASTA\n");
+  printf ("                                   only (a NUL byte, text before the first header and a header without sequence are refused).  Not with --merge,\n");
+  printf ("                                   --unpack or --list\n");
   printf ("  --merge                          the inputs are packed databases: joins them, in order, into the file that packing their texts together gives.\n");
   printf ("                                   -A then defaults to the inputs' common value; a smaller one drops the rows it excludes, a larger one than\n");
   printf ("                                   an input's is refused (that input no longer holds the rows it would keep)\n");
@@ -221,15 +230,121 @@ merge_main (int n_in, char **in, const char *out, int have_ambig, double ambig_r
   return EXIT_SUCCESS;
 }
 
+/* `uvaiapack --device-parse`.  The first record of the first file fixes the alignment length and opens the packer; rows of that length go
+ * to it as they lie in device memory, a record of another length is treated as on the default route (pack_main.c, the fill loop of main):
+ * dropped as too ambiguous, or the end of the command. */
+#define PARSE_MAX_RECORDS (1 << 18)     /* records per scan: 8 MiB of table; a block that holds more is scanned in several steps */
+
+struct device_parse {
+  uvaia_gpu_fasta *fasta;
+  struct uvdb_packer packer;
+  int open, nchar, non_n_ref, compact, device, max_records;
+  double ambig_r;
+  const char *out;
+  uvaia_gpu_fasta_record *rec;
+  int *row_of;
+  char **name;
+  long count, n_other_dropped;
+};
+
+static int
+parse_scan (void *user, const char *text, size_t n, int final, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off, char *err, size_t errlen)
+{
+  struct device_parse *d = (struct device_parse *) user;
+  if (!uvaia_gpu_fasta_scan (d->fasta, text, n, final, n_records, consumed)) return 0;
+  const unsigned kind = uvaia_gpu_fasta_bad (d->fasta, bad_off);       /* irregular text: the block reader names the byte of the stream */
+  *bad_kind = kind == UVAIA_GPU_FASTA_NUL ? FASTA_BAD_NUL : kind == UVAIA_GPU_FASTA_TEXT ? FASTA_BAD_TEXT : kind == UVAIA_GPU_FASTA_EMPTY ? FASTA_BAD_EMPTY : FASTA_BAD_NONE;
+  snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta));
+  return -1;
+}
+
+static int
+parse_records (void *user, char *text, size_t consumed, int n_records, char *err, size_t errlen)
+{
+  struct device_parse *d = (struct device_parse *) user;
+  if (uvaia_gpu_fasta_records (d->fasta, d->rec)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+  if (!d->open) {       /* the first record fixes the alignment length */
+    d->nchar = (int) d->rec[0].seq_len;
+    d->non_n_ref = (int) (d->nchar * (1. - d->ambig_r));
+    if (uvdb_packer_open (&d->packer, d->out, d->nchar, d->ambig_r, d->device, d->max_records, d->compact)) { snprintf (err, errlen, "%s", d->packer.err); return -1; }
+    d->open = 1;
+  }
+  const void *d_rows = NULL; size_t pitch = 0; int n_rows = 0;
+  if (uvaia_gpu_fasta_rows (d->fasta, d->nchar, &d_rows, &pitch, &n_rows, d->row_of)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+  d->count += n_records;
+  for (int k = 0; k < n_records; k++) {
+    const uvaia_gpu_fasta_record *r = d->rec + k;
+    text[r->name_off + r->name_len] = '\0';              /* the line end behind the name, or the byte of room behind the block */
+    if (d->row_of[k] >= 0) { d->name[d->row_of[k]] = text + r->name_off; continue; }
+    /* as the reference's fill loop (src/nearest.c:263-278): low-quality records are dropped first, only then must the length fit */
+    if (r->non_n < d->non_n_ref) { d->n_other_dropped++; continue; }
+    biomcmc_warning ("Reference sequence '%s' has %u sites but the first sequence has %d sites\n", text + r->name_off, r->seq_len, d->nchar);
+    snprintf (err, errlen, "all sequences must be aligned");
+    return -1;
+  }
+  if (n_rows && uvdb_packer_add_block (&d->packer, d_rows, pitch, n_rows, d->name)) { snprintf (err, errlen, "%s", d->packer.err); return -1; }
+  return 0;
+}
+
+static int
+device_parse_main (int n_in, char **in, const char *out, double ambig_r, int device, int compact, size_t block_bytes)
+{
+  char msg[1024];
+  int64_t time0[2];
+  biomcmc_get_time (time0);
+  struct device_parse d;
+  memset (&d, 0, sizeof d);
+  d.ambig_r = ambig_r; d.device = device; d.compact = compact; d.out = out;
+  d.max_records = block_bytes / 4 + 1 < PARSE_MAX_RECORDS ? (int) (block_bytes / 4 + 1) : PARSE_MAX_RECORDS;      /* (a record has four bytes at least) */
+  if (uvaia_gpu_fasta_open (&d.fasta, device, block_bytes, d.max_records)) biomcmc_error ("%s", uvaia_gpu_fasta_last_error (NULL));
+  d.rec = (uvaia_gpu_fasta_record *) biomcmc_malloc ((size_t) d.max_records * sizeof (uvaia_gpu_fasta_record));
+  d.row_of = (int *) biomcmc_malloc ((size_t) d.max_records * sizeof (int));
+  d.name = (char **) biomcmc_malloc ((size_t) d.max_records * sizeof (char *));
+  uint64_t bytes = 0;
+  for (int j = 0; j < n_in; j++) {
+    uint64_t nb = 0;
+    fasta_blocks fb = fasta_blocks_open (in[j], block_bytes, uvaia_gpu_fasta_pinned_alloc, uvaia_gpu_fasta_pinned_free, msg, sizeof msg);
+    int rc = fb ? fasta_blocks_run (fb, d.max_records, parse_scan, &d, parse_records, &d, &nb, msg, sizeof msg) : -1;
+    if (rc && d.open) remove (out);                           /* no output file is left behind, whatever ends the command */
+    char failed[1024];                                        /* a decompressor that failed mid-stream: what was read is not the file, and */
+    if (fasta_blocks_finish (fb, failed, sizeof failed)) {    /* what its cut end looked like (a short last record) is not the finding */
+      if (d.open) remove (out);
+      biomcmc_error ("%s", failed);
+    }
+    if (rc) {
+      const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
+      biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaiapack` without it reads this file line by line)" : "");
+    }
+    bytes += nb;
+    fprintf (stderr, "Finished reading file %s in %.3lf secs; %ld sequences so far, %ld kept, %ld too ambiguous.\n", in[j], biomcmc_update_elapsed_time (time0), d.count,
+             d.open ? d.packer.kept : 0L, d.n_other_dropped + (d.open ? d.packer.dropped : 0L));
+  }
+  if (!d.open) biomcmc_error ("no sequence found");
+  const long kept = d.packer.kept;
+  if (uvdb_packer_close (&d.packer)) { remove (out); biomcmc_error ("%s: %s", out, d.packer.err); }
+  double ms[2] = {0., 0.};
+  uvaia_gpu_fasta_kernel_ms (d.fasta, ms, 0);
+  fprintf (stderr, "device parse: {\"bytes\": %llu, \"block_bytes\": %zu, \"scan_ms\": %.3f, \"rows_ms\": %.3f, \"scan_gb_s\": %.2f, \"rows_gb_s\": %.2f}\n", (unsigned long long) bytes, block_bytes, ms[0], ms[1],
+           ms[0] > 0 ? (double) bytes / ms[0] * 1e-6 : 0., ms[1] > 0 ? (double) bytes / ms[1] * 1e-6 : 0.);
+  fprintf (stderr, "Packed %ld of %ld sequences (%d sites) into %s", kept, d.count, d.nchar, out);
+  if (compact) fprintf (stderr, "; compact tiles: %ld encoded on the device, %ld on the host", d.packer.tiles_device, d.packer.tiles_host);
+  fprintf (stderr, "\n");
+  uvaia_gpu_fasta_close (d.fasta);
+  free (d.rec); free (d.row_of); free (d.name);
+  return EXIT_SUCCESS;
+}
+
 int
 main (int argc, char **argv)
 {
   double ambig_r = 0.5;
   const char *out = NULL, *names_file = NULL;
-  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0, compact = 0, unpack = 0, to_stdout = 0, list = 0;
+  int device = -1, ch, errors = 0, merge = 0, have_ambig = 0, compact = 0, unpack = 0, to_stdout = 0, list = 0, device_parse = 0;
+  size_t parse_block = FASTA_BLOCK_BYTES;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"merge", no_argument, 0, 1003}, {"compact", no_argument, 0, 1004},
-    {"unpack", no_argument, 0, 1005}, {"stdout", no_argument, 0, 1006}, {"names", required_argument, 0, 1007}, {"list", no_argument, 0, 1008}, {0, 0, 0, 0}};
+    {"unpack", no_argument, 0, 1005}, {"stdout", no_argument, 0, 1006}, {"names", required_argument, 0, 1007}, {"list", no_argument, 0, 1008},
+    {"device-parse", no_argument, 0, 1009}, {"parse-block", required_argument, 0, 1010}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
@@ -242,9 +357,14 @@ main (int argc, char **argv)
     case 1006: to_stdout = 1; break;
     case 1007: names_file = optarg; break;
     case 1008: list = 1; break;
+    case 1009: device_parse = 1; break;
+    case 1010: parse_block = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the block size of --device-parse in bytes) */
     default: errors++;
   }
   /* what does not go together is refused here, before a file is opened or a GPU touched */
+  if (device_parse && (merge || unpack || list)) { fprintf (stderr, "--device-parse reads FASTA text: it does not go with --merge, --unpack or --list\n"); return EXIT_FAILURE; }
+  if (device_parse && (parse_block < 64 || parse_block > ((size_t) 1 << 30))) { fprintf (stderr, "--parse-block: expected 64 to 1073741824 bytes\n"); return EXIT_FAILURE; }
+  if (!device_parse && parse_block != FASTA_BLOCK_BYTES) { fprintf (stderr, "--parse-block sets the block size of --device-parse: it needs that option\n"); return EXIT_FAILURE; }
   if (list && (unpack || merge || compact || have_ambig || out || to_stdout || names_file)) { fprintf (stderr, "--list prints the stored names and takes no other option\n"); return EXIT_FAILURE; }
   if (unpack && (merge || compact || have_ambig)) { fprintf (stderr, "--unpack writes the references as they are stored: it does not go with --merge, --compact or -A\n"); return EXIT_FAILURE; }
   if (unpack && !errors && (!out) == (!to_stdout)) { fprintf (stderr, "--unpack needs exactly one of -o <prefix> and --stdout\n"); return EXIT_FAILURE; }
@@ -257,6 +377,7 @@ main (int argc, char **argv)
   if (ambig_r < 0.001) ambig_r = 0.001;
   if (ambig_r > 1.) ambig_r = 1.;
   if (merge) return merge_main (argc - optind, argv + optind, out, have_ambig, ambig_r, device, compact);
+  if (device_parse) return device_parse_main (argc - optind, argv + optind, out, ambig_r, device, compact, parse_block);
   int64_t time0[2];
   biomcmc_get_time (time0);
 

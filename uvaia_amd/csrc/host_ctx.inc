@@ -17,6 +17,14 @@ int fail(uvaia_gpu_ctx *c, int code, const char *fmt, ...);
 inline int hip_failed(uvaia_gpu_ctx *c, hipError_t e, const char *call, const char *file, int line)
 { return fail(c, e == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line); }
 
+// the same for the FASTA parser's handle (host_fasta.inc), which is no context
+int fasta_fail(uvaia_gpu_fasta *f, int code, const char *fmt, ...);
+inline int hip_failed(uvaia_gpu_fasta *f, hipError_t e, const char *call, const char *file, int line)
+{ return fasta_fail(f, e == hipErrorOutOfMemory ? UVAIA_GPU_ENOMEM : UVAIA_GPU_EHIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e), file, line); }
+// (a plain nullptr stays what it was: no context yet, the message of a failed uvaia_gpu_open)
+inline int hip_failed(std::nullptr_t, hipError_t e, const char *call, const char *file, int line)
+{ return hip_failed(static_cast<uvaia_gpu_ctx *>(nullptr), e, call, file, line); }
+
 }  // namespace
 
 #include "host_owners.h"

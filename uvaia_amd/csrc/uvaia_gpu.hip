@@ -82,6 +82,7 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "kernels_qprep.inc"
 #include "kernels_expand.inc"
 #include "kernels_encode.inc"
+#include "kernels_fasta.inc"
 
 // ------------------------------------------------------------------------------------------------------------
 // host side, in sections (one translation unit: the kernels above are templates the sections instantiate); the context and everything
@@ -99,3 +100,4 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "host_ball.inc"
 #include "host_window.inc"
 #include "host_encode.inc"
+#include "host_fasta.inc"
