@@ -71,6 +71,11 @@ int  uvaia_align_batch (uvaia_aligner *a, const char *const *seq, const int *seq
  * on the device), fetch copies them back. */
 int  uvaia_align_load (uvaia_aligner *a, const char *const *seq, const int *seq_len, int n);
 int  uvaia_align_load_block (uvaia_aligner *a, const char *bytes, const int64_t *offsets /* n + 1 */, int n);
+/* load_block with the bytes already in device memory (uvaia_gpu_fasta_sequences of include/uvaia_gpu.h gives this form): d_bytes must be
+ * memory of the aligner's device and [offsets[0], offsets[n]) must lie inside its allocation -- a host pointer, memory of another device
+ * and a range that ends beyond the allocation are refused with UVAIA_ALIGN_EINVAL before anything is read.  The queries are copied device
+ * to device: the source may go once the call has returned. */
+int  uvaia_align_load_device (uvaia_aligner *a, const void *d_bytes, const int64_t *offsets /* n + 1, host */, int n);
 int  uvaia_align_run (uvaia_aligner *a);
 int  uvaia_align_sync (uvaia_aligner *a);
 int  uvaia_align_fetch (uvaia_aligner *a, char *aln, int *score);

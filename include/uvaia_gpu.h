@@ -507,7 +507,20 @@ int uvaia_gpu_rows_set_run_cut (uvaia_gpu_ctx *ctx, unsigned cut);
  *                in device memory (pitch = nchar rounded up to 16; valid until the next scan).  row_of_record[i] = the row of record i, or
  *                -1 for a record of another length (may be NULL).
  * fasta_rows_host: diagnostics: the rows of the last fasta_rows, n_rows * pitch bytes, copied to host memory.
- * fasta_kernel_ms: device time in ms since the last reset of [0] pass 1, [1] pass 2. */
+ * fasta_kernel_ms: device time in ms since the last reset of [0] pass 1, [1] pass 2.
+ *
+ * For sequences that are not aligned yet (`uvaialign --device-parse`), on the records of the last scan:
+ * fasta_acgt:    acgt[k] = the body bytes of record k that are one of A C G T a c g t: the first counter of biomcmc_count_sequence_acgt
+ *                (uvaia_amd/csrc/host/biomcmc_lite.c:378-392), n_records entries.  Its second counter, the "N etc." set, needs no kernel: it
+ *                is seq_len - non_n of the record table, the same nine characters N n X x O o - ? . in both functions.
+ * fasta_sequences: the cleaned sequences of records record[0 .. n_sel) (NULL: records 0 .. n_sel - 1), each at its own length, back to back
+ *                in device memory: sequence k at d_bytes + offsets[k], offsets[k + 1] - offsets[k] = seq_len of that record, offsets[0] = 0
+ *                (offsets: n_sel + 1 entries, host memory) -- the bytes + offsets form of uvaia_align_load_block, for
+ *                uvaia_align_load_device.  Valid until the next scan or the next fasta_sequences; the call returns when the kernel is
+ *                done.  An index outside the last scan or one that is repeated fails with UVAIA_GPU_EINVAL before anything is launched.
+ * fasta_sequences_host: diagnostics: the buffer of the last fasta_sequences, offsets[n_sel] bytes and the 64 guard bytes behind them, which
+ *                fasta_sequences sets to 0xEE before its launch and the kernel leaves alone; n_bytes must be offsets[n_sel] + 64.
+ * fasta_sequences_ms: device time in ms since the last reset of [0] fasta_acgt, [1] fasta_sequences. */
 typedef struct uvaia_gpu_fasta uvaia_gpu_fasta;
 typedef struct {
   uint32_t name_off, name_len;   /* the bytes after the first '>' of the header line up to the end of that line */
@@ -529,6 +542,10 @@ int uvaia_gpu_fasta_records (uvaia_gpu_fasta *fasta, uvaia_gpu_fasta_record *out
 int uvaia_gpu_fasta_rows (uvaia_gpu_fasta *fasta, int nchar, const void **d_rows, size_t *pitch, int *n_rows, int *row_of_record);
 int uvaia_gpu_fasta_rows_host (uvaia_gpu_fasta *fasta, void *out);
 void uvaia_gpu_fasta_kernel_ms (uvaia_gpu_fasta *fasta, double out[2], int reset);
+int uvaia_gpu_fasta_acgt (uvaia_gpu_fasta *fasta, int *acgt);
+int uvaia_gpu_fasta_sequences (uvaia_gpu_fasta *fasta, const int *record, int n_sel, const void **d_bytes, int64_t *offsets /* n_sel + 1 */);
+int uvaia_gpu_fasta_sequences_host (uvaia_gpu_fasta *fasta, void *out, size_t n_bytes);
+void uvaia_gpu_fasta_sequences_ms (uvaia_gpu_fasta *fasta, double out[2], int reset);
 /* the bytes of text one block of pass 1 covers (tests place line ends and headers around its multiples) */
 size_t uvaia_gpu_fasta_chunk_bytes (void);
 /* page-locked host memory for the text blocks (NULL when there is none to be had), and its release */

@@ -9,7 +9,7 @@ from . import capi
 SYMBOLS = [
     "uvaia_align_default_options", "uvaia_align_open", "uvaia_align_close", "uvaia_align_last_error", "uvaia_align_batch",
     "uvaia_align_load", "uvaia_align_load_block", "uvaia_align_run", "uvaia_align_sync", "uvaia_align_fetch", "uvaia_align_stats",
-    "uvaia_align_device_rows",
+    "uvaia_align_device_rows", "uvaia_align_load_device",
 ]
 
 
@@ -42,6 +42,7 @@ def _lib():
         L.uvaia_align_batch.argtypes = [vp, C.POINTER(C.c_char_p), pi, C.c_int, C.c_void_p, pi]
         L.uvaia_align_load.argtypes = [vp, C.POINTER(C.c_char_p), pi, C.c_int]
         L.uvaia_align_load_block.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
+        L.uvaia_align_load_device.argtypes = [vp, C.c_void_p, C.POINTER(C.c_int64), C.c_int]
         L.uvaia_align_run.argtypes = [vp]
         L.uvaia_align_sync.argtypes = [vp]
         L.uvaia_align_fetch.argtypes = [vp, C.c_void_p, pi]
@@ -94,6 +95,14 @@ class Aligner:
         off[1:] = np.cumsum([len(s) for s in seqs])
         blob = b"".join(seqs)
         self._chk(self.L.uvaia_align_load_block(self.ptr, blob, off.ctypes.data_as(C.POINTER(C.c_int64)), n))
+        self.n = n
+
+    def load_device(self, d_bytes, offsets):
+        """the pool from device memory: d_bytes a device pointer (an int), offsets n + 1 byte offsets from it (uvaia_align_load_device)"""
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = len(off) - 1
+        self.n = 0
+        self._chk(self.L.uvaia_align_load_device(self.ptr, C.c_void_p(d_bytes), off.ctypes.data_as(C.POINTER(C.c_int64)), n))
         self.n = n
 
     def run(self):

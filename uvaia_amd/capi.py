@@ -36,6 +36,7 @@ SYMBOLS = [
     "uvaia_gpu_search_plan",
     "uvaia_gpu_fasta_open", "uvaia_gpu_fasta_close", "uvaia_gpu_fasta_last_error", "uvaia_gpu_fasta_scan", "uvaia_gpu_fasta_bad", "uvaia_gpu_fasta_records", "uvaia_gpu_fasta_rows", "uvaia_gpu_fasta_rows_host",
     "uvaia_gpu_fasta_kernel_ms", "uvaia_gpu_fasta_chunk_bytes", "uvaia_gpu_fasta_pinned_alloc", "uvaia_gpu_fasta_pinned_free",
+    "uvaia_gpu_fasta_acgt", "uvaia_gpu_fasta_sequences", "uvaia_gpu_fasta_sequences_host", "uvaia_gpu_fasta_sequences_ms",
 ]
 
 
@@ -219,6 +220,10 @@ def load_library():
         "uvaia_gpu_fasta_rows": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t), pi, pi]),
         "uvaia_gpu_fasta_rows_host": (C.c_int, [vp, C.c_void_p]),
         "uvaia_gpu_fasta_kernel_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_fasta_acgt": (C.c_int, [vp, pi]),
+        "uvaia_gpu_fasta_sequences": (C.c_int, [vp, pi, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64)]),
+        "uvaia_gpu_fasta_sequences_host": (C.c_int, [vp, C.c_void_p, C.c_size_t]),
+        "uvaia_gpu_fasta_sequences_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
         "uvaia_gpu_fasta_chunk_bytes": (C.c_size_t, []),
         "uvaia_gpu_fasta_pinned_alloc": (vp, [C.c_size_t]),
         "uvaia_gpu_fasta_pinned_free": (None, [vp]),
@@ -843,6 +848,31 @@ class Fasta:
     def kernel_ms(self, reset=False):
         out = (C.c_double * 2)()
         self.L.uvaia_gpu_fasta_kernel_ms(self.h, out, int(reset))
+        return list(out)
+
+    def acgt(self):
+        """per record of the last scan, its A C G T sites (upper or lower case)"""
+        out = np.zeros(max(self.n_records, 1), dtype=np.int32)
+        self._chk(self.L.uvaia_gpu_fasta_acgt(self.h, out.ctypes.data_as(C.POINTER(C.c_int))))
+        return out[:self.n_records]
+
+    def sequences(self, record=None, n_sel=None):
+        """the cleaned sequences of the records `record` (None: the first n_sel, or all) back to back: (device pointer, offsets [n_sel + 1])"""
+        sel = None if record is None else np.ascontiguousarray(record, dtype=np.int32)
+        n = int(len(sel) if sel is not None else (self.n_records if n_sel is None else n_sel))
+        p, off = C.c_void_p(), np.zeros(n + 1, dtype=np.int64)
+        self._chk(self.L.uvaia_gpu_fasta_sequences(self.h, None if sel is None else sel.ctypes.data_as(C.POINTER(C.c_int)), n, C.byref(p), off.ctypes.data_as(C.POINTER(C.c_int64))))
+        return p.value or 0, off
+
+    def sequences_host(self, n_bytes):
+        """the buffer of the last sequences(): n_bytes of sequences, then the 64 guard bytes, as (bytes, guard)"""
+        out = np.zeros(int(n_bytes) + 64, dtype=np.uint8)
+        self._chk(self.L.uvaia_gpu_fasta_sequences_host(self.h, out.ctypes.data, out.size))
+        return out[:int(n_bytes)].tobytes(), out[int(n_bytes):]
+
+    def sequences_ms(self, reset=False):
+        out = (C.c_double * 2)()
+        self.L.uvaia_gpu_fasta_sequences_ms(self.h, out, int(reset))
         return list(out)
 
     def close(self):

@@ -6,6 +6,9 @@
  * --packed (no counterpart in the reference): the aligned rows go from the aligner's device memory straight into a packed database
  * (uvdb.h), the file `uvaiapack` would write from the text output: census, -A filter, packing and exception runs happen on the rows where
  * they lie (include/uvaia_gpu.h, "rows that are already in device memory").  Own code.
+ *
+ * --device-parse (no counterpart either, off by default): the input is split into sequences on the GPU and handed to the aligner in device
+ * memory, see align_device_parse below.  Without the option the command takes the read loop of main as it was.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -18,6 +21,7 @@
 #include "gpu_glue.h"
 #include "uvdb.h"
 #include "uvdb_packer.h"
+#include "fasta_blocks.h"
 #include "../../../include/uvaia_align.h"
 #include "../../../include/uvaia_gpu.h"
 
@@ -31,10 +35,144 @@ packer_add_pool (struct uvdb_packer *p, uvaia_aligner *al, char **name, int fill
   return uvdb_packer_add_block (p, d_rows, pitch, n, name);
 }
 
+/* `uvaialign --device-parse`: the text is read in blocks (fasta_blocks.h) and split into records on the GPU (uvaia_gpu_fasta_scan); the
+ * filters of the fill loop in main run on the integers of the record table and the A C G T counts; the survivors of a scan go, a pool at a
+ * time and in record order, from the parser's device memory into the aligner's (uvaia_gpu_fasta_sequences, uvaia_align_load_device).  Only
+ * the names are taken from the host's copy of the text.  The reader thread fills the next block while this one is aligned. */
+#define PARSE_MAX_RECORDS (1 << 18)     /* records per scan, as in pack_main.c; a block that holds more is scanned in several steps */
+
+struct align_parse {
+  uvaia_gpu_fasta *fasta;
+  uvaia_aligner *al;
+  struct uvdb_packer *pk;               /* NULL without --packed */
+  file_compress_t outstream;
+  bool to_screen, write_text;
+  size_t aln_length;
+  double ambig, align_ms;
+  int pool, count, n_output, n_pool;
+  uvaia_gpu_fasta_record *rec;          /* max_records of each */
+  int *acgt, *sel;
+  int64_t *offsets;                     /* pool + 1 */
+  char **name, *aln;                    /* main's arrays of a pool */
+  int64_t *time1;
+};
+
+static int
+align_parse_scan (void *user, const char *text, size_t n, int final, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off, char *err, size_t errlen)
+{
+  struct align_parse *d = (struct align_parse *) user;
+  if (!uvaia_gpu_fasta_scan (d->fasta, text, n, final, n_records, consumed)) return 0;
+  const unsigned kind = uvaia_gpu_fasta_bad (d->fasta, bad_off);       /* irregular text: the block reader names the byte of the stream */
+  *bad_kind = kind == UVAIA_GPU_FASTA_NUL ? FASTA_BAD_NUL : kind == UVAIA_GPU_FASTA_TEXT ? FASTA_BAD_TEXT : kind == UVAIA_GPU_FASTA_EMPTY ? FASTA_BAD_EMPTY : FASTA_BAD_NONE;
+  snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta));
+  return -1;
+}
+
+static int
+align_parse_records (void *user, char *text, size_t consumed, int n_records, char *err, size_t errlen)
+{
+  struct align_parse *d = (struct align_parse *) user;
+  const size_t aln_length = d->aln_length;
+  const double ambig = d->ambig;
+  const int before = d->count;
+  if (uvaia_gpu_fasta_records (d->fasta, d->rec) || uvaia_gpu_fasta_acgt (d->fasta, d->acgt)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+  int n_sel = 0;
+  for (int k = 0; k < n_records; k++) {               /* the filters of main's fill loop, on the counts the device made */
+    const uvaia_gpu_fasta_record *r = d->rec + k;
+    char *name = text + r->name_off;
+    name[r->name_len] = '\0';                         /* the line end behind the name, or the byte of room behind the block */
+    const size_t seqlength = r->seq_len;
+    d->count++;
+    if (((3 * seqlength) < (2 * aln_length)) || ((2 * seqlength) > (3 * aln_length))) {
+      fprintf (stderr, "Sequence %s has size too different from reference (%lu vs %lu)\n", name, (unsigned long) seqlength, (unsigned long) aln_length);
+      continue;
+    }
+    const double l = seqlength ? (double) seqlength : 1.;          /* biomcmc_count_sequence_acgt: [0] and [2] */
+    const double frac_acgt = (double) d->acgt[k] / l, frac_bad = (double) ((size_t) r->seq_len - (size_t) r->non_n) / l;
+    if (frac_bad > ambig) {
+      fprintf (stderr, "Sequence %s has proportion of N etc. (=%lf) above threshold of %lf\n", name, frac_bad, ambig);
+      continue;
+    }
+    if (frac_acgt < 1. - 1.1 * ambig) {
+      fprintf (stderr, "Sequence %s has proportion of ACGT (=%lf) below threshold of %lf\n", name, frac_acgt, 1. - 1.1 * ambig);
+      continue;
+    }
+    d->sel[n_sel++] = k;
+  }
+  for (int a = 0; a < n_sel; a += d->pool) {
+    const int fill = n_sel - a < d->pool ? n_sel - a : d->pool;
+    const void *d_bytes = NULL;
+    double ms = 0.;
+    d->n_pool++;
+    for (int c = 0; c < fill; c++) d->name[c] = text + d->rec[d->sel[a + c]].name_off;
+    if (uvaia_gpu_fasta_sequences (d->fasta, d->sel + a, fill, &d_bytes, d->offsets)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+    if (uvaia_align_load_device (d->al, d_bytes, d->offsets, fill) || uvaia_align_run (d->al) || (d->write_text && uvaia_align_fetch (d->al, d->aln, NULL))) {
+      snprintf (err, errlen, "%s (counted from sequence %s, the first of a pool of %d; %d sequences were written before)", uvaia_align_last_error (d->al), d->name[0], fill, d->n_output);
+      return -1;
+    }
+    if (!uvaia_align_stats (d->al, NULL, NULL, NULL, &ms)) d->align_ms += ms;
+    if (d->pk && packer_add_pool (d->pk, d->al, d->name, fill)) {
+      snprintf (err, errlen, "packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", d->n_pool, fill, d->name[0], d->pk->err, d->pk->kept);
+      return -1;
+    }
+    for (int c = 0; c < fill; c++) {
+      d->n_output++;
+      if (!d->write_text) continue;
+      const char *row = d->aln + (size_t) c * (aln_length + 1);
+      if (d->to_screen) printf (">%s\n%s\n", d->name[c], row);
+      else write_fasta_record (d->outstream, d->name[c], row);
+    }
+  }
+  if (d->count / 5000 > before / 5000) {
+    fprintf (stderr, "%d\t sequences read, %d \t aligned. %.3lf secs elapsed.\n", d->count, d->n_output, biomcmc_update_elapsed_time (d->time1));
+    fflush (stderr);
+  }
+  return 0;
+}
+
+/* all files through the route above; whatever ends it, what was aligned so far is closed as a complete file before the command gives up */
+static void
+align_device_parse (struct align_parse *d, const char **fasta, int n_fasta, size_t block_bytes, int device)
+{
+  char msg[1024], failed[1024];
+  const int max_records = block_bytes / 4 + 1 < PARSE_MAX_RECORDS ? (int) (block_bytes / 4 + 1) : PARSE_MAX_RECORDS;      /* (a record has four bytes at least) */
+  if (uvaia_gpu_fasta_open (&d->fasta, device, block_bytes, max_records)) biomcmc_error ("%s", uvaia_gpu_fasta_last_error (NULL));
+  d->rec = (uvaia_gpu_fasta_record *) biomcmc_malloc ((size_t) max_records * sizeof (uvaia_gpu_fasta_record));
+  d->acgt = (int *) biomcmc_malloc ((size_t) max_records * sizeof (int));
+  d->sel = (int *) biomcmc_malloc ((size_t) max_records * sizeof (int));
+  d->offsets = (int64_t *) biomcmc_malloc (((size_t) d->pool + 1) * sizeof (int64_t));
+  uint64_t bytes = 0;
+  for (int j = 0; j < n_fasta; j++) {
+    uint64_t nb = 0;
+    fprintf (stderr, "Started  reading file %s\n", fasta[j]);
+    fasta_blocks fb = fasta_blocks_open (fasta[j], block_bytes, uvaia_gpu_fasta_pinned_alloc, uvaia_gpu_fasta_pinned_free, msg, sizeof msg);
+    const int rc = fb ? fasta_blocks_run (fb, max_records, align_parse_scan, d, align_parse_records, d, &nb, msg, sizeof msg) : -1;
+    const int broken = fasta_blocks_finish (fb, failed, sizeof failed);      /* a decompressor that failed mid-stream: that is the finding, not what its cut end looked like */
+    if (rc || broken) {
+      if (d->outstream) biomcmc_close_compress (d->outstream);
+      if (d->pk) uvdb_packer_close (d->pk);
+      if (broken) biomcmc_error ("%s", failed);
+      const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
+      biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaialign` without it reads this file line by line)" : "");
+    }
+    bytes += nb;
+    fprintf (stderr, "Finished reading file %s. In total %d sequences have been read.\n", fasta[j], d->count);
+    fflush (stderr);
+  }
+  double ms[2] = {0., 0.}, ms_seq[2] = {0., 0.};
+  uvaia_gpu_fasta_kernel_ms (d->fasta, ms, 0);
+  uvaia_gpu_fasta_sequences_ms (d->fasta, ms_seq, 0);
+  fprintf (stderr, "device parse: {\"bytes\": %llu, \"block_bytes\": %zu, \"scan_ms\": %.3f, \"count_ms\": %.3f, \"sequences_ms\": %.3f, \"align_ms\": %.3f}\n", (unsigned long long) bytes, block_bytes, ms[0], ms_seq[0],
+           ms_seq[1], d->align_ms);
+  uvaia_gpu_fasta_close (d->fasta);
+  free (d->rec); free (d->acgt); free (d->sel); free (d->offsets);
+}
+
 int
 main (int argc, char **argv)
 {
-  int help = 0, version = 0, to_screen = 0, pool = 256 * omp_get_max_threads (), device = 0, errors = 0, n_fasta = 0, compact = 0, ch;   /* src/align.c:59-63 */
+  int help = 0, version = 0, to_screen = 0, pool = 256 * omp_get_max_threads (), device = 0, errors = 0, n_fasta = 0, compact = 0, device_parse = 0, ch;   /* src/align.c:59-63 */
+  size_t parse_block = FASTA_BLOCK_BYTES;
   int devices[64], n_devices = 0;
   double ambig = 0.5, ambig_r = 0.5;
   const char *out = NULL, *ref_file = NULL, *packed = NULL;
@@ -42,7 +180,8 @@ main (int argc, char **argv)
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"stdout", no_argument, 0, 1000}, {"ambiguity", required_argument, 0, 'a'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002},
-    {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"compact", no_argument, 0, 1004}, {0, 0, 0, 0}};
+    {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"compact", no_argument, 0, 1004},
+    {"device-parse", no_argument, 0, 1005}, {"parse-block", required_argument, 0, 1006}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -56,6 +195,8 @@ main (int argc, char **argv)
     case 1002: n_devices = uvaia_parse_device_list (optarg, devices, 64); if (!n_devices) { fprintf (stderr, "--devices: expected a list such as 0-7 or 0,2,3\n"); exit (EXIT_FAILURE); } break;
     case 1003: packed = optarg; break;
     case 1004: compact = 1; break;
+    case 1005: device_parse = 1; break;
+    case 1006: parse_block = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the block size of --device-parse in bytes) */
     case 'A': ambig_r = atof (optarg); break;
     default: errors++;
   }
@@ -68,7 +209,7 @@ main (int argc, char **argv)
   }
   if (help || errors || !ref_file || n_fasta < 1 || pool < 1) {
     printf ("%s \nAlign query sequences against a reference\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] [--device-parse] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  --stdout                         print alignment to stdout (to redirect/pipe) instead of compress to file; much faster but may generate a big output\n");
     printf ("  -p, --pool=<int>                 How many query sequences are read in batch, to be aligned in parallel (defaults to 256 per thread)\n");
@@ -84,6 +225,11 @@ main (int argc, char **argv)
     printf ("  --compact                        with --packed: write the compact form of the database, the file `uvaiapack --compact` makes of the text output\n");
     printf ("                                   (several times smaller; encoded on the GPU once its base row is fixed, after 4096 sequences)\n");
     printf ("  -A, --ref_ambiguity=<double>     with --packed: maximum allowed ambiguity for an ALIGNED sequence to be kept in the database (default=0.5), as in `uvaiapack`\n");
+    printf ("  --device-parse                   split the text into sequences on the GPU instead of reading it line by line, and hand them to the aligner where\n");
+    printf ("                                   they lie: the same output, from regular FASTA only (a NUL byte, text before the first header and a header\n");
+    printf ("                                   without sequence are refused).  One GPU only; goes with -o, --stdout, --packed and --compact\n");
+    printf ("  --parse-block=<bytes>            with --device-parse: the text is read in blocks of this size (64 to 1073741824, default 67108864); a record\n");
+    printf ("                                   must fit one\n");
     if (help) {
       printf ("Based on the wavefront algorithm (WFA, https://github.com/smarco/WFA), computed on the GPU.\n");
       printf ("Since the sequences are assumed to be similar, sequences too short or too big w.r.t. the reference are rejected.\n\n");
@@ -101,6 +247,12 @@ main (int argc, char **argv)
     fprintf (stderr, "--packed writes the database from the rows on ONE GPU: give --device, or a --devices list of one device (%d were listed)\n", n_devices);
     return EXIT_FAILURE;
   }
+  if (device_parse && n_devices > 1) {   /* the parser's buffer, which the aligner loads its pool from, lies on one card */
+    fprintf (stderr, "--device-parse hands the sequences to the aligner in the memory of ONE GPU: give --device, or a --devices list of one device (%d were listed)\n", n_devices);
+    return EXIT_FAILURE;
+  }
+  if (device_parse && (parse_block < 64 || parse_block > ((size_t) 1 << 30))) { fprintf (stderr, "--parse-block: expected 64 to 1073741824 bytes\n"); return EXIT_FAILURE; }
+  if (!device_parse && parse_block != FASTA_BLOCK_BYTES) { fprintf (stderr, "--parse-block sets the block size of --device-parse: it needs that option\n"); return EXIT_FAILURE; }
   const bool write_text = !packed || out || to_screen;
   int64_t time0[2], time1[2];
   biomcmc_get_time (time0);
@@ -147,7 +299,14 @@ main (int argc, char **argv)
   double result[3];
 
   biomcmc_get_time (time1);
-  for (int j = 0; j < n_fasta; j++) {
+  if (device_parse) {
+    struct align_parse d;
+    memset (&d, 0, sizeof d);
+    d.al = gpu[0]; d.pk = packed ? &pk : NULL; d.outstream = outstream; d.to_screen = to_screen; d.write_text = write_text;
+    d.aln_length = aln_length; d.ambig = ambig; d.pool = pool; d.name = name; d.aln = aln; d.time1 = time1;
+    align_device_parse (&d, fasta, n_fasta, parse_block, devices[0]);
+    count = d.count; n_output = d.n_output; align_ms = d.align_ms;
+  } else for (int j = 0; j < n_fasta; j++) {
     fprintf (stderr, "Started  reading file %s\n", fasta[j]);
     rfas = new_readfasta (fasta[j]);
     bool end_of_file = false;

@@ -86,6 +86,17 @@ fasta_clean_host (const char *text, const uvaia_gpu_fasta_record *rec, char *out
 }
 
 int
+fasta_count_acgt_host (const char *text, const uvaia_gpu_fasta_record *rec)
+{
+  int acgt = 0;
+  for (size_t i = rec->body_off; i < (size_t) rec->body_off + rec->body_len; i++) {
+    const unsigned char up = (unsigned char) text[i] & 0xDF;
+    acgt += (up == 'A') | (up == 'C') | (up == 'G') | (up == 'T');
+  }
+  return acgt;
+}
+
+int
 fasta_scan_host_step (void *user, const char *text, size_t n, int final, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off, char *err, size_t errlen)
 {
   struct fasta_host_scan *h = (struct fasta_host_scan *) user;

@@ -31,6 +31,9 @@ enum { FASTA_BAD_NONE = 0, FASTA_BAD_NUL = 1, FASTA_BAD_TEXT = 2, FASTA_BAD_EMPT
 int fasta_scan_host (const char *text, size_t n, int final, int max_records, uvaia_gpu_fasta_record *rec, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off);
 /* the cleaned sequence of a record (white space dropped, a-z upper-cased) into out[0 .. rec->seq_len); returns the bytes written */
 size_t fasta_clean_host (const char *text, const uvaia_gpu_fasta_record *rec, char *out);
+/* the body bytes of a record that are one of A C G T a c g t: uvaia_gpu_fasta_acgt in plain C, the first counter of
+ * biomcmc_count_sequence_acgt on the cleaned sequence (the second is seq_len - non_n of the record) */
+int fasta_count_acgt_host (const char *text, const uvaia_gpu_fasta_record *rec);
 
 /* the scan step: 0 with *n_records and *consumed; or -1, for irregular text with its kind (FASTA_BAD_*) and its offset within text, for
  * anything else with *bad_kind left FASTA_BAD_NONE and a message */

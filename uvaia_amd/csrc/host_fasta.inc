@@ -10,15 +10,23 @@ struct uvaia_gpu_fasta {
   DevBuf<int4> d_sum;                    // per chunk: summary, then carry
   DevBuf<int> d_hdr;                     // first '>' of max_records + 1 header lines, the starts of those lines, the count of all
   DevBuf<FastaRec> d_rec;                // max_records records and the text before the first header line
-  DevBuf<int2> d_body;                   // per row of pass 2: offset and length of its body
+  DevBuf<int2> d_body;                   // per row of pass 2 / per selected sequence: offset and length of its body
+  DevBuf<int> d_acgt;                    // per record: its A C G T sites
+  DevBuf<long long> d_seqoff;            // per selected sequence, and one more: where it begins in d_seq
+  DevBuf<uint8_t> d_seq;                 // the selected sequences back to back, FASTA_SEQ_GUARD guard bytes behind them
+  std::vector<long long> seqoff;
+  std::vector<uint8_t> chosen;           // per record: is it in the selection being checked
   std::vector<uvaia_gpu_fasta_record> rec;
   std::vector<int2> body;
-  Event ev[6];
+  Event ev[6], ev_seq[4];
   int n_rec = 0, n_bytes = 0, mis = 0, n_rows = 0;   // of the last scan / rows call
   size_t pitch = 0, bad_off = 0;         // what the last scan refused
   unsigned bad_kind = 0;
-  double ms[2] = {0., 0.};
+  double ms[2] = {0., 0.}, ms_seq[2] = {0., 0.};
+  long long seq_bytes = -1;              // of the last fasta_sequences since the last scan; -1: there was none
 };
+
+constexpr size_t FASTA_SEQ_GUARD = 64;   // bytes behind the sequences that fasta_sequences sets to 0xEE and its kernel leaves alone
 
 static_assert(sizeof(FastaRec) == sizeof(uvaia_gpu_fasta_record) && sizeof(FastaRec) == 32, "the record table is a fixed layout");
 
@@ -39,6 +47,7 @@ int fasta_open_body(uvaia_gpu_fasta *f)
   HIPCHK(f, hipSetDevice(f->device));
   HIPCHK(f, hipStreamCreateWithFlags(&f->st.s, hipStreamNonBlocking));
   for (Event &e : f->ev) if (int rc = e.make(f)) return rc;
+  for (Event &e : f->ev_seq) if (int rc = e.make(f)) return rc;
   const size_t cap = (size_t)f->max_records + 1;
   if (int rc = f->d_text.reserve(f, f->block_bytes + 48)) return rc;
   if (int rc = f->d_sum.reserve(f, (f->block_bytes + 16) / FASTA_CHUNK + 2)) return rc;
@@ -84,7 +93,7 @@ int uvaia_gpu_fasta_scan(uvaia_gpu_fasta *f, const void *text, size_t n_bytes, i
   if (!f) return UVAIA_GPU_EINVAL;
   if (!n_records || !consumed || (n_bytes && !text)) return fasta_fail(f, UVAIA_GPU_EINVAL, "bad scan arguments");
   *n_records = 0; *consumed = 0;
-  f->n_rec = 0; f->n_rows = 0; f->n_bytes = 0; f->rec.clear();
+  f->n_rec = 0; f->n_rows = 0; f->n_bytes = 0; f->rec.clear(); f->seq_bytes = -1;
   f->bad_kind = 0; f->bad_off = 0;
   if (n_bytes > f->block_bytes) return fasta_fail(f, UVAIA_GPU_EINVAL, "%zu bytes of text, the parser was opened for blocks of %zu", n_bytes, f->block_bytes);
   if (n_bytes == 0) return 0;
@@ -189,6 +198,82 @@ int uvaia_gpu_fasta_rows_host(uvaia_gpu_fasta *f, void *out)
   HIPCHK(f, hipSetDevice(f->device));
   HIPCHK(f, hipMemcpy(out, f->d_rows.p, (size_t)f->n_rows * f->pitch, hipMemcpyDeviceToHost));
   return 0;
+}
+
+int uvaia_gpu_fasta_acgt(uvaia_gpu_fasta *f, int *acgt)
+{
+  if (!f) return UVAIA_GPU_EINVAL;
+  if (f->n_rec && !acgt) return fasta_fail(f, UVAIA_GPU_EINVAL, "NULL counts");
+  if (!f->n_rec) return 0;
+  HIPCHK(f, hipSetDevice(f->device));
+  if (int rc = f->d_acgt.reserve(f, (size_t)f->max_records)) return rc;
+  HIPCHK(f, hipEventRecord(f->ev_seq[0], f->st));
+  hipLaunchKernelGGL(fasta_acgt_kernel, dim3((unsigned)((f->n_rec + FASTA_TPB / 64 - 1) / (FASTA_TPB / 64))), dim3(FASTA_TPB), 0, f->st, reinterpret_cast<const uint4 *>(f->d_text.p + 16), f->mis, f->n_bytes, f->n_rec,
+                     (const FastaRec *)f->d_rec.p, f->d_acgt.p);
+  HIPCHK(f, hipGetLastError());
+  HIPCHK(f, hipEventRecord(f->ev_seq[1], f->st));
+  HIPCHK(f, hipMemcpyAsync(acgt, f->d_acgt.p, (size_t)f->n_rec * sizeof(int), hipMemcpyDeviceToHost, f->st));
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  float ms = 0; HIPCHK(f, hipEventElapsedTime(&ms, f->ev_seq[0], f->ev_seq[1])); f->ms_seq[0] += ms;
+  return 0;
+}
+
+int uvaia_gpu_fasta_sequences(uvaia_gpu_fasta *f, const int *record, int n_sel, const void **d_bytes, int64_t *offsets)
+{
+  if (!f) return UVAIA_GPU_EINVAL;
+  if (n_sel < 0 || !d_bytes || !offsets) return fasta_fail(f, UVAIA_GPU_EINVAL, "bad sequences arguments");
+  *d_bytes = nullptr; offsets[0] = 0;
+  f->seq_bytes = -1;
+  // the selection: inside the last scan, no record twice (two blocks would write one range, and the offsets would not be a partition)
+  if (n_sel > f->n_rec) return fasta_fail(f, UVAIA_GPU_EINVAL, "%d sequences asked for, the last scan returned %d records", n_sel, f->n_rec);
+  f->chosen.assign((size_t)f->n_rec, 0);
+  f->body.clear(); f->seqoff.assign(1, 0);
+  for (int k = 0; k < n_sel; k++) {
+    const int r = record ? record[k] : k;
+    if (r < 0 || r >= f->n_rec) return fasta_fail(f, UVAIA_GPU_EINVAL, "record[%d] = %d: the last scan returned %d records", k, r, f->n_rec);
+    if (f->chosen[(size_t)r]) return fasta_fail(f, UVAIA_GPU_EINVAL, "record[%d] = %d is in the selection twice", k, r);
+    f->chosen[(size_t)r] = 1;
+    f->body.push_back(make_int2((int)f->rec[(size_t)r].body_off, (int)f->rec[(size_t)r].body_len));
+    f->seqoff.push_back(f->seqoff.back() + (long long)f->rec[(size_t)r].seq_len);
+  }
+  const long long total = f->seqoff.back();
+  for (int k = 0; k <= n_sel; k++) offsets[k] = (int64_t)f->seqoff[(size_t)k];
+  HIPCHK(f, hipSetDevice(f->device));
+  if (int rc = f->d_seq.reserve(f, ((size_t)total + FASTA_SEQ_GUARD + 15) & ~(size_t)15)) return rc;
+  HIPCHK(f, hipMemsetAsync(f->d_seq.p + total, 0xEE, FASTA_SEQ_GUARD, f->st));
+  if (n_sel) {
+    if (int rc = f->d_body.reserve(f, (size_t)n_sel)) return rc;
+    if (int rc = f->d_seqoff.reserve(f, (size_t)n_sel + 1)) return rc;
+    HIPCHK(f, hipMemcpyAsync(f->d_body.p, f->body.data(), (size_t)n_sel * sizeof(int2), hipMemcpyHostToDevice, f->st));
+    HIPCHK(f, hipMemcpyAsync(f->d_seqoff.p, f->seqoff.data(), ((size_t)n_sel + 1) * sizeof(long long), hipMemcpyHostToDevice, f->st));
+    HIPCHK(f, hipEventRecord(f->ev_seq[2], f->st));
+    hipLaunchKernelGGL(fasta_sequences_kernel, dim3((unsigned)n_sel), dim3(FASTA_TPB), 0, f->st, reinterpret_cast<const uint4 *>(f->d_text.p + 16), f->mis, f->n_bytes, (const int2 *)f->d_body.p,
+                       (const long long *)f->d_seqoff.p, total, f->d_seq.p);
+    HIPCHK(f, hipGetLastError());
+    HIPCHK(f, hipEventRecord(f->ev_seq[3], f->st));
+  }
+  HIPCHK(f, hipStreamSynchronize(f->st));
+  if (n_sel) { float ms = 0; HIPCHK(f, hipEventElapsedTime(&ms, f->ev_seq[2], f->ev_seq[3])); f->ms_seq[1] += ms; }
+  f->seq_bytes = total;
+  *d_bytes = f->d_seq.p;
+  return 0;
+}
+
+int uvaia_gpu_fasta_sequences_host(uvaia_gpu_fasta *f, void *out, size_t n_bytes)
+{
+  if (!f) return UVAIA_GPU_EINVAL;
+  if (f->seq_bytes < 0) return fasta_fail(f, UVAIA_GPU_EINVAL, "no sequences were made since the last scan");
+  if (!out || n_bytes != (size_t)f->seq_bytes + FASTA_SEQ_GUARD) return fasta_fail(f, UVAIA_GPU_EINVAL, "the sequences and their guard are %zu bytes (%zu given)", (size_t)f->seq_bytes + FASTA_SEQ_GUARD, n_bytes);
+  HIPCHK(f, hipSetDevice(f->device));
+  HIPCHK(f, hipMemcpy(out, f->d_seq.p, n_bytes, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+void uvaia_gpu_fasta_sequences_ms(uvaia_gpu_fasta *f, double out[2], int reset)
+{
+  if (!f) return;
+  if (out) { out[0] = f->ms_seq[0]; out[1] = f->ms_seq[1]; }
+  if (reset) f->ms_seq[0] = f->ms_seq[1] = 0.;
 }
 
 void uvaia_gpu_fasta_kernel_ms(uvaia_gpu_fasta *f, double out[2], int reset)

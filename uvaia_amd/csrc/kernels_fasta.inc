@@ -346,4 +346,95 @@ __global__ __launch_bounds__(FASTA_TPB) void fasta_rows_kernel(const uint4 *base
   }
 }
 
+// acgt[k] = the body bytes of record k that are one of A C G T a c g t (the first counter of biomcmc_count_sequence_acgt,
+// biomcmc_lite.c:378-392); one wave per record, over the body the record table names.
+__global__ __launch_bounds__(FASTA_TPB) void fasta_acgt_kernel(const uint4 *base, int mis, int n, int n_rec, const FastaRec *rec, int *acgt)
+{
+  const int lane = threadIdx.x & 63;
+  const long long w = (long long)blockIdx.x * (FASTA_TPB / 64) + (threadIdx.x >> 6);
+  if (w >= n_rec) return;
+  const FastaRec r = rec[w];
+  const int lo = (int)min((unsigned long long)r.body_off, (unsigned long long)n), hi = (int)min((unsigned long long)lo + r.body_len, (unsigned long long)n);
+  int count = 0;
+  for (long long pc = ((long long)lo + mis) / 16; pc * 16 - mis < hi; pc += 64) {
+    const int p0 = (int)((pc + lane) * 16 - mis);
+    const uint4 v = fasta_load(base, pc + lane, p0, hi);
+    const int a = min(max(lo - p0, 0), 16), b = min(max(hi - p0, 0), 16);
+    const uint32_t valid = b > a ? ((1u << b) - 1u) & ~((1u << a) - 1u) : 0u;
+    uint32_t is = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const uint32_t up = fasta_byte(v, j) & 0xDFu;
+      is |= (uint32_t)((up == 'A') | (up == 'C') | (up == 'G') | (up == 'T')) << j;
+    }
+    count += __popc(is & valid);
+  }
+  count = fasta_wave_sum(count);
+  if (lane == 0) acgt[w] = count;
+}
+
+// Sequence k = the cleaned text of body[k] = (offset, length) in the block, at out[dst[k] .. dst[k + 1]): any byte offset, any length, the
+// sequences back to back.  As fasta_rows_kernel, one block per sequence and the kept bytes compacted through LDS; the stage is seeded with
+// dst[k] & 15 phantom bytes, so that stage position s is the byte out[(dst[k] & ~15) + s] and whole pieces leave as aligned 16-byte stores.
+// The piece the sequence begins in and the one it ends in may belong to its neighbours as well, whose blocks run at the same time: of
+// those only the bytes in [dst[k], dst[k + 1]) are stored, one by one.  total = bytes of out that sequences may take: nothing is stored
+// at or past it.
+__global__ __launch_bounds__(FASTA_TPB) void fasta_sequences_kernel(const uint4 *base, int mis, int n, const int2 *body, const long long *dst, long long total, uint8_t *out)
+{
+  __shared__ __attribute__((aligned(16))) unsigned char stage[FASTA_CHUNK + 32];
+  __shared__ int sh[FASTA_TPB / 64];
+  const int2 bd = body[blockIdx.x];
+  const int lo = min(max(bd.x, 0), n), hi = (int)min((long long)lo + max(bd.y, 0), (long long)n);
+  const long long d0 = min(max(dst[blockIdx.x], 0ll), total), d1 = min(max(dst[blockIdx.x + 1], d0), total);
+  const int phantom = (int)(d0 & 15);
+  const int last = phantom + (int)min(d1 - d0, (long long)0x40000000);     // stage positions [phantom, last) are the sequence
+  uint8_t *line = out + (d0 - phantom);                                    // 16-byte aligned: out is
+  int carry = phantom, flushed = 0;                                        // bytes waiting at the front of stage; stage positions already stored
+  for (long long pc = ((long long)lo + mis) / 16; pc * 16 - mis < hi; pc += FASTA_TPB) {
+    const int p0 = (int)((pc + threadIdx.x) * 16 - mis);
+    const uint4 v = fasta_load(base, pc + threadIdx.x, p0, hi);
+    const FastaMasks m = fasta_classify(v, p0, lo, hi);
+    const uint32_t keep = m.valid & ~m.ws;
+    int total_kept;
+    int at = carry + fasta_block_sum_scan(__popc(keep), sh, total_kept);
+    const int room = last - flushed;                        // stage positions from `room` on would lie past the sequence
+    if (keep == 0xFFFFu && !(at & 3) && at + 16 <= room) {  // nothing dropped and a word-aligned place: four words (upper-cased as in fasta_rows_kernel)
+      uint32_t *d = reinterpret_cast<uint32_t *>(stage + at);
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const uint32_t x = u4c(v, q);
+        const uint32_t l = x & 0x7F7F7F7Fu, ge = l + 0x1F1F1F1Fu, gt = l + 0x05050505u;
+        const uint32_t is = ge & ~gt & ~x & 0x80808080u;
+        d[q] = x ^ (is >> 2);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        if ((keep >> j) & 1u) {
+          uint32_t c = fasta_byte(v, j);
+          c -= ((c - 'a') < 26u) ? 32u : 0u;
+          if (at < room) stage[at] = (unsigned char)c;
+          at++;
+        }
+      }
+    }
+    __syncthreads();
+    const int avail = max(min(carry + total_kept, room), 0), nfull = avail / 16, rest = avail - nfull * 16;
+    for (int i = threadIdx.x; i < nfull; i += FASTA_TPB) {
+      const int s = flushed + i * 16;                       // (s + 16 <= last: the piece ends inside the sequence)
+      if (s >= phantom) *reinterpret_cast<uint4 *>(line + s) = *reinterpret_cast<const uint4 *>(stage + (size_t)i * 16);
+      else for (int j = phantom; j < 16; j++) line[j] = stage[j];     // the piece the sequence begins in (s = 0)
+    }
+    unsigned char keepb = 0;
+    if ((int)threadIdx.x < rest) keepb = stage[nfull * 16 + threadIdx.x];
+    __syncthreads();
+    if ((int)threadIdx.x < rest) stage[threadIdx.x] = keepb;
+    flushed += nfull * 16; carry = rest;
+    __syncthreads();
+  }
+  // the piece the sequence ends in (and begins in, if it is that short)
+  const int s = flushed + (int)threadIdx.x;
+  if ((int)threadIdx.x < carry && s >= phantom && s < last) line[s] = stage[threadIdx.x];
+}
+
 }  // namespace

@@ -738,20 +738,16 @@ int uvaia_align_open(uvaia_aligner **out, const char *ref, int ref_len, int devi
   return 0;
 }
 
-int uvaia_align_load_block(uvaia_aligner *a, const char *bytes, const int64_t *offsets, int n)
+// A pool of n >= 1 queries whose bytes lie at bytes + offsets[0], in host memory or (kind = hipMemcpyDeviceToDevice) in the memory of the
+// aligner's device: one copy into d_seqs, the offsets, and the order the queries are started in.  Returns when all of it is done.
+static int load_pool(uvaia_aligner *a, const char *bytes, const int64_t *offsets, int n, hipMemcpyKind kind)
 {
-  if (!a) return UVAIA_ALIGN_EINVAL;
-  if (n < 0 || (n > 0 && (!bytes || !offsets))) return afail(a, UVAIA_ALIGN_EINVAL, "bad pool");
-  HIPCHK(a, hipSetDevice(a->device));
-  a->n = 0; a->ran = false;
-  if (n == 0) return 0;
-  for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return afail(a, UVAIA_ALIGN_EINVAL, "bad length of sequence %d", i);
   const size_t total = (size_t)(offsets[n] - offsets[0]);
   int rc = ensure_pool(a, total, n); if (rc) return rc;
   a->h_off.resize((size_t)n + 1);
   for (int i = 0; i <= n; i++) a->h_off[(size_t)i] = (long long)(offsets[i] - offsets[0]);
   HIPCHK(a, hipStreamSynchronize(a->stream));
-  if (total) HIPCHK(a, hipMemcpyAsync(a->d_seqs, bytes + offsets[0], total, hipMemcpyHostToDevice, a->stream));
+  if (total) HIPCHK(a, hipMemcpyAsync(a->d_seqs, bytes + offsets[0], total, kind, a->stream));
   HIPCHK(a, hipMemcpyAsync(a->d_off, a->h_off.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, a->stream));
   {   // the order the queries are started in (d_status is free until the run: it takes the estimates)
     hipLaunchKernelGGL(expected_cost_kernel, dim3((unsigned)n), dim3(256), 0, a->stream, a->d_seqs, a->d_off, a->plen, n, a->d_status);
@@ -770,6 +766,44 @@ int uvaia_align_load_block(uvaia_aligner *a, const char *bytes, const int64_t *o
   HIPCHK(a, hipStreamSynchronize(a->stream));
   a->n = n;
   return 0;
+}
+
+// what load_block and load_device refuse alike; 1 = an empty pool, nothing more to do
+static int load_begin(uvaia_aligner *a, const void *bytes, const int64_t *offsets, int n)
+{
+  if (n < 0 || (n > 0 && (!bytes || !offsets))) return afail(a, UVAIA_ALIGN_EINVAL, "bad pool");
+  HIPCHK(a, hipSetDevice(a->device));
+  a->n = 0; a->ran = false;
+  if (n == 0) return 1;
+  for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return afail(a, UVAIA_ALIGN_EINVAL, "bad length of sequence %d", i);
+  return 0;
+}
+
+int uvaia_align_load_block(uvaia_aligner *a, const char *bytes, const int64_t *offsets, int n)
+{
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  if (int rc = load_begin(a, bytes, offsets, n)) return rc > 0 ? 0 : rc;
+  return load_pool(a, bytes, offsets, n, hipMemcpyHostToDevice);
+}
+
+int uvaia_align_load_device(uvaia_aligner *a, const void *d_bytes, const int64_t *offsets, int n)
+{
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  if (int rc = load_begin(a, d_bytes, offsets, n)) return rc > 0 ? 0 : rc;
+  // the bytes must be device memory of the aligner's device (asked of the runtime: the pointer is not dereferenced before) and
+  // [offsets[0], offsets[n]) must lie inside its allocation
+  if (offsets[0] < 0) return afail(a, UVAIA_ALIGN_EINVAL, "offsets[0] = %lld is negative", (long long)offsets[0]);
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, d_bytes) != hipSuccess) { (void)hipGetLastError(); return afail(a, UVAIA_ALIGN_EINVAL, "the sequences are not in device memory"); }
+  if (at.type != hipMemoryTypeDevice || at.device != a->device)
+    return afail(a, UVAIA_ALIGN_EINVAL, "the sequences must be in the memory of device %d (memory type %d, device %d)", a->device, (int)at.type, at.device);
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(d_bytes)) != hipSuccess) { (void)hipGetLastError(); return afail(a, UVAIA_ALIGN_EINVAL, "the sequences are not inside a device allocation"); }
+  const size_t off = (size_t)(reinterpret_cast<const char *>(d_bytes) - reinterpret_cast<const char *>(base));
+  if (off > size || (size_t)offsets[n] > size - off)
+    return afail(a, UVAIA_ALIGN_EINVAL, "the sequences end beyond the device allocation they lie in (%lld bytes, %zu from its start, %zu in all)", (long long)offsets[n], off, size);
+  return load_pool(a, static_cast<const char *>(d_bytes), offsets, n, hipMemcpyDeviceToDevice);
 }
 
 int uvaia_align_load(uvaia_aligner *a, const char *const *seq, const int *seq_len, int n)
