@@ -84,6 +84,17 @@ int  uvaia_clust_push (uvaia_clust_ctx *c, int n, const char *const *seq, const 
  * record fails the call with UVAIA_GPU_EINVAL before anything is copied: nothing is pushed and the context stays usable. */
 int  uvaia_clust_push_packed (uvaia_clust_ctx *c, int n, const void *planes, const uint64_t *exc_offsets, const void *exc, const int *queue);
 
+/* The same for n sequences whose text is already in the memory of the context's device (what the FASTA parser leaves behind,
+ * uvaia_gpu_fasta_rows of include/uvaia_gpu.h; a tensor of the caller): replaces, for such rows, the host copy of uvaia_clust_push -- every
+ * row into a padded host block and over the bus.  Sequence i of the push is row row_index[i] of the block (NULL: row i), the nchar bytes at
+ * d_rows + row * pitch.  The block has the contract of uvaia_gpu_db_append_device: any pitch >= nchar, any alignment, and the pointer is
+ * checked the same way before anything reads it.  Push ordinals, queues, the byte check (UVAIA_GPU_EALPHABET by push ordinal, the context
+ * unusable afterwards) and keep-medoids staging are those of uvaia_clust_push; the three kinds of push may be mixed in one context and the
+ * result does not depend on how the sequences are cut into pushes.  A host pointer, another device's memory, a block that ends beyond its
+ * allocation, a negative row or a pitch below nchar fails the call with UVAIA_GPU_EINVAL before anything is launched: nothing is pushed and
+ * the context stays usable.  Returns when the rows have been read and placed. */
+int  uvaia_clust_push_device (uvaia_clust_ctx *c, int n, const void *d_rows, size_t pitch, const int *row_index, const int *queue);
+
 /* The upper-case text of pushed sequences, before or after finish: row k of `rows` (pitch >= nchar bytes apart, nchar bytes written, no
  * NUL) = the sequence with push ordinal ordinal[k]; any order, repeats allowed.  Gathered on the device, one copy back per call: the caller
  * bounds its memory by the n of a call (the medoids of <prefix>.aln.xz are fetched in batches).
@@ -125,6 +136,9 @@ int  uvaia_clust_stats (uvaia_clust_ctx *c, double *prep_ms, double *queue_ms, d
 
 /* Kernel milliseconds of the packed pushes so far: decoding the tiles to rows, writing the exception runs over them. */
 int  uvaia_clust_unpack_ms (uvaia_clust_ctx *c, double *decode_ms, double *overlay_ms);
+
+/* Kernel milliseconds of the device pushes so far: copying the rows out of the caller's block. */
+int  uvaia_clust_push_device_ms (uvaia_clust_ctx *c, double *rows_in_ms);
 
 #ifdef __cplusplus
 }

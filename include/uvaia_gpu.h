@@ -484,6 +484,29 @@ void uvaia_gpu_rows_kernel_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 /* diagnostics: the length exception runs are cut at (0 = the file format's 0xFFFFFF), so that tests reach the cut with short rows */
 int uvaia_gpu_rows_set_run_cut (uvaia_gpu_ctx *ctx, unsigned cut);
 
+/* ---- text row store: the text of rows that came from device memory, kept on the device as text next to the resident database (`uvaia -r
+ * --device-parse`).  Replaces, for such rows, the host copies of the sequences that the dump of src/nearest.c:299-304 writes from: a reference
+ * appended by uvaia_gpu_db_append_device has no text on the host, uvaia_gpu_db_unpack_rows answers only for windows that came through
+ * load_staged / append_staged, and an --acgt context keeps no four-plane image of other rows.  Store rows are nchar rounded up to 16 bytes
+ * apart and 16-byte aligned.  Plain contexts only (no reference shards: UVAIA_GPU_ESTATE).
+ *   text_append_device  rows row_index[0 .. n_sel) of a block in device memory (NULL: rows 0 .. n_sel - 1) are appended to the store in that
+ *                  order.  The block has the contract of uvaia_gpu_db_append_device (any pitch >= nchar, any alignment; the pointer is
+ *                  checked the same way).  The store grows on its own and keeps its content.  Returns when the rows have been read.
+ *   text_size      rows in the store
+ *   text_rows      store rows index[0 .. n) to host memory at rows + k * pitch: any order, repeats allowed, pitch >= nchar; nchar bytes of
+ *                  each row are defined.  Gathered on the device, one copy back per round of a pool of rows.
+ *   text_clear     empties the store, keeps its capacity
+ *   text_reserve   room for n_rows rows in all (the content is kept)
+ *   text_ms        device time in ms since the last reset of [0] the gathers in, [1] the gathers out
+ * Refused with UVAIA_GPU_EINVAL, nothing copied, the store unchanged and the context usable: a host pointer, another device's memory or a
+ * block that ends beyond its allocation; a negative count or row index; an index[k] at or beyond text_size; a pitch below nchar. */
+int uvaia_gpu_text_append_device (uvaia_gpu_ctx *ctx, const void *d_rows, size_t pitch, const int *row_index, int n_sel);
+size_t uvaia_gpu_text_size (const uvaia_gpu_ctx *ctx);
+int uvaia_gpu_text_rows (uvaia_gpu_ctx *ctx, const int *index, int n, char *rows, size_t pitch);
+int uvaia_gpu_text_clear (uvaia_gpu_ctx *ctx);
+int uvaia_gpu_text_reserve (uvaia_gpu_ctx *ctx, size_t n_rows);
+void uvaia_gpu_text_ms (uvaia_gpu_ctx *ctx, double out[2], int reset);
+
 /* ---- FASTA text split into rows on the device (`uvaiapack --device-parse`).  Replaces, for a block of decompressed text, the line loop of
  * readfasta_next (uvaia_amd/csrc/host/seq_query.c:54-80: getline, realloc, the cleaning pass), quick_count_sequence_non_N and the copy of
  * every row into pinned memory: the rows are made where uvaia_gpu_rows_census and uvaia_gpu_db_append_device read them.  The rules of a

@@ -37,6 +37,7 @@ SYMBOLS = [
     "uvaia_gpu_fasta_open", "uvaia_gpu_fasta_close", "uvaia_gpu_fasta_last_error", "uvaia_gpu_fasta_scan", "uvaia_gpu_fasta_bad", "uvaia_gpu_fasta_records", "uvaia_gpu_fasta_rows", "uvaia_gpu_fasta_rows_host",
     "uvaia_gpu_fasta_kernel_ms", "uvaia_gpu_fasta_chunk_bytes", "uvaia_gpu_fasta_pinned_alloc", "uvaia_gpu_fasta_pinned_free",
     "uvaia_gpu_fasta_acgt", "uvaia_gpu_fasta_sequences", "uvaia_gpu_fasta_sequences_host", "uvaia_gpu_fasta_sequences_ms",
+    "uvaia_gpu_text_append_device", "uvaia_gpu_text_size", "uvaia_gpu_text_rows", "uvaia_gpu_text_clear", "uvaia_gpu_text_reserve", "uvaia_gpu_text_ms",
 ]
 
 
@@ -227,6 +228,12 @@ def load_library():
         "uvaia_gpu_fasta_chunk_bytes": (C.c_size_t, []),
         "uvaia_gpu_fasta_pinned_alloc": (vp, [C.c_size_t]),
         "uvaia_gpu_fasta_pinned_free": (None, [vp]),
+        "uvaia_gpu_text_append_device": (C.c_int, [vp, C.c_void_p, C.c_size_t, pi, C.c_int]),
+        "uvaia_gpu_text_size": (C.c_size_t, [vp]),
+        "uvaia_gpu_text_rows": (C.c_int, [vp, pi, C.c_int, C.c_void_p, C.c_size_t]),
+        "uvaia_gpu_text_clear": (C.c_int, [vp]),
+        "uvaia_gpu_text_reserve": (C.c_int, [vp, C.c_size_t]),
+        "uvaia_gpu_text_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -397,6 +404,36 @@ class Engine:
 
     def rows_set_run_cut(self, cut):
         self._chk(self.L.uvaia_gpu_rows_set_run_cut(self.ctx, int(cut)))
+
+    # ---- text row store: the text of rows that came from device memory, kept on the device
+    def text_append_device(self, rows, row_index=None, pitch=None, n=None):
+        """appends rows row_index (None: all n) of a block in device memory to the text row store"""
+        ptr, pitch, n, _keep = self._device_block(rows, pitch, n)
+        _k1, ri = _int_ptr(row_index)
+        self._chk(self.L.uvaia_gpu_text_append_device(self.ctx, ptr, pitch, ri, n if row_index is None else len(row_index)))
+
+    def text_size(self):
+        return int(self.L.uvaia_gpu_text_size(self.ctx))
+
+    def text_rows(self, index, pitch=None, out=None):
+        """uint8 [len(index), pitch] (pitch >= nchar, default nchar): store rows `index`, any order, repeats allowed; out: a C-contiguous
+        uint8 array of at least len(index) * pitch bytes to write into"""
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        pitch = self.nchar if pitch is None else int(pitch)
+        rows = np.zeros((len(idx), pitch), dtype=np.uint8) if out is None else out
+        self._chk(self.L.uvaia_gpu_text_rows(self.ctx, idx.ctypes.data_as(C.POINTER(C.c_int)), len(idx), rows.ctypes.data, pitch))
+        return rows
+
+    def text_clear(self):
+        self._chk(self.L.uvaia_gpu_text_clear(self.ctx))
+
+    def text_reserve(self, n_rows):
+        self._chk(self.L.uvaia_gpu_text_reserve(self.ctx, int(n_rows)))
+
+    def text_ms(self, reset=False):
+        out = (C.c_double * 2)()
+        self.L.uvaia_gpu_text_ms(self.ctx, out, int(reset))
+        return {"in": out[0], "out": out[1]}
 
     def set_active_queries(self, q0, q1):
         self._chk(self.L.uvaia_gpu_set_active_queries(self.ctx, int(q0), int(q1)))

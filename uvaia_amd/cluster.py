@@ -9,7 +9,7 @@ from . import capi
 SYMBOLS = [
     "uvaia_clust_open", "uvaia_clust_close", "uvaia_clust_last_error", "uvaia_clust_push", "uvaia_clust_finish", "uvaia_clust_result",
     "uvaia_clust_stats", "uvaia_clust_push_packed", "uvaia_clust_rows", "uvaia_clust_device_rows", "uvaia_clust_unpack_ms",
-    "uvaia_clust_keep_medoids", "uvaia_clust_gather_device", "uvaia_clust_memory",
+    "uvaia_clust_keep_medoids", "uvaia_clust_gather_device", "uvaia_clust_memory", "uvaia_clust_push_device", "uvaia_clust_push_device_ms",
 ]
 
 
@@ -43,6 +43,8 @@ def _lib():
         L.uvaia_clust_keep_medoids.argtypes = [vp, C.c_int]
         L.uvaia_clust_gather_device.argtypes = [vp, pl, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
         L.uvaia_clust_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.uvaia_clust_push_device.argtypes = [vp, C.c_int, vp, C.c_size_t, pi, pi]
+        L.uvaia_clust_push_device_ms.argtypes = [vp, C.POINTER(C.c_double)]
         _ready = True
     return L
 
@@ -118,6 +120,27 @@ class Clusterer:
         self._chk(self.L.uvaia_clust_push_packed(self.ptr, n, planes.ctypes.data, off.ctypes.data_as(C.POINTER(C.c_uint64)) if off is not None else None,
                                                  rec.ctypes.data if rec is not None and len(rec) else None, q.ctypes.data_as(C.POINTER(C.c_int))))
         self.pushed += n
+
+    def push_device(self, d_rows, pitch, queues, row_index=None):
+        """sequences that are text rows in device memory: row row_index[i] (None: row i) of the block at device address d_rows, `pitch`
+        bytes apart; one queue per pushed sequence"""
+        q = np.ascontiguousarray(queues, dtype=np.int32)
+        n = len(q)
+        ri = None
+        if row_index is not None:
+            ri = np.ascontiguousarray(row_index, dtype=np.int32)
+            if len(ri) != n:
+                raise ValueError("one queue per selected row")
+        if not n:
+            return
+        self._chk(self.L.uvaia_clust_push_device(self.ptr, n, d_rows, int(pitch), ri.ctypes.data_as(C.POINTER(C.c_int)) if ri is not None else None,
+                                                 q.ctypes.data_as(C.POINTER(C.c_int))))
+        self.pushed += n
+
+    def push_device_ms(self):
+        a = C.c_double(0)
+        self._chk(self.L.uvaia_clust_push_device_ms(self.ptr, C.byref(a)))
+        return a.value
 
     def rows(self, ordinals):
         """upper-case text of pushed sequences (push ordinals, any order, repeats allowed) as a list of bytes"""

@@ -13,6 +13,10 @@
  * (uvaia_clust_keep_medoids), so device memory follows the number of clusters and not the number of sequences; same output files.  With
  * --packed it is chosen without being asked for when the file's sequence count says that the row store could not grow to hold them
  * (clust_plan.h).  Own code.
+ *
+ * --device-parse (no counterpart either, off by default): the alignment files are read in blocks (fasta_blocks.h), split into records and
+ * rows on the GPU (uvaia_gpu_fasta_scan, uvaia_gpu_fasta_rows) and pushed from the parser's device memory (uvaia_clust_push_device).  Only
+ * the names stay on the host; the medoids of <prefix>.aln.xz come back from the device in batches, as with --packed.  Same output files.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -25,6 +29,7 @@
 #include "uvdb_packer.h"
 #include "uvdb_set.h"
 #include "clust_plan.h"
+#include "fasta_blocks.h"
 #include "../../../include/uvaia_cluster.h"
 
 /* read_reference_sequence (src/cluster.c:260-277): the first record of the file, filled by up to nseqs - 1 more while Ns remain
@@ -202,13 +207,119 @@ write_packed_out (const char *path, uvaia_clust_ctx *ctx, int device, int nchar,
   free (slot); free (m_nn); free (m_exc); free (nn); free (ne); free (row); free (name);
 }
 
+/* `uvaiaclust --device-parse`: every record of a scan is a row (a record of another length ends the command, as on the default route), so the
+ * rows of a scan are one push, sequence k of the FILE to queue k mod Q. */
+#define PARSE_MAX_RECORDS (1 << 18)     /* records per scan, as in pack_main.c; a block that holds more is scanned in several steps */
+
+struct clust_parse {
+  gpu_state *g;
+  uvaia_gpu_fasta *fasta;
+  int max_records;
+  uvaia_gpu_fasta_record *rec;          /* max_records of each */
+  int *queue;
+  str_vec *names;
+  int64_t count, k;                     /* sequences pushed so far; of the file being read */
+};
+
+static int
+clust_parse_scan (void *user, const char *text, size_t n, int final, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off, char *err, size_t errlen)
+{
+  struct clust_parse *d = (struct clust_parse *) user;
+  if (!uvaia_gpu_fasta_scan (d->fasta, text, n, final, n_records, consumed)) return 0;
+  const unsigned kind = uvaia_gpu_fasta_bad (d->fasta, bad_off);       /* irregular text: the block reader names the byte of the stream */
+  *bad_kind = kind == UVAIA_GPU_FASTA_NUL ? FASTA_BAD_NUL : kind == UVAIA_GPU_FASTA_TEXT ? FASTA_BAD_TEXT : kind == UVAIA_GPU_FASTA_EMPTY ? FASTA_BAD_EMPTY : FASTA_BAD_NONE;
+  snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta));
+  return -1;
+}
+
+/* a push refused for a byte >= 0x80: the message of the default route, from the parser's rows */
+static void
+clust_parse_bad_byte (struct clust_parse *d, int n_rows, size_t pitch, int64_t first, char *err, size_t errlen)
+{
+  const int nchar = d->g->nchar;
+  unsigned char *rows = (unsigned char *) biomcmc_malloc ((size_t) n_rows * pitch);
+  if (!uvaia_gpu_fasta_rows_host (d->fasta, rows)) for (int r = 0; r < n_rows; r++) for (int i = 0; i < nchar; i++) if (rows[(size_t) r * pitch + i] >= 0x80) {
+    snprintf (err, errlen, "sequence %s holds byte 0x%02x at site %d: only bytes 1-127 are defined", d->names->v[first + r], rows[(size_t) r * pitch + i], i + 1);
+    free (rows);
+    return;
+  }
+  free (rows);
+}
+
+static int
+clust_parse_records (void *user, char *text, size_t consumed, int n_records, char *err, size_t errlen)
+{
+  struct clust_parse *d = (struct clust_parse *) user;
+  gpu_state *g = d->g;
+  const void *d_rows = NULL; size_t pitch = 0; int n_rows = 0;
+  if (uvaia_gpu_fasta_records (d->fasta, d->rec)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+  const int64_t first = d->count;
+  for (int k = 0; k < n_records; k++) {
+    const uvaia_gpu_fasta_record *r = d->rec + k;
+    char *name = text + r->name_off;
+    name[r->name_len] = '\0';                         /* the line end behind the name, or the byte of room behind the block */
+    if ((int64_t) r->seq_len != g->nchar) {
+      snprintf (err, errlen, "%s cannot work with unaligned sequences; sequence %s has %lu sites while reference has %d.", UVAIA_PACKAGE_STRING, name, (unsigned long) r->seq_len, g->nchar);
+      return -1;
+    }
+    str_vec_push (d->names, strdup (name));           /* the block buffer is recycled */
+    d->queue[k] = (int) (d->k++ % g->n_clust);
+  }
+  if (uvaia_gpu_fasta_rows (d->fasta, g->nchar, &d_rows, &pitch, &n_rows, NULL)) { snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta)); return -1; }
+  open_context (g);
+  const int rc = uvaia_clust_push_device (g->ctx, n_rows, d_rows, pitch, NULL, d->queue);
+  if (rc) {
+    snprintf (err, errlen, "%s", uvaia_clust_last_error (g->ctx));
+    if (rc == UVAIA_GPU_EALPHABET) clust_parse_bad_byte (d, n_rows, pitch, first, err, errlen);
+    return -1;
+  }
+  d->count += n_rows;
+  return 0;
+}
+
+/* all files through the route above; returns the number of sequences pushed */
+static int64_t
+cluster_device_parse (gpu_state *g, const char **fasta, int n_fasta, size_t block_bytes, str_vec *names, int64_t *time0)
+{
+  char msg[1024], failed[1024];
+  struct clust_parse d;
+  memset (&d, 0, sizeof d);
+  d.g = g; d.names = names;
+  d.max_records = block_bytes / 4 + 1 < PARSE_MAX_RECORDS ? (int) (block_bytes / 4 + 1) : PARSE_MAX_RECORDS;      /* (a record has four bytes at least) */
+  if (uvaia_gpu_fasta_open (&d.fasta, g->device, block_bytes, d.max_records)) biomcmc_error ("%s", uvaia_gpu_fasta_last_error (NULL));
+  d.rec = (uvaia_gpu_fasta_record *) biomcmc_malloc ((size_t) d.max_records * sizeof (uvaia_gpu_fasta_record));
+  d.queue = (int *) biomcmc_malloc ((size_t) d.max_records * sizeof (int));
+  uint64_t bytes = 0;
+  for (int j = 0; j < n_fasta; j++) {
+    uint64_t nb = 0;
+    d.k = 0;                                            /* sequence k of a file to queue k mod Q (src/cluster.c:164-181) */
+    fasta_blocks fb = fasta_blocks_open (fasta[j], block_bytes, uvaia_gpu_fasta_pinned_alloc, uvaia_gpu_fasta_pinned_free, msg, sizeof msg);
+    const int rc = fb ? fasta_blocks_run (fb, d.max_records, clust_parse_scan, &d, clust_parse_records, &d, &nb, msg, sizeof msg) : -1;
+    if (fasta_blocks_finish (fb, failed, sizeof failed)) biomcmc_error ("%s", failed);      /* a decompressor that failed mid-stream: that is the finding */
+    if (rc) {
+      const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
+      biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaiaclust` without it reads this file line by line)" : "");
+    }
+    bytes += nb;
+    fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", fasta[j], biomcmc_update_elapsed_time (time0), (long) d.count);
+  }
+  double ms[2] = {0., 0.}, rows_in_ms = 0.;
+  uvaia_gpu_fasta_kernel_ms (d.fasta, ms, 0);
+  if (g->ctx) uvaia_clust_push_device_ms (g->ctx, &rows_in_ms);
+  fprintf (stderr, "device parse: {\"bytes\": %llu, \"block_bytes\": %zu, \"scan_ms\": %.3f, \"rows_ms\": %.3f, \"rows_in_ms\": %.3f}\n", (unsigned long long) bytes, block_bytes, ms[0], ms[1], rows_in_ms);
+  uvaia_gpu_fasta_close (d.fasta);
+  free (d.rec); free (d.queue);
+  return d.count;
+}
+
 static const char *name_from_vec (void *v, int64_t i) { return ((str_vec *) v)->v[i]; }
 static const char *name_from_db (void *v, int64_t i) { return uvdb_set_name ((uvdb_set) v, (uint64_t) i); }      /* i: position in the stream of all --packed files */
 
 int
 main (int argc, char **argv)
 {
-  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, compact = 0, ch;   /* src/cluster.c:57-64 */
+  int help = 0, version = 0, dist = 1, trim = 0, snps = 1, pool = 4 * omp_get_max_threads (), device = 0, errors = 0, keep_medoids = 0, compact = 0, device_parse = 0, ch;   /* src/cluster.c:57-64 */
+  size_t parse_block = FASTA_BLOCK_BYTES;
   double ambig_r = -1.;
   const char *out = "cluster_uvaia", *ref_file = NULL, *packed = NULL, *packed_out = NULL;
   const char **packed_files = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *)); int n_packed = 0;
@@ -216,7 +327,8 @@ main (int argc, char **argv)
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"distance", required_argument, 0, 'd'}, {"trim", required_argument, 0, 1000},
     {"pool", required_argument, 0, 'p'}, {"snps", required_argument, 0, 's'}, {"reference", required_argument, 0, 'r'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"packed", required_argument, 0, 1002},
-    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"keep-medoids", no_argument, 0, 1004}, {"compact", no_argument, 0, 1005}, {0, 0, 0, 0}};
+    {"packed-out", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"keep-medoids", no_argument, 0, 1004}, {"compact", no_argument, 0, 1005},
+    {"device-parse", no_argument, 0, 1006}, {"parse-block", required_argument, 0, 1007}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvd:p:s:r:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -231,12 +343,18 @@ main (int argc, char **argv)
     case 1003: if (packed_out) errors++; packed_out = optarg; break;
     case 1004: keep_medoids = 1; break;
     case 1005: compact = 1; break;
+    case 1006: device_parse = 1; break;
+    case 1007: parse_block = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the block size of --device-parse in bytes) */
     case 'A': ambig_r = atof (optarg); if (ambig_r < 0.) ambig_r = 0.; break;
     default: errors++;
   }
   const char **fasta = (const char **) argv + optind;
   const int n_fasta = argc - optind;
   if (version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS; }
+  /* --device-parse: what does not go with it is refused here, before a file is opened or a GPU touched */
+  if (!help && device_parse && packed) { fprintf (stderr, "--device-parse reads FASTA text: it does not go with --packed, which holds no text to parse\n"); return EXIT_FAILURE; }
+  if (!help && device_parse && (parse_block < 64 || parse_block > ((size_t) 1 << 30))) { fprintf (stderr, "--parse-block: expected 64 to 1073741824 bytes\n"); return EXIT_FAILURE; }
+  if (!help && !device_parse && parse_block != FASTA_BLOCK_BYTES) { fprintf (stderr, "--parse-block sets the block size of --device-parse: it needs that option\n"); return EXIT_FAILURE; }
   if (!help && !errors && packed && n_fasta > 0) {
     fprintf (stderr, "--packed %s takes the place of the alignment files: give one or the other, not both (%s was given as well)\n", packed, fasta[0]);
     errors++;
@@ -247,7 +365,7 @@ main (int argc, char **argv)
   }
   if (help || errors || (!packed && n_fasta < 1) || n_fasta > 1024 || n_packed > UVDB_SET_MAX_FILES) {
     printf ("%s \nCluster and dedups alignments\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb> [--compact]] [-A <double>] [--keep-medoids] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb> [--packed <in.uvdb>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [-d <int>] [--trim=<int>] [-p <int>] [-s <int>] [-r <ref.fa(.gz,.xz)>] [--packed-out <out.uvdb> [--compact]] [-A <double>] [--keep-medoids] [--device-parse] [-o <without suffix>] <seqs.fa(.gz,.xz)> [<seqs.fa(.gz,.xz)>]... | --packed <in.uvdb> [--packed <in.uvdb>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  -d, --distance=<int>             seqs with this SNP differences or less will be merged (default=1)\n");
     printf ("  --trim=<int>                     number of sites to trim from both ends (default=0, suggested for sarscov2=230)\n");
@@ -267,6 +385,12 @@ main (int argc, char **argv)
     printf ("                                   (default: the value recorded in the --packed database, 0.5 for alignment files)\n");
     printf ("  --keep-medoids                   keep only the sequences that found a cluster in GPU memory, not every sequence: memory follows the number of\n");
     printf ("                                   clusters; same output files (with --packed: chosen by itself when the sequences would not fit otherwise)\n");
+    printf ("  --device-parse                   split the alignment files into sequences on the GPU instead of reading them line by line, and cluster them where\n");
+    printf ("                                   they lie: no sequence text is held on the host (only names).  Same output files, from regular FASTA only (a NUL\n");
+    printf ("                                   byte, text before the first header and a header without sequence are refused).  Not with --packed.  Behind .gz or\n");
+    printf ("                                   .xz the decompressor sets the pace and little time is gained; the memory is saved all the same\n");
+    printf ("  --parse-block=<bytes>            with --device-parse: the text is read in blocks of this size (64 to 1073741824, default 67108864); a record\n");
+    printf ("                                   must fit a block\n");
     if (help) {
       printf ("One-pass clustering similar to canopy clustering with single, tight distance, computed on the GPU.\n");
       printf ("A pool of independent clustering queues is created, such that each sequence is compared to only one of them at first.\n\n");
@@ -344,7 +468,8 @@ main (int argc, char **argv)
       fprintf (stderr, "Finished reading file %s in %.3lf secs; Commulative %ld sequences read\n", packed_files[f], biomcmc_update_elapsed_time (time0), (long) count);
     }
     free (queue);
-  } else {
+  } else if (device_parse) count = cluster_device_parse (&g, fasta, n_fasta, parse_block, &names, time0);
+  else {
     /* read every file, sequence k of a file to queue k mod Q (src/cluster.c:164-181); push in batches of 4 Q */
     const int batch = 4 * n_clust;
     int *queue = (int *) biomcmc_malloc ((size_t) batch * sizeof (int));
@@ -406,7 +531,7 @@ main (int argc, char **argv)
   if (bad) fprintf (stderr, "File %s may not be correctly compressed, %d error%s occurred.\n", outfilename, bad, bad > 1 ? "s" : "");
   strcpy (outfilename + outlength, ".aln.xz");
   file_compress_t aln = biomcmc_open_compress (outfilename, "w");
-  if (db) {   /* the text of the medoids exists on the device only: a bounded batch of it at a time */
+  if (db || device_parse) {   /* the text of the medoids exists on the device only: a bounded batch of it at a time */
     const size_t pitch = (size_t) nchar + 1;
     char *text = (char *) biomcmc_malloc (ROWS_BATCH * pitch);
     memset (text, 0, ROWS_BATCH * pitch);
@@ -426,7 +551,8 @@ main (int argc, char **argv)
            prep_ms, queue_ms, merge_ms, decode_ms, overlay_ms);
   fprintf (stderr, "Finished sorting clusters and saving files in %lf secs\n", biomcmc_update_elapsed_time (time0));
 
-  for (int64_t i = 0; i < seqs.n; i++) { free (seqs.v[i]); free (names.v[i]); }
+  for (int64_t i = 0; i < seqs.n; i++) free (seqs.v[i]);
+  for (int64_t i = 0; i < names.n; i++) free (names.v[i]);
   free (seqs.v); free (names.v); free (medoid); free (offsets); free (members); free (outfilename);
   uvdb_set_close (set);
   free (packed_files);

@@ -16,6 +16,7 @@
 #include "uvdb_window.h"
 #include "uvdb_set.h"
 #include "uvdb_extract.h"
+#include "fasta_blocks.h"
 
 typedef struct {
   int help, version, acgt, keep_resolved, exclude_self, nbest, trim, pool, threads, threads_given, device, devices[64], n_devices;
@@ -25,6 +26,8 @@ typedef struct {
   const char *out, *query;
   const char **ref; int n_ref;
   const char **packed_files; int n_packed;
+  int device_parse, parse_block_given, parse_window_given;
+  size_t parse_block; long long parse_window;
 } options;
 
 static void
@@ -33,7 +36,7 @@ usage (const char *prog, int long_help)
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("For every query sequence, finds closest neighbours in reference alignment. \n");
   printf ("The score-distance scan and the neighbour heaps run on an AMD MI355X GPU.\n\n");
-  printf ("The complete syntax is:\n\n %s [-hvkx] [--acgt] [-n <int>] [--trim=<int>] [-A <double>] [-a <double>] [-p <int>] -r <ref.fa(.gz,.xz)> [-r <ref.fa(.gz,.xz)>]... <seqs.fa(.gz,.xz)> [-t <int>] [-o <without suffix>]\n\n", prog);
+  printf ("The complete syntax is:\n\n %s [-hvkx] [--acgt] [-n <int>] [--trim=<int>] [-A <double>] [-a <double>] [-p <int>] [--device-parse] -r <ref.fa(.gz,.xz)> [-r <ref.fa(.gz,.xz)>]... <seqs.fa(.gz,.xz)> [-t <int>] [-o <without suffix>]\n\n", prog);
   printf ("  -h, --help                       print a longer help and exit\n");
   printf ("  -v, --version                    print version and exit\n");
   printf ("  --acgt                           considers only ACGT sites (i.e. unambiguous SNP differences) in query sequences (mismatch-based)\n");
@@ -45,6 +48,9 @@ usage (const char *prog, int long_help)
   printf ("  -a, --query_ambiguity=<double>   maximum allowed ambiguity for QUERY sequence to be excluded (default=0.5)\n");
   printf ("  -p, --pool=<int>                 Pool size, i.e. how many reference seqs are sent to the GPU per batch (defaults to 64 per host thread; larger is faster)\n");
   printf ("  -r, --reference=<ref.fa(.gz,.xz)> aligned reference sequences (can be several files)\n");
+  printf ("  --device-parse                   with -r: split the reference text into sequences on the GPU instead of reading it line by line; the references\n                                   are searched a window at a time and only those that become neighbours come back as text.  The same files,\n                                   from regular FASTA only (a NUL byte, text before the first header and a header without sequence are refused);\n                                   on one GPU, not with --packed.  Behind .gz or .xz the decompressor sets the pace and little is gained\n");
+  printf ("  --parse-block=<bytes>            with --device-parse: the text is read in blocks of this size (64 to 1073741824, default 67108864); a record\n                                   must fit a block\n");
+  printf ("  --parse-window=<refs>            with --device-parse: this many accepted references are resident before they are searched (rounded up to whole\n                                   pools; default: 65536, fewer when GPU memory is short)\n");
   printf ("  --packed=<db.uvdb>               reference database packed by `uvaiapack` (instead of -r): loaded as it is, no text parsing; can be several\n                                   files, searched in the order given as one database (all packed with the same -A: see `uvaiapack --merge -A`).\n                                   Compact files (`uvaiapack --compact`) are expanded on the GPU, on one device (not with a --devices list of several)\n");
   printf ("  --window=<refs>                  with --packed: keep only this many references on the GPU at a time (rounded up to whole pools and tiles\n                                   of 64), for a database larger than GPU memory; chosen automatically when the database does not fit\n");
   printf ("  --window-report                  with --packed: one line on stderr with the GPU's free memory before and after and the time of the window steps\n");
@@ -73,6 +79,7 @@ parse_options (int argc, char **argv)
   options o;
   memset (&o, 0, sizeof o);
   o.nbest = 100; o.ambig_q = o.ambig_r = 0.5; o.pool = 64 * omp_get_max_threads (); o.device = -1;
+  o.parse_block = FASTA_BLOCK_BYTES;
   o.ref = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *));
   o.packed_files = (const char **) biomcmc_malloc ((size_t) argc * sizeof (char *));
   static const struct option longopts[] = {
@@ -82,7 +89,8 @@ parse_options (int argc, char **argv)
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1002}, {"packed", required_argument, 0, 1003}, {"devices", required_argument, 0, 1004},
     {"window", required_argument, 0, 1005}, {"window-report", no_argument, 0, 1006},
-    {"final-aln", no_argument, 0, 1007}, {"final-rank", required_argument, 0, 1008}, {"final-only", no_argument, 0, 1009}, {0, 0, 0, 0}};
+    {"final-aln", no_argument, 0, 1007}, {"final-rank", required_argument, 0, 1008}, {"final-only", no_argument, 0, 1009},
+    {"device-parse", no_argument, 0, 1010}, {"parse-block", required_argument, 0, 1011}, {"parse-window", required_argument, 0, 1012}, {0, 0, 0, 0}};
   int ch, errors = 0;
   while ((ch = getopt_long (argc, argv, "hvkxn:a:A:p:r:t:o:", longopts, NULL)) != -1) switch (ch) {
     case 'h': o.help = 1; break;
@@ -106,12 +114,25 @@ parse_options (int argc, char **argv)
     case 1007: o.final_aln = 1; break;
     case 1008: o.final_rank = atoi (optarg); o.final_rank_given = 1; break;
     case 1009: o.final_only = 1; break;
+    case 1010: o.device_parse = 1; break;
+    case 1011: o.parse_block = (size_t) strtoull (optarg, NULL, 10); o.parse_block_given = 1; break;      /* (for tests: the block size of --device-parse in bytes) */
+    case 1012: o.parse_window = atoll (optarg); o.parse_window_given = 1; break;                          /* (for tests: the window of --device-parse in references) */
     default: errors++;
   }
   if (optind < argc) o.query = argv[optind++];
   if (optind < argc) errors++;
   if (o.version) { printf ("%s\n", UVAIA_PACKAGE_VERSION); exit (EXIT_SUCCESS); }
   if (o.help) { usage (basename (argv[0]), 1); exit (EXIT_SUCCESS); }
+  /* --device-parse: what does not go with it is refused here, before a GPU is touched or a file created */
+  if (o.device_parse && o.n_packed) { fprintf (stderr, "--device-parse reads FASTA text (-r): it does not go with --packed, which holds no text to parse\n"); exit (EXIT_FAILURE); }
+  if (o.device_parse && o.n_devices > 1) {
+    fprintf (stderr, "--device-parse hands the references to the search in the memory of ONE GPU: give --device, or a --devices list of one device (%d were listed)\n", o.n_devices);
+    exit (EXIT_FAILURE);
+  }
+  if (o.device_parse && (o.parse_block < 64 || o.parse_block > ((size_t) 1 << 30))) { fprintf (stderr, "--parse-block: expected 64 to 1073741824 bytes\n"); exit (EXIT_FAILURE); }
+  if (!o.device_parse && o.parse_block_given) { fprintf (stderr, "--parse-block sets the block size of --device-parse: it needs that option\n"); exit (EXIT_FAILURE); }
+  if (!o.device_parse && o.parse_window_given) { fprintf (stderr, "--parse-window sets the window of --device-parse: it needs that option\n"); exit (EXIT_FAILURE); }
+  if (o.parse_window_given && o.parse_window < 1) { fprintf (stderr, "--parse-window: expected a positive number of references\n"); exit (EXIT_FAILURE); }
   if (errors || !o.query || (!o.n_ref && !o.n_packed) || (o.n_ref && o.n_packed)) {
     printf ("Error when reading arguments from command line:\n");
     usage (basename (argv[0]), 0);
@@ -435,6 +456,173 @@ save_final_alignment (const options *o, query_t query, uvaia_gpu_group *grp, uva
   return u;
 }
 
+/* ---- `uvaia -r --device-parse`.  The text is read in blocks (fasta_blocks.h) and split into records and rows on the GPU
+ * (uvaia_gpu_fasta_scan, uvaia_gpu_fasta_rows); the filters of the fill loop in main run on the integers of the record table; the rows of the
+ * survivors go from the parser's memory into the resident database and, as text, into the text row store.  When `window` references (a
+ * multiple of the pool) are resident, and at the end of every file, they are searched in pools -- the pools of the fill loop, whose short
+ * last pool also ends a file -- and those that entered a heap come back as text.  Only the names are taken from the host's copy of the text. */
+#define PARSE_MAX_RECORDS (1 << 18)     /* records per scan, as in pack_main.c; a block that holds more is scanned in several steps */
+#define PARSE_ROWS_BATCH 256            /* rows of text per copy back */
+
+struct search_parse {
+  const options *o;
+  query_t query;
+  uvaia_gpu_ctx *gpu;
+  uvaia_gpu_fasta *fasta;
+  file_compress_t outstream;
+  name_table *names;
+  int nchar, non_n_ref, max_records, resident, window;
+  size_t row_pitch;
+  uvaia_gpu_fasta_record *rec;          /* max_records of each */
+  int *row_of, *sel, *nn;
+  char **name;                          /* of the resident references: window */
+  uint8_t *entered;
+  char *rows; int index[PARSE_ROWS_BATCH];
+  int count, n_invalid, same_name, n_output, last_print;
+  int64_t ordinal, *time1;
+};
+
+static int
+search_parse_scan (void *user, const char *text, size_t n, int final, int *n_records, size_t *consumed, int *bad_kind, size_t *bad_off, char *err, size_t errlen)
+{
+  struct search_parse *d = (struct search_parse *) user;
+  if (!uvaia_gpu_fasta_scan (d->fasta, text, n, final, n_records, consumed)) return 0;
+  const unsigned kind = uvaia_gpu_fasta_bad (d->fasta, bad_off);       /* irregular text: the block reader names the byte of the stream */
+  *bad_kind = kind == UVAIA_GPU_FASTA_NUL ? FASTA_BAD_NUL : kind == UVAIA_GPU_FASTA_TEXT ? FASTA_BAD_TEXT : kind == UVAIA_GPU_FASTA_EMPTY ? FASTA_BAD_EMPTY : FASTA_BAD_NONE;
+  snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta));
+  return -1;
+}
+
+/* the resident references are searched, those that entered a heap written in stream order, and the window is emptied */
+static int
+search_parse_flush (struct search_parse *d, char *err, size_t errlen)
+{
+  const int n = d->resident, nchar = d->nchar;
+  if (!n) return 0;
+  if (uvaia_gpu_search_resident (d->gpu, (size_t) d->o->pool, d->ordinal, d->entered)) { snprintf (err, errlen, "%s", uvaia_gpu_last_error (d->gpu)); return -1; }
+  for (int k = 0; k < n;) {
+    int m = 0;
+    for (; k < n && m < PARSE_ROWS_BATCH; k++) if (d->entered[k]) d->index[m++] = k;
+    if (!m) break;
+    if (uvaia_gpu_text_rows (d->gpu, d->index, m, d->rows, d->row_pitch)) { snprintf (err, errlen, "%s", uvaia_gpu_last_error (d->gpu)); return -1; }
+    for (int j = 0; j < m; j++) {
+      char *row = d->rows + (size_t) j * d->row_pitch, after = row[nchar];
+      row[nchar] = '\0';
+      write_fasta_record (d->outstream, d->name[d->index[j]], row);
+      row[nchar] = after;
+      name_table_set (d->names, d->ordinal + d->index[j], d->name[d->index[j]]);
+      d->n_output++;
+    }
+  }
+  d->ordinal += n;
+  if (uvaia_gpu_db_clear (d->gpu) || uvaia_gpu_text_clear (d->gpu)) { snprintf (err, errlen, "%s", uvaia_gpu_last_error (d->gpu)); return -1; }
+  for (int k = 0; k < n; k++) free (d->name[k]);
+  d->resident = 0;
+  if (d->count / 10000 > d->last_print / 10000) {       /* the progress line of the fill loop, per window */
+    int highest = 0;
+    uvaia_gpu_max_tolerance (d->gpu, &highest);
+    fprintf (stderr, "Total: %d sequences analysed, %d saved, %d poorly resolved. Highest number of ACGT mismatches = %d in current neighbourhood. %.3lf secs elapsed. ",
+             d->count, d->n_output, d->n_invalid, highest, biomcmc_update_elapsed_time (d->time1));
+    if (d->o->exclude_self) fprintf (stderr, " %d already present in query alignment.\n", d->same_name); else fprintf (stderr, "\n");
+    d->last_print = d->count;
+  }
+  return 0;
+}
+
+static int
+search_parse_records (void *user, char *text, size_t consumed, int n_records, char *err, size_t errlen)
+{
+  struct search_parse *d = (struct search_parse *) user;
+  const void *d_rows = NULL; size_t pitch = 0; int n_rows = 0, n_sel = 0;
+  if (uvaia_gpu_fasta_records (d->fasta, d->rec) || uvaia_gpu_fasta_rows (d->fasta, d->nchar, &d_rows, &pitch, &n_rows, d->row_of)) {
+    snprintf (err, errlen, "%s", uvaia_gpu_fasta_last_error (d->fasta));
+    return -1;
+  }
+  for (int k = 0; k < n_records; k++) {               /* the filters of main's fill loop, in its order, on the counts the device made */
+    const uvaia_gpu_fasta_record *r = d->rec + k;
+    char *name = text + r->name_off;
+    name[r->name_len] = '\0';                         /* the line end behind the name, or the byte of room behind the block */
+    d->count++;
+    if (d->o->exclude_self && lookup_hashtable (d->query->aln->taxlabel_hash, name) > -1) { d->same_name++; continue; }
+    if (r->non_n < d->non_n_ref) { d->n_invalid++; continue; }
+    if (d->row_of[k] < 0) {
+      biomcmc_warning ("Reference sequence '%s' has %u sites but query sequences have %d sites\n", name, r->seq_len, d->nchar);
+      snprintf (err, errlen, "all sequences must be aligned");
+      return -1;
+    }
+    d->sel[n_sel] = d->row_of[k]; d->nn[n_sel] = r->non_n;
+    d->rec[n_sel++].name_off = r->name_off;            /* (n_sel <= k: the table is read ahead of where it is written) */
+  }
+  for (int a = 0; a < n_sel;) {                        /* into the window, as much as it still takes; a full window is searched */
+    const int room = d->window - d->resident, m = n_sel - a < room ? n_sel - a : room;
+    if (uvaia_gpu_db_append_device (d->gpu, d_rows, pitch, d->sel + a, m, d->nn + a) || uvaia_gpu_text_append_device (d->gpu, d_rows, pitch, d->sel + a, m)) {
+      snprintf (err, errlen, "%s", uvaia_gpu_last_error (d->gpu));
+      return -1;
+    }
+    for (int c = 0; c < m; c++) d->name[d->resident + c] = strdup (text + d->rec[a + c].name_off);      /* the block buffer is recycled */
+    d->resident += m; a += m;
+    if (d->resident == d->window && search_parse_flush (d, err, errlen)) return -1;
+  }
+  return 0;
+}
+
+static void
+search_parse_open (struct search_parse *d, const options *o, query_t query, uvaia_gpu_ctx *gpu, file_compress_t outstream, name_table *names, int64_t *time1)
+{
+  memset (d, 0, sizeof *d);
+  d->o = o; d->query = query; d->gpu = gpu; d->outstream = outstream; d->names = names; d->time1 = time1;
+  d->nchar = query->aln->nchar;
+  d->non_n_ref = (int) (d->nchar * (1. - o->ambig_r));
+  d->row_pitch = ((size_t) d->nchar + 15) / 16 * 16;
+  d->max_records = o->parse_block / 4 + 1 < PARSE_MAX_RECORDS ? (int) (o->parse_block / 4 + 1) : PARSE_MAX_RECORDS;      /* (a record has four bytes at least) */
+  if (uvaia_gpu_fasta_open (&d->fasta, o->devices[0], o->parse_block, d->max_records)) biomcmc_error ("%s", uvaia_gpu_fasta_last_error (NULL));
+  /* per resident reference: what search_packed counts (packed planes, derived planes, side row, counts and flag) and its row of text; the
+     parser's own rows, at most a block's worth, come out of the free memory first */
+  const uint64_t bpr = uvaia_gpu_packed_bytes_per_ref (gpu) + uvaia_gpu_derived_bytes_per_ref (gpu) + uvaia_gpu_db_tile_bytes (gpu) / 256
+                     + (uint64_t) uvaia_gpu_db_side_row_ints () * 4 + 20 + d->row_pitch;
+  uint64_t mem = uvaia_gpu_free_bytes (gpu);
+  if (mem) mem = mem > 2 * (uint64_t) o->parse_block ? mem - 2 * (uint64_t) o->parse_block : 1;
+  d->window = (int) uvdb_parse_window ((uint64_t) o->pool, o->parse_window_given ? (uint64_t) o->parse_window : 0, bpr, mem);
+  if (d->window < 1) biomcmc_error ("--device-parse: no window for a pool of %d", o->pool);
+  if (uvaia_gpu_db_reserve (gpu, (size_t) d->window) || uvaia_gpu_text_reserve (gpu, (size_t) d->window)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+  d->rec = (uvaia_gpu_fasta_record *) biomcmc_malloc ((size_t) d->max_records * sizeof (uvaia_gpu_fasta_record));
+  d->row_of = (int *) biomcmc_malloc ((size_t) d->max_records * sizeof (int));
+  d->sel = (int *) biomcmc_malloc ((size_t) d->max_records * sizeof (int));
+  d->nn = (int *) biomcmc_malloc ((size_t) d->max_records * sizeof (int));
+  d->name = (char **) biomcmc_malloc ((size_t) d->window * sizeof (char *));
+  d->entered = (uint8_t *) biomcmc_malloc ((size_t) d->window);
+  d->rows = (char *) biomcmc_malloc (PARSE_ROWS_BATCH * d->row_pitch + 1);
+}
+
+/* one -r file; the window is searched at its end, so that no pool spans two files */
+static uint64_t
+search_parse_file (struct search_parse *d, const char *path)
+{
+  char msg[1024], failed[1024];
+  uint64_t nb = 0;
+  fasta_blocks fb = fasta_blocks_open (path, d->o->parse_block, uvaia_gpu_fasta_pinned_alloc, uvaia_gpu_fasta_pinned_free, msg, sizeof msg);
+  int rc = fb ? fasta_blocks_run (fb, d->max_records, search_parse_scan, d, search_parse_records, d, &nb, msg, sizeof msg) : -1;
+  if (fasta_blocks_finish (fb, failed, sizeof failed)) biomcmc_error ("%s", failed);      /* a decompressor that failed mid-stream: that is the finding */
+  if (rc) {
+    const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
+    biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaia` without it reads this file line by line)" : "");
+  }
+  if (search_parse_flush (d, msg, sizeof msg)) biomcmc_error ("%s: %s", path, msg);
+  return nb;
+}
+
+static void
+search_parse_close (struct search_parse *d, uint64_t bytes)
+{
+  double ms[2] = {0., 0.}, text_ms[2] = {0., 0.};
+  uvaia_gpu_fasta_kernel_ms (d->fasta, ms, 0);
+  uvaia_gpu_text_ms (d->gpu, text_ms, 0);
+  fprintf (stderr, "device parse: {\"bytes\": %llu, \"block_bytes\": %zu, \"window\": %d, \"scan_ms\": %.3f, \"rows_ms\": %.3f, \"text_in_ms\": %.3f, \"text_out_ms\": %.3f}\n", (unsigned long long) bytes,
+           d->o->parse_block, d->window, ms[0], ms[1], text_ms[0], text_ms[1]);
+  uvaia_gpu_fasta_close (d->fasta);
+  free (d->rec); free (d->row_of); free (d->sel); free (d->nn); free (d->name); free (d->entered); free (d->rows);
+}
+
 static void
 save_distance_table (heap_t *heap, query_t query, const char *filename)
 {
@@ -531,56 +719,66 @@ main (int argc, char **argv)
     else           fprintf (stderr, "Total of %d sequences searched; none saved during the search (--final-only). %.3lf secs elapsed. \n", count, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
   }
+  struct search_parse parse;
+  uint64_t parse_bytes = 0;
+  if (o.device_parse) search_parse_open (&parse, &o, query, gpu, outstream, &names, time1);
   for (int j = 0; j < o.n_ref; j++) {
-    readfasta_t rfas = new_readfasta (o.ref[j]);
-    bool end_of_file = false;
-    while (!end_of_file) {
-      int fill = 0;
-      while (fill < o.pool && !end_of_file) {          /* the serial slot-filling loop of the reference (src/nearest.c:251-286) */
-        if (readfasta_next (rfas) < 0) { end_of_file = true; break; }
-        count++;
-        if (o.exclude_self && lookup_hashtable (query->aln->taxlabel_hash, rfas->name) > -1) { same_name++; continue; }
-        int nn = quick_count_sequence_non_N (rfas->seq, rfas->seqlength);
-        if (nn < non_n_ref) { n_invalid++; continue; }
-        if (rfas->seqlength != (size_t) query->aln->nchar) {
-          biomcmc_warning ("Reference sequence '%s' has %zu sites but query sequences have %d sites\n", rfas->name, rfas->seqlength, query->aln->nchar);
-          biomcmc_error ("all sequences must be aligned");
+    if (o.device_parse) {       /* the same filters, pools and files, from rows made on the GPU */
+      parse.count = count; parse.n_invalid = n_invalid; parse.same_name = same_name; parse.n_output = n_output; parse.ordinal = ordinal;
+      parse_bytes += search_parse_file (&parse, o.ref[j]);
+      count = parse.count; n_invalid = parse.n_invalid; same_name = parse.same_name; n_output = parse.n_output; ordinal = parse.ordinal;
+    } else {
+      readfasta_t rfas = new_readfasta (o.ref[j]);
+      bool end_of_file = false;
+      while (!end_of_file) {
+        int fill = 0;
+        while (fill < o.pool && !end_of_file) {          /* the serial slot-filling loop of the reference (src/nearest.c:251-286) */
+          if (readfasta_next (rfas) < 0) { end_of_file = true; break; }
+          count++;
+          if (o.exclude_self && lookup_hashtable (query->aln->taxlabel_hash, rfas->name) > -1) { same_name++; continue; }
+          int nn = quick_count_sequence_non_N (rfas->seq, rfas->seqlength);
+          if (nn < non_n_ref) { n_invalid++; continue; }
+          if (rfas->seqlength != (size_t) query->aln->nchar) {
+            biomcmc_warning ("Reference sequence '%s' has %zu sites but query sequences have %d sites\n", rfas->name, rfas->seqlength, query->aln->nchar);
+            biomcmc_error ("all sequences must be aligned");
+          }
+          non_n[fill] = nn;
+          seq[fill] = rfas->seq; rfas->seq = NULL;       /* steal the buffers, as the reference does */
+          name[fill] = rfas->name; rfas->name = NULL;
+          fill++;
         }
-        non_n[fill] = nn;
-        seq[fill] = rfas->seq; rfas->seq = NULL;       /* steal the buffers, as the reference does */
-        name[fill] = rfas->name; rfas->name = NULL;
-        fill++;
-      }
-      if (fill) {
-        if (uvaia_gpu_group_push (grp, (const char *const *) seq, non_n, fill, ordinal, entered)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
-        for (int c = 0; c < fill; c++) if (entered[c]) {   /* dump every sequence that entered some heap, in stream order */
-          n_output++;
-          write_fasta_record (outstream, name[c], seq[c]);
-          name_table_set (&names, ordinal + c, name[c]);
+        if (fill) {
+          if (uvaia_gpu_group_push (grp, (const char *const *) seq, non_n, fill, ordinal, entered)) biomcmc_error ("%s", uvaia_gpu_group_last_error (grp));
+          for (int c = 0; c < fill; c++) if (entered[c]) {   /* dump every sequence that entered some heap, in stream order */
+            n_output++;
+            write_fasta_record (outstream, name[c], seq[c]);
+            name_table_set (&names, ordinal + c, name[c]);
+          }
+          ordinal += fill;
+          for (int c = 0; c < fill; c++) { free (seq[c]); free (name[c]); }
         }
-        ordinal += fill;
-        for (int c = 0; c < fill; c++) { free (seq[c]); free (name[c]); }
-      }
-      if (count >= print_interval && (count % print_interval) < o.pool) {
-        int highest = 0;       /* cq->max_incompatible: the largest tolerance over all heaps (src/nearest.c:290-291,323-324) */
-        for (int d = 0; d < o.n_devices; d++) {
-          int v = 0, q0 = 0, q1 = query->aln->ntax;
-          uvaia_gpu_ctx *cx = uvaia_gpu_group_member (grp, d);
-          if (o.n_devices > 1) { uvaia_gpu_group_sync (grp); uvaia_gpu_group_query_shard (grp, d, &q0, &q1); if (q1 <= q0) continue; uvaia_gpu_set_active_queries (cx, q0, q1); }
-          if (!uvaia_gpu_max_tolerance (cx, &v) && v > highest) highest = v;
-          if (o.n_devices > 1) uvaia_gpu_set_active_queries (cx, 0, query->aln->ntax);
+        if (count >= print_interval && (count % print_interval) < o.pool) {
+          int highest = 0;       /* cq->max_incompatible: the largest tolerance over all heaps (src/nearest.c:290-291,323-324) */
+          for (int d = 0; d < o.n_devices; d++) {
+            int v = 0, q0 = 0, q1 = query->aln->ntax;
+            uvaia_gpu_ctx *cx = uvaia_gpu_group_member (grp, d);
+            if (o.n_devices > 1) { uvaia_gpu_group_sync (grp); uvaia_gpu_group_query_shard (grp, d, &q0, &q1); if (q1 <= q0) continue; uvaia_gpu_set_active_queries (cx, q0, q1); }
+            if (!uvaia_gpu_max_tolerance (cx, &v) && v > highest) highest = v;
+            if (o.n_devices > 1) uvaia_gpu_set_active_queries (cx, 0, query->aln->ntax);
+          }
+          fprintf (stderr, "Total: %d sequences analysed, %d saved, %d poorly resolved. Highest number of ACGT mismatches = %d in current neighbourhood. %.3lf secs elapsed. ",
+                   count, n_output, n_invalid, highest, biomcmc_update_elapsed_time (time1));
+          if (o.exclude_self) fprintf (stderr, " %d already present in query alignment.\n", same_name); else fprintf (stderr, "\n");
         }
-        fprintf (stderr, "Total: %d sequences analysed, %d saved, %d poorly resolved. Highest number of ACGT mismatches = %d in current neighbourhood. %.3lf secs elapsed. ",
-                 count, n_output, n_invalid, highest, biomcmc_update_elapsed_time (time1));
-        if (o.exclude_self) fprintf (stderr, " %d already present in query alignment.\n", same_name); else fprintf (stderr, "\n");
       }
+      del_readfasta (rfas);
     }
-    del_readfasta (rfas);
     fprintf (stderr, "Finished reading file %s in %.3lf secs;\n", o.ref[j], biomcmc_update_elapsed_time (time0));
     fprintf (stderr, "Total of %d sequences read; %d saved sequences include closest neighbours and intermediate, %d too ambiguous (excluded). %.3lf secs elapsed. \n",
              count, n_output, n_invalid, biomcmc_update_elapsed_time (time1));
     if (o.exclude_self) fprintf (stderr, " %d reference sequences already present in query alignment (based on name only).\n", same_name);
   }
+  if (o.device_parse) search_parse_close (&parse, parse_bytes);
   if (outstream) {
     biomcmc_close_compress (outstream);
     fprintf (stderr, "Saved %d sequences to file %s , %.3lf secs elapsed.\n", n_output, outfilename, biomcmc_update_elapsed_time (time0));

@@ -49,3 +49,18 @@ uvdb_window_choose (uint64_t n_kept, uint64_t pool, uint64_t bytes_per_ref, uint
   if (w > WINDOW_MAX) w = WINDOW_MAX / unit * unit;
   return w ? (int64_t) w : -1;
 }
+
+uint64_t
+uvdb_parse_window (uint64_t pool, uint64_t request, uint64_t bytes_per_ref, uint64_t free_bytes)
+{
+  if (pool < 1 || pool > WINDOW_MAX) return 0;
+  if (!request) request = 65536;
+  if (request > WINDOW_MAX) request = WINDOW_MAX;
+  uint64_t w = (request + pool - 1) / pool * pool;
+  if (w > WINDOW_MAX) w = WINDOW_MAX / pool * pool;
+  if (free_bytes && bytes_per_ref) {
+    const uint64_t fit = free_bytes / 2 / bytes_per_ref / pool * pool;
+    if (fit < w) w = fit;
+  }
+  return w < pool ? pool : w;
+}

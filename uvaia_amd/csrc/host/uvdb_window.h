@@ -35,6 +35,13 @@ int uvdb_window_span (const uint64_t *keep, uint64_t a, uint64_t b, uint64_t *fi
  * search and for what the runtime itself keeps -- and not a tuned figure. */
 int64_t uvdb_window_choose (uint64_t n_kept, uint64_t pool, uint64_t bytes_per_ref, uint64_t free_bytes);
 
+/* The window of `uvaia -r --device-parse`: how many accepted references are resident -- planes and text -- before they are searched and
+ * cleared.  A multiple of the pool and at least one pool, because a flush must end on a pool boundary for the pools to be those of the
+ * command without the option.  request rounded up to a multiple of the pool (0: the smallest multiple that is >= 65 536), lowered to the
+ * largest multiple of the pool whose bytes_per_ref * window fit half of free_bytes, but never below one pool (free_bytes 0 = unknown: not
+ * lowered), and to what the engine counts in an int.  0 for a pool below 1 or beyond that count. */
+uint64_t uvdb_parse_window (uint64_t pool, uint64_t request, uint64_t bytes_per_ref, uint64_t free_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,14 @@ struct uvaia_gpu_ctx {
     uint32_t run_cut = 0xFFFFFFu;                         // longest exception run of a record (uvaia_gpu_rows_set_run_cut)
     std::vector<Event> evs; double ms[3] = {0., 0., 0.};  // per-kernel time of census, gather, exception fill
   } rows;
+  // ---- text row store (host_text.inc): the cleaned text of the references a command appended from device memory, kept as text next to the
+  // resident database so that those that enter a heap can be written out; rows of nchar rounded up to 16 bytes, 16-byte aligned
+  struct Text {
+    DevBuf<uint8_t> d_store, d_out;                       // cap rows of the store; the gathered rows of one round of uvaia_gpu_text_rows
+    DevBuf<int> d_idx;
+    size_t cap = 0, n = 0;
+    Event ev[4]; double ms[2] = {0., 0.};                 // device time of the gathers in, of the gathers out
+  } text;
   // ---- windowed search over a packed database larger than device memory (host_window.inc): two staging slots of whole file tiles filled by a copy
   // stream of their own, and (--acgt) the four-plane image of the window loaded last, which the text is decoded from
   struct Window {

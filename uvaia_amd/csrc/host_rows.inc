@@ -3,23 +3,12 @@
 
 namespace {
 
-// A block of rows handed in by device pointer: it must be device memory of the context's device (asked of the runtime, the pointer is not
-// dereferenced before) and rows 0 .. last_row must lie inside its allocation.
+// A block of rows handed in by device pointer: it must be device memory of the context's device and rows 0 .. last_row must lie inside its
+// allocation (rows_block.h has the check).
 int rows_check_block(uvaia_gpu_ctx *c, const void *d_rows, size_t pitch, long long last_row)
 {
-  if (!d_rows) return fail(c, UVAIA_GPU_EINVAL, "NULL rows");
-  if (pitch < (size_t)c->nchar) return fail(c, UVAIA_GPU_EINVAL, "pitch %zu is below the %d sites of a row", pitch, c->nchar);
-  hipPointerAttribute_t at;
-  memset(&at, 0, sizeof at);
-  if (hipPointerGetAttributes(&at, d_rows) != hipSuccess) { (void)hipGetLastError(); return fail(c, UVAIA_GPU_EINVAL, "the rows are not in device memory"); }
-  if (at.type != hipMemoryTypeDevice || at.device != c->device)
-    return fail(c, UVAIA_GPU_EINVAL, "the rows must be in the memory of device %d (memory type %d, device %d)", c->device, (int)at.type, at.device);
-  hipDeviceptr_t base = nullptr; size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(d_rows)) != hipSuccess) { (void)hipGetLastError(); return fail(c, UVAIA_GPU_EINVAL, "the rows are not inside a device allocation"); }
-  const size_t off = (size_t)(reinterpret_cast<const char *>(d_rows) - reinterpret_cast<const char *>(base));
-  if (last_row >= 0 && (off > size || (size_t)last_row > (size - off) / pitch || (size_t)last_row * pitch + (size_t)c->nchar > size - off))
-    return fail(c, UVAIA_GPU_EINVAL, "row %lld ends beyond the device allocation the rows lie in (%zu bytes from its start, %zu in all)", last_row, off, size);
-  return 0;
+  char msg[256];
+  return rows_block_ok(d_rows, pitch, c->nchar, c->device, last_row, msg, sizeof msg) ? 0 : fail(c, UVAIA_GPU_EINVAL, "%s", msg);
 }
 
 // largest row a selection names (row_index NULL: rows 0 .. n_sel - 1); negative entries are refused

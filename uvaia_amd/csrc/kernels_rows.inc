@@ -20,29 +20,8 @@ static __device__ __forceinline__ void rows_class_table(uint8_t *cls)
   __syncthreads();
 }
 
-// sites site0 .. site0 + 15 of a row (site0 < nchar, a multiple of 16); bytes at and beyond nchar read 'N'
-static __device__ __forceinline__ uint4 rows_load16(const uint8_t *row, int nchar, int site0)
-{
-  const uint8_t *p = row + site0;
-  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && site0 + 16 <= nchar) return *reinterpret_cast<const uint4 *>(p);
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p) & ~(uintptr_t)3, end = reinterpret_cast<uintptr_t>(row) + (size_t)nchar;
-  const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
-  uint32_t w[5], o[4];
-#pragma unroll
-  for (int i = 0; i < 5; i++) w[i] = (a + 4 * i < end) ? *reinterpret_cast<const uint32_t *>(a + 4 * i) : 0x4E4E4E4Eu;     // (a dword that starts inside the row)
-#pragma unroll
-  for (int i = 0; i < 4; i++) o[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], sh);
-  const int rem = nchar - site0;
-  if (rem < 16) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int keep = min(max(rem - 4 * i, 0), 4);                      // bytes of this dword that belong to the row
-      const uint32_t m = keep == 4 ? 0xFFFFFFFFu : ((1u << (8 * keep)) - 1u);
-      o[i] = (o[i] & m) | (0x4E4E4E4Eu & ~m);
-    }
-  }
-  return make_uint4(o[0], o[1], o[2], o[3]);
-}
+// sites site0 .. site0 + 15 of a row (site0 < nchar, a multiple of 16); bytes at and beyond nchar read 'N' (rows_block.h has the load)
+static __device__ __forceinline__ uint4 rows_load16(const uint8_t *row, int nchar, int site0) { return rows_load16_fill<0x4E4E4E4Eu>(row, nchar, site0); }
 
 // block-wide exclusive scans in thread order (all ROWS_TPB threads call them); wsh: four ints of LDS
 static __device__ __forceinline__ uint32_t rows_scan_sum(uint32_t v, uint32_t *wsh, uint32_t &total)

@@ -21,6 +21,9 @@
 //     transpose through an XOR-swizzled LDS image so that every row's 128 characters of a word group leave as eight 16-byte stores.
 //     overlay: the exception runs ('-', '?', 'X', 'O', '.': the planes hold them all as the empty set) are written over the decoded rows,
 //     one wave per run, the lanes spread over its length.  Prep and queue then run on these rows as on rows that came as text.
+//   * device pushes (uvaia_clust_push_device): the rows come as text that is already in device memory (what the FASTA parser leaves behind,
+//     uvaia_gpu_fasta_rows), at any pitch and alignment.  rows_in: one block per row copies its nchar bytes to the store or the staging row
+//     and pads it with zero bytes, as the host's copy of uvaia_clust_push does; prep and queue then run as on any other push.
 //   * keep medoids (uvaia_clust_keep_medoids): the second residency mode.  A row is read again after phase 2 has placed it only if it
 //     founded a cluster, so only founders are kept: the rows of a push land in a staging buffer, the queue kernel reads the row it places
 //     and the founders of the running push from staging and earlier founders from their slot, and after it the founders of the push get
@@ -40,6 +43,7 @@
 
 #include "../../include/uvaia_cluster.h"
 #include "iupac_decode.h"
+#include "rows_block.h"
 
 namespace {
 
@@ -51,6 +55,7 @@ constexpr int UNROLL = 4;               // 16-B loads in flight per lane in a co
 constexpr int UTPB = 256;               // unpack: four waves, each with a transpose image of its own (4 x 8 KiB of LDS)
 constexpr int UGROUPS = 16;             // unpack: word groups per work unit (a 29 903-site alignment is 15 units per tile)
 constexpr int OTPB = 256;               // overlay: one block per row, one wave per run
+constexpr int RTPB = 256;               // rows in: one block per row, 16 sites per thread
 constexpr int KTPB = 256;               // keep medoids: rows of a push per block of the founder prefix sum
 constexpr int SLAB_ROWS = 65536;        // keep medoids: default rows per slab (1.96 GB at 29 952 B per row); a design choice, not measured
 
@@ -370,6 +375,21 @@ __global__ __launch_bounds__(OTPB) void clust_overlay_runs_kernel(uint8_t *__res
   }
 }
 
+// uvaia_clust_push_device: block i copies row row_index[i] (NULL: row i) of a block of text rows in device memory -- `pitch` bytes apart, no
+// alignment assumed -- to row i of dst (the place of the push in the store, or the staging buffer: 16-byte aligned, dst_pitch a multiple of
+// 64).  16 sites per thread (rows_block.h: one dwordx4 load where the source piece is aligned, five aligned dwords otherwise; no dword is
+// touched that holds no byte of the row), one dwordx4 store each; the bytes from nchar to dst_pitch are zero, which never differ.
+__global__ __launch_bounds__(RTPB) void clust_rows_in_kernel(const uint8_t *__restrict__ rows, size_t pitch, int nchar, const int *__restrict__ row_index,
+                                                             uint8_t *__restrict__ dst, size_t dst_pitch)
+{
+  const int r = row_index ? row_index[blockIdx.x] : (int)blockIdx.x;
+  const uint8_t *row = rows + (size_t)r * pitch;
+  uint4 *out = reinterpret_cast<uint4 *>(dst + (size_t)blockIdx.x * dst_pitch);
+  const int n16 = (int)(dst_pitch >> 4);
+  for (int t = threadIdx.x; t < n16; t += RTPB)
+    out[t] = (t * 16 < nchar) ? rows_load16_fill<0u>(row, nchar, t * 16) : make_uint4(0u, 0u, 0u, 0u);
+}
+
 // uvaia_clust_rows: row k of dst = row ord[k] of the store (whole pitch, 16 bytes per thread)
 template <class Rows>
 __global__ __launch_bounds__(256) void clust_gather_rows_kernel(const Rows rows, const int *__restrict__ ord, uint8_t *__restrict__ dst)
@@ -469,7 +489,7 @@ struct uvaia_clust_ctx {
   DevBuf<int> d_qoff, d_qlist, d_mcount, d_mord, d_mst;    // d_mord, d_mst (and d_mloc): m_cap slots per queue
   DevBuf<uint8_t> d_tiles, d_gather;                       // packed pushes: the tiles of a push; uvaia_clust_rows: the gathered rows
   DevBuf<uint32_t> d_xoff; DevBuf<uint2> d_xrec;           // packed pushes: record offsets per row of the push, and the records
-  DevBuf<int> d_gord;
+  DevBuf<int> d_gord, d_rsel;                              // the ordinals of a gather; device pushes: the rows selected from the caller's block
   size_t rows_cap = 0;
   int m_cap = 0;
   long long pushed = 0;
@@ -486,7 +506,7 @@ struct uvaia_clust_ctx {
   std::vector<int> queue_of;               // queue of every pushed row
   std::vector<uint8_t> h_rows;
   std::vector<uint32_t> h_xoff;
-  double prep_ms = 0, queue_ms = 0, merge_ms = 0, decode_ms = 0, overlay_ms = 0;
+  double prep_ms = 0, queue_ms = 0, merge_ms = 0, decode_ms = 0, overlay_ms = 0, rows_in_ms = 0;
   bool finished = false, broken = false;
   // after finish: clusters in the final order
   std::vector<long long> r_medoid, r_offsets, r_members;
@@ -1021,6 +1041,43 @@ int uvaia_clust_push_packed(uvaia_clust_ctx *c, int n, const void *planes, const
       }))) return rc;
   if ((rc = push_lists(c, first, n, queue))) return rc;
   return push_kernels(c, dst, first, n, nullptr);
+}
+
+int uvaia_clust_push_device(uvaia_clust_ctx *c, int n, const void *d_rows, size_t pitch, const int *row_index, const int *queue)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (int rc = push_check(c, n, d_rows != nullptr, queue)) return rc;
+  if (!n) return 0;
+  // the block, before anything is launched: the largest row the selection names must lie inside the allocation the pointer belongs to
+  long long last = row_index ? -1 : (long long)n - 1;
+  for (int i = 0; row_index && i < n; i++) {
+    if (row_index[i] < 0) return cfail(c, UVAIA_GPU_EINVAL, "row_index[%d] = %d is negative", i, row_index[i]);
+    last = std::max<long long>(last, row_index[i]);
+  }
+  hipSetDevice(c->device);
+  char msg[256];
+  if (!rows_block_ok(d_rows, pitch, c->nchar, c->device, last, msg, sizeof msg)) return cfail(c, UVAIA_GPU_EINVAL, "%s", msg);
+  int rc;
+  const long long first = c->pushed;
+  uint8_t *dst = nullptr;
+  if ((rc = push_rows_dst(c, first, n, &dst))) return rc;
+  if (row_index) {
+    if ((rc = reserve_idle(c, c->d_rsel, (size_t)n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_rsel, row_index, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  }
+  if ((rc = timed(c, c->rows_in_ms, [&] {
+        hipLaunchKernelGGL(clust_rows_in_kernel, dim3((unsigned)n), dim3(RTPB), 0, c->stream, reinterpret_cast<const uint8_t *>(d_rows), pitch, c->nchar,
+                           row_index ? c->d_rsel.p : (const int *)nullptr, dst, c->pitch);
+      }))) return rc;                                  // (the caller's rows have been read: it may overwrite them)
+  if ((rc = push_lists(c, first, n, queue))) return rc;
+  return push_kernels(c, dst, first, n, nullptr);
+}
+
+int uvaia_clust_push_device_ms(uvaia_clust_ctx *c, double *rows_in_ms)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (rows_in_ms) *rows_in_ms = c->rows_in_ms;
+  return 0;
 }
 
 int uvaia_clust_rows(uvaia_clust_ctx *c, const int64_t *ordinal, int n, char *rows, size_t pitch)

@@ -31,6 +31,7 @@
 
 #include "../../include/uvaia_gpu.h"
 #include "iupac_decode.h"
+#include "rows_block.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // small helpers
@@ -96,6 +97,7 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "host_batch.inc"
 #include "host_resident.inc"
 #include "host_rows.inc"
+#include "host_text.inc"
 #include "host_shards.inc"
 #include "host_ball.inc"
 #include "host_window.inc"
