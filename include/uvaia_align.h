@@ -79,12 +79,28 @@ int  uvaia_align_load_device (uvaia_aligner *a, const void *d_bytes, const int64
 int  uvaia_align_run (uvaia_aligner *a);
 int  uvaia_align_sync (uvaia_aligner *a);
 int  uvaia_align_fetch (uvaia_aligner *a, char *aln, int *score);
-/* Instead of the fetch (the copy of uvaia_amd/csrc/uvaia_align.hip:819 and everything a caller then does to the text to bring it back to a
+/* Instead of the fetch (the copy in uvaia_align_fetch of uvaia_amd/csrc/uvaia_align.hip and everything a caller then does to the text to bring it back to a
  * GPU): where the rows of the last completed run lie in device memory -- *n rows of ref_len characters, *pitch = ref_len + 1 bytes apart,
  * on HIP device *device (any of the four may be NULL).  They stay valid from the end of the run (uvaia_align_run returns when its kernels
  * are done; uvaia_align_sync otherwise) until the next load or close, and go to the engine as they are (include/uvaia_gpu.h, "rows that
  * are already in device memory").  UVAIA_ALIGN_ESTATE before a run has completed. */
 int  uvaia_align_device_rows (uvaia_aligner *a, const void **d_rows, size_t *pitch, int *n, int *device);
+
+/* The characters the projection drops (the `I` operations of update_query_aligned, src/align.c:366-390; the reference has no such output).
+ * An insertion run is a maximal stretch of I operations of one query's alignment: ref_pos reference sites (0 .. ref_len; M, X and D
+ * operations) and seq_pos query characters (M, X and I operations) lie to its left, and its bases are seq[seq_pos .. seq_pos + length). */
+typedef struct { int query, ref_pos, seq_pos, length; } uvaia_align_insertion;
+/* src/align.c:366-390: keep the runs of the following runs of this aligner (off by default; rows, scores and the statistics do not change).
+ * capacity_records is the record buffer of one kernel launch, 0 = the library's choice; a launch that fills it runs the queries concerned
+ * again with a buffer as large as they need, so no capacity makes a call fail or lose a record (tests pass a tiny one to reach that path) */
+int  uvaia_align_set_insertions (uvaia_aligner *a, int on, size_t capacity_records);
+/* src/align.c:366-390: the runs of the last completed run (uvaia_align_run / _sync / _batch) with the option on, and all their bases;
+ * UVAIA_ALIGN_ESTATE with the option off or before such a run has completed.  Either pointer may be NULL. */
+int  uvaia_align_insertion_counts (uvaia_aligner *a, long long *n_records, long long *n_bases);
+/* src/align.c:366-390: the records sorted by (query, ref_pos) and their bases one after the other in that order (n_records records, n_bases
+ * bytes, no NUL; either may be NULL).  The bases are gathered on the device from the aligner's own copy of the pool, so they are there
+ * after uvaia_align_load_device too.  Valid until the next load or close.  UVAIA_ALIGN_ESTATE as above. */
+int  uvaia_align_fetch_insertions (uvaia_aligner *a, uvaia_align_insertion *rec, char *bases);
 
 /* work of the last run: M-wavefront cells computed, wavefront bytes written + read by the recurrences (13 + 20 per cell),
  * kernel passes (queries that find the workspace's pool empty are run again in a less crowded pass), kernel time in ms */

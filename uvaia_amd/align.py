@@ -9,7 +9,8 @@ from . import capi
 SYMBOLS = [
     "uvaia_align_default_options", "uvaia_align_open", "uvaia_align_close", "uvaia_align_last_error", "uvaia_align_batch",
     "uvaia_align_load", "uvaia_align_load_block", "uvaia_align_run", "uvaia_align_sync", "uvaia_align_fetch", "uvaia_align_stats",
-    "uvaia_align_device_rows", "uvaia_align_load_device",
+    "uvaia_align_device_rows", "uvaia_align_load_device", "uvaia_align_set_insertions", "uvaia_align_insertion_counts",
+    "uvaia_align_fetch_insertions",
 ]
 
 
@@ -22,6 +23,10 @@ class AlignError(RuntimeError):
 class Options(C.Structure):
     _fields_ = [("mismatch", C.c_int), ("gap_opening", C.c_int), ("gap_extension", C.c_int), ("min_wavefront_length", C.c_int),
                 ("max_distance_threshold", C.c_int), ("workspace_bytes", C.c_size_t), ("max_blocks", C.c_int)]
+
+
+class Insertion(C.Structure):
+    _fields_ = [("query", C.c_int), ("ref_pos", C.c_int), ("seq_pos", C.c_int), ("length", C.c_int)]
 
 
 _ready = False
@@ -48,6 +53,9 @@ def _lib():
         L.uvaia_align_fetch.argtypes = [vp, C.c_void_p, pi]
         L.uvaia_align_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_double), pi, C.POINTER(C.c_double)]
         L.uvaia_align_device_rows.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), pi, pi]
+        L.uvaia_align_set_insertions.argtypes = [vp, C.c_int, C.c_size_t]
+        L.uvaia_align_insertion_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        L.uvaia_align_fetch_insertions.argtypes = [vp, C.c_void_p, C.c_void_p]
         _ready = True
     return L
 
@@ -131,6 +139,24 @@ class Aligner:
         self._chk(self.L.uvaia_align_batch(self.ptr, arr, lens, n, rows.ctypes.data, score.ctypes.data_as(C.POINTER(C.c_int))))
         self.n = n
         return score, rows[:, :self.ref_len]
+
+    def set_insertions(self, on, capacity=0):
+        """keep the insertion runs of the following runs (uvaia_align_set_insertions); capacity: records a kernel launch has room for,
+        0 = the library's choice (a launch that fills it runs the queries concerned again: nothing is lost)"""
+        self._chk(self.L.uvaia_align_set_insertions(self.ptr, 1 if on else 0, capacity))
+
+    def insertions(self):
+        """the insertion runs of the last completed run as a list of (query, ref_pos, seq_pos, bases), sorted by (query, ref_pos)"""
+        n_rec, n_bases = C.c_longlong(0), C.c_longlong(0)
+        self._chk(self.L.uvaia_align_insertion_counts(self.ptr, C.byref(n_rec), C.byref(n_bases)))
+        rec = (Insertion * max(n_rec.value, 1))()
+        bases = C.create_string_buffer(max(n_bases.value, 1))
+        self._chk(self.L.uvaia_align_fetch_insertions(self.ptr, C.cast(rec, C.c_void_p), C.cast(bases, C.c_void_p)))
+        out, at, raw = [], 0, bases.raw
+        for r in rec[:n_rec.value]:
+            out.append((r.query, r.ref_pos, r.seq_pos, raw[at:at + r.length]))
+            at += r.length
+        return out
 
     def stats(self):
         cells, nbytes, passes, ms = C.c_ulonglong(0), C.c_double(0), C.c_int(0), C.c_double(0)

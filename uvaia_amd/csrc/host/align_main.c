@@ -9,6 +9,9 @@
  *
  * --device-parse (no counterpart either, off by default): the input is split into sequences on the GPU and handed to the aligner in device
  * memory, see align_device_parse below.  Without the option the command takes the read loop of main as it was.
+ *
+ * --insertions (no counterpart either): the characters the projection drops (the I operations of src/align.c:366-390) go to a table, one
+ * line per insertion run, from the records the aligner keeps (include/uvaia_align.h, uvaia_align_fetch_insertions).
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -35,6 +38,65 @@ packer_add_pool (struct uvdb_packer *p, uvaia_aligner *al, char **name, int fill
   return uvdb_packer_add_block (p, d_rows, pitch, n, name);
 }
 
+/* `uvaialign --insertions <file>`: sequence,ref_pos,length,bases for every insertion run of every aligned sequence, in the order the
+ * sequences are written and by ref_pos within one; names go out raw, as the search's table writes them */
+struct ins_table {
+  file_compress_t out;                  /* NULL without --insertions */
+  long n_seqs; long long n_bases;
+  uvaia_align_insertion *rec; char *bases, *line;
+  size_t rec_cap, bases_cap, line_cap;
+  char err[512];
+};
+
+static void
+ins_table_open (struct ins_table *t, const char *filename)
+{
+  static const char header[] = "sequence,ref_pos,length,bases\n";
+  memset (t, 0, sizeof *t);
+  if (!filename) return;
+  t->out = biomcmc_open_compress (filename, "w");
+  if (biomcmc_write_compress (t->out, header) != (int) strlen (header)) fprintf (stderr, "File %s may not be correctly compressed: its first line could not be written.\n", filename);
+}
+
+static void
+ins_table_close (struct ins_table *t)
+{
+  if (t->out) biomcmc_close_compress (t->out);
+  free (t->rec); free (t->bases); free (t->line);
+  t->out = NULL; t->rec = NULL; t->bases = NULL; t->line = NULL;
+}
+
+/* the runs of the aligner's last run: its queries are name[0 ..] */
+static int
+ins_table_add (struct ins_table *t, uvaia_aligner *al, char **name)
+{
+  long long n_rec = 0, n_bases = 0;
+  if (!t->out) return 0;
+  if (uvaia_align_insertion_counts (al, &n_rec, &n_bases)) { snprintf (t->err, sizeof t->err, "%s", uvaia_align_last_error (al)); return -1; }
+  if (!n_rec) return 0;
+  if ((size_t) n_rec > t->rec_cap) { t->rec_cap = (size_t) n_rec * 2; t->rec = (uvaia_align_insertion *) biomcmc_realloc (t->rec, t->rec_cap * sizeof (uvaia_align_insertion)); }
+  if ((size_t) n_bases > t->bases_cap) { t->bases_cap = (size_t) n_bases * 2; t->bases = (char *) biomcmc_realloc (t->bases, t->bases_cap); }
+  if (uvaia_align_fetch_insertions (al, t->rec, t->bases)) { snprintf (t->err, sizeof t->err, "%s", uvaia_align_last_error (al)); return -1; }
+  int bad = 0;
+  size_t at = 0;
+  for (long long r = 0; r < n_rec; r++) {
+    const uvaia_align_insertion *c = t->rec + r;
+    const char *nm = name[c->query];
+    const size_t need = strlen (nm) + (size_t) c->length + 64;
+    if (need > t->line_cap) { t->line_cap = need * 2; t->line = (char *) biomcmc_realloc (t->line, t->line_cap); }
+    int w = snprintf (t->line, t->line_cap, "%s,%d,%d,", nm, c->ref_pos, c->length);
+    memcpy (t->line + w, t->bases + at, (size_t) c->length);
+    w += c->length;
+    t->line[w++] = '\n'; t->line[w] = '\0';
+    bad += biomcmc_write_compress (t->out, t->line) != w;
+    at += (size_t) c->length;
+    if (!r || c[-1].query != c->query) t->n_seqs++;
+  }
+  t->n_bases += n_bases;
+  if (bad) fprintf (stderr, "File %s may not be correctly compressed, %d error%s occurred when saving insertions.\n", t->out->filename, bad, bad > 1 ? "s" : "");
+  return 0;
+}
+
 /* `uvaialign --device-parse`: the text is read in blocks (fasta_blocks.h) and split into records on the GPU (uvaia_gpu_fasta_scan); the
  * filters of the fill loop in main run on the integers of the record table and the A C G T counts; the survivors of a scan go, a pool at a
  * time and in record order, from the parser's device memory into the aligner's (uvaia_gpu_fasta_sequences, uvaia_align_load_device).  Only
@@ -45,6 +107,7 @@ struct align_parse {
   uvaia_gpu_fasta *fasta;
   uvaia_aligner *al;
   struct uvdb_packer *pk;               /* NULL without --packed */
+  struct ins_table *ins;
   file_compress_t outstream;
   bool to_screen, write_text;
   size_t aln_length;
@@ -111,6 +174,10 @@ align_parse_records (void *user, char *text, size_t consumed, int n_records, cha
       return -1;
     }
     if (!uvaia_align_stats (d->al, NULL, NULL, NULL, &ms)) d->align_ms += ms;
+    if (ins_table_add (d->ins, d->al, d->name)) {
+      snprintf (err, errlen, "%s (insertions of the pool that starts with sequence %s; %d sequences were written before)", d->ins->err, d->name[0], d->n_output);
+      return -1;
+    }
     if (d->pk && packer_add_pool (d->pk, d->al, d->name, fill)) {
       snprintf (err, errlen, "packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", d->n_pool, fill, d->name[0], d->pk->err, d->pk->kept);
       return -1;
@@ -151,6 +218,7 @@ align_device_parse (struct align_parse *d, const char **fasta, int n_fasta, size
     if (rc || broken) {
       if (d->outstream) biomcmc_close_compress (d->outstream);
       if (d->pk) uvdb_packer_close (d->pk);
+      ins_table_close (d->ins);
       if (broken) biomcmc_error ("%s", failed);
       const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
       biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaialign` without it reads this file line by line)" : "");
@@ -175,13 +243,14 @@ main (int argc, char **argv)
   size_t parse_block = FASTA_BLOCK_BYTES;
   int devices[64], n_devices = 0;
   double ambig = 0.5, ambig_r = 0.5;
-  const char *out = NULL, *ref_file = NULL, *packed = NULL;
+  const char *out = NULL, *ref_file = NULL, *packed = NULL, *insertions = NULL;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"stdout", no_argument, 0, 1000}, {"ambiguity", required_argument, 0, 'a'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002},
     {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"compact", no_argument, 0, 1004},
-    {"device-parse", no_argument, 0, 1005}, {"parse-block", required_argument, 0, 1006}, {0, 0, 0, 0}};
+    {"device-parse", no_argument, 0, 1005}, {"parse-block", required_argument, 0, 1006}, {"insertions", required_argument, 0, 1007},
+    {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
     case 'v': version = 1; break;
@@ -197,6 +266,7 @@ main (int argc, char **argv)
     case 1004: compact = 1; break;
     case 1005: device_parse = 1; break;
     case 1006: parse_block = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the block size of --device-parse in bytes) */
+    case 1007: insertions = optarg; break;
     case 'A': ambig_r = atof (optarg); break;
     default: errors++;
   }
@@ -209,7 +279,7 @@ main (int argc, char **argv)
   }
   if (help || errors || !ref_file || n_fasta < 1 || pool < 1) {
     printf ("%s \nAlign query sequences against a reference\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] [--device-parse] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] [--device-parse] [--insertions <file>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  --stdout                         print alignment to stdout (to redirect/pipe) instead of compress to file; much faster but may generate a big output\n");
     printf ("  -p, --pool=<int>                 How many query sequences are read in batch, to be aligned in parallel (defaults to 256 per thread)\n");
@@ -228,6 +298,9 @@ main (int argc, char **argv)
     printf ("  --device-parse                   split the text into sequences on the GPU instead of reading it line by line, and hand them to the aligner where\n");
     printf ("                                   they lie: the same output, from regular FASTA only (a NUL byte, text before the first header and a header\n");
     printf ("                                   without sequence are refused).  One GPU only; goes with -o, --stdout, --packed and --compact\n");
+    printf ("  --insertions=<file>              write the characters the alignment drops -- insertions relative to the reference -- as a table\n");
+    printf ("                                   sequence,ref_pos,length,bases: one line per run, ref_pos = reference sites to its left (0 = before the first);\n");
+    printf ("                                   compressed by the file's suffix (gz, xz, bz2).  Goes with every other option\n");
     printf ("  --parse-block=<bytes>            with --device-parse: the text is read in blocks of this size (64 to 1073741824, default 67108864); a record\n");
     printf ("                                   must fit one\n");
     if (help) {
@@ -291,6 +364,12 @@ main (int argc, char **argv)
     fprintf (stderr, "Aligned sequences with at least %d valid sites will be packed into %s.\n", pk.non_n_ref, packed);
   }
   file_compress_t outstream = (to_screen || !write_text) ? NULL : biomcmc_open_compress (outfilename, "w");
+  struct ins_table ins;
+  ins_table_open (&ins, insertions);
+  if (insertions) {
+    for (int d = 0; d < n_devices; d++) if (uvaia_align_set_insertions (gpu[d], 1, 0)) biomcmc_error ("%s", uvaia_align_last_error (gpu[d]));
+    fprintf (stderr, "Insertions relative to the reference will be saved into file %s.\n", insertions);
+  }
   char **seq = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *)), **name = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *));
   int *len = (int *) biomcmc_malloc ((size_t) pool * sizeof (int));
   char *aln = write_text ? (char *) biomcmc_malloc ((size_t) pool * (aln_length + 1)) : NULL;
@@ -302,7 +381,7 @@ main (int argc, char **argv)
   if (device_parse) {
     struct align_parse d;
     memset (&d, 0, sizeof d);
-    d.al = gpu[0]; d.pk = packed ? &pk : NULL; d.outstream = outstream; d.to_screen = to_screen; d.write_text = write_text;
+    d.al = gpu[0]; d.pk = packed ? &pk : NULL; d.ins = &ins; d.outstream = outstream; d.to_screen = to_screen; d.write_text = write_text;
     d.aln_length = aln_length; d.ambig = ambig; d.pool = pool; d.name = name; d.aln = aln; d.time1 = time1;
     align_device_parse (&d, fasta, n_fasta, parse_block, devices[0]);
     count = d.count; n_output = d.n_output; align_ms = d.align_ms;
@@ -357,13 +436,24 @@ main (int argc, char **argv)
           const int a = (int) ((long long) fill * failed / n_devices), b = (int) ((long long) fill * (failed + 1) / n_devices);
           if (outstream) biomcmc_close_compress (outstream);
           if (packed) uvdb_packer_close (&pk);
+          ins_table_close (&ins);
           biomcmc_error ("%s (counted from sequence %s, the first of the %d handed to device %d; %d sequences were written before)",
                          uvaia_align_last_error (gpu[failed]), name[a], b - a, failed, n_output);
+        }
+        for (int d = 0; d < n_devices; d++) {   /* the slices of the pool in their order: a record counts its query from the slice's start */
+          const int a = (int) ((long long) fill * d / n_devices), b = (int) ((long long) fill * (d + 1) / n_devices);
+          if (b > a && ins_table_add (&ins, gpu[d], name + a)) {
+            if (outstream) biomcmc_close_compress (outstream);
+            if (packed) uvdb_packer_close (&pk);
+            ins_table_close (&ins);
+            biomcmc_error ("%s (insertions of the %d sequences from %s on, handed to device %d; %d sequences were written before)", ins.err, b - a, name[a], d, n_output);
+          }
         }
         if (packed && packer_add_pool (&pk, gpu[0], name, fill)) {   /* both files stay complete: close them before giving up */
           char msg[640];
           snprintf (msg, sizeof msg, "%s", pk.err);
           if (outstream) biomcmc_close_compress (outstream);
+          ins_table_close (&ins);
           const long kept = pk.kept;
           uvdb_packer_close (&pk);
           biomcmc_error ("packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", n_pool, fill, name[0], msg, kept);
@@ -393,6 +483,10 @@ main (int argc, char **argv)
     fprintf (stderr, "Packed %ld of %d aligned sequences (%zu sites) into %s; %ld too ambiguous.\n", kept, n_output, aln_length, packed, dropped);
     fprintf (stderr, "Device time: alignment %.3lf ms; census %.3lf ms, gather %.3lf ms, exception runs %.3lf ms.\n", align_ms, pk.rows_ms[0], pk.rows_ms[1], pk.rows_ms[2]);
     if (compact) fprintf (stderr, "Compact tiles: %ld encoded on the device (count and prefix %.3lf ms, emit %.3lf ms), %ld on the host.\n", pk.tiles_device, pk.encode_ms[0], pk.encode_ms[1], pk.tiles_host);
+  }
+  if (insertions) {
+    fprintf (stderr, "Insertions: %ld sequences with insertions, %lld inserted bases saved to file %s.\n", ins.n_seqs, ins.n_bases, insertions);
+    ins_table_close (&ins);
   }
   if (to_screen) fprintf (stderr, "Output %d aligned sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
   else if (!write_text) fprintf (stderr, "Aligned %d sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
