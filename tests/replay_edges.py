@@ -3,7 +3,8 @@ by launch_replay in host_launch.inc) to its edges -- walks of the tile bounds ov
 becomes needed after the tolerance rose, heaps whose entries tie on all six keys so that only the layout of src/min_heap.c decides who is
 evicted, candidates that tie the worst kept entry on keys 0..j-1 and differ by one at key j, tolerances on both sides of every entry of
 TB8_THR, ambiguity-word lists of exactly AMB_CAP and AMB_CAP + 1 words, ordinals with a high word, the last alignment length of the 16-bit
-scan -- and a small model (MinHeap, walk2, walk3) that says which edge an input reaches.  The model never judges a result: the oracle does.
+scan, consensus pre-scores cut at the batch snapshot in every word, bit and lane position of the cut walk -- and a small model (MinHeap,
+walk2, walk3, cut_walk) that says which edge an input reaches.  The model never judges a result: the oracle does.
 Deterministic and seeded; no GPU code here.  tests/test_replay_edges_cpu.py shows that every input reaches the edge it is built for,
 tests/test_replay_edges_gpu.py runs the inputs on the device.
 
@@ -33,7 +34,13 @@ The edge table: which line each group is aimed at (kernels_replay.inc unless ano
   F  range ends                        replay_kernel: `e[6] = (int)(unsigned)(ord & 0xffffffffll); e[7] = (int)(ord >> 32);`  replay_admit: `if ((lane & 7) == 7) v = (int)(ord >> 32);`  `const long long ord = ord_base + (rl - r_begin);`
                                        `const bool valid = (base_u + lane >= r_begin) && (base_u + lane < r_end);`  host_open.inc: `if (c->nchar > 49000) c->fullscan = true;`
                                        `return !c ? -2 : c->fullscan ? -1 : c->scan_variant;`  host_launch.inc: `if (c->fullscan) {` of launch_replay, `bool lean = lean_replay_context(c) && L.prefetch == 2 && lq_words == 0;`
-                                       host_open.inc: `c->use_ext = !c->fullscan && !c->acgt && tn.replay_extras != 1 && (c->scan_variant == 0 ||`  `c->replay_half = (want_half == 32 || want_half == 16 || want_half == 8) ? want_half : c->nq <= 8 ? 32 : c->nq <= 24 ? 16 : 8;`"""
+                                       host_open.inc: `c->use_ext = !c->fullscan && !c->acgt && tn.replay_extras != 1 && (c->scan_variant == 0 ||`  `c->replay_half = (want_half == 32 || want_half == 16 || want_half == 8) ? want_half : c->nq <= 8 ? 32 : c->nq <= 24 ? 16 : 8;`
+  C  the cut of the pre-score         kernels_consensus.inc, wave_truncated_consensus: `const int NW = W4 * 4, B = (NW + 63) / 64;`  `const int w_lo = min(lane * B, NW), w_hi = min(w_lo + B, NW);`
+                                       `for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o); if (lane >= o) incl += v; }`  `const unsigned long long reach = __ballot(snap > 0 && incl >= snap);`
+                                       `int mcur = excl;`  `if (mcur + pw >= snap) {`  `const uint32_t pmask = prefix_through_nth_bit(M, snap - mcur);`  `for (int k = 1; k < nth; k++) m &= m - 1;`
+                                       `r[3] = dbw[base + (size_t)(P - 1) * 256];`  consensus_kernel: `if (!done && mcur + pm >= snap) {`  `const uint32_t pmask = prefix_through_nth_bit(M, snap - mcur);`
+                                       replay_kernel: `const int4 rc = (mc_true >= snap) ? tr[r] : a;`  replay2_kernel: `cut[u] = CONS && mc_true >= snap;`  `m[u] = K3[u] - K0[u] - (cut[u] ? mc_true - snap : 0);`
+                                       `if (cut[u]) return K0[u] >= W[0];`  replay3_kernel: `const int m = V - K0 - (cut ? mc_true - snap : 0);`  host_open.inc: `c->W = (c->nchar + 31) / 32; c->W4 = (c->W + 3) / 4;`"""
 import collections
 import functools
 
@@ -169,7 +176,7 @@ def queries_for(case, regime):
 def _query(key, regime):
     case = CASES[key]
     seqs = queries_for(case, regime)
-    return O.Query(seqs, names(len(seqs), "q"), acgt=REGIMES[regime].acgt, ambig_q=1.0)
+    return O.Query(seqs, names(len(seqs), "q"), trim=case.meta.get("trim", 0), acgt=REGIMES[regime].acgt, ambig_q=1.0)
 
 
 def query(key, regime):
@@ -281,7 +288,8 @@ class MinHeap:
 
 def replay_model(scores, nbest, nchar, prefer_right=False, acgt=False):
     """The search of ONE query over untruncated score vectors (valid where no pre-score is cut: a single pool, or no constant-and-complete
-    column): src/nearest.c:488-508.  Returns the heap and, per reference, (entered, tolerance after it, worst kept key 0 after it)."""
+    column): src/nearest.c:488-508.  Returns the heap and, per reference, (entered, tolerance after it, worst kept key 0 after it).
+    What a cut pair's pre-score holds, and where its walk stops, is cut_walk's business (group C)."""
     h = MinHeap(nbest, prefer_right)
     trace = []
     for o, s in enumerate(scores):
@@ -410,6 +418,101 @@ def walk3(scores, nbest, nchar, half):
                 if len(st.entered) != n_in or st.T != T_used:
                     P = {x for x in needed(rnd, half * hb, half * (hb + 1)) if x > t}
     return st.entered, late, opened
+
+
+def _byte_table(chars, value=True, dtype=bool):
+    t = np.zeros(256, dtype=dtype)
+    for c in chars:
+        t[c] = value
+    return t
+
+
+_IS_ACGT = _byte_table(b"ACGTacgt")                               # src/utils.c:262
+_IS_INVALID = _byte_table(b"NnXx-?Oo.")                           # src/utils.c:263
+_IUPAC = np.zeros(256, dtype=np.uint8)
+for _c, _m in zip(b"ACGTMRWSYKVHDB", (1, 2, 4, 8, 3, 5, 9, 6, 10, 12, 7, 11, 13, 14)):
+    _IUPAC[_c] = _IUPAC[_c + 32] = _m
+
+CUT_WRONG = ("early", "late", "word", "carry", "noidx")
+CutWalk = collections.namedtuple("CutWalk", "cut counters col word bit lane pos mis_before mis_after match_after")
+
+
+def lane_split(nchar):
+    """(W4, NW, B, lanes that hold words) of wave_truncated_consensus: `c->W = (c->nchar + 31) / 32; c->W4 = (c->W + 3) / 4;`,
+    `const int NW = W4 * 4, B = (NW + 63) / 64;`, `const int w_lo = min(lane * B, NW), w_hi = min(w_lo + B, NW);`"""
+    W4 = ((nchar + 31) // 32 + 3) // 4
+    NW = 4 * W4
+    B = (NW + 63) // 64
+    return W4, NW, B, -(-NW // B)
+
+
+def _as_u8(x):
+    return np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.asarray(x, dtype=np.uint8)
+
+
+def cut_walk(consensus, idx_c, ref, snap, acgt, W4=None, wrong=None, every=None):
+    """The consensus pre-score of one reference as src/nearest.c:428-433 leaves it with maxdist = snap: the sites of idx_c are walked in order
+    and the walk stops right after the site at which the mismatch counter reaches snap.  Returns a CutWalk: cut (the counter reaches snap),
+    counters (default: ACGT matches, text matches, partial matches, valid pairs; --acgt: mismatches, pairs of two ACGT, 0, 0), and where the
+    cut falls: the column, its 32-site word and bit and -- given W4 -- the lane `word // B` of wave_truncated_consensus and the word's place
+    in that lane's range ("first", "inner", "last", or "only" where the range is one word); the set bits of the word's mismatch plane before
+    and after the cut bit, and the matching idx_c sites after it in the same word.  The model never judges a device result: the CPU test
+    holds its counters against oracle_lib.score4 / score_acgt.
+    wrong = one of CUT_WRONG gives the counters of a WRONG walk, kept to show that the inputs tell it from the right one: "early" / "late"
+    stop one mismatch before / after, "word" counts the whole word of the cut, "carry" loses the mismatches of the lanes in front when it
+    walks the lane of the cut (needs W4), "noidx" walks every column (against `every`, a query, where the consensus has no letter)."""
+    cons, ref = _as_u8(consensus), _as_u8(ref)
+    idx = np.asarray(idx_c, dtype=np.int64)
+    if wrong == "noidx":
+        cons = np.where(_IS_ACGT[cons], cons, _as_u8(every))
+        idx = np.arange(len(ref), dtype=np.int64)
+    a, b = ref[idx], cons[idx]
+    zero = np.zeros(len(idx), dtype=bool)
+    if acgt:
+        both = _IS_ACGT[a] & _IS_ACGT[b]
+        mis = both & (a != b)
+        planes, match = (mis, both, zero, zero), both & (a == b)
+    else:
+        valid = ~_IS_INVALID[a] & ~_IS_INVALID[b]
+        text = valid & (a == b)
+        match = text & _IS_ACGT[a]
+        planes, mis = (match, text, valid & ((_IUPAC[a] & _IUPAC[b]) != 0), valid), valid & ~match
+    cum = np.cumsum(mis)
+    n = len(idx)
+
+    def stop_at(count, lo=0, hi=n):
+        """sites walked when the walk over [lo, hi) stops right after its count-th mismatch (counted from lo)"""
+        if count <= 0:
+            return lo
+        local = np.cumsum(mis[lo:hi])
+        return lo + int(np.argmax(local >= count)) + 1 if len(local) and local[-1] >= count else hi
+    cut = bool(n and cum[-1] >= snap)
+    stop = stop_at(snap)
+    where = (None,) * 8
+    if cut:
+        col = int(idx[stop - 1])
+        w, bit = col // 32, col % 32
+        in_w = (idx // 32) == w
+        before, after = in_w & (idx < col), in_w & (idx > col)
+        lane = pos = None
+        if W4 is not None:
+            NW = 4 * W4
+            B = (NW + 63) // 64
+            lane = w // B
+            w_lo, w_hi = min(lane * B, NW), min(lane * B + B, NW)
+            pos = "only" if w_hi - w_lo == 1 else "first" if w == w_lo else "last" if w == w_hi - 1 else "inner"
+        where = (col, w, bit, lane, pos, int((mis & before).sum()), int((mis & after).sum()), int((match & after).sum()))
+    if wrong == "early":
+        stop = stop_at(snap - 1)
+    elif wrong == "late":
+        stop = stop_at(snap + 1)
+    elif wrong == "word" and cut:
+        stop = int(np.searchsorted(idx, 32 * (where[1] + 1)))
+    elif wrong == "carry" and cut:
+        B = (4 * W4 + 63) // 64
+        lo, hi = (int(np.searchsorted(idx, 32 * B * (where[3] + d))) for d in (0, 1))
+        stop = stop_at(snap, lo, hi)
+    return CutWalk(cut, tuple(int(p[:stop].sum()) for p in planes), *where)
 
 
 CASES = collections.OrderedDict()
@@ -902,6 +1005,220 @@ def _f_cases():
                       ["auto", "auto-acgt"], {"nchar": nchar, "wide": nchar > WIDE_ABOVE}))
 
 
+# ---------------------------------------------------------------------------------------------------------------------------- C
+# The cut of the consensus pre-score.  Heaps of C_NBEST.  Pool 0 is C_NBEST `lows` -- references with a few valid sites on idx_c and N everywhere else --
+# and nothing that enters after them: ROOT1 (one match, snap1 - 1 mismatches: the worst kept entry, T = snap1, the snapshot of pool 1), n1 - 1 lows of two
+# matches and snap1 + C_BIG mismatches, ROOT2 (three matches, snap2 - 1 mismatches) and lows of four matches and snap2 + C_BIG mismatches.  In pool 1 an EARLY
+# plant (fewer than snap1 mismatches) evicts ROOT1: T = snap1 + C_BIG + 1.  The plants follow: each is cut at snap1, passes the gate with exactly snap1
+# mismatches, keeps at least C_KEY0_MIN matches in front of its cut and so evicts one low of two matches.  Pool 1 holds n1 admissions, so its last one
+# leaves ROOT2 at the root: T = snap2, the snapshot of pool 2, where the same happens with snap2.  Fewer than C_NBEST references enter, so every plant is in
+# the final heap with its cut scores.  Every other reference of pools 1 and 2 is a decoy: the pool's snapshot of mismatches on the FIRST columns of idx_c (cut
+# with no match at all: it passes the gate and loses on key 0; uncut it would win), thirty more anywhere and N on the columns outside idx_c.
+# Query sets: `single` the clean probe alone (idx_c is every column); `trim` the same under trim = C_TRIM; `three` the probe, a query that differs from it on
+# the whole word C_OUT_WORD and on six more columns, and one that differs on 24 others and holds N at three (trim = C_TRIM: idx_c is a proper subset with
+# a whole word outside it; the plants have dozens of mismatches against the two other queries, whose tolerances stay at snap1, below the snapshot of pool 2);
+# `two` the probe and a query that differs from it at three columns, where ROOT1 holds that query's letters: its heap starts pool 1 with the tolerance
+# snap1 - 1, the snapshot is snap1 and no plant passes its gate.
+C_NBEST, C_KEY0_MIN, C_BIG, C_TRIM, C_OUT_WORD = 60, 5, 8, 40, 5
+C_SNAPS = (1, 2, 3, 40)
+C_GEOMETRIES = {2048: (64, 1, 64), 2049: (68, 2, 34), 4096: (128, 2, 64), 4200: (132, 3, 44)}      # columns: (NW, B, lanes that hold words) -- lane_split
+C_POOLS = (TILE, 2 * TILE + 9)
+C_PUSH = ["replay3", "replay3-h8", "replay2", "replay2-acgt", "wide", "wide-acgt"]
+C_RESIDENT = ["replay3-res-h32", "replay2-acgt-res"]
+# (columns, query set, snapshots of pools 1 and 2, pool): with more than one query the snapshot is the largest tolerance, so it cannot fall
+C_LIST = ((2048, "single", (2, 40), 0), (2048, "three", (1, 3), 1), (2049, "single", (3, 1), 1), (2049, "three", (2, 40), 0), (4096, "single", (40, 3), 1),
+          (4096, "three", (1, 2), 0), (4200, "single", (40, 1), 0), (4200, "three", (2, 3), 1), (4200, "two", (3,), 0), (2048, "trim", (3,), 0))
+
+
+def c_queries(nchar, kind, seed):
+    """(root, queries, trim): queries[0] is the probe, equal to the root"""
+    root = make_root(nchar, seed)
+    if kind in ("single", "trim"):
+        return root, [root], C_TRIM if kind == "trim" else 0
+    if kind == "two":
+        return root, [root, edit(root, subs=[32 * w + 5 for w in (7, 15, 23)])], 0
+    p1 = list(range(32 * C_OUT_WORD, 32 * C_OUT_WORD + 32)) + [32 * w + 5 for w in (9, 17, 25, 33, 41, 49)]
+    p2 = [32 * w + b for w in range(10, 58, 4) for b in (11, 19)]
+    return root, [root, edit(root, subs=p1), edit(root, subs=p2, to_n=[32 * w + 13 for w in (11, 27, 43)])], C_TRIM
+
+
+def c_idx_c(queries, trim):
+    """the constant-and-complete columns of src/fastaseq.c:732-777 for queries of A, C, G, T and N (the CPU test: equal to the oracle's idx_c)"""
+    q = np.array(queries, dtype=np.uint8)
+    ok = _IS_ACGT[q].all(axis=0) & (q == q[0]).all(axis=0)
+    ok[:trim] = False
+    ok[q.shape[1] - trim:] = False
+    return np.nonzero(ok)[0]
+
+
+def c_tags(cw, row, root, ic, snap, nchar):
+    """what a cut plant reaches, from cut_walk (default mode, W4 given) and the row itself: the names the coverage lists use"""
+    _W4, _NW, B, _lanes = lane_split(nchar)
+    row, root = _as_u8(row), _as_u8(root)
+    tags = {"snap%d" % snap, "bit%d" % cw.bit if cw.bit in (0, 31) else "bit-inside", "pos-" + cw.pos, "lane%d" % cw.lane}
+    if cw.pos == "only":
+        tags |= {"pos-first", "pos-last"}
+    if cw.lane == (int(ic[-1]) // 32) // B:
+        tags.add("lane-of-the-last-site")
+    if cw.col == int(ic[-1]):
+        tags.add("last-column")
+    if cw.mis_before >= 1:
+        tags.add("nth>1")
+    if cw.mis_after >= 1 and cw.match_after >= 1:
+        tags.add("behind")
+    front = ic[ic <= cw.col]
+    mis_cols = front[(row[front] != root[front]) & ~_IS_INVALID[row[front]]]            # the snap mismatches of the walk, in order
+    lanes_of = (mis_cols // 32) // B
+    if snap >= 2 and len(set(lanes_of.tolist())) == snap:
+        tags.add("spread")
+    if snap >= 2 and (cw.word % B == 0) and cw.mis_before == 0 and int(mis_cols[-2]) // 32 == cw.word - 1:
+        tags.add("cross")
+    if int(((row[ic] != root[ic]) & ~_IS_INVALID[row[ic]]).sum()) > snap + C_BIG:     # uncut, the pair fails the gate at every tolerance of the case
+        tags.add("beyond-the-gate")
+    if (_IS_INVALID[row[front]]).any():
+        tags.add("n-before")
+    if (row[front] == ord("R")).any():
+        tags.add("r-before")
+    out = np.setdiff1d(np.arange(cw.col), ic)
+    if len(out) and (row[out] != root[out]).any():
+        tags.add("off-before")
+    if len(out) and ((out // 32) == C_OUT_WORD).sum() == 32 and cw.word > C_OUT_WORD and (mis_cols // 32 < C_OUT_WORD).any():
+        tags.add("over-a-word-outside")
+    return tags
+
+
+def c_required_tags(nchar):
+    """every item of the lists of cut positions that exists at a geometry"""
+    _NW, B, lanes = C_GEOMETRIES[nchar]
+    req = {"bit0", "bit31", "pos-first", "pos-last", "lane0", "lane-of-the-last-site", "last-column", "nth>1", "behind", "spread", "cross",
+           "n-before", "r-before", "off-before", "over-a-word-outside", "uncut-by-one", "beyond-the-gate"} | {"snap%d" % s for s in C_SNAPS}
+    if B >= 3:
+        req.add("pos-inner")
+    if lanes == 64:
+        req.add("lane63")
+    return req
+
+
+def _c_plants(root, ic, snap, nchar, kind):
+    """the plants of one pool: [(name, row, wanted tags)]; a plant that cannot be placed at this geometry and snapshot (too few sites or lanes in front of it for
+    snap mismatches and C_KEY0_MIN matches) is left out -- test_c_covers_every_position holds the rest against c_required_tags"""
+    W4, NW, B, lanes = lane_split(nchar)
+    pos = {int(c): i for i, c in enumerate(ic)}
+    last_lane = (int(ic[-1]) // 32) // B
+    out = []
+
+    def plant(name, col, want, lead="run", tail=True, far=False, n=0, r=False, off=(), target=True):
+        if col not in pos or pos[col] < snap - 1 + n:
+            return
+        pt = pos[col]
+        if lead == "run":
+            lead_cols = [int(c) for c in ic[pt - (snap - 1):pt]]
+        else:                                                       # one mismatch per lane, in the snap - 1 lanes in front of the target's
+            lane = (col // 32) // B
+            lead_cols = [32 * ((lane - j) * B + j % B) + 3 for j in range(snap - 1, 0, -1)]
+            if lane < snap - 1 or any(c not in pos for c in lead_cols):
+                return
+        first = pos[lead_cols[0]] if lead_cols else pt
+        cols = lead_cols + ([col] if target else [])
+        if tail:
+            cols += [int(ic[p]) for p in (pt + 2, pt + 5) if p < len(ic)]
+        if far:                                                     # uncut the pair is beyond every tolerance of the case: only `mc_true - snap` lets it through the gate
+            cols += [int(c) for c in ic[pt + 40:pt + 40 + 3 * C_BIG]]
+        put = {}
+        if r:
+            rc = lead_cols[0] if lead_cols else col
+            if root[rc] != ord("A"):
+                return
+            put[rc] = "R"
+        row = edit(root, subs=cols + list(off), to_n=[int(c) for c in ic[first - n:first]], put=put)
+        cw = cut_walk(root, ic, row, snap, False, W4)
+        if target and not (cw.cut and cw.col == col and cw.counters[0] >= C_KEY0_MIN and want <= c_tags(cw, row, root, ic, snap, nchar)):
+            return
+        out.append((name, row, set(want) if target else {"uncut-by-one"}))
+
+    def first_col(lo, ok):
+        return next((int(c) for c in ic[ic >= lo] if ok(int(c))), -1)
+    mid = max(8, min(20, last_lane - 6))                           # a lane in the middle, clear of the word outside idx_c
+    plant("bit0-first-cross", 32 * mid * B, {"bit0", "pos-first"} | ({"cross"} if snap >= 2 else set()), far=True)
+    plant("bit31-last", 32 * ((mid + 2) * B + B - 1) + 31, {"bit31", "pos-last"})
+    if B >= 3:
+        plant("inner", 32 * ((mid + 4) * B + 1) + 12, {"pos-inner", "beyond-the-gate"}, lead="lanes" if snap <= mid else "run", far=True)
+    lane0 = ic[ic < 32 * B]
+    plant("lane0", int(lane0[-1]) if len(lane0) >= snap + C_KEY0_MIN else -1, {"lane0"}, far=True)
+    plant("last-column", int(ic[-1]), {"last-column", "lane-of-the-last-site"}, tail=False)
+    if lanes == 64 and (int(ic[-1]) // 32) // B == 63:
+        plant("lane63-spread", 32 * 63 * B + 9, {"lane63"} | ({"spread"} if snap >= 2 else set()), lead="lanes")
+    plant("spread", 32 * (last_lane - 1) * B + 17, {"spread"} if snap >= 2 else set(), lead="lanes")
+    plant("one-word", 32 * ((mid + 6) * B) + 20, {"behind", "beyond-the-gate"} | ({"nth>1"} if snap >= 2 else set()), far=True)
+    plant("one-short", 32 * ((mid + 6) * B) + 20, set(), tail=False, target=False)            # the same without its last mismatch: snap - 1, not cut
+    plant("n-before", 32 * ((mid + 7) * B + B - 1) + 24, {"n-before", "behind"}, n=3)
+    plant("r-before", first_col(32 * (mid + 8) * B + snap, lambda c: root[int(ic[pos[c] - (snap - 1)])] == ord("A") and 2 <= c % 32 <= 26), {"r-before"}, r=True)
+    if kind != "single":
+        outside = np.setdiff1d(np.arange(nchar), ic)
+        lo = {"three": 32 * (C_OUT_WORD + 1) + 2, "trim": 32 * 2 + 2, "two": 32 * 8 + 2}[kind]
+        off = sorted(set([int(c) for c in outside[outside < lo][-2:]] + [int(outside[0])]))      # (trimmed columns, polymorphic ones)
+        plant("off-before", first_col(lo, lambda c: True), {"off-before"}, off=off)
+        if kind == "three":
+            plant("over-a-word-outside", 32 * (C_OUT_WORD + 1), {"over-a-word-outside", "bit0"} if snap >= 2 else {"bit0"}, off=off[:1])
+    return out
+
+
+def _c_low(root, ic, k, m):
+    """a low: k matches and m mismatches on the last columns of idx_c, N elsewhere"""
+    keep = [int(c) for c in ic[len(ic) - (k + m):]]
+    a = edit(root, subs=keep[k:])
+    gone = np.ones(len(a), dtype=bool)
+    gone[keep] = False
+    a[gone] = ord("N")
+    return a
+
+
+def _c_build(nchar, kind, snaps, pool, seed):
+    root, qs, trim = c_queries(nchar, kind, seed)
+    ic = c_idx_c(qs, trim)
+    sets = [_c_plants(root, ic, s, nchar, kind) for s in snaps]
+    step = [max(1, (pool - 8) // max(1, len(p))) for p in sets]
+    assert all(6 + st * len(p) < pool for st, p in zip(step, sets))
+    n_in = [1 + len(p) for p in sets]                              # admissions of pools 1 and 2: the EARLY plant and every plant
+    assert sum(n_in) + 2 <= C_NBEST <= pool
+    # ---- pool 0: the lows, worst first; then references without a match, which do not enter
+    lows = [_c_low(root, ic, 2, snaps[0] + C_BIG) for _ in range(n_in[0] - 1)]
+    root1 = _c_low(root, ic, 1, snaps[0] - 1)
+    if kind == "two":                                              # one of ROOT1's mismatches moves to a column where it holds the other query's letter
+        root1 = _c_low(root, ic, 1, snaps[0] - 2)
+        root1[32 * 7 + 5] = qs[1][32 * 7 + 5]
+    if len(snaps) == 2:
+        lows += [_c_low(root, ic, 3, snaps[1] - 1)] + [_c_low(root, ic, 4, snaps[1] + C_BIG) for _ in range(C_NBEST - n_in[0] - 1)]
+    else:
+        lows += [_c_low(root, ic, 2, snaps[0] + C_BIG) for _ in range(C_NBEST - n_in[0])]
+    refs = lows + [root1] + [_c_low(root, ic, 0, max(snaps) + 2 * C_BIG) for _ in range(pool - C_NBEST)]
+    plants = {}
+    for p, (s, plist) in enumerate(zip(snaps, sets), start=1):
+        n_here = pool if p < len(snaps) else pool - 5                # the last pool ends inside a tile
+        block = far_rows(root, n_here, 30, seed + 10 * p)
+        block[:, ic[:s]] = _ROT[root[ic[:s]]]                        # decoys: cut with no match in front ...
+        block[:, np.setdiff1d(np.arange(nchar), ic)] = ord("N")     # ... and none on the columns outside idx_c, which count for key 0 too
+        block[3] = edit(root, subs=[int(c) for c in ic[-1 - max(0, s - 2):-1]])     # EARLY: s - 2 mismatches (against the probe)
+        for i, (name, row, want) in enumerate(plist):
+            o = 6 + step[p - 1] * i
+            if pool > 2 * TILE and i == len(plist) - 1:             # the last one in the pool's short third tile
+                o = 2 * TILE + 2
+            block[o] = row
+            plants[p * pool + o] = {"name": name, "snap": s, "want": want, "pool": p}
+        refs += list(block)
+    return qs, rows(refs), plants, trim
+
+
+def _c_cases():
+    for i, (nchar, kind, snaps, pi) in enumerate(C_LIST):
+        pool = C_POOLS[pi]
+        lz = _Lazy(functools.partial(_c_build, nchar, kind, snaps, pool, 900 + 10 * i))
+        regs = C_PUSH + (C_RESIDENT if nchar in (2049, 4200) else [])
+        _root, qs, trim = c_queries(nchar, kind, 900 + 10 * i)
+        _add(Case("n%d-%s-snap%s-pool%d" % (nchar, kind, "+".join(str(s) for s in snaps), pool), "C", qs, _LazyList(lambda lz=lz: lz.get()[1]), C_NBEST, pool, regs,
+                  {"ncol": nchar, "kind": kind, "snaps": snaps, "trim": trim, "plants": _Lazy(lambda lz=lz: lz.get()[2])}))
+
+
 _r_cases()
 _g_cases()
 _h_cases()
@@ -909,3 +1226,4 @@ _k_cases()
 _t_cases()
 _s_cases()
 _f_cases()
+_c_cases()

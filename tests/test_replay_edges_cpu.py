@@ -2,6 +2,7 @@
 it is built for -- shown from the oracle's pair scores (Query.allpairs), the oracle's answers to the stream and to prefixes of it, and the
 model of replay_edges (MinHeap, walk2, walk3), whose own answer is held against the oracle's first, so that what it says about an input
 can be relied on.  The device runs the same inputs in tests/test_replay_edges_gpu.py."""
+import functools
 import glob
 import math
 import os
@@ -36,9 +37,10 @@ def check_model(key, scores):
 def test_every_case_id_names_group_regime_and_edge():
     ids = [RE.run_id(k, r) for k, r in RE.runs()]
     assert len(set(ids)) == len(ids)
-    assert all(i.split("-")[0] in "RGHKTSF" and len(i.split("-")) >= 3 for i in ids)
-    assert set(c.group for c in RE.CASES.values()) == set("RGHKTSF")
-    kernels = {g: set(RE.REGIMES[r].kernel for k, r in RE.runs(g)) for g in "RGHKTSF"}
+    assert all(i.split("-")[0] in "RGHKTSFC" and len(i.split("-")) >= 3 for i in ids)
+    assert set(c.group for c in RE.CASES.values()) == set("RGHKTSFC")
+    kernels = {g: set(RE.REGIMES[r].kernel for k, r in RE.runs(g)) for g in "RGHKTSFC"}
+    assert {"replay", "replay2", "replay3"} <= kernels["C"]                 # (the lean kernel runs without a constant-and-complete column: nothing to cut)
     for g in "RHKF":                                                    # these groups run on all four kernels
         assert {"replay", "replay2", "lean", "replay3"} <= kernels[g], g
     assert {"replay2", "lean", "replay3"} <= kernels["G"] and {"replay2", "replay3"} <= kernels["T"] and {"replay2", "replay3"} <= kernels["S"]
@@ -368,3 +370,149 @@ def test_f_lengths_on_both_sides_of_the_switch():
     assert refs[17] == probe and set(refs[64]) == {ord("N")} and set(refs[65]) == {ord("-")}
     assert all(a != b for a, b in zip(refs[66], probe))
     assert RE.WIDE_ABOVE < 2 ** 16 and not case.meta["wide"] and RE.CASES["F-nchar%d-q1" % (RE.WIDE_ABOVE + 1)].meta["wide"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------- C
+def _c_expected_row(q, pi, ref, snap, acgt):
+    """the six scores the oracle's loop gives a pair whose pre-score is cut at snap, from the oracle's own pieces: the untruncated scores of the pair
+    (Query.allpairs) less what the cut takes from the consensus counters (score4 / score_acgt with and without maxdist)"""
+    full = [int(x) for x in q.allpairs([ref])[0, pi]]
+    score = O.score_acgt if acgt else O.score4
+    u, c = score(ref, q.consensus, idx=q.idx_c), score(ref, q.consensus, maxdist=snap, idx=q.idx_c)
+    if acgt:                                                            # src/nearest.c:462-469: matches, pairs, matches off idx_c, valid sites, mismatches on idx_c + idx_m, on idx
+        lost_mis, lost_both = u[0] - c[0], u[1] - c[1]
+        return (full[0] - (lost_both - lost_mis), full[1] - lost_both, full[2], full[3], full[4] - lost_mis, full[5]), c, u
+    return tuple(full[i] - (u[i] - c[i]) for i in range(4)) + (full[4], full[5]), c, u      # src/nearest.c:497-500
+
+
+@functools.lru_cache(maxsize=None)
+def _c_report(key):
+    """per plant of a case and per mode: cut_walk's answer, the oracle's cut and uncut consensus counters, the row the final heap must hold, and the
+    counters of every wrong walk"""
+    case = RE.CASES[key]
+    refs, plants = list(case.refs), case.meta["plants"].get()
+    W4 = RE.lane_split(case.meta["ncol"])[0]
+    out = {}
+    for acgt, regime in ((False, "replay3"), (True, "replay2-acgt")):
+        q, pi = RE.query(key, regime), RE.probe_index(key, regime)
+        for o, p in plants.items():
+            cw = RE.cut_walk(q.consensus, q.idx_c, refs[o], p["snap"], acgt, W4)
+            row, c, u = _c_expected_row(q, pi, refs[o], p["snap"], acgt)
+            wrong = {w: RE.cut_walk(q.consensus, q.idx_c, refs[o], p["snap"], acgt, W4, wrong=w, every=q.seqs[pi]).counters for w in RE.CUT_WRONG}
+            out[o, acgt] = (cw, tuple(c), tuple(u), row, wrong)
+    return out
+
+
+def test_c_geometries_snapshots_pools_and_regimes():
+    assert {n: RE.lane_split(n)[1:] for n in RE.C_GEOMETRIES} == RE.C_GEOMETRIES
+    assert [RE.C_GEOMETRIES[n][1] for n in sorted(RE.C_GEOMETRIES)] == [1, 2, 2, 3]                      # one word per lane | two, ragged | two, full | three, ragged
+    assert 2048 == 64 * 32 and 2049 == 2048 + 1 and 4096 == 2 * 2048                                    # the last length of B = 1, the first of B = 2, the last of B = 2
+    assert RE.lane_split(4097)[2] == 3 and 4200 % 32 == 8 and -(-4200 // 32) == RE.C_GEOMETRIES[4200][0]   # 4200: the last word holds eight sites, no padding word
+    assert RE.C_GEOMETRIES[2049][0] - (-(-2049 // 32)) == 3                                             # 2049: three padding words, lane 33 holds nothing but them
+    assert RE.C_POOLS == (RE.TILE, 2 * RE.TILE + 9) and RE.C_NBEST <= min(RE.C_POOLS) and RE.C_NBEST <= RE.MC_LIMIT
+    cases = [RE.CASES[k] for k in RE.keys("C")]
+    for n in RE.C_GEOMETRIES:
+        mine = [c for c in cases if c.meta["ncol"] == n]
+        assert set(s for c in mine for s in c.meta["snaps"]) == set(RE.C_SNAPS) and {"single"} < set(c.meta["kind"] for c in mine), n
+        assert all((set(RE.C_RESIDENT) <= set(c.regimes)) == (n in (2049, 4200)) for c in mine)
+    assert max(RE.C_SNAPS) > 32 and {1, 2, 3} < set(RE.C_SNAPS)
+    assert set(c.pool for c in cases) == set(RE.C_POOLS) and {"single", "trim", "three", "two"} == set(c.meta["kind"] for c in cases)
+    assert all(set(RE.C_PUSH) <= set(c.regimes) and len(c.refs) <= 3 * c.pool for c in cases)
+    assert set(RE.C_PUSH) == {"replay3", "replay3-h8", "replay2", "replay2-acgt", "wide", "wide-acgt"}
+
+
+@pytest.mark.parametrize("key", RE.keys("C"))
+def test_c_every_plant_is_cut_where_it_is_named_and_keeps_its_cut_scores(key):
+    case = RE.CASES[key]
+    m = case.meta
+    refs, plants, pool, snaps = list(case.refs), m["plants"].get(), case.pool, m["snaps"]
+    ncol, window = m["ncol"], m["ncol"] - 2 * m["trim"]
+    rep = _c_report(key)
+    for acgt, regime in ((False, "replay3"), (True, "replay2-acgt")):
+        q, pi, g = RE.query(key, regime), RE.probe_index(key, regime), RE.gold(key, regime)
+        # ---- the query set: idx_c as the builder computed it, a proper subset of the window unless the probe is alone and untrimmed
+        ic = RE.c_idx_c(case.queries, m["trim"])
+        assert np.array_equal(q.idx_c, ic) and q.consensus[int(ic[0])] == RE.rows(case.queries)[0][int(ic[0])] and q.trim == m["trim"]
+        assert 0 < len(q.idx_c) <= window and (len(q.idx_c) < window) == (m["kind"] in ("three", "two")) and (window < ncol) == (m["kind"] in ("three", "trim"))
+        if m["kind"] == "three":
+            assert not set(range(32 * RE.C_OUT_WORD, 32 * RE.C_OUT_WORD + 32)) & set(ic.tolist()) and len(q.idx_m) == 3 and len(q.idx) == 62
+        # ---- the snapshots: the largest tolerance at the start of pools 1 and 2 is the one the plants are built for, and it has risen when they arrive
+        for p, s in enumerate(snaps, start=1):
+            before = O.search(q, refs[:p * pool], RE.names(p * pool), pool=pool, nbest=case.nbest, ambig_r=1.0)
+            assert max(before.final_T) == before.final_T[pi] == s and all(n == case.nbest for n in before.heap_n)
+            early = p * pool + 3
+            after = O.search(q, refs[:early + 1], RE.names(early + 1), pool=pool, nbest=case.nbest, ambig_r=1.0)
+            assert after.final_T[pi] == s + RE.C_BIG + 1 and early in after.saved
+            if q.ntax > 1:                                              # the other queries' tolerances stay below: the plants are cut for them too and stop at their gates
+                others = [t for i, t in enumerate(before.final_T) if i != pi]
+                assert all(t < s for t in others) if (p == 2 or m["kind"] == "two") else all(t == s for t in others)
+                assert [t for i, t in enumerate(g.final_T) if i != pi] == [t for i, t in enumerate(O.search(q, refs[:pool], RE.names(pool), pool=pool, nbest=case.nbest, ambig_r=1.0).final_T) if i != pi]
+        assert g.final_T[pi] == snaps[-1] + RE.C_BIG + 1
+        # ---- who enters: the lows, the two early plants, every plant -- and no decoy, each of which is cut with no match in front of the cut
+        assert g.saved.tolist() == sorted(list(range(RE.C_NBEST)) + [p * pool + 3 for p in range(1, len(snaps) + 1)] + list(plants))
+        for p, s in enumerate(snaps, start=1):
+            for o in (p * pool + 2, p * pool + 4, min(len(refs), (p + 1) * pool) - 1):
+                cw = RE.cut_walk(q.consensus, q.idx_c, refs[o], s, acgt)
+                assert o not in plants and cw.cut and cw.counters[0 if not acgt else 1] == (0 if not acgt else s) and cw.col == int(ic[s - 1])
+        final = RE.want_rows(g, q.ntax)
+        assert sum(1 for _s, o in final[pi] if o < RE.C_NBEST) >= 2                  # lows are left: no plant was ever the worst kept entry
+        for iq in range(q.ntax):
+            assert iq == pi or not set(o for _s, o in final[iq]) & set(plants)
+        # ---- every plant
+        for o, p in plants.items():
+            cw, c, u, row, _wrong = rep[o, acgt]
+            s = p["snap"]
+            assert o // pool == p["pool"] and s == snaps[p["pool"] - 1]
+            assert cw.counters[:len(c)] == c, (key, p["name"], acgt)                  # the model's walk is the oracle's
+            mis_u = u[0] if acgt else u[3] - u[0]
+            assert cw.cut == (mis_u >= s)
+            assert (row, o) in final[pi], (key, p["name"], acgt)                      # in the final heap, with the scores the cut leaves
+            if "uncut-by-one" in p["want"]:
+                assert not cw.cut and mis_u == s - 1 and c == u
+                continue
+            assert cw.cut and (c != u or cw.col == int(ic[-1])) and (c[0] if not acgt else c[1] - c[0]) >= RE.C_KEY0_MIN
+            if not acgt:
+                tags = RE.c_tags(cw, refs[o], case.queries[0], ic, s, ncol)
+                assert p["want"] <= tags, (key, p["name"], p["want"] - tags)
+                if "last-column" in tags:
+                    assert c == u
+                if "r-before" in tags:                                  # R over the consensus's A: a mismatch of the default walk, no pair at all under --acgt
+                    assert rep[o, True][0].col > cw.col
+    # pools of two tiles and nine: plants behind the early one in its tile and in both later tiles
+    if pool > RE.TILE:
+        for p in range(1, len(snaps) + 1):
+            assert set((o - p * pool) // RE.TILE for o, x in plants.items() if x["pool"] == p) == {0, 1, 2}
+
+
+@pytest.mark.parametrize("ncol", sorted(RE.C_GEOMETRIES))
+def test_c_covers_every_position(ncol):
+    seen, regimes = set(), set()
+    for key in RE.keys("C"):
+        case = RE.CASES[key]
+        if case.meta["ncol"] != ncol:
+            continue
+        ic = RE.c_idx_c(case.queries, case.meta["trim"])
+        refs = list(case.refs)
+        for o, p in case.meta["plants"].get().items():
+            cw = _c_report(key)[o, False][0]
+            seen |= RE.c_tags(cw, refs[o], case.queries[0], ic, p["snap"], ncol) if cw.cut else {"uncut-by-one"}
+        regimes |= set(case.regimes)
+    req = RE.c_required_tags(ncol)
+    assert req <= seen, sorted(req - seen)
+    NW, B, lanes = RE.C_GEOMETRIES[ncol]
+    assert ("pos-inner" in req) == (B == 3) and ("lane63" in req) == (lanes == 64) and ("pos-only" in seen) == (B == 1)
+    assert "lane%d" % ((ncol - 1) // 32 // B) in seen                   # the last lane that holds a site
+    assert set(RE.C_PUSH) <= regimes
+
+
+@pytest.mark.parametrize("wrong", RE.CUT_WRONG)
+@pytest.mark.parametrize("ncol", sorted(RE.C_GEOMETRIES))
+def test_c_a_wrong_cut_does_not_pass(ncol, wrong):
+    """stop one mismatch early, one late, count the whole word of the cut, lose the lanes in front at the lane of the cut, walk every column: in either mode some
+    plant of every geometry has other counters than the oracle's, so its printed row would differ"""
+    for acgt in (False, True):
+        differ = []
+        for key in RE.keys("C"):
+            if RE.CASES[key].meta["ncol"] == ncol:
+                differ += [RE.CASES[key].meta["plants"].get()[o]["name"] for (o, a), (_cw, c, _u, _row, w) in _c_report(key).items() if a == acgt and w[wrong][:len(c)] != c]
+        assert differ, (ncol, wrong, acgt)

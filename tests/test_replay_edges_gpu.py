@@ -65,7 +65,7 @@ def check(key, regime):
     kernel = r.kernel or ("replay" if case.meta["wide"] else "replay2" if (r.acgt or q.ntax > 32) else "replay3")
     assert facts["scan"] == (-1 if kernel == "replay" else 0 if q.ntax <= 32 else 2), facts
     if kernel == "replay3":
-        assert facts["opened"] > 0 and (case.group == "S" or facts["demanded"] < facts["admitted"]), facts
+        assert facts["opened"] > 0 and (case.group in "SC" or facts["demanded"] < facts["admitted"]), facts     # (S, C: slow pairs are evaluated on demand)
     elif kernel == "replay":
         assert facts["opened"] == 0 and facts["admitted"] == 0 and facts["demanded"] == 0, facts      # replay_kernel keeps no statistics
     else:
@@ -114,6 +114,16 @@ def test_s_slow_pairs(key, regime):
     facts = check(key, regime)
     if RE.REGIMES[regime].kernel in ("replay2", "replay3"):
         assert (facts["dense"] > 0) == RE.CASES[key].meta["dense"], facts
+
+
+@cases("C")
+def test_c_the_cut_of_the_consensus_prescore(key, regime):
+    """pre-scores cut at snapshots of 1, 2, 3 and 40 at 2048, 2049, 4096 and 4200 columns: the cut at bit 0 and bit 31, in the first, an inner and the last word
+    of a lane's range, in lane 0, lane 63 and the last lane that holds a site, at the last column of idx_c, behind N, R and substitutions outside idx_c; every
+    cut pair stays in the final heap, so a cut one site off is a wrong row"""
+    facts = check(key, regime)
+    if RE.REGIMES[regime].kernel in ("replay2", "replay3"):
+        assert facts["demanded"] > 0, facts                                                           # the on-demand walk ran
 
 
 @cases("F")
