@@ -68,7 +68,7 @@ int  uvaia_align_batch (uvaia_aligner *a, const char *const *seq, const int *seq
 
 /* The same in three steps, for callers that keep a pool resident (bench.py times uvaia_align_run with the queries in HBM):
  * load copies the queries to the device, run aligns the loaded pool and returns when its kernels are done (rows and scores stay
- * on the device), fetch copies them back. */
+ * on the device), fetch copies them back (aln may be NULL when only the scores are wanted: the rows then stay on the device). */
 int  uvaia_align_load (uvaia_aligner *a, const char *const *seq, const int *seq_len, int n);
 int  uvaia_align_load_block (uvaia_aligner *a, const char *bytes, const int64_t *offsets /* n + 1 */, int n);
 /* load_block with the bytes already in device memory (uvaia_gpu_fasta_sequences of include/uvaia_gpu.h gives this form): d_bytes must be
@@ -101,6 +101,37 @@ int  uvaia_align_insertion_counts (uvaia_aligner *a, long long *n_records, long 
  * bytes, no NUL; either may be NULL).  The bases are gathered on the device from the aligner's own copy of the pool, so they are there
  * after uvaia_align_load_device too.  Valid until the next load or close.  UVAIA_ALIGN_ESTATE as above. */
 int  uvaia_align_fetch_insertions (uvaia_aligner *a, uvaia_align_insertion *rec, char *bases);
+
+/* What a row on the reference's columns differs from the reference by (the rows update_query_aligned writes, src/align.c:366-390; the
+ * reference has no such output).  Bytes are taken as they are: A C G T are bases, '-' is a gap, 'N' is unknown, every other byte is "other".
+ *   substitution 'S': a site where the row holds a base that is not the reference's byte: ref_pos = the site, length = 1, ref and alt the
+ *                     two bytes.  Neighbouring substitutions are not merged.
+ *   deletion 'D':     a maximal run of gaps: ref_pos = its first site, length = its sites, ref = alt = 0.  Runs that touch the row's first
+ *                     or last site are deletions like any other (first_site / last_site say where the row's coverage starts and ends).
+ * The records of one row are in ascending ref_pos.  Per row: matches (a base equal to the reference's byte), substitutions, deletion_runs,
+ * deleted_sites, unknown_sites, other_sites -- matches + substitutions + deleted_sites + unknown_sites + other_sites == ref_len -- and the
+ * first and last site that is no gap (ref_len and -1 for a row of gaps). */
+typedef struct { int query, ref_pos, length; uint32_t kind_ref_alt; } uvaia_align_variant;      /* 'S' or 'D' | ref << 8 | alt << 16 */
+typedef struct { int matches, substitutions, deletion_runs, deleted_sites, unknown_sites, other_sites, first_site, last_site; } uvaia_align_row_qc;
+/* src/align.c:366-390: derive the records and counts of the rows of the following runs of this aligner (uvaia_align_run / _sync / _batch,
+ * whichever way the pool was loaded) on the device, after the projection (off by default; rows, scores, insertions and the statistics are
+ * the same either way). */
+int  uvaia_align_set_variants (uvaia_aligner *a, int on);
+/* src/align.c:366-390: how many records and rows the last answer holds: that of the last completed run with the option on, or of
+ * uvaia_align_variants_of, whichever came last.  UVAIA_ALIGN_ESTATE before either has happened, and after a load or a run with the option
+ * off that followed a run's answer.  Either pointer may be NULL. */
+int  uvaia_align_variant_counts (uvaia_aligner *a, long long *n_records, int *n_rows);
+/* src/align.c:366-390: the n_records records, sorted by (query, ref_pos) as the device wrote them, and the n_rows counts; either may be NULL.
+ * UVAIA_ALIGN_ESTATE as above. */
+int  uvaia_align_fetch_variants (uvaia_aligner *a, uvaia_align_variant *rec, uvaia_align_row_qc *qc);
+/* src/align.c:366-390, for rows aligned elsewhere: n rows of ref_len bytes in host memory, pitch >= ref_len bytes apart, are copied to a
+ * buffer of the aligner's own and go through the same passes, whether or not the option is on.  The loaded pool, its rows, scores and
+ * insertions are not touched.  n == 0 is an empty answer; pitch < ref_len, n < 0 and n > 0 with NULL rows are refused with
+ * UVAIA_ALIGN_EINVAL. */
+int  uvaia_align_variants_of (uvaia_aligner *a, const char *rows, size_t pitch, int n);
+/* src/align.c:366-390: device time in ms of the passes since the aligner was opened or since the last call with reset != 0 (the count is
+ * reset after it is read).  It is NOT part of the kernel_ms of uvaia_align_stats. */
+double uvaia_align_variants_ms (uvaia_aligner *a, int reset);
 
 /* work of the last run: M-wavefront cells computed, wavefront bytes written + read by the recurrences (13 + 20 per cell),
  * kernel passes (queries that find the workspace's pool empty are run again in a less crowded pass), kernel time in ms */

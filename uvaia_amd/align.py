@@ -10,8 +10,13 @@ SYMBOLS = [
     "uvaia_align_default_options", "uvaia_align_open", "uvaia_align_close", "uvaia_align_last_error", "uvaia_align_batch",
     "uvaia_align_load", "uvaia_align_load_block", "uvaia_align_run", "uvaia_align_sync", "uvaia_align_fetch", "uvaia_align_stats",
     "uvaia_align_device_rows", "uvaia_align_load_device", "uvaia_align_set_insertions", "uvaia_align_insertion_counts",
-    "uvaia_align_fetch_insertions",
+    "uvaia_align_fetch_insertions", "uvaia_align_set_variants", "uvaia_align_variant_counts", "uvaia_align_fetch_variants",
+    "uvaia_align_variants_of", "uvaia_align_variants_ms",
 ]
+
+# uvaia_align_variant and uvaia_align_row_qc as numpy sees them
+VARIANT_DTYPE = np.dtype([("query", "<i4"), ("ref_pos", "<i4"), ("length", "<i4"), ("kind", "u1"), ("ref", "u1"), ("alt", "u1"), ("pad", "u1")])
+QC_DTYPE = np.dtype([(k, "<i4") for k in ("matches", "substitutions", "deletion_runs", "deleted_sites", "unknown_sites", "other_sites", "first_site", "last_site")])
 
 
 class AlignError(RuntimeError):
@@ -56,6 +61,12 @@ def _lib():
         L.uvaia_align_set_insertions.argtypes = [vp, C.c_int, C.c_size_t]
         L.uvaia_align_insertion_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
         L.uvaia_align_fetch_insertions.argtypes = [vp, C.c_void_p, C.c_void_p]
+        L.uvaia_align_set_variants.argtypes = [vp, C.c_int]
+        L.uvaia_align_variant_counts.argtypes = [vp, C.POINTER(C.c_longlong), pi]
+        L.uvaia_align_fetch_variants.argtypes = [vp, C.c_void_p, C.c_void_p]
+        L.uvaia_align_variants_of.argtypes = [vp, C.c_void_p, C.c_size_t, C.c_int]
+        L.uvaia_align_variants_ms.argtypes = [vp, C.c_int]
+        L.uvaia_align_variants_ms.restype = C.c_double
         _ready = True
     return L
 
@@ -157,6 +168,46 @@ class Aligner:
             out.append((r.query, r.ref_pos, r.seq_pos, raw[at:at + r.length]))
             at += r.length
         return out
+
+    def set_variants(self, on):
+        """derive substitutions, deletions and per-row counts from the rows of the following runs (uvaia_align_set_variants)"""
+        self._chk(self.L.uvaia_align_set_variants(self.ptr, 1 if on else 0))
+
+    def variants(self):
+        """(records, qc) of the last completed run with the option on, or of variants_of, whichever came last: numpy structured arrays of
+        VARIANT_DTYPE (sorted by query, then ref_pos; kind is ord('S') or ord('D')) and QC_DTYPE (one entry per row)"""
+        n_rec, n_rows = C.c_longlong(0), C.c_int(0)
+        self._chk(self.L.uvaia_align_variant_counts(self.ptr, C.byref(n_rec), C.byref(n_rows)))
+        rec = np.zeros(n_rec.value, dtype=VARIANT_DTYPE)
+        qc = np.zeros(n_rows.value, dtype=QC_DTYPE)
+        self._chk(self.L.uvaia_align_fetch_variants(self.ptr, rec.ctypes.data if rec.size else None, qc.ctypes.data if qc.size else None))
+        return rec, qc
+
+    def variants_of(self, rows, pitch=None):
+        """records and counts of rows aligned elsewhere (uvaia_align_variants_of): rows is a 2-D uint8 array [n, >= ref_len], a list of
+        bytes of ref_len characters each, or, with pitch, a flat buffer of rows pitch bytes apart.  Returns what variants() returns."""
+        if pitch is None:
+            if isinstance(rows, np.ndarray):
+                arr = np.ascontiguousarray(rows, dtype=np.uint8)
+                if arr.ndim != 2:
+                    raise ValueError("rows: a 2-D array, or a flat buffer together with pitch")
+            else:
+                rows = list(rows)
+                if any(len(r) != self.ref_len for r in rows):
+                    raise ValueError("every row has ref_len = %d characters" % self.ref_len)
+                arr = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), self.ref_len)
+            n, pitch = arr.shape[0], (arr.shape[1] if arr.shape[0] else self.ref_len)
+        else:
+            arr = np.ascontiguousarray(np.frombuffer(rows, dtype=np.uint8) if not isinstance(rows, np.ndarray) else rows.reshape(-1), dtype=np.uint8)
+            if pitch < 1 or (arr.size and arr.size < self.ref_len):
+                raise ValueError("a flat buffer holds at least one row")
+            n = 0 if not arr.size else (arr.size - self.ref_len) // pitch + 1
+        self._chk(self.L.uvaia_align_variants_of(self.ptr, arr.ctypes.data if arr.size else None, pitch, n))
+        return self.variants()
+
+    def variants_ms(self, reset=False):
+        """device time of the variant passes in ms since the aligner was opened or last reset; not part of stats()['kernel_ms']"""
+        return float(self.L.uvaia_align_variants_ms(self.ptr, 1 if reset else 0))
 
     def stats(self):
         cells, nbytes, passes, ms = C.c_ulonglong(0), C.c_double(0), C.c_int(0), C.c_double(0)

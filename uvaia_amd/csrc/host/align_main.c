@@ -12,6 +12,10 @@
  *
  * --insertions (no counterpart either): the characters the projection drops (the I operations of src/align.c:366-390) go to a table, one
  * line per insertion run, from the records the aligner keeps (include/uvaia_align.h, uvaia_align_fetch_insertions).
+ *
+ * --variants, --qc (no counterpart either): what every aligned row differs from the reference by -- substitutions and deletions, which the
+ * aligner derives from the rows where they lie (uvaia_align_set_variants), merged with the insertion runs -- and one line of counts per
+ * aligned sequence.
  */
 #define _GNU_SOURCE
 #include <getopt.h>
@@ -97,6 +101,109 @@ ins_table_add (struct ins_table *t, uvaia_aligner *al, char **name)
   return 0;
 }
 
+/* `uvaialign --variants <file>`: sequence,kind,ref_pos,length,ref,alt -- S (ref and alt bytes), D (both empty) and I (the inserted bases in
+ * alt) of every aligned sequence, in the order the sequences are written and by ref_pos within one; at equal ref_pos the I goes first, since
+ * it lies left of that site.  `--qc <file>`: one line of counts per aligned sequence.  Either file may be absent. */
+struct var_table {
+  file_compress_t variants, qc;         /* NULL without the option */
+  long n_seqs; long long n_sub, n_del, n_del_sites, n_ins, n_ins_bases;
+  uvaia_align_variant *rec; uvaia_align_row_qc *row; uvaia_align_insertion *ins; char *bases, *line; int *score;
+  size_t rec_cap, row_cap, ins_cap, bases_cap, line_cap;
+  int bad;
+  char err[512];
+};
+
+static void
+var_table_open (struct var_table *t, const char *variants, const char *qc)
+{
+  static const char head_v[] = "sequence,kind,ref_pos,length,ref,alt\n";
+  static const char head_q[] = "sequence,length,score,matches,substitutions,deletions,deleted_sites,insertions,inserted_bases,unknown_sites,other_sites,first_site,last_site\n";
+  memset (t, 0, sizeof *t);
+  if (variants) {
+    t->variants = biomcmc_open_compress (variants, "w");
+    if (biomcmc_write_compress (t->variants, head_v) != (int) strlen (head_v)) fprintf (stderr, "File %s may not be correctly compressed: its first line could not be written.\n", variants);
+  }
+  if (qc) {
+    t->qc = biomcmc_open_compress (qc, "w");
+    if (biomcmc_write_compress (t->qc, head_q) != (int) strlen (head_q)) fprintf (stderr, "File %s may not be correctly compressed: its first line could not be written.\n", qc);
+  }
+}
+
+static void
+var_table_close (struct var_table *t)
+{
+  if (t->variants) biomcmc_close_compress (t->variants);
+  if (t->qc) biomcmc_close_compress (t->qc);
+  free (t->rec); free (t->row); free (t->ins); free (t->bases); free (t->line); free (t->score);
+  t->variants = t->qc = NULL; t->rec = NULL; t->row = NULL; t->ins = NULL; t->bases = NULL; t->line = NULL; t->score = NULL;
+}
+
+/* the aligner's last run: its queries are name[0 ..], len[0 ..] characters long */
+static int
+var_table_add (struct var_table *t, uvaia_aligner *al, char **name, const int *len)
+{
+  long long n_rec = 0, n_ins = 0, n_bases = 0;
+  int n_rows = 0;
+  if (!t->variants && !t->qc) return 0;
+  if (uvaia_align_variant_counts (al, &n_rec, &n_rows) || uvaia_align_insertion_counts (al, &n_ins, &n_bases)) { snprintf (t->err, sizeof t->err, "%s", uvaia_align_last_error (al)); return -1; }
+  if (!n_rows) return 0;
+  if ((size_t) n_rec > t->rec_cap) { t->rec_cap = (size_t) n_rec * 2; t->rec = (uvaia_align_variant *) biomcmc_realloc (t->rec, t->rec_cap * sizeof (uvaia_align_variant)); }
+  if ((size_t) n_rows > t->row_cap) {
+    t->row_cap = (size_t) n_rows * 2;
+    t->row = (uvaia_align_row_qc *) biomcmc_realloc (t->row, t->row_cap * sizeof (uvaia_align_row_qc));
+    t->score = (int *) biomcmc_realloc (t->score, t->row_cap * sizeof (int));
+  }
+  if ((size_t) n_ins > t->ins_cap) { t->ins_cap = (size_t) n_ins * 2; t->ins = (uvaia_align_insertion *) biomcmc_realloc (t->ins, t->ins_cap * sizeof (uvaia_align_insertion)); }
+  if ((size_t) n_bases > t->bases_cap) { t->bases_cap = (size_t) n_bases * 2; t->bases = (char *) biomcmc_realloc (t->bases, t->bases_cap); }
+  if (uvaia_align_fetch_variants (al, t->rec, t->row) || uvaia_align_fetch_insertions (al, t->ins, t->bases) || uvaia_align_fetch (al, NULL, t->score)) {
+    snprintf (t->err, sizeof t->err, "%s", uvaia_align_last_error (al));
+    return -1;
+  }
+  long long iv = 0, ii = 0;
+  size_t at = 0;
+  int bad = 0;
+  for (int q = 0; q < n_rows; q++) {     /* both lists are sorted by (query, ref_pos): one merge per sequence */
+    const uvaia_align_row_qc *c = t->row + q;
+    const char *nm = name[q];
+    const size_t nm_len = strlen (nm);
+    int q_ins = 0;
+    long long q_bases = 0;
+    for (;;) {
+      const int has_v = iv < n_rec && t->rec[iv].query == q, has_i = ii < n_ins && t->ins[ii].query == q;
+      if (!has_v && !has_i) break;
+      const int take_i = has_i && (!has_v || t->ins[ii].ref_pos <= t->rec[iv].ref_pos);
+      const size_t need = nm_len + 96 + (take_i ? (size_t) t->ins[ii].length : 0);
+      if (need > t->line_cap) { t->line_cap = need * 2; t->line = (char *) biomcmc_realloc (t->line, t->line_cap); }
+      int w;
+      if (take_i) {
+        const uvaia_align_insertion *r = t->ins + ii++;
+        w = snprintf (t->line, t->line_cap, "%s,I,%d,%d,,", nm, r->ref_pos, r->length);
+        memcpy (t->line + w, t->bases + at, (size_t) r->length);
+        w += r->length; at += (size_t) r->length;
+        q_ins++; q_bases += r->length;
+      } else {
+        const uvaia_align_variant *r = t->rec + iv++;
+        const int kind = (int) (r->kind_ref_alt & 0xFF);
+        if (kind == 'S') w = snprintf (t->line, t->line_cap, "%s,S,%d,%d,%c,%c", nm, r->ref_pos, r->length, (int) ((r->kind_ref_alt >> 8) & 0xFF), (int) ((r->kind_ref_alt >> 16) & 0xFF));
+        else w = snprintf (t->line, t->line_cap, "%s,%c,%d,%d,,", nm, kind, r->ref_pos, r->length);
+      }
+      t->line[w++] = '\n'; t->line[w] = '\0';
+      if (t->variants) bad += biomcmc_write_compress (t->variants, t->line) != w;
+    }
+    if (t->qc) {
+      if (nm_len + 256 > t->line_cap) { t->line_cap = (nm_len + 256) * 2; t->line = (char *) biomcmc_realloc (t->line, t->line_cap); }
+      const int w = snprintf (t->line, t->line_cap, "%s,%d,%d,%d,%d,%d,%d,%d,%lld,%d,%d,%d,%d\n", nm, len[q], t->score[q], c->matches, c->substitutions, c->deletion_runs, c->deleted_sites, q_ins, q_bases,
+                              c->unknown_sites, c->other_sites, c->first_site, c->last_site);
+      bad += biomcmc_write_compress (t->qc, t->line) != w;
+    }
+    t->n_seqs++;
+    t->n_sub += c->substitutions; t->n_del += c->deletion_runs; t->n_del_sites += c->deleted_sites; t->n_ins += q_ins; t->n_ins_bases += q_bases;
+  }
+  if (iv != n_rec || ii != n_ins) { snprintf (t->err, sizeof t->err, "records of a sequence the pool does not hold, or out of order (%lld of %lld variants, %lld of %lld insertions taken)", iv, n_rec, ii, n_ins); return -1; }
+  if (bad) fprintf (stderr, "The variant or QC table may not be correctly compressed, %d error%s occurred when saving %d sequences.\n", bad, bad > 1 ? "s" : "", n_rows);
+  return 0;
+}
+
 /* `uvaialign --device-parse`: the text is read in blocks (fasta_blocks.h) and split into records on the GPU (uvaia_gpu_fasta_scan); the
  * filters of the fill loop in main run on the integers of the record table and the A C G T counts; the survivors of a scan go, a pool at a
  * time and in record order, from the parser's device memory into the aligner's (uvaia_gpu_fasta_sequences, uvaia_align_load_device).  Only
@@ -108,6 +215,8 @@ struct align_parse {
   uvaia_aligner *al;
   struct uvdb_packer *pk;               /* NULL without --packed */
   struct ins_table *ins;
+  struct var_table *var;
+  int *len;                             /* main's array of a pool: the queries' lengths, for the QC table */
   file_compress_t outstream;
   bool to_screen, write_text;
   size_t aln_length;
@@ -178,6 +287,11 @@ align_parse_records (void *user, char *text, size_t consumed, int n_records, cha
       snprintf (err, errlen, "%s (insertions of the pool that starts with sequence %s; %d sequences were written before)", d->ins->err, d->name[0], d->n_output);
       return -1;
     }
+    for (int c = 0; c < fill; c++) d->len[c] = (int) (d->offsets[c + 1] - d->offsets[c]);
+    if (var_table_add (d->var, d->al, d->name, d->len)) {
+      snprintf (err, errlen, "%s (variants of the pool that starts with sequence %s; %d sequences were written before)", d->var->err, d->name[0], d->n_output);
+      return -1;
+    }
     if (d->pk && packer_add_pool (d->pk, d->al, d->name, fill)) {
       snprintf (err, errlen, "packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", d->n_pool, fill, d->name[0], d->pk->err, d->pk->kept);
       return -1;
@@ -219,6 +333,7 @@ align_device_parse (struct align_parse *d, const char **fasta, int n_fasta, size
       if (d->outstream) biomcmc_close_compress (d->outstream);
       if (d->pk) uvdb_packer_close (d->pk);
       ins_table_close (d->ins);
+      var_table_close (d->var);
       if (broken) biomcmc_error ("%s", failed);
       const int text = strstr (msg, "FASTA text:") || strstr (msg, "does not fit a block");     /* what the parser refuses, the line reader takes */
       biomcmc_error ("%s%s", msg, text ? " (--device-parse takes regular FASTA whose records fit a block: `uvaialign` without it reads this file line by line)" : "");
@@ -243,13 +358,14 @@ main (int argc, char **argv)
   size_t parse_block = FASTA_BLOCK_BYTES;
   int devices[64], n_devices = 0;
   double ambig = 0.5, ambig_r = 0.5;
-  const char *out = NULL, *ref_file = NULL, *packed = NULL, *insertions = NULL;
+  const char *out = NULL, *ref_file = NULL, *packed = NULL, *insertions = NULL, *variants = NULL, *qc = NULL;
   static const struct option longopts[] = {
     {"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"stdout", no_argument, 0, 1000}, {"ambiguity", required_argument, 0, 'a'},
     {"pool", required_argument, 0, 'p'}, {"reference", required_argument, 0, 'r'}, {"nthreads", required_argument, 0, 't'},
     {"output", required_argument, 0, 'o'}, {"device", required_argument, 0, 1001}, {"devices", required_argument, 0, 1002},
     {"packed", required_argument, 0, 1003}, {"ref_ambiguity", required_argument, 0, 'A'}, {"compact", no_argument, 0, 1004},
     {"device-parse", no_argument, 0, 1005}, {"parse-block", required_argument, 0, 1006}, {"insertions", required_argument, 0, 1007},
+    {"variants", required_argument, 0, 1008}, {"qc", required_argument, 0, 1009},
     {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hva:p:r:t:o:A:", longopts, NULL)) != -1) switch (ch) {
     case 'h': help = 1; break;
@@ -267,6 +383,8 @@ main (int argc, char **argv)
     case 1005: device_parse = 1; break;
     case 1006: parse_block = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the block size of --device-parse in bytes) */
     case 1007: insertions = optarg; break;
+    case 1008: variants = optarg; break;
+    case 1009: qc = optarg; break;
     case 'A': ambig_r = atof (optarg); break;
     default: errors++;
   }
@@ -277,9 +395,26 @@ main (int argc, char **argv)
     fprintf (stderr, "--compact chooses the form of the packed database: it needs --packed <out.uvdb>\n");
     errors++;
   }
+  if (!help && !errors) {   /* the tables are files of their own: none of them is another table or an output of -o or --packed */
+    const char *table[3] = {insertions, variants, qc};
+    static const char *const table_opt[3] = {"--insertions", "--variants", "--qc"};
+    size_t outlen = 0;
+    char *text_out = out ? outfile_from_prefix (out, &outlen) : NULL;
+    for (int i = 0; i < 3 && !errors; i++) {
+      if (!table[i]) continue;
+      for (int k = i + 1; k < 3 && !errors; k++) if (table[k] && !strcmp (table[i], table[k])) {
+        fprintf (stderr, "%s and %s name the same file %s: every table needs a file of its own\n", table_opt[i], table_opt[k], table[i]);
+        errors++;
+      }
+      if (!errors && text_out && !to_screen && !strcmp (table[i], text_out)) { fprintf (stderr, "%s names %s, the file -o writes the alignment to\n", table_opt[i], table[i]); errors++; }
+      if (!errors && packed && !strcmp (table[i], packed)) { fprintf (stderr, "%s names %s, the database --packed writes\n", table_opt[i], table[i]); errors++; }
+    }
+    free (text_out);
+    if (errors) return EXIT_FAILURE;
+  }
   if (help || errors || !ref_file || n_fasta < 1 || pool < 1) {
     printf ("%s \nAlign query sequences against a reference\nThe complete syntax is:\n\n", UVAIA_PACKAGE_STRING);
-    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] [--device-parse] [--insertions <file>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
+    printf (" %s [-hv] [--stdout] [-p <int>] [-t <int>] [-o <without suffix>] [-a <double>] [--packed <out.uvdb> [--compact]] [-A <double>] [--device-parse] [--insertions <file>] [--variants <file>] [--qc <file>] -r <ref.fa|ref.fa.xz> <seqs.fa|seqs.fa.xz> [<seqs.fa|seqs.fa.xz>]...\n\n", basename (argv[0]));
     printf ("  -h, --help                       print a longer help and exit\n  -v, --version                    print version and exit\n");
     printf ("  --stdout                         print alignment to stdout (to redirect/pipe) instead of compress to file; much faster but may generate a big output\n");
     printf ("  -p, --pool=<int>                 How many query sequences are read in batch, to be aligned in parallel (defaults to 256 per thread)\n");
@@ -301,6 +436,12 @@ main (int argc, char **argv)
     printf ("  --insertions=<file>              write the characters the alignment drops -- insertions relative to the reference -- as a table\n");
     printf ("                                   sequence,ref_pos,length,bases: one line per run, ref_pos = reference sites to its left (0 = before the first);\n");
     printf ("                                   compressed by the file's suffix (gz, xz, bz2).  Goes with every other option\n");
+    printf ("  --variants=<file>                write what every aligned sequence differs from the reference by as a table sequence,kind,ref_pos,length,ref,alt:\n");
+    printf ("                                   S = substitution (a base A C G T unlike the reference; ref and alt), D = deletion (a run of gaps from ref_pos on),\n");
+    printf ("                                   I = insertion (ref_pos sites to its left, the bases in alt); by ref_pos within a sequence.  Compressed by suffix\n");
+    printf ("  --qc=<file>                      write one line per aligned sequence:\n");
+    printf ("                                   sequence,length,score,matches,substitutions,deletions,deleted_sites,insertions,inserted_bases,unknown_sites,other_sites,first_site,last_site\n");
+    printf ("                                   (first_site, last_site: the first and last reference site that is no gap).  Both go with every other option\n");
     printf ("  --parse-block=<bytes>            with --device-parse: the text is read in blocks of this size (64 to 1073741824, default 67108864); a record\n");
     printf ("                                   must fit one\n");
     if (help) {
@@ -370,6 +511,13 @@ main (int argc, char **argv)
     for (int d = 0; d < n_devices; d++) if (uvaia_align_set_insertions (gpu[d], 1, 0)) biomcmc_error ("%s", uvaia_align_last_error (gpu[d]));
     fprintf (stderr, "Insertions relative to the reference will be saved into file %s.\n", insertions);
   }
+  struct var_table var;
+  var_table_open (&var, variants, qc);
+  if (variants || qc) {   /* the I lines and the insertion counts come from the insertion records */
+    for (int d = 0; d < n_devices; d++) if (uvaia_align_set_insertions (gpu[d], 1, 0) || uvaia_align_set_variants (gpu[d], 1)) biomcmc_error ("%s", uvaia_align_last_error (gpu[d]));
+    if (variants) fprintf (stderr, "Substitutions, deletions and insertions relative to the reference will be saved into file %s.\n", variants);
+    if (qc) fprintf (stderr, "One line of counts per aligned sequence will be saved into file %s.\n", qc);
+  }
   char **seq = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *)), **name = (char **) biomcmc_malloc ((size_t) pool * sizeof (char *));
   int *len = (int *) biomcmc_malloc ((size_t) pool * sizeof (int));
   char *aln = write_text ? (char *) biomcmc_malloc ((size_t) pool * (aln_length + 1)) : NULL;
@@ -381,7 +529,7 @@ main (int argc, char **argv)
   if (device_parse) {
     struct align_parse d;
     memset (&d, 0, sizeof d);
-    d.al = gpu[0]; d.pk = packed ? &pk : NULL; d.ins = &ins; d.outstream = outstream; d.to_screen = to_screen; d.write_text = write_text;
+    d.al = gpu[0]; d.pk = packed ? &pk : NULL; d.ins = &ins; d.var = &var; d.len = len; d.outstream = outstream; d.to_screen = to_screen; d.write_text = write_text;
     d.aln_length = aln_length; d.ambig = ambig; d.pool = pool; d.name = name; d.aln = aln; d.time1 = time1;
     align_device_parse (&d, fasta, n_fasta, parse_block, devices[0]);
     count = d.count; n_output = d.n_output; align_ms = d.align_ms;
@@ -437,6 +585,7 @@ main (int argc, char **argv)
           if (outstream) biomcmc_close_compress (outstream);
           if (packed) uvdb_packer_close (&pk);
           ins_table_close (&ins);
+          var_table_close (&var);
           biomcmc_error ("%s (counted from sequence %s, the first of the %d handed to device %d; %d sequences were written before)",
                          uvaia_align_last_error (gpu[failed]), name[a], b - a, failed, n_output);
         }
@@ -446,7 +595,15 @@ main (int argc, char **argv)
             if (outstream) biomcmc_close_compress (outstream);
             if (packed) uvdb_packer_close (&pk);
             ins_table_close (&ins);
+            var_table_close (&var);
             biomcmc_error ("%s (insertions of the %d sequences from %s on, handed to device %d; %d sequences were written before)", ins.err, b - a, name[a], d, n_output);
+          }
+          if (b > a && var_table_add (&var, gpu[d], name + a, len + a)) {
+            if (outstream) biomcmc_close_compress (outstream);
+            if (packed) uvdb_packer_close (&pk);
+            ins_table_close (&ins);
+            var_table_close (&var);
+            biomcmc_error ("%s (variants of the %d sequences from %s on, handed to device %d; %d sequences were written before)", var.err, b - a, name[a], d, n_output);
           }
         }
         if (packed && packer_add_pool (&pk, gpu[0], name, fill)) {   /* both files stay complete: close them before giving up */
@@ -454,6 +611,7 @@ main (int argc, char **argv)
           snprintf (msg, sizeof msg, "%s", pk.err);
           if (outstream) biomcmc_close_compress (outstream);
           ins_table_close (&ins);
+          var_table_close (&var);
           const long kept = pk.kept;
           uvdb_packer_close (&pk);
           biomcmc_error ("packing pool %d (%d sequences, the first is %s): %s; %ld sequences were packed before", n_pool, fill, name[0], msg, kept);
@@ -487,6 +645,13 @@ main (int argc, char **argv)
   if (insertions) {
     fprintf (stderr, "Insertions: %ld sequences with insertions, %lld inserted bases saved to file %s.\n", ins.n_seqs, ins.n_bases, insertions);
     ins_table_close (&ins);
+  }
+  if (variants || qc) {
+    fprintf (stderr, "Variants: %ld sequences with %lld substitutions, %lld deletions (%lld sites) and %lld insertions (%lld bases)", var.n_seqs, var.n_sub, var.n_del, var.n_del_sites, var.n_ins, var.n_ins_bases);
+    if (variants) fprintf (stderr, "; records saved to file %s", variants);
+    if (qc) fprintf (stderr, "; counts saved to file %s", qc);
+    fprintf (stderr, ".\n");
+    var_table_close (&var);
   }
   if (to_screen) fprintf (stderr, "Output %d aligned sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));
   else if (!write_text) fprintf (stderr, "Aligned %d sequences. Total elapsed time: %.3lf secs\n", n_output, biomcmc_update_elapsed_time (time0));

@@ -26,6 +26,8 @@
 //     match runs are copied 64 characters at a time, runs of mismatches (N runs) are taken 63 steps per round trip.
 //   * the characters the projection drops (insertion runs) are reported on request (uvaia_align_set_insertions): the kernel's body,
 //     wfa_align_body.inc, is compiled a second time as wfa_align_insertions_kernel, whose backtrace writes one record per run.
+//   * what a finished row differs from the reference by (substitutions, deletion runs, per-row counts) is derived from the rows where they
+//     lie, on request (uvaia_align_set_variants, uvaia_align_variants_of): three small kernels of their own, align_variants.inc.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,6 +39,7 @@
 #include <vector>
 
 #include "../../include/uvaia_align.h"
+#include "rows_block.h"
 
 // build-time shape (tools/ab_align.sh measures variants): groups of 64 diagonals a wave has in flight, waves per block
 #ifndef WFA_GROUP
@@ -166,6 +169,8 @@ __global__ __launch_bounds__(256) void expected_cost_kernel(const uint8_t *__res
   if (threadIdx.x == 0) cost[q] = 4 * (part[0] + part[1] + part[2] + part[3]) + 2 * abs(tlen - plen);
 }
 
+#include "align_variants.inc"
+
 thread_local std::string g_align_open_error;
 
 }  // namespace
@@ -210,6 +215,16 @@ struct uvaia_aligner {
     DevBuf<int4> rec, sorted; DevBuf<int> n_rec, runs; DevBuf<long long> at; DevBuf<uint8_t> bases;
     std::vector<uvaia_align_insertion> h_rec; std::vector<char> h_bases;
   } ins;
+  // substitutions, deletions and per-row counts (uvaia_align_set_variants, uvaia_align_variants_of): the last answer stays on the device
+  // until it is fetched -- two int4 of counts per row, the rows' offsets into the records, the records; `rows` holds what variants_of copies in
+  struct Variants {
+    bool on = false, done = false, from_run = false;
+    int n_rows = 0;
+    long long total = 0;
+    double ms = 0;
+    DevBuf<uint8_t> rows; DevBuf<int4> qc, rec; DevBuf<long long> off;
+    Event e0, e1, e2, e3;
+  } var;
   std::string err;
 };
 
@@ -393,6 +408,44 @@ int gather_insertions(uvaia_aligner *a)
   return 0;
 }
 
+// The three passes of align_variants.inc over n rows on the device.  Only the number of records comes to the host between the second and
+// the third, to size the record buffer.
+int run_variants(uvaia_aligner *a, const uint8_t *d_rows, size_t pitch, int n, bool from_run)
+{
+  uvaia_aligner::Variants &V = a->var;
+  V.done = false; V.from_run = from_run; V.n_rows = 0; V.total = 0;
+  if (n > 0) {
+    int rc;
+    if ((rc = V.qc.reserve(a, 2 * (size_t)n)) || (rc = V.off.reserve(a, (size_t)n + 1)) || (rc = V.e0.make(a)) || (rc = V.e1.make(a)) || (rc = V.e2.make(a)) || (rc = V.e3.make(a))) return rc;
+    const unsigned blocks = (unsigned)(((size_t)n + 3) / 4);
+    long long total = 0;
+    float ms = 0, ms_emit = 0;
+    HIPCHK(a, hipEventRecord(V.e0, a->stream));
+    hipLaunchKernelGGL(variants_count_kernel, dim3(blocks), dim3(256), 0, a->stream, d_rows, pitch, n, a->d_ref, a->plen, V.qc);
+    HIPCHK(a, hipGetLastError());
+    hipLaunchKernelGGL(variants_offsets_kernel, dim3(1), dim3(1024), 0, a->stream, V.qc, n, V.off);
+    HIPCHK(a, hipGetLastError());
+    HIPCHK(a, hipEventRecord(V.e1, a->stream));
+    HIPCHK(a, hipMemcpyAsync(&total, V.off.p + n, sizeof total, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(a, hipStreamSynchronize(a->stream));
+    if (total < 0 || total > (long long)n * ((long long)a->plen + 1)) return afail(a, UVAIA_ALIGN_ESTATE, "%lld variant records for %d rows of %d sites", total, n, a->plen);
+    if (total) {
+      if ((rc = V.rec.reserve(a, (size_t)total))) return rc;
+      HIPCHK(a, hipEventRecord(V.e2, a->stream));
+      hipLaunchKernelGGL(variants_emit_kernel, dim3(blocks), dim3(256), 0, a->stream, d_rows, pitch, n, a->d_ref, a->plen, V.off, V.rec);
+      HIPCHK(a, hipGetLastError());
+      HIPCHK(a, hipEventRecord(V.e3, a->stream));
+      HIPCHK(a, hipEventSynchronize(V.e3));
+      HIPCHK(a, hipEventElapsedTime(&ms_emit, V.e2, V.e3));
+    }
+    HIPCHK(a, hipEventElapsedTime(&ms, V.e0, V.e1));
+    V.ms += (double)ms + ms_emit;
+    V.total = total;
+  }
+  V.n_rows = n; V.done = true;
+  return 0;
+}
+
 struct CloseAligner { void operator()(uvaia_aligner *a) const { uvaia_align_close(a); } };
 
 }  // namespace
@@ -495,6 +548,7 @@ static int load_begin(uvaia_aligner *a, const void *bytes, const int64_t *offset
   if (n < 0 || (n > 0 && (!bytes || !offsets))) return afail(a, UVAIA_ALIGN_EINVAL, "bad pool");
   HIPCHK(a, hipSetDevice(a->device));
   a->n = 0; a->ran = false; a->ins.done = false;
+  if (a->var.from_run) a->var.done = false;
   if (n == 0) return 1;
   for (int i = 0; i < n; i++) if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] > 0x3fffffff) return afail(a, UVAIA_ALIGN_EINVAL, "bad length of sequence %d", i);
   return 0;
@@ -543,7 +597,13 @@ int uvaia_align_run(uvaia_aligner *a)
   if (!a) return UVAIA_ALIGN_EINVAL;
   HIPCHK(a, hipSetDevice(a->device));
   a->passes = 0; a->cells = 0; a->kernel_ms = 0; a->ran = false; a->ins.done = false;
-  if (a->n == 0) { a->ins.h_rec.clear(); a->ins.h_bases.clear(); a->ins.done = a->ins.on; a->ran = true; return 0; }
+  if (a->var.from_run || a->var.on) a->var.done = false;               // (with the option off, an answer of uvaia_align_variants_of stands)
+  if (a->n == 0) {
+    a->ins.h_rec.clear(); a->ins.h_bases.clear(); a->ins.done = a->ins.on;
+    if (a->var.on) { if (int rc = run_variants(a, nullptr, 0, 0, true)) return rc; }
+    a->ran = true;
+    return 0;
+  }
   int rc = ensure_pool_memory(a, false, nullptr); if (rc) return rc;
   HIPCHK(a, hipMemsetAsync(a->d_cells, 0, sizeof(unsigned long long), a->stream));
   HIPCHK(a, hipEventRecord(a->ev_a, a->stream));
@@ -553,6 +613,7 @@ int uvaia_align_run(uvaia_aligner *a)
   HIPCHK(a, hipEventSynchronize(a->ev_b));
   float ms = 0; HIPCHK(a, hipEventElapsedTime(&ms, a->ev_a, a->ev_b)); a->kernel_ms = ms;
   HIPCHK(a, hipMemcpy(&a->cells, a->d_cells, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (a->var.on) { rc = run_variants(a, a->d_aln, (size_t)a->plen + 1, a->n, true); if (rc) return rc; }   // (after kernel_ms: the passes have a clock of their own)
   a->ran = true; a->ins.done = a->ins.on;
   return 0;
 }
@@ -570,9 +631,9 @@ int uvaia_align_fetch(uvaia_aligner *a, char *aln, int *score)
   if (!a) return UVAIA_ALIGN_EINVAL;
   if (!a->ran) return afail(a, UVAIA_ALIGN_ESTATE, "fetch without a completed run");
   if (a->n == 0) return 0;
-  if (!aln) return afail(a, UVAIA_ALIGN_EINVAL, "NULL row buffer");
+  if (!aln && !score) return afail(a, UVAIA_ALIGN_EINVAL, "NULL row buffer");
   HIPCHK(a, hipSetDevice(a->device));
-  HIPCHK(a, hipMemcpyAsync(aln, a->d_aln, (size_t)a->n * ((size_t)a->plen + 1), hipMemcpyDeviceToHost, a->stream));
+  if (aln) HIPCHK(a, hipMemcpyAsync(aln, a->d_aln, (size_t)a->n * ((size_t)a->plen + 1), hipMemcpyDeviceToHost, a->stream));   // (scores alone: the rows stay where they are)
   if (score) HIPCHK(a, hipMemcpyAsync(score, a->d_score, (size_t)a->n * sizeof(int), hipMemcpyDeviceToHost, a->stream));
   HIPCHK(a, hipStreamSynchronize(a->stream));
   return 0;
@@ -619,6 +680,56 @@ int uvaia_align_fetch_insertions(uvaia_aligner *a, uvaia_align_insertion *rec, c
   if (rec && !a->ins.h_rec.empty()) memcpy(rec, a->ins.h_rec.data(), a->ins.h_rec.size() * sizeof(uvaia_align_insertion));
   if (bases && !a->ins.h_bases.empty()) memcpy(bases, a->ins.h_bases.data(), a->ins.h_bases.size());
   return 0;
+}
+
+int uvaia_align_set_variants(uvaia_aligner *a, int on)
+{ // src/align.c:366-390 writes the rows: with the option on the next runs also say what each of them differs from the reference by
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  a->var.on = on != 0;
+  if (a->var.from_run) a->var.done = false;
+  return 0;
+}
+
+int uvaia_align_variant_counts(uvaia_aligner *a, long long *n_records, int *n_rows)
+{
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  if (!a->var.done) return afail(a, UVAIA_ALIGN_ESTATE, "no variants yet: neither a completed run with uvaia_align_set_variants on nor uvaia_align_variants_of");
+  if (n_records) *n_records = a->var.total;
+  if (n_rows) *n_rows = a->var.n_rows;
+  return 0;
+}
+
+int uvaia_align_fetch_variants(uvaia_aligner *a, uvaia_align_variant *rec, uvaia_align_row_qc *qc)
+{
+  if (int rc = uvaia_align_variant_counts(a, nullptr, nullptr)) return rc;
+  HIPCHK(a, hipSetDevice(a->device));
+  if (rec && a->var.total) HIPCHK(a, hipMemcpyAsync(rec, a->var.rec, (size_t)a->var.total * sizeof(uvaia_align_variant), hipMemcpyDeviceToHost, a->stream));
+  if (qc && a->var.n_rows) HIPCHK(a, hipMemcpyAsync(qc, a->var.qc, (size_t)a->var.n_rows * sizeof(uvaia_align_row_qc), hipMemcpyDeviceToHost, a->stream));
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  return 0;
+}
+
+int uvaia_align_variants_of(uvaia_aligner *a, const char *rows, size_t pitch, int n)
+{ // rows on the reference's columns that another aligner made, in place of those src/align.c:366-390 writes
+  if (!a) return UVAIA_ALIGN_EINVAL;
+  if (n < 0 || (n > 0 && !rows)) return afail(a, UVAIA_ALIGN_EINVAL, "bad rows (%d of them%s)", n, rows ? "" : ", NULL");
+  if (pitch < (size_t)a->plen) return afail(a, UVAIA_ALIGN_EINVAL, "pitch %zu is below the %d sites of a row", pitch, a->plen);
+  HIPCHK(a, hipSetDevice(a->device));
+  if (n == 0) return run_variants(a, nullptr, pitch, 0, false);
+  const size_t bytes = (size_t)(n - 1) * pitch + (size_t)a->plen;      // (the last row may end with its last site)
+  a->var.done = false;
+  HIPCHK(a, hipStreamSynchronize(a->stream));
+  if (int rc = a->var.rows.reserve(a, bytes + 16)) return rc;          // (the load of 16 sites reads whole dwords)
+  HIPCHK(a, hipMemcpyAsync(a->var.rows, rows, bytes, hipMemcpyHostToDevice, a->stream));
+  return run_variants(a, a->var.rows, pitch, n, false);
+}
+
+double uvaia_align_variants_ms(uvaia_aligner *a, int reset)
+{
+  if (!a) return 0.;
+  const double ms = a->var.ms;
+  if (reset) a->var.ms = 0;
+  return ms;
 }
 
 int uvaia_align_stats(uvaia_aligner *a, unsigned long long *cells, double *wavefront_bytes, int *passes, double *kernel_ms)
