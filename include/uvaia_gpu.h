@@ -575,6 +575,40 @@ size_t uvaia_gpu_fasta_chunk_bytes (void);
 void *uvaia_gpu_fasta_pinned_alloc (size_t bytes);
 void uvaia_gpu_fasta_pinned_free (void *p);
 
+/* ---- all pairs of the resident database against each other (`uvaiadist`).  What users of the reference do next with a set of aligned
+ * genomes -- pairwise distances for trees and transmission clusters -- computed where the rows already are.  The counters of two resident
+ * references a, b are taken over the sites [trim, nchar - trim), with nothing truncated:
+ *   count[0] ACGT_matches            equal and ACGT             (first counter of the biomcmc 4-count kernel)
+ *   count[1] text_matches            equal and both valid       (its second)
+ *   count[2] partial_matches         IUPAC sets intersect       (its third)
+ *   count[3] valid_pair_comparisons  both valid                 (its fourth)
+ *   count[4] ACGT_pair_comparisons   both ACGT                  (second score of src/fastaseq.c:585-596)
+ * and two distances come from them: snp = count[4] - count[0] (both ACGT and different: what snp-dists prints), uvaia = count[3] - count[2].
+ *
+ * db_pairs:        rows [row0, row0 + n_rows) against columns [col0, col0 + n_cols) of the resident database; out is host memory:
+ *                    UVAIA_GPU_PAIRS_SNP     out[i * ld + j]           = snp distance
+ *                    UVAIA_GPU_PAIRS_COUNTS  out[(i * ld + j) * 5 + c] = count[c]                  (ld >= n_cols, in pairs)
+ *                  (UVAIA_GPU_PAIRS_SNP_ALT: the numbers of _SNP by the kernel's other row-tile height, for measurements).  Elements of out
+ *                  between n_cols and ld are not written.
+ * db_pairs_within: the pairs of that rectangle whose distance under `metric` is <= max_dist, upper != 0: only those with row < col (database
+ *                  positions); sorted by (row, col); *n_found = how many there are; when *n_found > cap, out[0 .. cap) is unspecified and
+ *                  nothing past cap is written.
+ * pairs_ms:        device time in ms since the last reset of [0] the row operands, [1] the dense kernels, [2] the threshold kernels (and the
+ *                  host's sort of the list).
+ * Only a plain default-mode context is accepted: an --acgt context and a context of a reference shard answer UVAIA_GPU_ESTATE.  A rectangle
+ * outside the database, 2 * trim > nchar, an unknown `what` or `metric`, a negative max_dist, a NULL out with something to write and
+ * ld < n_cols are UVAIA_GPU_EINVAL, refused before anything is launched.  2 * trim == nchar gives all zeros; empty ranges succeed and write
+ * nothing.  The database, the derived planes, the heaps and the tolerances are not touched; the calls wait for searches in flight and return when
+ * out is complete.  Working memory is the context's, bounded by the rectangle of one launch: large rectangles are cut into launches. */
+enum { UVAIA_GPU_PAIRS_SNP = 1, UVAIA_GPU_PAIRS_COUNTS = 2, UVAIA_GPU_PAIRS_SNP_ALT = 3 };   /* what */
+enum { UVAIA_GPU_DIST_SNP = 1, UVAIA_GPU_DIST_UVAIA = 2 };                                   /* metric */
+#define UVAIA_GPU_PAIR_NCOUNT 5
+typedef struct { uint32_t row, col; int32_t count[UVAIA_GPU_PAIR_NCOUNT]; } uvaia_gpu_pair;
+int uvaia_gpu_db_pairs (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, size_t col0, size_t n_cols, size_t trim, int what, int32_t *out, size_t ld);
+int uvaia_gpu_db_pairs_within (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, size_t col0, size_t n_cols, size_t trim, int metric, int max_dist, int upper,
+                               uvaia_gpu_pair *out, size_t cap, unsigned long long *n_found);
+void uvaia_gpu_pairs_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
+
 /* bytes the pair scan reads per reference (the default scan reads planes derived from the packed record for this query set) */
 size_t uvaia_gpu_scan_bytes_per_ref (const uvaia_gpu_ctx *ctx);
 /* the pair scan of this context: 2 = column-compressed scan over planes derived for the query set (default above 32 queries),

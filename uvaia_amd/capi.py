@@ -38,7 +38,14 @@ SYMBOLS = [
     "uvaia_gpu_fasta_kernel_ms", "uvaia_gpu_fasta_chunk_bytes", "uvaia_gpu_fasta_pinned_alloc", "uvaia_gpu_fasta_pinned_free",
     "uvaia_gpu_fasta_acgt", "uvaia_gpu_fasta_sequences", "uvaia_gpu_fasta_sequences_host", "uvaia_gpu_fasta_sequences_ms",
     "uvaia_gpu_text_append_device", "uvaia_gpu_text_size", "uvaia_gpu_text_rows", "uvaia_gpu_text_clear", "uvaia_gpu_text_reserve", "uvaia_gpu_text_ms",
+    "uvaia_gpu_db_pairs", "uvaia_gpu_db_pairs_within", "uvaia_gpu_pairs_ms",
 ]
+
+PAIR_NCOUNT = 5
+PAIRS_SNP, PAIRS_COUNTS, PAIRS_SNP_ALT = 1, 2, 3        # `what` of uvaia_gpu_db_pairs
+DIST_SNP, DIST_UVAIA = 1, 2                             # `metric` of uvaia_gpu_db_pairs_within
+# uvaia_gpu_pair: (row, col, count[5])
+PAIR_DTYPE = np.dtype([("row", np.uint32), ("col", np.uint32), ("count", np.int32, (PAIR_NCOUNT,))])
 
 
 class GpuError(RuntimeError):
@@ -234,6 +241,9 @@ def load_library():
         "uvaia_gpu_text_clear": (C.c_int, [vp]),
         "uvaia_gpu_text_reserve": (C.c_int, [vp, C.c_size_t]),
         "uvaia_gpu_text_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_db_pairs": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]),
+        "uvaia_gpu_db_pairs_within": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
+        "uvaia_gpu_pairs_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -401,6 +411,42 @@ class Engine:
         out = (C.c_double * 3)()
         self.L.uvaia_gpu_rows_kernel_ms(self.ctx, out, int(reset))
         return {"census": out[0], "gather": out[1], "exceptions": out[2]}
+
+    # ---- all pairs of the resident database against each other
+    def db_pairs(self, rows=None, cols=None, trim=0, what=PAIRS_SNP, out=None, ld=None):
+        """counters of rows (first, n) against cols (first, n) of the resident database (None: all of it): int32 [n_rows, ld] snp distances
+        (what = PAIRS_SNP) or [n_rows, ld, 5] counters (PAIRS_COUNTS); the columns of out between n_cols and ld are left as they are"""
+        r0, nr = (0, self.db_size()) if rows is None else rows
+        c0, nc = (0, self.db_size()) if cols is None else cols
+        ld = nc if ld is None else ld
+        shape = (nr, ld, PAIR_NCOUNT) if what == PAIRS_COUNTS else (nr, ld)
+        if out is None:
+            out = np.zeros(shape, dtype=np.int32)
+        if out.dtype != np.int32 or not out.flags.c_contiguous or out.size < int(np.prod(shape)):
+            raise GpuError(-1, "out must be a contiguous int32 array of at least %r" % (shape,))
+        self._chk(self.L.uvaia_gpu_db_pairs(self.ctx, int(r0), int(nr), int(c0), int(nc), int(trim), int(what), out.ctypes.data, int(ld)))
+        return out
+
+    def db_pairs_within(self, max_dist, rows=None, cols=None, trim=0, metric=DIST_SNP, upper=True, cap=None, out=None):
+        """(records of PAIR_DTYPE, n_found): the pairs of the rectangle within max_dist, sorted by (row, col); cap None: the list is grown
+        until everything fits; otherwise out (or a fresh array) of cap records is handed in as it is and n_found may exceed it"""
+        r0, nr = (0, self.db_size()) if rows is None else rows
+        c0, nc = (0, self.db_size()) if cols is None else cols
+        n = C.c_ulonglong()
+        grow = cap is None
+        cap = 1024 if grow else int(cap)
+        while True:
+            buf = out if out is not None else np.zeros(cap, dtype=PAIR_DTYPE)
+            self._chk(self.L.uvaia_gpu_db_pairs_within(self.ctx, int(r0), int(nr), int(c0), int(nc), int(trim), int(metric), int(max_dist), int(bool(upper)),
+                                                       buf.ctypes.data if buf.size else None, cap, C.byref(n)))
+            if not grow or n.value <= cap:
+                return (buf[:n.value] if grow else buf), n.value
+            cap = int(n.value)
+
+    def pairs_ms(self, reset=False):
+        out = (C.c_double * 3)()
+        self.L.uvaia_gpu_pairs_ms(self.ctx, out, int(reset))
+        return {"rows": out[0], "dense": out[1], "within": out[2]}
 
     def rows_set_run_cut(self, cut):
         self._chk(self.L.uvaia_gpu_rows_set_run_cut(self.ctx, int(cut)))

@@ -210,6 +210,12 @@ struct uvaia_gpu_ctx {
     Event ev[4]; double ms[2] = {0., 0.};              // device time of count + prefix, of emit
     bool plan = false; size_t first_tile = 0, n_tiles = 0; unsigned long long db_gen = 0, n_heads = 0, n_lits = 0;
   } enc;
+  // ---- all pairs of the resident database (host_pairs.inc): the row operand records of a band, the counters of one launch, the list of one
+  // launch and its length; everything is sized by the rectangle of a launch
+  struct Pairs {
+    DevBuf<uint32_t> d_rec; DevBuf<int> d_out; DevBuf<uvaia_gpu_pair> d_list; DevBuf<unsigned long long> d_count;
+    Event ev[2]; double ms[3] = {0., 0., 0.};          // device time of the row operands, the dense kernels, the threshold kernels (+ the host's sort)
+  } pairs;
   // last batch (introspection)
   struct { const TileStore *store = nullptr; long long tile_first = 0; int n_tiles = 0, n = 0, rbegin = 0, ppad = 0; const int4 *rt = nullptr; } last;
   // ---- statistics

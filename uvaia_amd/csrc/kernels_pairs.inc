@@ -1,0 +1,232 @@
+// kernels_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within): pairs_rows_kernel builds the row-side operand records of a band of rows, pairs_snp_kernel and pairs_counts_kernel count every (row, column) pair of a rectangle, the latter also into a list of the pairs within a distance.
+
+// ------------------------------------------------------------------------------------------------------------
+// device: all-pairs counters over the resident four-plane tiles
+// ------------------------------------------------------------------------------------------------------------
+// Counters of a pair (a, b) over the sites [trim, nchar - trim), nothing truncated (include/uvaia_gpu.h):
+//   0 ACGT_matches  1 text_matches  2 partial_matches  3 valid_pair_comparisons  4 ACGT_pair_comparisons
+// On the planes a site is valid iff some plane bit is set and ACGT iff exactly one is; two sites are equal and valid iff the four planes are
+// equal and one is set; the sets intersect iff some plane has both bits set.
+//
+// The column side of a pair is a lane of a resident tile, read as the scans read it.  The row side is wave-uniform: a record of dwords per
+// (row, word group) at an address every lane shares, so that it arrives through scalar loads and is an SGPR operand of the bit operations.
+//   SNP record,    12 dwords: lo[4] hi[4] is[4]                 (the 2-bit code of import_tiles_kernel<3> and "is ACGT", words 4 w4 .. 4 w4 + 3)
+//   COUNTS record, 24 dwords: (A C G T valid single) x 4 words   (the qp layout of scan_iupac_kernel)
+// rec[(row - first row of the band) * W4 + w4][dwords]; the band is padded to whole blocks of 64 rows with cleared records.
+constexpr int PAIRS_SNP_DW = 12, PAIRS_CNT_DW = 24;
+constexpr int PAIRS_CNT_RT = 16;      // rows per wave of pairs_counts_kernel: 80 accumulators, no scratch (kernel-resource-usage)
+
+static __device__ __forceinline__ uint32_t pairs_window_mask(int word, int lo_site, int hi_site)
+{ // the bits of alignment word `word` (sites 32 word .. 32 word + 31) that lie in [lo_site, hi_site)
+  const int a = max(lo_site - word * 32, 0), b = min(hi_site - word * 32, 32);
+  if (a >= b) return 0u;
+  const uint32_t below_b = b >= 32 ? 0xFFFFFFFFu : ((1u << b) - 1u);
+  return below_b & ~((1u << a) - 1u);                  // (a < b <= 32: the shift is defined)
+}
+
+// The trim window is applied here and only here: the row-side words are cleared outside [lo_site, hi_site), the first and last word of the
+// window by bit.  Where the row side is cleared every counter of the pair is 0 whatever the column holds there (q = row side, r = column side):
+//   0 ACGT_matches       counts  equal & q.single              q.single = 0                                         -> 0
+//   1 text_matches       counts  equal & r.valid               a cleared row side equals the column only where the column is the empty set too
+//                                                              ("equal" is 1 there), and there r.valid = 0; elsewhere equal = 0  -> 0
+//   2 partial_matches    counts  (A & A') | ... | (T & T')     every row plane is 0                                 -> 0
+//   3 valid_pair_comp.   counts  r.valid & q.valid             q.valid = 0                                          -> 0
+//   4 ACGT_pair_comp.    counts  r.single & q.single           q.single = 0                                         -> 0
+//   snp pair             counts  differ & r.is & q.is          q.is = 0                                             -> 0
+// The column side therefore needs no mask, and sites at and past nchar (zero in tiles this library packed, anything in tiles that were handed
+// in) never count: the window ends at nchar - trim.
+// One block per (64 rows of the band, 4 word groups): thread = (row, word group) reads its four plane words as the tiles hold them (a wave =
+// 64 rows of one word group, contiguous where the rows share a tile), the records are turned through LDS so that a row's 4 x D dwords leave
+// as one contiguous run.
+template <int D>
+__global__ __launch_bounds__(256) void pairs_rows_kernel(const uint4 *__restrict__ db, int W4, long long row0, int n_rows, int lo_site, int hi_site,
+                                                          uint32_t *__restrict__ rec)
+{
+  __shared__ uint32_t turn[64 * 4 * D];
+  const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
+  const int rr = blockIdx.x * 64 + lane, w4 = blockIdx.y * 4 + wq;
+  uint32_t v[D];
+#pragma unroll
+  for (int k = 0; k < D; k++) v[k] = 0u;
+  if (rr < n_rows && w4 < W4) {
+    const long long r = row0 + rr;
+    const uint4 *t = db + ((size_t)(r >> 6) * W4 + w4) * 4 * 64 + (r & 63);
+    const uint4 pA = t[0], pC = t[64], pG = t[128], pT = t[192];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t m = pairs_window_mask(w4 * 4 + j, lo_site, hi_site);
+      const uint32_t a = u4c(pA, j) & m, cc = u4c(pC, j) & m, g = u4c(pG, j) & m, tt = u4c(pT, j) & m;
+      const uint32_t par = a ^ cc ^ g ^ tt, three = (a & cc & (g | tt)) | (g & tt & (a | cc));
+      const uint32_t single = par & ~three;
+      if (D == PAIRS_SNP_DW) { v[j] = (cc | tt) & single; v[4 + j] = (g | tt) & single; v[8 + j] = single; }
+      else { v[j * 6 + 0] = a; v[j * 6 + 1] = cc; v[j * 6 + 2] = g; v[j * 6 + 3] = tt; v[j * 6 + 4] = a | cc | g | tt; v[j * 6 + 5] = single; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < D; k++) turn[(lane * 4 + wq) * D + k] = v[k];
+  __syncthreads();
+  const int nw = min(4, W4 - (int)blockIdx.y * 4);     // word groups of this block that exist
+  for (int i = threadIdx.x; i < 64 * 4 * D; i += 256) {
+    const int l = i / (4 * D), o = i % (4 * D);
+    if (o < nw * D) rec[((size_t)(blockIdx.x * 64 + l) * W4 + (size_t)blockIdx.y * 4) * D + o] = turn[i];
+  }
+}
+
+// The snp distance (both ACGT and different = ACGT_pair_comparisons - ACGT_matches) of RT rows x 64 columns per wave: lane = column reference,
+// one column tile per wave, the four waves of a block take four neighbouring column tiles against the same rows.  The column's (lo, hi, is)
+// are derived in registers once per word; per row and word  x = lo ^ lo'  (v_xor),  y = x | (hi ^ hi')  (v_bitop3),  m = y & is & is'
+// (v_bitop3),  acc += popcount(m)  (v_bcnt): 4 vector instructions per pair-word, the row operands SGPRs.
+// Grid: block b = (row tile b % n_rtiles, column group b / n_rtiles) -- the row tile runs fastest, so the blocks resident together read the
+// same few column tiles out of the caches and each others' row records.
+// out[i * ld_out + (col - col0)] for rows i < n_rows of the band and columns in [col0, col0 + n_cols); nothing else is written.
+template <int RT>
+__global__ __launch_bounds__(256) void pairs_snp_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, int n_rows, int n_rtiles,
+                                                         long long ctile0, int n_ctiles, long long col0, int n_cols, int *__restrict__ out, size_t ld_out)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rt = blockIdx.x % n_rtiles, ct = (blockIdx.x / n_rtiles) * 4 + wave;
+  if (ct >= n_ctiles) return;
+  int acc[RT];
+#pragma unroll
+  for (int r = 0; r < RT; r++) acc[r] = 0;
+  const uint4 *t = db + (size_t)(ctile0 + ct) * W4 * 4 * 64 + lane;
+  const size_t rstride = (size_t)W4 * PAIRS_SNP_DW;
+  const uint32_t *rb = rec + (size_t)rt * RT * rstride;
+  for (int w4 = 0; w4 < W4; w4++) {
+    const uint4 pA = t[(size_t)(w4 * 4 + 0) * 64], pC = t[(size_t)(w4 * 4 + 1) * 64], pG = t[(size_t)(w4 * 4 + 2) * 64], pT = t[(size_t)(w4 * 4 + 3) * 64];
+    uint32_t cL[4], cH[4], cI[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t a = u4c(pA, j), cc = u4c(pC, j), g = u4c(pG, j), tt = u4c(pT, j);
+      const uint32_t par = a ^ cc ^ g ^ tt, three = (a & cc & (g | tt)) | (g & tt & (a | cc));
+      cI[j] = par & ~three; cL[j] = (cc | tt) & cI[j]; cH[j] = (g | tt) & cI[j];
+    }
+    const uint32_t *s0 = rb + (size_t)w4 * PAIRS_SNP_DW;
+    QWords<PAIRS_SNP_DW> cur, nxt;
+    load_qwords(cur, s0);
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      if (r + 1 < RT) load_qwords(nxt, s0 + (size_t)(r + 1) * rstride);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t x = cL[j] ^ cur.v[j];
+        const uint32_t y = B3(cH[j], cur.v[4 + j], x, (TT_A ^ TT_B) | TT_C);          // codes differ
+        acc[r] = bcnt_acc(B3(y, cI[j], cur.v[8 + j], TT_A & TT_B & TT_C), acc[r]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (r + 1 < RT) cur = nxt;
+    }
+  }
+  const long long j = (ctile0 + ct) * 64 + lane - col0;
+  if (j < 0 || j >= n_cols) return;
+#pragma unroll
+  for (int r = 0; r < RT; r++) {
+    const int i = rt * RT + r;
+    if (i < n_rows) out[(size_t)i * ld_out + (size_t)j] = acc[r];
+  }
+}
+
+// The five counters of PAIRS_CNT_RT rows x 64 columns per wave, same mapping and grid order as pairs_snp_kernel; the plane-equality and
+// intersect chains of scan_iupac_kernel plus one `single & single'` count: 17 vector instructions per pair-word.
+// LIST = false: out[(i * ld_out + (col - col0)) * 5 + c].
+// LIST = true: nothing dense is written; the pairs of the rectangle with distance <= max_dist (metric 1: count[4] - count[0], metric 2:
+// count[3] - count[2]) and, with upper, row < col (database positions) go into list[]: a wave counts its hits by ballots, ONE lane reserves that
+// many slots by one vector atomicAdd on *n_list, and every store is bounded by list_cap -- *n_list ends as the number of hits, whatever fitted.
+template <bool LIST>
+__global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, long long row0, int n_rows, int n_rtiles,
+                                                            long long ctile0, int n_ctiles, long long col0, int n_cols, int *__restrict__ out, size_t ld_out,
+                                                            int metric, int max_dist, int upper, uvaia_gpu_pair *__restrict__ list, unsigned long long list_cap,
+                                                            unsigned long long *__restrict__ n_list)
+{
+  constexpr int RT = PAIRS_CNT_RT;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rt = blockIdx.x % n_rtiles, ct = (blockIdx.x / n_rtiles) * 4 + wave;
+  if (ct >= n_ctiles) return;
+  int acc[RT][5];
+#pragma unroll
+  for (int r = 0; r < RT; r++) { acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = acc[r][4] = 0; }
+  const uint4 *t = db + (size_t)(ctile0 + ct) * W4 * 4 * 64 + lane;
+  const size_t rstride = (size_t)W4 * PAIRS_CNT_DW;
+  const uint32_t *rb = rec + (size_t)rt * RT * rstride;
+  for (int w4 = 0; w4 < W4; w4++) {
+    const uint4 pA = t[(size_t)(w4 * 4 + 0) * 64], pC = t[(size_t)(w4 * 4 + 1) * 64], pG = t[(size_t)(w4 * 4 + 2) * 64], pT = t[(size_t)(w4 * 4 + 3) * 64];
+    const uint32_t rA[4] = {pA.x, pA.y, pA.z, pA.w}, rC[4] = {pC.x, pC.y, pC.z, pC.w}, rG[4] = {pG.x, pG.y, pG.z, pG.w}, rT[4] = {pT.x, pT.y, pT.z, pT.w};
+    uint32_t rv[4], rs[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      rv[j] = rA[j] | rC[j] | rG[j] | rT[j];
+      const uint32_t par = rA[j] ^ rC[j] ^ rG[j] ^ rT[j], three = (rA[j] & rC[j] & (rG[j] | rT[j])) | (rG[j] & rT[j] & (rA[j] | rC[j]));
+      rs[j] = par & ~three;
+    }
+    const uint32_t *s0 = rb + (size_t)w4 * PAIRS_CNT_DW;
+    QWords<PAIRS_CNT_DW> cur, nxt;
+    load_qwords(cur, s0);
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      if (r + 1 < RT) load_qwords(nxt, s0 + (size_t)(r + 1) * rstride);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t qA = cur.v[j * 6 + 0], qC = cur.v[j * 6 + 1], qG = cur.v[j * 6 + 2], qT_ = cur.v[j * 6 + 3], qv = cur.v[j * 6 + 4], qs = cur.v[j * 6 + 5];
+        uint32_t d = rA[j] ^ qA;
+        d = B3(rC[j], qC, d, (TT_A ^ TT_B) | TT_C);
+        d = B3(rG[j], qG, d, (TT_A ^ TT_B) | TT_C);
+        const uint32_t nd = B3(rT[j], qT_, d, ~((TT_A ^ TT_B) | TT_C));   // all four planes equal
+        uint32_t x = rA[j] & qA;
+        x = B3(rC[j], qC, x, (TT_A & TT_B) | TT_C);
+        x = B3(rG[j], qG, x, (TT_A & TT_B) | TT_C);
+        x = B3(rT[j], qT_, x, (TT_A & TT_B) | TT_C);                       // sets intersect (implies both valid)
+        acc[r][0] = bcnt_acc(nd & qs, acc[r][0]);
+        acc[r][1] = bcnt_acc(nd & rv[j], acc[r][1]);
+        acc[r][2] = bcnt_acc(x, acc[r][2]);
+        acc[r][3] = bcnt_acc(rv[j] & qv, acc[r][3]);
+        acc[r][4] = bcnt_acc(rs[j] & qs, acc[r][4]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (r + 1 < RT) cur = nxt;
+    }
+  }
+  const long long col = (ctile0 + ct) * 64 + lane, j = col - col0;
+  const bool col_ok = j >= 0 && j < n_cols;
+  if (!LIST) {
+    if (!col_ok) return;
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      const int i = rt * RT + r;
+      if (i < n_rows) {
+        int *o = out + ((size_t)i * ld_out + (size_t)j) * UVAIA_GPU_PAIR_NCOUNT;
+#pragma unroll
+        for (int k = 0; k < UVAIA_GPU_PAIR_NCOUNT; k++) o[k] = acc[r][k];
+      }
+    }
+  } else {
+    auto hit = [&](int r) {
+      const int i = rt * RT + r;
+      const int dist = metric == UVAIA_GPU_DIST_SNP ? acc[r][4] - acc[r][0] : acc[r][3] - acc[r][2];
+      return col_ok && i < n_rows && dist <= max_dist && (!upper || row0 + i < col);
+    };
+    unsigned total = 0;                                // wave-uniform: ballots
+#pragma unroll
+    for (int r = 0; r < RT; r++) total += (unsigned)__popcll(__ballot(hit(r)));
+    if (total == 0) return;
+    unsigned long long base = 0;
+    if (lane == 0) base = atomicAdd(n_list, (unsigned long long)total);
+    base = ((unsigned long long)(uint32_t)__shfl((int)(base >> 32), 0) << 32) | (uint32_t)__shfl((int)(uint32_t)base, 0);
+    const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      const bool h = hit(r);
+      const unsigned long long b = __ballot(h);
+      const unsigned long long pos = base + (unsigned long long)__popcll(b & below);
+      if (h && pos < list_cap) {
+        uvaia_gpu_pair p;
+        p.row = (uint32_t)(row0 + rt * RT + r); p.col = (uint32_t)col;
+#pragma unroll
+        for (int k = 0; k < UVAIA_GPU_PAIR_NCOUNT; k++) p.count[k] = acc[r][k];
+        list[pos] = p;
+      }
+      base += (unsigned long long)__popcll(b);
+    }
+  }
+}

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -84,6 +85,7 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "kernels_expand.inc"
 #include "kernels_encode.inc"
 #include "kernels_fasta.inc"
+#include "kernels_pairs.inc"
 
 // ------------------------------------------------------------------------------------------------------------
 // host side, in sections (one translation unit: the kernels above are templates the sections instantiate); the context and everything
@@ -103,3 +105,4 @@ constexpr int NBUF = 4;                // counter buffers: the scan may run this
 #include "host_window.inc"
 #include "host_encode.inc"
 #include "host_fasta.inc"
+#include "host_pairs.inc"
