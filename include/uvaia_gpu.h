@@ -609,6 +609,34 @@ int uvaia_gpu_db_pairs_within (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, s
                                uvaia_gpu_pair *out, size_t cap, unsigned long long *n_found);
 void uvaia_gpu_pairs_ms (uvaia_gpu_ctx *ctx, double out[3], int reset);
 
+/* ---- single-linkage clusters within a distance (`uvaiadist -d D --clusters`): the cluster every resident reference belongs to, labelled on
+ * the device.  Take the rows [0, n) of the resident database, a trim, a metric, a distance max_dist >= 0 and a floor min_compared >= 0.  Two
+ * rows a < b are LINKED iff  dist(a, b) <= max_dist  and  compared(a, b) >= min_compared,  where under UVAIA_GPU_DIST_SNP dist = count[4] -
+ * count[0] and compared = count[4] (ACGT_pair_comparisons), under UVAIA_GPU_DIST_UVAIA dist = count[3] - count[2] and compared = count[3]
+ * (valid_pair_comparisons), the counters above over [trim, nchar - trim).  A cluster is a connected component of that graph and its label
+ * the smallest database position among its members: a function of the rows alone, whatever the order of the calls, of the launches or of
+ * the waves, and however the caller cut the matrix.
+ *   The floor is part of the definition, not a repair: under snp a row with no ACGT site (all N, all gaps) is at distance 0 from EVERY row,
+ * so with min_compared = 0 one such row joins all clusters into one.  min_compared >= 1 is what a caller sets against it.
+ *
+ * db_link_begin:  checks as db_pairs does (over the whole database), sets every resident reference to a cluster of its own and remembers
+ *                 the parameters and the size of the database.
+ * db_link:        links the pairs row < col (database positions) of rows [row0, row0 + n_rows) x columns [col0, col0 + n_cols) and ADDS
+ *                 their number to *n_links (a pair linked by two calls is counted twice; the clusters do not change).  Cut into the launches
+ *                 of db_pairs; launches wholly at or below the diagonal are skipped.  The whole matrix needs every pair row < col covered
+ *                 once, e.g. one call per band of rows against all columns.
+ * db_link_labels: labels[i] for the references resident at `begin`; may be called more than once, and between db_link calls (the
+ *                 components of the links made so far).
+ * link_ms:        device time in ms of the link and label kernels since the last reset (the row operands go to pairs_ms [0]); pairs_ms
+ *                 is unchanged.
+ * db_link and db_link_labels answer UVAIA_GPU_ESTATE without a db_link_begin and once the database changed after it; contexts are refused
+ * as by db_pairs; an unknown metric, negative max_dist or min_compared, 2 * trim > nchar, a rectangle outside the database and a NULL
+ * n_links or labels are UVAIA_GPU_EINVAL.  Nothing dense is written and nothing but *n_links and the labels crosses the bus. */
+int uvaia_gpu_db_link_begin (uvaia_gpu_ctx *ctx, size_t trim, int metric, int max_dist, int min_compared);
+int uvaia_gpu_db_link (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, size_t col0, size_t n_cols, unsigned long long *n_links);
+int uvaia_gpu_db_link_labels (uvaia_gpu_ctx *ctx, uint32_t *labels);
+void uvaia_gpu_link_ms (uvaia_gpu_ctx *ctx, double *ms, int reset);
+
 /* bytes the pair scan reads per reference (the default scan reads planes derived from the packed record for this query set) */
 size_t uvaia_gpu_scan_bytes_per_ref (const uvaia_gpu_ctx *ctx);
 /* the pair scan of this context: 2 = column-compressed scan over planes derived for the query set (default above 32 queries),

@@ -39,6 +39,7 @@ SYMBOLS = [
     "uvaia_gpu_fasta_acgt", "uvaia_gpu_fasta_sequences", "uvaia_gpu_fasta_sequences_host", "uvaia_gpu_fasta_sequences_ms",
     "uvaia_gpu_text_append_device", "uvaia_gpu_text_size", "uvaia_gpu_text_rows", "uvaia_gpu_text_clear", "uvaia_gpu_text_reserve", "uvaia_gpu_text_ms",
     "uvaia_gpu_db_pairs", "uvaia_gpu_db_pairs_within", "uvaia_gpu_pairs_ms",
+    "uvaia_gpu_db_link_begin", "uvaia_gpu_db_link", "uvaia_gpu_db_link_labels", "uvaia_gpu_link_ms",
 ]
 
 PAIR_NCOUNT = 5
@@ -244,6 +245,10 @@ def load_library():
         "uvaia_gpu_db_pairs": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t]),
         "uvaia_gpu_db_pairs_within": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_ulonglong)]),
         "uvaia_gpu_pairs_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_db_link_begin": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+        "uvaia_gpu_db_link": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong)]),
+        "uvaia_gpu_db_link_labels": (C.c_int, [vp, C.c_void_p]),
+        "uvaia_gpu_link_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -447,6 +452,31 @@ class Engine:
         out = (C.c_double * 3)()
         self.L.uvaia_gpu_pairs_ms(self.ctx, out, int(reset))
         return {"rows": out[0], "dense": out[1], "within": out[2]}
+
+    # ---- single-linkage clusters within a distance
+    def db_link_begin(self, max_dist, trim=0, metric=DIST_SNP, min_compared=0):
+        """every resident reference a cluster of its own; the links of db_link are the pairs with distance <= max_dist under metric over at
+        least min_compared compared sites"""
+        self._chk(self.L.uvaia_gpu_db_link_begin(self.ctx, int(trim), int(metric), int(max_dist), int(min_compared)))
+
+    def db_link(self, rows=None, cols=None):
+        """links the pairs row < col of rows (first, n) x cols (first, n) (None: all of the database); returns how many there were"""
+        r0, nr = (0, self.db_size()) if rows is None else rows
+        c0, nc = (0, self.db_size()) if cols is None else cols
+        n = C.c_ulonglong(0)
+        self._chk(self.L.uvaia_gpu_db_link(self.ctx, int(r0), int(nr), int(c0), int(nc), C.byref(n)))
+        return int(n.value)
+
+    def db_link_labels(self):
+        """uint32 [db_size]: the smallest database position of every reference's cluster, by the links made so far"""
+        labels = np.zeros(self.db_size(), dtype=np.uint32)
+        self._chk(self.L.uvaia_gpu_db_link_labels(self.ctx, labels.ctypes.data if labels.size else None))
+        return labels
+
+    def link_ms(self, reset=False):
+        out = C.c_double(0.)
+        self.L.uvaia_gpu_link_ms(self.ctx, C.byref(out), int(reset))
+        return float(out.value)
 
     def rows_set_run_cut(self, cut):
         self._chk(self.L.uvaia_gpu_rows_set_run_cut(self.ctx, int(cut)))

@@ -3,13 +3,15 @@
  * one stream) or aligned FASTA.  No counterpart in the reference: its README sends users to snp-dists for this step ("uvaia reports
  * matches, not distances").  The counters of every pair are taken on the GPU over the bit planes the engine keeps resident
  * (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within); this file loads the rows, asks for the matrix in bands of rows and writes a band as
- * text while the next is computed.  Own code.
+ * text while the next is computed.  `-d D --clusters` asks for no pairs at all: the engine unites the pairs within D on the device
+ * (uvaia_gpu_db_link_*) and hands back one label per sequence.  Own code.
  *
  *   snp   = both ACGT and different (what snp-dists prints)        uvaia = valid_pair_comparisons - partial_matches (README, line 302)
  */
 #define _GNU_SOURCE
 #include <getopt.h>
 #include <libgen.h>
+#include <limits.h>
 #include <omp.h>
 #include <pthread.h>
 
@@ -34,7 +36,7 @@ usage (const char *prog)
   printf ("%s \n", UVAIA_PACKAGE_STRING);
   printf ("All-pairs distance matrix of aligned sequences, counted on the GPU over the packed bit planes.\n\n");
   printf (" %s [-hv] [--metric=snp|uvaia] [--trim=<int>] [-A <double>] [--long | --counts] [-d <int>] [--csv]\n", prog);
-  printf ("          [--band-rows=<int>] [--device=<int>] (-o <file> | --stdout)\n");
+  printf ("          [--clusters [--min-compared=<int>] [--min-size=<int>]] [--band-rows=<int>] [--device=<int>] (-o <file> | --stdout)\n");
   printf ("          (--packed <db.uvdb> [--packed <db.uvdb>]... | <aln.fa(.gz,.xz)> [<aln.fa(.gz,.xz)>]...)\n\n");
   printf ("  --metric=snp|uvaia               snp (default): sites where both sequences are one of ACGT and differ, the number snp-dists prints;\n");
   printf ("                                   uvaia: valid_pair_comparisons - partial_matches, sites where both are valid and their IUPAC sets do not meet\n");
@@ -43,7 +45,13 @@ usage (const char *prog)
   printf ("  --long                           one line `a,b,dist` per pair a before b, instead of the square table\n");
   printf ("  --counts                         one line per pair a before b with the five counters and the snp distance\n");
   printf ("  -d <int>                         only the pairs with distance <= <int> under --metric; implies --long unless --counts is given\n");
-  printf ("  --csv                            the square table with commas instead of tabs\n");
+  printf ("  --clusters                       with -d: single-linkage clusters instead of pairs, one line `sequence<tab>cluster<tab>size` per sequence in\n");
+  printf ("                                   input order; two sequences are linked when their distance is <= -d, a cluster is a connected set, clusters\n");
+  printf ("                                   are numbered 1, 2, ... by their first member.  Under snp a sequence with no ACGT site is at distance 0 from\n");
+  printf ("                                   every other and joins all clusters into one: set --min-compared against that\n");
+  printf ("  --min-compared=<int>             with --clusters: link only pairs compared over at least <int> sites (snp: both ACGT; uvaia: both valid; default=0)\n");
+  printf ("  --min-size=<int>                 with --clusters: leave out the sequences of clusters smaller than <int> (default=1; the numbering does not change)\n");
+  printf ("  --csv                            commas instead of tabs in the square table and the cluster lines\n");
   printf ("  --band-rows=<int>                rows of the matrix computed at a time (default: what keeps a band near 256 MiB)\n");
   printf ("  -o, --output=<file>              file to write, compressed by its suffix (.xz, .bz2, .gz)\n");
   printf ("  --stdout                         uncompressed text on standard output instead of -o\n");
@@ -262,13 +270,14 @@ main (int argc, char **argv)
   double ambig = 1.;
   const char *out = NULL, *metric_name = "snp";
   char **packed = (char **) biomcmc_malloc ((size_t) (argc + 1) * sizeof (char *));
-  int n_packed = 0, device = -1, ch, errors = 0, want_long = 0, want_counts = 0, want_dense = 0, have_d = 0, max_dist = 0, csv = 0, to_stdout = 0;
-  long trim = 0, band_rows = 0;
+  int n_packed = 0, device = -1, ch, errors = 0, want_long = 0, want_counts = 0, want_dense = 0, have_d = 0, max_dist = 0, csv = 0, to_stdout = 0, want_clusters = 0, have_min_compared = 0, have_min_size = 0;
+  long trim = 0, band_rows = 0, min_compared = 0, min_size = 1;
   size_t list_cap = LIST_CAP0;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
     {"output", required_argument, 0, 'o'}, {"trim", required_argument, 0, 't'}, {"metric", required_argument, 0, 1001}, {"device", required_argument, 0, 1002},
     {"long", no_argument, 0, 1003}, {"counts", no_argument, 0, 1004}, {"csv", no_argument, 0, 1005}, {"band-rows", required_argument, 0, 1006},
-    {"stdout", no_argument, 0, 1007}, {"packed", required_argument, 0, 1008}, {"list-cap", required_argument, 0, 1009}, {"dense", no_argument, 0, 1010}, {0, 0, 0, 0}};
+    {"stdout", no_argument, 0, 1007}, {"packed", required_argument, 0, 1008}, {"list-cap", required_argument, 0, 1009}, {"dense", no_argument, 0, 1010},
+    {"clusters", no_argument, 0, 1011}, {"min-compared", required_argument, 0, 1012}, {"min-size", required_argument, 0, 1013}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:t:d:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
@@ -286,6 +295,9 @@ main (int argc, char **argv)
     case 1008: packed[n_packed++] = optarg; break;
     case 1009: list_cap = (size_t) strtoull (optarg, NULL, 10); break;      /* (for tests: the first capacity of the -d list, so that it has to grow) */
     case 1010: want_dense = 1; break;                                       /* the default form, spelled out */
+    case 1011: want_clusters = 1; break;
+    case 1012: have_min_compared = 1; min_compared = atol (optarg); break;
+    case 1013: have_min_size = 1; min_size = atol (optarg); break;
     default: errors++;
   }
   /* what does not go together is refused here, before a file is opened or a GPU touched */
@@ -295,8 +307,16 @@ main (int argc, char **argv)
   else { fprintf (stderr, "unknown metric '%s': --metric takes snp or uvaia\n", metric_name); return EXIT_FAILURE; }
   if (want_long && want_counts) { fprintf (stderr, "--long and --counts are two forms of the output: give one\n"); return EXIT_FAILURE; }
   if (want_dense && (want_long || want_counts)) { fprintf (stderr, "--dense does not go with --long or --counts\n"); return EXIT_FAILURE; }
+  if (want_clusters && want_long) { fprintf (stderr, "--clusters does not go with --long: it writes one line per sequence, not per pair\n"); return EXIT_FAILURE; }
+  if (want_clusters && want_counts) { fprintf (stderr, "--clusters does not go with --counts: it writes one line per sequence, not per pair\n"); return EXIT_FAILURE; }
+  if (want_clusters && want_dense) { fprintf (stderr, "--clusters does not go with --dense: it writes one line per sequence, not a table\n"); return EXIT_FAILURE; }
   if (have_d && want_dense) { fprintf (stderr, "-d needs a long form (--long or --counts): a square table has a cell for every pair\n"); return EXIT_FAILURE; }
   if (have_d && max_dist < 0) { fprintf (stderr, "-d takes a distance of 0 or more\n"); return EXIT_FAILURE; }
+  if (want_clusters && !have_d) { fprintf (stderr, "--clusters needs -d: clusters are the sequences connected by pairs within a distance\n"); return EXIT_FAILURE; }
+  if (have_min_compared && !want_clusters) { fprintf (stderr, "--min-compared needs --clusters: it decides which pairs link two sequences\n"); return EXIT_FAILURE; }
+  if (have_min_size && !want_clusters) { fprintf (stderr, "--min-size needs --clusters: it leaves out the sequences of small clusters\n"); return EXIT_FAILURE; }
+  if (min_compared < 0 || min_compared > INT_MAX) { fprintf (stderr, "--min-compared takes a number of 0 or more\n"); return EXIT_FAILURE; }
+  if (min_size < 0) { fprintf (stderr, "--min-size takes a number of 0 or more\n"); return EXIT_FAILURE; }
   if (n_packed && optind < argc) { fprintf (stderr, "packed databases and FASTA files cannot be mixed: give --packed files or alignments\n"); return EXIT_FAILURE; }
   if (!errors && !out && !to_stdout) { fprintf (stderr, "where to write: give -o <file> or --stdout\n"); return EXIT_FAILURE; }
   if (out && to_stdout) { fprintf (stderr, "both -o and --stdout were given: the output goes to one place\n"); return EXIT_FAILURE; }
@@ -337,7 +357,40 @@ main (int argc, char **argv)
   }
   sink_write (&snk, &head);
 
-  if (have_d && n) {
+  unsigned long long n_links = 0;
+  size_t n_clusters = 0, largest = 0;
+  if (want_clusters && n) {
+    /* clusters: a band of rows against all columns is linked on the device, nothing but the count of links comes back per band; the labels
+     * (smallest member of every sequence's cluster) come back once, and are numbered here by first member */
+    const size_t band = band_rows ? (size_t) band_rows : 4096;
+    if (uvaia_gpu_db_link_begin (gpu, (size_t) trim, metric, max_dist, (int) min_compared)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    for (size_t r0 = 0; r0 < n; r0 += band, n_bands++)
+      if (uvaia_gpu_db_link (gpu, r0, n - r0 < band ? n - r0 : band, 0, n, &n_links)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    uint32_t *label = (uint32_t *) biomcmc_malloc (n * sizeof (uint32_t));
+    if (uvaia_gpu_db_link_labels (gpu, label)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    t0 = now_ms ();
+    size_t *size = (size_t *) biomcmc_malloc (n * sizeof (size_t)), *number = (size_t *) biomcmc_malloc (n * sizeof (size_t));
+    for (size_t i = 0; i < n; i++) size[i] = 0;
+    for (size_t i = 0; i < n; i++) {
+      if (label[i] > i) biomcmc_error ("the engine labelled sequence %zu with the later sequence %u", i, label[i]);
+      if (label[i] == i) number[i] = ++n_clusters;      /* a cluster's label is its first member: numbered in that order */
+      size[label[i]]++;
+    }
+    textbuf t = {NULL, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+      const size_t sz = size[label[i]];
+      if (sz > largest) largest = sz;
+      if (sz < (size_t) min_size) continue;
+      text_room (&t, name_len[i] + 2 * 24);
+      text_bytes (&t, rows.name[i], name_len[i]); t.p[t.n++] = sep;
+      text_int (&t, (int) number[label[i]]); t.p[t.n++] = sep;
+      text_int (&t, (int) sz); t.p[t.n++] = '\n';
+      if (t.n > ((size_t) 1 << 24)) { format_ms += now_ms () - t0; sink_write (&snk, &t); t0 = now_ms (); }
+    }
+    format_ms += now_ms () - t0;
+    sink_write (&snk, &t);
+    free (t.p); free (label); free (size); free (number);
+  } else if (have_d && n) {
     /* the pairs within the distance: a band of rows against everything behind the diagonal; the list grows until a band fits */
     const size_t band = band_rows ? (size_t) band_rows : 4096;
     uvaia_gpu_pair *list = (uvaia_gpu_pair *) biomcmc_malloc ((list_cap ? list_cap : 1) * sizeof (uvaia_gpu_pair));
@@ -423,10 +476,17 @@ main (int argc, char **argv)
 
   double ms[3] = {0., 0., 0.};
   uvaia_gpu_pairs_ms (gpu, ms, 0);
-  fprintf (stderr, "Wrote the %s distances of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n", metric_name, n, rows.count, rows.nchar, trim,
+  fprintf (stderr, want_clusters ? "Wrote the %s clusters of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n"
+                                 : "Wrote the %s distances of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n", metric_name, n, rows.count, rows.nchar, trim,
            out ? out : "standard output", biomcmc_update_elapsed_time (time0));
-  fprintf (stderr, "dist report: {\"sequences\": %zu, \"pairs\": %llu, \"bands\": %zu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",
-           n, n_pairs, n_bands, rows.load_ms, ms[0] + ms[1] + ms[2], format_ms, snk.write_ms);
+  if (want_clusters) {
+    double link_ms = 0.;
+    uvaia_gpu_link_ms (gpu, &link_ms, 0);
+    fprintf (stderr, "dist report: {\"sequences\": %zu, \"links\": %llu, \"clusters\": %zu, \"largest\": %zu, \"bands\": %zu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",
+             n, n_links, n_clusters, largest, n_bands, rows.load_ms, ms[0] + link_ms, format_ms, snk.write_ms);
+  } else
+    fprintf (stderr, "dist report: {\"sequences\": %zu, \"pairs\": %llu, \"bands\": %zu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",
+             n, n_pairs, n_bands, rows.load_ms, ms[0] + ms[1] + ms[2], format_ms, snk.write_ms);
   uvaia_gpu_close (gpu);
   for (size_t i = 0; i < n; i++) free (rows.name[i]);
   free (rows.name); free (name_len); free (head.p); free (packed);

@@ -215,6 +215,10 @@ struct uvaia_gpu_ctx {
   struct Pairs {
     DevBuf<uint32_t> d_rec; DevBuf<int> d_out; DevBuf<uvaia_gpu_pair> d_list; DevBuf<unsigned long long> d_count;
     Event ev[2]; double ms[3] = {0., 0., 0.};          // device time of the row operands, the dense kernels, the threshold kernels (+ the host's sort)
+    // single-linkage clusters (uvaia_gpu_db_link_*): the forest, one dword per reference resident at `begin`, the labels read off it, what
+    // `begin` was given, and the database it was given for (links are refused once db_gen has moved on)
+    DevBuf<uint32_t> d_parent, d_labels; double link_ms = 0.;      // device time of the link and label kernels
+    struct { bool begun = false; unsigned long long db_gen = 0; size_t n = 0, trim = 0; int metric = 0, max_dist = 0, min_compared = 0; } link;
   } pairs;
   // last batch (introspection)
   struct { const TileStore *store = nullptr; long long tile_first = 0; int n_tiles = 0, n = 0, rbegin = 0, ppad = 0; const int4 *rt = nullptr; } last;

@@ -1,5 +1,6 @@
 // host_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other:
-// the checks, the cut of a rectangle into launches, the copies back, the list of the pairs within a distance.
+// the checks, the cut of a rectangle into launches, the copies back, the list of the pairs within a distance, and the single-linkage
+// clusters within a distance (a forest on the device: begin, link, labels).
 
 namespace {
 
@@ -52,6 +53,15 @@ template <int D> int pairs_build_rows(uvaia_gpu_ctx *c, size_t row0, size_t n, s
 
 inline unsigned pairs_grid(size_t n_rows, int rt, int n_ctiles) { return (unsigned)((n_rows + rt - 1) / rt) * (unsigned)((n_ctiles + 3) / 4); }
 
+// a clustering is open, and over the database as it is now (the forest has one node per reference resident at `begin`)
+int link_state(uvaia_gpu_ctx *c)
+{
+  const auto &k = c->pairs.link;
+  if (!k.begun) return fail(c, UVAIA_GPU_ESTATE, "no clustering is open: call uvaia_gpu_db_link_begin first");
+  if (k.db_gen != c->db_gen || k.n != c->db_n) return fail(c, UVAIA_GPU_ESTATE, "the database changed since uvaia_gpu_db_link_begin: begin again");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -81,8 +91,8 @@ int uvaia_gpu_db_pairs(uvaia_gpu_ctx *c, size_t row0, size_t n_rows, size_t col0
       const dim3 grid(pairs_grid(nr, rt, n_ct));
       HIPCHK(c, hipEventRecord(c->pairs.ev[0], c->st.stream));
       if (counts)
-        hipLaunchKernelGGL((pairs_counts_kernel<false>), grid, dim3(256), 0, c->st.stream, db, c->W4, (const uint32_t *)c->pairs.d_rec.p, (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct,
-                           (long long)c0, (int)nc, c->pairs.d_out.p, nc, 0, 0, 0, (uvaia_gpu_pair *)nullptr, 0ull, (unsigned long long *)nullptr);
+        hipLaunchKernelGGL((pairs_counts_kernel<PAIRS_DENSE>), grid, dim3(256), 0, c->st.stream, db, c->W4, (const uint32_t *)c->pairs.d_rec.p, (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct,
+                           (long long)c0, (int)nc, c->pairs.d_out.p, nc, 0, 0, 0, (uvaia_gpu_pair *)nullptr, 0ull, (unsigned long long *)nullptr, 0, (uint32_t *)nullptr);
       else if (rt == 32)
         hipLaunchKernelGGL((pairs_snp_kernel<32>), grid, dim3(256), 0, c->st.stream, db, c->W4, (const uint32_t *)c->pairs.d_rec.p, (int)nr, n_rt, ct0, n_ct, (long long)c0, (int)nc, c->pairs.d_out.p, nc);
       else
@@ -128,9 +138,9 @@ int uvaia_gpu_db_pairs_within(uvaia_gpu_ctx *c, size_t row0, size_t n_rows, size
       const unsigned long long room = found < cap ? std::min<unsigned long long>(cap - found, nr * nc) : 0ull;
       HIPCHK(c, hipMemsetAsync(c->pairs.d_count.p, 0, sizeof(unsigned long long), c->st.stream));
       HIPCHK(c, hipEventRecord(c->pairs.ev[0], c->st.stream));
-      hipLaunchKernelGGL((pairs_counts_kernel<true>), dim3(pairs_grid(nr, PAIRS_CNT_RT, n_ct)), dim3(256), 0, c->st.stream, db, c->W4, (const uint32_t *)c->pairs.d_rec.p,
+      hipLaunchKernelGGL((pairs_counts_kernel<PAIRS_LIST>), dim3(pairs_grid(nr, PAIRS_CNT_RT, n_ct)), dim3(256), 0, c->st.stream, db, c->W4, (const uint32_t *)c->pairs.d_rec.p,
                          (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct, (long long)c0, (int)nc, (int *)nullptr, (size_t)0, metric, max_dist, upper ? 1 : 0,
-                         c->pairs.d_list.p, room, c->pairs.d_count.p);
+                         c->pairs.d_list.p, room, c->pairs.d_count.p, 0, (uint32_t *)nullptr);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, hipEventRecord(c->pairs.ev[1], c->st.stream));
       unsigned long long n_here = 0;
@@ -156,6 +166,111 @@ void uvaia_gpu_pairs_ms(uvaia_gpu_ctx *c, double out[3], int reset)
   if (!c) return;
   if (out) for (int i = 0; i < 3; i++) out[i] = c->pairs.ms[i];
   if (reset) c->pairs.ms[0] = c->pairs.ms[1] = c->pairs.ms[2] = 0.;
+}
+
+// ---- single-linkage clusters: the pairs within a distance united in a forest on the device
+int uvaia_gpu_db_link_begin(uvaia_gpu_ctx *c, size_t trim, int metric, int max_dist, int min_compared)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (metric != UVAIA_GPU_DIST_SNP && metric != UVAIA_GPU_DIST_UVAIA) return fail(c, UVAIA_GPU_EINVAL, "unknown metric %d", metric);
+  if (max_dist < 0) return fail(c, UVAIA_GPU_EINVAL, "negative distance %d", max_dist);
+  if (min_compared < 0) return fail(c, UVAIA_GPU_EINVAL, "negative floor of compared sites %d", min_compared);
+  if (int rc = pairs_check(c, 0, c->db_n, 0, c->db_n, trim)) return rc;
+  if (c->db_n > 0xFFFFFFFFull) return fail(c, UVAIA_GPU_EINVAL, "cluster labels are 32-bit database positions: %zu references are too many", c->db_n);
+  auto &k = c->pairs.link;
+  k.begun = false;
+  if (int rc = pairs_wait(c)) return rc;
+  if (int rc = c->pairs.d_parent.reserve(c, std::max<size_t>(1, c->db_n))) return rc;
+  if (c->db_n) {
+    hipLaunchKernelGGL(pairs_link_init_kernel, dim3((unsigned)((c->db_n + 255) / 256)), dim3(256), 0, c->st.stream, c->pairs.d_parent.p, (uint32_t)c->db_n);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  }
+  k.begun = true; k.db_gen = c->db_gen; k.n = c->db_n; k.trim = trim; k.metric = metric; k.max_dist = max_dist; k.min_compared = min_compared;
+  return 0;
+}
+
+int uvaia_gpu_db_link(uvaia_gpu_ctx *c, size_t row0, size_t n_rows, size_t col0, size_t n_cols, unsigned long long *n_links)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (int rc = link_state(c)) return rc;
+  if (!n_links) return fail(c, UVAIA_GPU_EINVAL, "NULL count of links");
+  const auto &k = c->pairs.link;
+  if (int rc = pairs_check(c, row0, n_rows, col0, n_cols, k.trim)) return rc;
+  if (!n_rows || !n_cols) return 0;
+  if (int rc = pairs_wait(c)) return rc;
+  if (int rc = c->pairs.ev[0].make(c)) return rc;
+  if (int rc = c->pairs.ev[1].make(c)) return rc;
+  if (int rc = c->pairs.d_count.reserve(c, 1)) return rc;
+  const bool snp = k.metric == UVAIA_GPU_DIST_SNP;
+  const int rt = snp ? PAIRS_SNP_RT : PAIRS_CNT_RT;
+  const uint4 *db = c->db.planes;
+  const uint32_t *rec = nullptr;
+  HIPCHK(c, hipMemsetAsync(c->pairs.d_count.p, 0, sizeof(unsigned long long), c->st.stream));      // one count for the launches of this call
+  for (size_t rb = 0; rb < n_rows; rb += PAIRS_LAUNCH_ROWS) {
+    const size_t nr = std::min(PAIRS_LAUNCH_ROWS, n_rows - rb);
+    if (col0 + n_cols <= row0 + rb + 1) break;                   // this band and every later one lie at or below the diagonal
+    if (int rc = snp ? pairs_build_rows<PAIRS_SNP_DW>(c, row0 + rb, nr, k.trim) : pairs_build_rows<PAIRS_CNT_DW>(c, row0 + rb, nr, k.trim)) return rc;
+    rec = c->pairs.d_rec.p;
+    for (size_t cb = 0; cb < n_cols; cb += PAIRS_LAUNCH_COLS) {
+      const size_t nc = std::min(PAIRS_LAUNCH_COLS, n_cols - cb), c0 = col0 + cb;
+      if (c0 + nc <= row0 + rb + 1) continue;                    // no pair of this launch has row < col
+      const long long ct0 = (long long)(c0 / 64);
+      const int n_ct = (int)((c0 + nc - 1) / 64 - c0 / 64 + 1), n_rt = (int)((nr + rt - 1) / rt);
+      const dim3 grid(pairs_grid(nr, rt, n_ct));
+      HIPCHK(c, hipEventRecord(c->pairs.ev[0], c->st.stream));
+      if (!snp)
+        hipLaunchKernelGGL((pairs_counts_kernel<PAIRS_LINK>), grid, dim3(256), 0, c->st.stream, db, c->W4, rec, (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct, (long long)c0, (int)nc,
+                           (int *)nullptr, (size_t)0, k.metric, k.max_dist, 1, (uvaia_gpu_pair *)nullptr, 0ull, c->pairs.d_count.p, k.min_compared, c->pairs.d_parent.p);
+      else if (k.min_compared > 0)
+        hipLaunchKernelGGL((pairs_link_snp_kernel<true>), grid, dim3(256), 0, c->st.stream, db, c->W4, rec, (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct, (long long)c0, (int)nc,
+                           k.max_dist, k.min_compared, c->pairs.d_parent.p, c->pairs.d_count.p);
+      else
+        hipLaunchKernelGGL((pairs_link_snp_kernel<false>), grid, dim3(256), 0, c->st.stream, db, c->W4, rec, (long long)(row0 + rb), (int)nr, n_rt, ct0, n_ct, (long long)c0, (int)nc,
+                           k.max_dist, 0, c->pairs.d_parent.p, c->pairs.d_count.p);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipEventRecord(c->pairs.ev[1], c->st.stream));
+      HIPCHK(c, hipStreamSynchronize(c->st.stream));             // (the next band's row records overwrite the ones this launch reads)
+      float ms = 0;
+      HIPCHK(c, hipEventElapsedTime(&ms, c->pairs.ev[0], c->pairs.ev[1]));
+      c->pairs.link_ms += ms;
+    }
+  }
+  unsigned long long found = 0;                                  // read in stream order: behind the memset also where every launch was skipped
+  HIPCHK(c, hipMemcpyAsync(&found, c->pairs.d_count.p, sizeof found, hipMemcpyDeviceToHost, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  *n_links += found;
+  return 0;
+}
+
+int uvaia_gpu_db_link_labels(uvaia_gpu_ctx *c, uint32_t *labels)
+{
+  if (!c) return UVAIA_GPU_EINVAL;
+  if (int rc = link_state(c)) return rc;
+  const size_t n = c->pairs.link.n;
+  if (!n) return 0;
+  if (!labels) return fail(c, UVAIA_GPU_EINVAL, "NULL labels");
+  if (int rc = pairs_wait(c)) return rc;
+  if (int rc = c->pairs.ev[0].make(c)) return rc;
+  if (int rc = c->pairs.ev[1].make(c)) return rc;
+  if (int rc = c->pairs.d_labels.reserve(c, n)) return rc;
+  HIPCHK(c, hipEventRecord(c->pairs.ev[0], c->st.stream));
+  hipLaunchKernelGGL(pairs_labels_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->st.stream, (const uint32_t *)c->pairs.d_parent.p, (uint32_t)n, c->pairs.d_labels.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->pairs.ev[1], c->st.stream));
+  HIPCHK(c, hipMemcpyAsync(labels, c->pairs.d_labels.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->st.stream));
+  HIPCHK(c, hipStreamSynchronize(c->st.stream));
+  float ms = 0;
+  HIPCHK(c, hipEventElapsedTime(&ms, c->pairs.ev[0], c->pairs.ev[1]));
+  c->pairs.link_ms += ms;
+  return 0;
+}
+
+void uvaia_gpu_link_ms(uvaia_gpu_ctx *c, double *ms, int reset)
+{
+  if (!c) return;
+  if (ms) *ms = c->pairs.link_ms;
+  if (reset) c->pairs.link_ms = 0.;
 }
 
 }  // extern "C"

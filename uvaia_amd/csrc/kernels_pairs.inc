@@ -1,4 +1,4 @@
-// kernels_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within): pairs_rows_kernel builds the row-side operand records of a band of rows, pairs_snp_kernel and pairs_counts_kernel count every (row, column) pair of a rectangle, the latter also into a list of the pairs within a distance.
+// kernels_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within): pairs_rows_kernel builds the row-side operand records of a band of rows, pairs_snp_kernel and pairs_counts_kernel count every (row, column) pair of a rectangle, the latter also into a list of the pairs within a distance; pairs_link_snp_kernel and the link mode of pairs_counts_kernel unite the pairs within a distance in a union-find forest instead (uvaia_gpu_db_link), pairs_labels_kernel reads the cluster labels off it.
 
 // ------------------------------------------------------------------------------------------------------------
 // device: all-pairs counters over the resident four-plane tiles
@@ -127,17 +127,150 @@ __global__ __launch_bounds__(256) void pairs_snp_kernel(const uint4 *__restrict_
   }
 }
 
+// ---- single-linkage clusters: the pairs within a distance united in a forest (uvaia_gpu_db_link_begin / _link / _link_labels)
+// parent[] holds one dword per resident reference, parent[i] = i at the start.  While link kernels run, the ONLY stores to it are agent-scope
+// atomic read-modify-writes (the compare-and-swap of a hook, the atomicMin of path shortening); nothing waits for another wave, no flag is
+// spun on, no fence is issued.  Why that is enough on a chip whose per-XCD L2s and per-CU L1s are not coherent within a launch:
+//   - every value parent[x] ever held is x itself or a SMALLER node of x's component (a hook stores lo < hi, a shortening stores an
+//     ancestor, and ancestors are smaller), so a walk over stale values only ever steps to smaller nodes of the right component: it ends;
+//   - a hook succeeds only through atomicCAS(&parent[hi], hi, lo), that is on a node that IS a root at that moment, whatever the walks saw;
+//   - a failed CAS hands back the real parent of hi, strictly smaller than hi, and the loop goes on from (that value, lo) -- from what the
+//     CAS returned, not from a reload that might be stale again: the larger of the two nodes drops with every round, so the loop ends on its own;
+//   - hooks go from the larger root to the smaller, so the root of a finished component is its smallest member: the label.
+// It rests on nothing but the device-wide atomicity the list kernel's atomicAdd on *n_list already rests on.  Reads are relaxed agent-scope
+// atomic loads: they go past the L1, so fewer walks start from stale values (a stale walk costs time, never the answer).
+static __device__ __forceinline__ uint32_t pairs_link_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+static __device__ __forceinline__ uint32_t pairs_link_root(const uint32_t *parent, uint32_t x)
+{ // (p > x cannot happen; it ends the walk too, so that the walk ends whatever the array holds)
+  for (;;) {
+    const uint32_t p = pairs_link_load(parent + x);
+    if (p >= x) return x;
+    x = p;
+  }
+}
+
+// One lane's hits of a row tile: bit r of `hits` links database position row_first + r to `col` (row_first + r < col).  The wave's hits
+// (`total`, from ballots) are added to *n_links by ONE lane with one vector atomicAdd.  The column's root is carried from hit to hit; where
+// both sides already show one root nothing is stored, which keeps a dense cluster -- every lane hitting every row -- to reads.
+static __device__ __forceinline__ void pairs_link_hits(uint32_t *parent, unsigned long long *n_links, uint32_t row_first, uint32_t col, uint32_t hits,
+                                                       unsigned total, int lane)
+{
+  if (total == 0) return;
+  if (lane == 0) atomicAdd(n_links, (unsigned long long)total);
+  if (!hits) return;
+  const uint32_t seen = pairs_link_load(parent + col);
+  uint32_t rc = seen >= col ? col : pairs_link_root(parent, seen);
+  while (hits) {
+    const uint32_t r = (uint32_t)__ffs((int)hits) - 1u;
+    hits &= hits - 1u;
+    uint32_t rr = pairs_link_root(parent, row_first + r);
+    while (rr != rc) {
+      const uint32_t hi = max(rr, rc), lo = min(rr, rc);
+      const uint32_t old = atomicCAS(parent + hi, hi, lo);
+      if (old >= hi) { rc = lo; break; }               // hooked (old == hi; a larger value cannot be there)
+      rr = pairs_link_root(parent, old);               // hi had been hooked by someone else: on from its real parent
+      rc = pairs_link_root(parent, lo);
+    }
+  }
+  if (rc < seen) atomicMin(parent + col, rc);          // path shortening: an ancestor, never a plain store
+}
+
+// parent[i] = i for the references resident at uvaia_gpu_db_link_begin
+__global__ __launch_bounds__(256) void pairs_link_init_kernel(uint32_t *__restrict__ parent, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) parent[i] = i;
+}
+
+// labels[i] = the root of i.  A launch of its own behind the last link kernel: plain loads; parent[] is not written.
+__global__ __launch_bounds__(256) void pairs_labels_kernel(const uint32_t *__restrict__ parent, uint32_t n, uint32_t *__restrict__ labels)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  uint32_t x = i;
+  for (;;) {
+    const uint32_t p = parent[x];
+    if (p >= x) break;
+    x = p;
+  }
+  labels[i] = x;
+}
+
+// The links of RT = 32 rows x 64 columns per wave under the snp metric: the loop of pairs_snp_kernel<32> -- same operand records, same grid
+// order, row operands in SGPRs, 4 vector instructions per pair-word -- and with FLOOR two more, `is & is'` (v_and) and its count (v_bcnt)
+// into a second accumulator per row: ACGT_pair_comparisons, the floor's "compared".  Nothing dense is written.  hit = column and row in
+// range, row < col (database positions), dist <= max_dist and with FLOOR compared >= min_compared; the hits go to pairs_link_hits.
+template <bool FLOOR>
+__global__ __launch_bounds__(256) void pairs_link_snp_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, long long row0, int n_rows, int n_rtiles,
+                                                              long long ctile0, int n_ctiles, long long col0, int n_cols, int max_dist, int min_compared,
+                                                              uint32_t *parent, unsigned long long *__restrict__ n_links)
+{
+  constexpr int RT = 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rt = blockIdx.x % n_rtiles, ct = (blockIdx.x / n_rtiles) * 4 + wave;
+  if (ct >= n_ctiles) return;
+  int acc[RT], cmp[FLOOR ? RT : 1];
+#pragma unroll
+  for (int r = 0; r < RT; r++) { acc[r] = 0; if (FLOOR) cmp[r] = 0; }
+  const uint4 *t = db + (size_t)(ctile0 + ct) * W4 * 4 * 64 + lane;
+  const size_t rstride = (size_t)W4 * PAIRS_SNP_DW;
+  const uint32_t *rb = rec + (size_t)rt * RT * rstride;
+  for (int w4 = 0; w4 < W4; w4++) {
+    const uint4 pA = t[(size_t)(w4 * 4 + 0) * 64], pC = t[(size_t)(w4 * 4 + 1) * 64], pG = t[(size_t)(w4 * 4 + 2) * 64], pT = t[(size_t)(w4 * 4 + 3) * 64];
+    uint32_t cL[4], cH[4], cI[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t a = u4c(pA, j), cc = u4c(pC, j), g = u4c(pG, j), tt = u4c(pT, j);
+      const uint32_t par = a ^ cc ^ g ^ tt, three = (a & cc & (g | tt)) | (g & tt & (a | cc));
+      cI[j] = par & ~three; cL[j] = (cc | tt) & cI[j]; cH[j] = (g | tt) & cI[j];
+    }
+    const uint32_t *s0 = rb + (size_t)w4 * PAIRS_SNP_DW;
+    QWords<PAIRS_SNP_DW> cur, nxt;
+    load_qwords(cur, s0);
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      if (r + 1 < RT) load_qwords(nxt, s0 + (size_t)(r + 1) * rstride);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t x = cL[j] ^ cur.v[j];
+        const uint32_t y = B3(cH[j], cur.v[4 + j], x, (TT_A ^ TT_B) | TT_C);          // codes differ
+        acc[r] = bcnt_acc(B3(y, cI[j], cur.v[8 + j], TT_A & TT_B & TT_C), acc[r]);
+        if (FLOOR) cmp[r] = bcnt_acc(cI[j] & cur.v[8 + j], cmp[r]);                   // both ACGT
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (r + 1 < RT) cur = nxt;
+    }
+  }
+  const long long col = (ctile0 + ct) * 64 + lane, j = col - col0;
+  const bool col_ok = j >= 0 && j < n_cols;
+  uint32_t hits = 0;                                   // bit r: this lane's column is linked to row r of the tile
+  unsigned total = 0;                                  // wave-uniform: ballots
+#pragma unroll
+  for (int r = 0; r < RT; r++) {
+    const int i = rt * RT + r;
+    const bool h = col_ok && i < n_rows && row0 + i < col && acc[r] <= max_dist && (!FLOOR || cmp[r] >= min_compared);
+    total += (unsigned)__popcll(__ballot(h));
+    hits |= (uint32_t)h << r;
+  }
+  pairs_link_hits(parent, n_links, (uint32_t)(row0 + rt * RT), (uint32_t)col, hits, total, lane);
+}
+
 // The five counters of PAIRS_CNT_RT rows x 64 columns per wave, same mapping and grid order as pairs_snp_kernel; the plane-equality and
 // intersect chains of scan_iupac_kernel plus one `single & single'` count: 17 vector instructions per pair-word.
-// LIST = false: out[(i * ld_out + (col - col0)) * 5 + c].
-// LIST = true: nothing dense is written; the pairs of the rectangle with distance <= max_dist (metric 1: count[4] - count[0], metric 2:
+// MODE = PAIRS_DENSE: out[(i * ld_out + (col - col0)) * 5 + c].
+// MODE = PAIRS_LIST: nothing dense is written; the pairs of the rectangle with distance <= max_dist (metric 1: count[4] - count[0], metric 2:
 // count[3] - count[2]) and, with upper, row < col (database positions) go into list[]: a wave counts its hits by ballots, ONE lane reserves that
 // many slots by one vector atomicAdd on *n_list, and every store is bounded by list_cap -- *n_list ends as the number of hits, whatever fitted.
-template <bool LIST>
+// MODE = PAIRS_LINK: nothing dense and no list; the pairs row < col with distance <= max_dist and, under the same metric, compared
+// (count[4] under metric 1, count[3] under metric 2) >= min_compared are united in parent[] and counted into *n_list (pairs_link_hits).
+enum { PAIRS_DENSE = 0, PAIRS_LIST = 1, PAIRS_LINK = 2 };
+template <int MODE>
 __global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, long long row0, int n_rows, int n_rtiles,
                                                             long long ctile0, int n_ctiles, long long col0, int n_cols, int *__restrict__ out, size_t ld_out,
                                                             int metric, int max_dist, int upper, uvaia_gpu_pair *__restrict__ list, unsigned long long list_cap,
-                                                            unsigned long long *__restrict__ n_list)
+                                                            unsigned long long *__restrict__ n_list, int min_compared, uint32_t *parent)
 {
   constexpr int RT = PAIRS_CNT_RT;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -189,7 +322,7 @@ __global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restri
   }
   const long long col = (ctile0 + ct) * 64 + lane, j = col - col0;
   const bool col_ok = j >= 0 && j < n_cols;
-  if (!LIST) {
+  if (MODE == PAIRS_DENSE) {
     if (!col_ok) return;
 #pragma unroll
     for (int r = 0; r < RT; r++) {
@@ -200,6 +333,20 @@ __global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restri
         for (int k = 0; k < UVAIA_GPU_PAIR_NCOUNT; k++) o[k] = acc[r][k];
       }
     }
+  } else if (MODE == PAIRS_LINK) {
+    uint32_t hits = 0;                                 // bit r: this lane's column is linked to row r of the tile
+    unsigned total = 0;                                // wave-uniform: ballots
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      const int i = rt * RT + r;
+      const bool snp = metric == UVAIA_GPU_DIST_SNP;
+      const int c0 = acc[r][0], c2 = acc[r][2], c3 = acc[r][3], c4 = acc[r][4];      // (read first: a choice between two elements would index the accumulators at run time)
+      const int dist = snp ? c4 - c0 : c3 - c2, compared = snp ? c4 : c3;
+      const bool h = col_ok && i < n_rows && row0 + i < col && dist <= max_dist && compared >= min_compared;
+      total += (unsigned)__popcll(__ballot(h));
+      hits |= (uint32_t)h << r;
+    }
+    pairs_link_hits(parent, n_list, (uint32_t)(row0 + rt * RT), (uint32_t)col, hits, total, lane);
   } else {
     auto hit = [&](int r) {
       const int i = rt * RT + r;
