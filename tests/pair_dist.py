@@ -116,7 +116,8 @@ def window_masks(n_words, nchar, trim):
 
 def plane_counts_of(seqs, nchar, trim=0, rows=None):
     """the same [n, n, 5] from the packed tiles alone: valid = some plane bit, ACGT = exactly one, equal and valid = four equal planes with
-    one set, intersect = some plane with both bits; the window clears one side only.  rows: only the first so many rows, [rows, n, 5]"""
+    one set, intersect = some plane with both bits; the window clears one side only.  rows: only the first so many rows, [rows, n, 5], or
+    (first, count): only rows [first, first + count), [count, n, 5]"""
     planes, _non_n = P.pack_tiles(seqs, nchar)
     n, W4 = len(seqs), ((nchar + 31) // 32 + 3) // 4
     t = planes.reshape(-1).view(np.uint32).reshape(-1, W4, 4, 64, 4)                  # [tile, w4, plane, lane, j]
@@ -126,10 +127,11 @@ def plane_counts_of(seqs, nchar, trim=0, rows=None):
     par, three = A ^ Cc ^ G ^ T, (A & Cc & (G | T)) | (G & T & (A | Cc))
     single = par & ~three
     m = window_masks(W4 * 4, nchar, trim)
-    n_rows = n if rows is None else rows
+    first, n_rows = (0, n) if rows is None else rows if isinstance(rows, tuple) else (0, rows)
+    assert 0 <= first and first + n_rows <= n
     out = np.zeros((n_rows, n, NCOUNT), dtype=np.int32)
     for i in range(n_rows):                            # row side: cleared outside the window
-        a, c, g, tt, v, s = (x[i] & m for x in (A, Cc, G, T, valid, single))
+        a, c, g, tt, v, s = (x[first + i] & m for x in (A, Cc, G, T, valid, single))
         equal = ~((A ^ a) | (Cc ^ c) | (G ^ g) | (T ^ tt))
         inter = (A & a) | (Cc & c) | (G & g) | (T & tt)
         out[i, :, 0] = _popcount(equal & s).sum(axis=1)
