@@ -637,6 +637,56 @@ int uvaia_gpu_db_link (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, size_t co
 int uvaia_gpu_db_link_labels (uvaia_gpu_ctx *ctx, uint32_t *labels);
 void uvaia_gpu_link_ms (uvaia_gpu_ctx *ctx, double *ms, int reset);
 
+/* ---- minimum spanning tree and closest row (`uvaiadist --mst`, `--nearest`): for every resident reference its closest reference of ANOTHER
+ * component, and around that the minimum spanning forest of the database by Boruvka rounds.  Nothing dense is written.
+ *   dist and compared of two database positions a != b over the sites [trim, nchar - trim) are those of db_link_begin: under
+ * UVAIA_GPU_DIST_SNP dist = count[4] - count[0] and compared = count[4], under UVAIA_GPU_DIST_UVAIA dist = count[3] - count[2] and
+ * compared = count[3].
+ *   EDGES.  {a, b} is an edge iff compared(a, b) >= min_compared.  With min_compared = 0 the graph is complete; with a floor it may fall
+ * apart, and the answer is then a spanning FOREST.
+ *   ORDER.  Edges are ordered by the triple (dist, lo, hi), lexicographically, lo < hi the two positions.  The order is strict and total,
+ * so the minimum spanning forest is unique: it is what Kruskal's algorithm builds when it takes the edges in that order.  Every tie is
+ * decided by it; nothing in the output depends on the order of launches, of atomics or on how the matrix was cut.
+ *   NEAREST.  Given comp[] (one value per reference), near(x) is the smallest key (dist(x, y), y) over the y with {x, y} an edge and
+ * comp[y] != comp[x], packed as (uint64_t) dist << 32 | y; UVAIA_GPU_NEAR_NONE says there is no such y.  For a fixed x the order of
+ * (dist, y) agrees with the order of (dist, lo, hi), so a component's minimum outgoing edge is the minimum, under the edge order, of its
+ * members' near.
+ *   As under db_link_begin, a row with no ACGT site is under snp at distance 0 from every row: with min_compared = 0 it is the hub of the
+ * tree and everyone's nearest.  min_compared >= 1 is what a caller sets against it.
+ *
+ * db_near_begin:      checks as db_link_begin does, remembers the parameters and the size of the database, sets every reference to a
+ *                     component of its own and every key to NONE.  12 bytes of device memory per reference.
+ * db_near_components: comp[i] for the references resident at `begin` (NULL: every reference its own), and every key back to NONE.
+ * db_near:            lowers the keys of BOTH ends of every counting pair row < col (database positions) of rows [row0, row0 + n_rows) x
+ *                     columns [col0, col0 + n_cols): the upper triangle, covered once, is the whole matrix.  Calls accumulate until the
+ *                     next db_near_components.  Cut into the launches of db_link; launches wholly at or below the diagonal are skipped,
+ *                     and so is a launch whose rows and columns all carry one comp.  Inside a launch a tile pair (32 rows under snp, 16
+ *                     under uvaia, x one tile of 64 columns) whose rows and columns in range all carry one comp is skipped before any
+ *                     site is counted.  stats (may be NULL): ADDS to stats[0] the tile pairs walked and to stats[1] the tile pairs skipped
+ *                     (those of launches skipped for their comp included, those of launches at or below the diagonal not).
+ * db_near_fetch:      best[i] = near(i) over the pairs covered so far, for the references resident at `begin`.
+ * db_mst:             the minimum spanning forest under the order above: begins, then rounds of (components, near over the whole matrix,
+ *                     fetch, and on the host every component's minimum and a union-find) until a round adds nothing or one tree is left.
+ *                     edges has room for db_size - 1; *n_edges edges come back sorted by (dist, a, b), a < b; *n_rounds (may be NULL)
+ *                     counts the passes of the matrix.  More than 64 rounds are an error (UVAIA_GPU_ESTATE), never a retry.  Leaves a
+ *                     db_near_begin of its parameters open.
+ * near_ms:            device time in ms of the near kernels since the last reset (the row operands go to pairs_ms [0]).
+ * near_tiles:         out[0] the tile pairs walked and out[1] the tile pairs skipped by every db_near since the last reset, those that
+ *                     db_mst made included.
+ * db_near_components, db_near and db_near_fetch answer UVAIA_GPU_ESTATE without a db_near_begin and once the database changed after it;
+ * contexts are refused as by db_pairs; an unknown metric, a negative min_compared, 2 * trim > nchar, a rectangle outside the database and
+ * a NULL best, edges (with two references or more) or n_edges are UVAIA_GPU_EINVAL.  An empty database is fine and returns nothing.  The
+ * database, the forest of db_link and everything of the searches are not touched. */
+#define UVAIA_GPU_NEAR_NONE UINT64_MAX
+typedef struct { uint32_t a, b; int32_t dist; } uvaia_gpu_edge;
+int uvaia_gpu_db_near_begin (uvaia_gpu_ctx *ctx, size_t trim, int metric, int min_compared);
+int uvaia_gpu_db_near_components (uvaia_gpu_ctx *ctx, const uint32_t *comp);
+int uvaia_gpu_db_near (uvaia_gpu_ctx *ctx, size_t row0, size_t n_rows, size_t col0, size_t n_cols, unsigned long long stats[2]);
+int uvaia_gpu_db_near_fetch (uvaia_gpu_ctx *ctx, uint64_t *best);
+int uvaia_gpu_db_mst (uvaia_gpu_ctx *ctx, size_t trim, int metric, int min_compared, uvaia_gpu_edge *edges, size_t *n_edges, int *n_rounds);
+void uvaia_gpu_near_ms (uvaia_gpu_ctx *ctx, double *ms, int reset);
+void uvaia_gpu_near_tiles (uvaia_gpu_ctx *ctx, unsigned long long out[2], int reset);
+
 /* bytes the pair scan reads per reference (the default scan reads planes derived from the packed record for this query set) */
 size_t uvaia_gpu_scan_bytes_per_ref (const uvaia_gpu_ctx *ctx);
 /* the pair scan of this context: 2 = column-compressed scan over planes derived for the query set (default above 32 queries),

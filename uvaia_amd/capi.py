@@ -40,6 +40,7 @@ SYMBOLS = [
     "uvaia_gpu_text_append_device", "uvaia_gpu_text_size", "uvaia_gpu_text_rows", "uvaia_gpu_text_clear", "uvaia_gpu_text_reserve", "uvaia_gpu_text_ms",
     "uvaia_gpu_db_pairs", "uvaia_gpu_db_pairs_within", "uvaia_gpu_pairs_ms",
     "uvaia_gpu_db_link_begin", "uvaia_gpu_db_link", "uvaia_gpu_db_link_labels", "uvaia_gpu_link_ms",
+    "uvaia_gpu_db_near_begin", "uvaia_gpu_db_near_components", "uvaia_gpu_db_near", "uvaia_gpu_db_near_fetch", "uvaia_gpu_db_mst", "uvaia_gpu_near_ms", "uvaia_gpu_near_tiles",
 ]
 
 PAIR_NCOUNT = 5
@@ -47,6 +48,9 @@ PAIRS_SNP, PAIRS_COUNTS, PAIRS_SNP_ALT = 1, 2, 3        # `what` of uvaia_gpu_db
 DIST_SNP, DIST_UVAIA = 1, 2                             # `metric` of uvaia_gpu_db_pairs_within
 # uvaia_gpu_pair: (row, col, count[5])
 PAIR_DTYPE = np.dtype([("row", np.uint32), ("col", np.uint32), ("count", np.int32, (PAIR_NCOUNT,))])
+# uvaia_gpu_edge: (a, b, dist), a < b
+EDGE_DTYPE = np.dtype([("a", np.uint32), ("b", np.uint32), ("dist", np.int32)])
+NEAR_NONE = 2 ** 64 - 1                                 # UVAIA_GPU_NEAR_NONE: no reference of another component is an edge away
 
 
 class GpuError(RuntimeError):
@@ -249,6 +253,13 @@ def load_library():
         "uvaia_gpu_db_link": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong)]),
         "uvaia_gpu_db_link_labels": (C.c_int, [vp, C.c_void_p]),
         "uvaia_gpu_link_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_db_near_begin": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int]),
+        "uvaia_gpu_db_near_components": (C.c_int, [vp, C.c_void_p]),
+        "uvaia_gpu_db_near": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_ulonglong)]),
+        "uvaia_gpu_db_near_fetch": (C.c_int, [vp, C.c_void_p]),
+        "uvaia_gpu_db_mst": (C.c_int, [vp, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+        "uvaia_gpu_near_ms": (None, [vp, C.POINTER(C.c_double), C.c_int]),
+        "uvaia_gpu_near_tiles": (None, [vp, C.POINTER(C.c_ulonglong), C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -477,6 +488,52 @@ class Engine:
         out = C.c_double(0.)
         self.L.uvaia_gpu_link_ms(self.ctx, C.byref(out), int(reset))
         return float(out.value)
+
+    # ---- closest reference of another component, minimum spanning forest
+    def db_near_begin(self, trim=0, metric=DIST_SNP, min_compared=0):
+        """every resident reference a component of its own, every key NEAR_NONE; an edge is a pair compared over at least min_compared sites"""
+        self._chk(self.L.uvaia_gpu_db_near_begin(self.ctx, int(trim), int(metric), int(min_compared)))
+
+    def db_near_components(self, comp=None):
+        """comp: one uint32 per resident reference (None: every reference its own); every key back to NEAR_NONE"""
+        if comp is not None:
+            comp = np.ascontiguousarray(comp, dtype=np.uint32)
+            if comp.shape != (self.db_size(),):
+                raise GpuError(-1, "comp must hold one value per resident reference")
+        self._chk(self.L.uvaia_gpu_db_near_components(self.ctx, comp.ctypes.data if comp is not None and comp.size else None))
+
+    def db_near(self, rows=None, cols=None, stats=True):
+        """lowers the keys of both ends of the counting pairs row < col of rows (first, n) x cols (first, n) (None: all of the database);
+        returns (tile pairs walked, tile pairs skipped) of this call, or None with stats=False (a NULL stats)"""
+        r0, nr = (0, self.db_size()) if rows is None else rows
+        c0, nc = (0, self.db_size()) if cols is None else cols
+        st = (C.c_ulonglong * 2)(0, 0)
+        self._chk(self.L.uvaia_gpu_db_near(self.ctx, int(r0), int(nr), int(c0), int(nc), st if stats else None))
+        return (int(st[0]), int(st[1])) if stats else None
+
+    def db_near_fetch(self):
+        """uint64 [db_size]: dist << 32 | position of every reference's closest reference of another component so far, or NEAR_NONE"""
+        best = np.zeros(self.db_size(), dtype=np.uint64)
+        self._chk(self.L.uvaia_gpu_db_near_fetch(self.ctx, best.ctypes.data if best.size else None))
+        return best
+
+    def db_mst(self, trim=0, metric=DIST_SNP, min_compared=0):
+        """(records of EDGE_DTYPE sorted by (dist, a, b), rounds): the minimum spanning forest of the resident database"""
+        edges = np.zeros(max(self.db_size() - 1, 0), dtype=EDGE_DTYPE)
+        n, rounds = C.c_size_t(0), C.c_int(0)
+        self._chk(self.L.uvaia_gpu_db_mst(self.ctx, int(trim), int(metric), int(min_compared), edges.ctypes.data if edges.size else None, C.byref(n), C.byref(rounds)))
+        return edges[:n.value], int(rounds.value)
+
+    def near_ms(self, reset=False):
+        out = C.c_double(0.)
+        self.L.uvaia_gpu_near_ms(self.ctx, C.byref(out), int(reset))
+        return float(out.value)
+
+    def near_tiles(self, reset=False):
+        """(tile pairs walked, tile pairs skipped) by every db_near since the last reset, those of db_mst included"""
+        out = (C.c_ulonglong * 2)(0, 0)
+        self.L.uvaia_gpu_near_tiles(self.ctx, out, int(reset))
+        return int(out[0]), int(out[1])
 
     def rows_set_run_cut(self, cut):
         self._chk(self.L.uvaia_gpu_rows_set_run_cut(self.ctx, int(cut)))

@@ -4,7 +4,9 @@
  * matches, not distances").  The counters of every pair are taken on the GPU over the bit planes the engine keeps resident
  * (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within); this file loads the rows, asks for the matrix in bands of rows and writes a band as
  * text while the next is computed.  `-d D --clusters` asks for no pairs at all: the engine unites the pairs within D on the device
- * (uvaia_gpu_db_link_*) and hands back one label per sequence.  Own code.
+ * (uvaia_gpu_db_link_*) and hands back one label per sequence.  `--mst` and `--nearest` ask for none either: the engine keeps every
+ * sequence's closest sequence of another component on the device (uvaia_gpu_db_near_*) and builds the minimum spanning tree around that
+ * (uvaia_gpu_db_mst); N numbers come back.  Own code.
  *
  *   snp   = both ACGT and different (what snp-dists prints)        uvaia = valid_pair_comparisons - partial_matches (README, line 302)
  */
@@ -37,6 +39,7 @@ usage (const char *prog)
   printf ("All-pairs distance matrix of aligned sequences, counted on the GPU over the packed bit planes.\n\n");
   printf (" %s [-hv] [--metric=snp|uvaia] [--trim=<int>] [-A <double>] [--long | --counts] [-d <int>] [--csv]\n", prog);
   printf ("          [--clusters [--min-compared=<int>] [--min-size=<int>]] [--band-rows=<int>] [--device=<int>] (-o <file> | --stdout)\n");
+  printf ("          [(--mst | --nearest) [--min-compared=<int>]]\n");
   printf ("          (--packed <db.uvdb> [--packed <db.uvdb>]... | <aln.fa(.gz,.xz)> [<aln.fa(.gz,.xz)>]...)\n\n");
   printf ("  --metric=snp|uvaia               snp (default): sites where both sequences are one of ACGT and differ, the number snp-dists prints;\n");
   printf ("                                   uvaia: valid_pair_comparisons - partial_matches, sites where both are valid and their IUPAC sets do not meet\n");
@@ -49,7 +52,15 @@ usage (const char *prog)
   printf ("                                   input order; two sequences are linked when their distance is <= -d, a cluster is a connected set, clusters\n");
   printf ("                                   are numbered 1, 2, ... by their first member.  Under snp a sequence with no ACGT site is at distance 0 from\n");
   printf ("                                   every other and joins all clusters into one: set --min-compared against that\n");
+  printf ("  --mst                            the minimum spanning tree instead of the table, one line `a<tab>b<tab>dist` per edge, sorted by distance, then by\n");
+  printf ("                                   the input order of a (the earlier sequence of the two), then of b.  Ties between edges are decided by that same\n");
+  printf ("                                   order, so the tree is unique; its edges up to a distance D join exactly the clusters of -d D --clusters\n");
+  printf ("  --nearest                        every sequence's closest other sequence instead of the table, one line `sequence<tab>nearest<tab>dist` per sequence\n");
+  printf ("                                   in input order; ties go to the earliest sequence; with no comparable partner the nearest is empty and dist -1\n");
+  printf ("                                   Under snp a sequence with no ACGT site is at distance 0 from every other: it is the hub of the tree and\n");
+  printf ("                                   everyone's nearest.  Set --min-compared against that (the tree may then be a forest)\n");
   printf ("  --min-compared=<int>             with --clusters: link only pairs compared over at least <int> sites (snp: both ACGT; uvaia: both valid; default=0)\n");
+  printf ("                                   with --mst, --nearest: only such pairs are edges, or can be nearest\n");
   printf ("  --min-size=<int>                 with --clusters: leave out the sequences of clusters smaller than <int> (default=1; the numbering does not change)\n");
   printf ("  --csv                            commas instead of tabs in the square table and the cluster lines\n");
   printf ("  --band-rows=<int>                rows of the matrix computed at a time (default: what keeps a band near 256 MiB)\n");
@@ -270,14 +281,15 @@ main (int argc, char **argv)
   double ambig = 1.;
   const char *out = NULL, *metric_name = "snp";
   char **packed = (char **) biomcmc_malloc ((size_t) (argc + 1) * sizeof (char *));
-  int n_packed = 0, device = -1, ch, errors = 0, want_long = 0, want_counts = 0, want_dense = 0, have_d = 0, max_dist = 0, csv = 0, to_stdout = 0, want_clusters = 0, have_min_compared = 0, have_min_size = 0;
+  int n_packed = 0, device = -1, ch, errors = 0, want_long = 0, want_counts = 0, want_dense = 0, have_d = 0, max_dist = 0, csv = 0, to_stdout = 0, want_clusters = 0, have_min_compared = 0, have_min_size = 0, want_mst = 0, want_nearest = 0;
   long trim = 0, band_rows = 0, min_compared = 0, min_size = 1;
   size_t list_cap = LIST_CAP0;
   static const struct option longopts[] = {{"help", no_argument, 0, 'h'}, {"version", no_argument, 0, 'v'}, {"ref_ambiguity", required_argument, 0, 'A'},
     {"output", required_argument, 0, 'o'}, {"trim", required_argument, 0, 't'}, {"metric", required_argument, 0, 1001}, {"device", required_argument, 0, 1002},
     {"long", no_argument, 0, 1003}, {"counts", no_argument, 0, 1004}, {"csv", no_argument, 0, 1005}, {"band-rows", required_argument, 0, 1006},
     {"stdout", no_argument, 0, 1007}, {"packed", required_argument, 0, 1008}, {"list-cap", required_argument, 0, 1009}, {"dense", no_argument, 0, 1010},
-    {"clusters", no_argument, 0, 1011}, {"min-compared", required_argument, 0, 1012}, {"min-size", required_argument, 0, 1013}, {0, 0, 0, 0}};
+    {"clusters", no_argument, 0, 1011}, {"min-compared", required_argument, 0, 1012}, {"min-size", required_argument, 0, 1013},
+    {"mst", no_argument, 0, 1014}, {"nearest", no_argument, 0, 1015}, {0, 0, 0, 0}};
   while ((ch = getopt_long (argc, argv, "hvA:o:t:d:", longopts, NULL)) != -1) switch (ch) {
     case 'h': usage (basename (argv[0])); return EXIT_SUCCESS;
     case 'v': printf ("%s\n", UVAIA_PACKAGE_VERSION); return EXIT_SUCCESS;
@@ -298,6 +310,8 @@ main (int argc, char **argv)
     case 1011: want_clusters = 1; break;
     case 1012: have_min_compared = 1; min_compared = atol (optarg); break;
     case 1013: have_min_size = 1; min_size = atol (optarg); break;
+    case 1014: want_mst = 1; break;
+    case 1015: want_nearest = 1; break;
     default: errors++;
   }
   /* what does not go together is refused here, before a file is opened or a GPU touched */
@@ -305,6 +319,16 @@ main (int argc, char **argv)
   if (!strcmp (metric_name, "snp")) metric = UVAIA_GPU_DIST_SNP;
   else if (!strcmp (metric_name, "uvaia")) metric = UVAIA_GPU_DIST_UVAIA;
   else { fprintf (stderr, "unknown metric '%s': --metric takes snp or uvaia\n", metric_name); return EXIT_FAILURE; }
+  if (want_mst && want_nearest) { fprintf (stderr, "--mst and --nearest are two forms of the output: give one\n"); return EXIT_FAILURE; }
+  if (want_mst || want_nearest) {
+    const char *me = want_mst ? "--mst" : "--nearest", *writes = want_mst ? "one line per edge of the tree" : "one line per sequence";
+    if (have_d) { fprintf (stderr, "%s does not go with -d: it looks at every pair, whatever its distance\n", me); return EXIT_FAILURE; }
+    if (want_clusters) { fprintf (stderr, "%s does not go with --clusters: it writes %s, not clusters\n", me, writes); return EXIT_FAILURE; }
+    if (want_long) { fprintf (stderr, "%s does not go with --long: it writes %s, not per pair\n", me, writes); return EXIT_FAILURE; }
+    if (want_counts) { fprintf (stderr, "%s does not go with --counts: it writes %s, not per pair\n", me, writes); return EXIT_FAILURE; }
+    if (want_dense) { fprintf (stderr, "%s does not go with --dense: it writes %s, not a table\n", me, writes); return EXIT_FAILURE; }
+    if (have_min_size) { fprintf (stderr, "%s does not go with --min-size: there are no clusters to leave out\n", me); return EXIT_FAILURE; }
+  }
   if (want_long && want_counts) { fprintf (stderr, "--long and --counts are two forms of the output: give one\n"); return EXIT_FAILURE; }
   if (want_dense && (want_long || want_counts)) { fprintf (stderr, "--dense does not go with --long or --counts\n"); return EXIT_FAILURE; }
   if (want_clusters && want_long) { fprintf (stderr, "--clusters does not go with --long: it writes one line per sequence, not per pair\n"); return EXIT_FAILURE; }
@@ -313,7 +337,8 @@ main (int argc, char **argv)
   if (have_d && want_dense) { fprintf (stderr, "-d needs a long form (--long or --counts): a square table has a cell for every pair\n"); return EXIT_FAILURE; }
   if (have_d && max_dist < 0) { fprintf (stderr, "-d takes a distance of 0 or more\n"); return EXIT_FAILURE; }
   if (want_clusters && !have_d) { fprintf (stderr, "--clusters needs -d: clusters are the sequences connected by pairs within a distance\n"); return EXIT_FAILURE; }
-  if (have_min_compared && !want_clusters) { fprintf (stderr, "--min-compared needs --clusters: it decides which pairs link two sequences\n"); return EXIT_FAILURE; }
+  const int want_tree = want_mst || want_nearest;
+  if (have_min_compared && !want_clusters && !want_tree) { fprintf (stderr, "--min-compared needs --clusters: it decides which pairs link two sequences\n"); return EXIT_FAILURE; }
   if (have_min_size && !want_clusters) { fprintf (stderr, "--min-size needs --clusters: it leaves out the sequences of small clusters\n"); return EXIT_FAILURE; }
   if (min_compared < 0 || min_compared > INT_MAX) { fprintf (stderr, "--min-compared takes a number of 0 or more\n"); return EXIT_FAILURE; }
   if (min_size < 0) { fprintf (stderr, "--min-size takes a number of 0 or more\n"); return EXIT_FAILURE; }
@@ -324,7 +349,7 @@ main (int argc, char **argv)
   if (errors || (!n_packed && optind >= argc)) { printf ("Error when reading arguments from command line:\n"); usage (basename (argv[0])); return EXIT_FAILURE; }
   if (ambig < 0.001) ambig = 0.001;
   if (ambig > 1.) ambig = 1.;
-  const int form = want_counts ? FORM_COUNTS : (want_long || have_d) ? FORM_LONG : FORM_DENSE;
+  const int form = want_counts ? FORM_COUNTS : (want_long || have_d || want_tree) ? FORM_LONG : FORM_DENSE;      /* (--mst, --nearest: no header) */
   if (omp_get_max_threads () > MAX_THREADS) omp_set_num_threads (MAX_THREADS);
 
   int64_t time0[2];
@@ -357,9 +382,57 @@ main (int argc, char **argv)
   }
   sink_write (&snk, &head);
 
-  unsigned long long n_links = 0;
-  size_t n_clusters = 0, largest = 0;
-  if (want_clusters && n) {
+  unsigned long long n_links = 0, tiles[2] = {0, 0};
+  size_t n_clusters = 0, largest = 0, n_edges = 0;
+  long long weight = 0;
+  int n_rounds = 0;
+  if (want_mst && n) {
+    /* the tree: the engine's rounds hand back at most n - 1 edges, sorted as they are written */
+    uvaia_gpu_edge *edge = (uvaia_gpu_edge *) biomcmc_malloc (n * sizeof (uvaia_gpu_edge));
+    if (uvaia_gpu_db_mst (gpu, (size_t) trim, metric, (int) min_compared, edge, &n_edges, &n_rounds)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    uvaia_gpu_near_tiles (gpu, tiles, 0);
+    t0 = now_ms ();
+    textbuf t = {NULL, 0, 0};
+    for (size_t k = 0; k < n_edges; k++) {
+      const uvaia_gpu_edge *e = edge + k;
+      if (e->a >= e->b || e->b >= n) biomcmc_error ("the engine handed back the edge %u - %u of %zu sequences", e->a, e->b, n);
+      weight += e->dist;
+      text_room (&t, name_len[e->a] + name_len[e->b] + 2 * 12);
+      text_bytes (&t, rows.name[e->a], name_len[e->a]); t.p[t.n++] = sep;
+      text_bytes (&t, rows.name[e->b], name_len[e->b]); t.p[t.n++] = sep;
+      text_int (&t, e->dist); t.p[t.n++] = '\n';
+      if (t.n > ((size_t) 1 << 24)) { format_ms += now_ms () - t0; sink_write (&snk, &t); t0 = now_ms (); }
+    }
+    format_ms += now_ms () - t0;
+    sink_write (&snk, &t);
+    free (t.p); free (edge);
+  } else if (want_nearest && n) {
+    /* one pass with every sequence a component of its own: a band of rows against all columns at a time, the keys come back once */
+    const size_t band = band_rows ? (size_t) band_rows : 4096;
+    if (uvaia_gpu_db_near_begin (gpu, (size_t) trim, metric, (int) min_compared)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    for (size_t r0 = 0; r0 < n; r0 += band, n_bands++)
+      if (uvaia_gpu_db_near (gpu, r0, n - r0 < band ? n - r0 : band, 0, n, tiles)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    n_rounds = 1;
+    uint64_t *best = (uint64_t *) biomcmc_malloc (n * sizeof (uint64_t));
+    if (uvaia_gpu_db_near_fetch (gpu, best)) biomcmc_error ("%s", uvaia_gpu_last_error (gpu));
+    t0 = now_ms ();
+    textbuf t = {NULL, 0, 0};
+    for (size_t i = 0; i < n; i++) {
+      const int none = best[i] == UVAIA_GPU_NEAR_NONE;
+      const size_t y = none ? 0 : (size_t) (best[i] & 0xFFFFFFFFu);
+      if (!none && (y >= n || y == i)) biomcmc_error ("the engine named sequence %zu as the nearest of sequence %zu of %zu", y, i, n);
+      if (!none) { n_edges++; weight += (long long) (best[i] >> 32); }
+      text_room (&t, name_len[i] + (none ? 0 : name_len[y]) + 2 * 12);
+      text_bytes (&t, rows.name[i], name_len[i]); t.p[t.n++] = sep;
+      if (!none) text_bytes (&t, rows.name[y], name_len[y]);
+      t.p[t.n++] = sep;
+      text_int (&t, none ? -1 : (int) (best[i] >> 32)); t.p[t.n++] = '\n';
+      if (t.n > ((size_t) 1 << 24)) { format_ms += now_ms () - t0; sink_write (&snk, &t); t0 = now_ms (); }
+    }
+    format_ms += now_ms () - t0;
+    sink_write (&snk, &t);
+    free (t.p); free (best);
+  } else if (want_clusters && n) {
     /* clusters: a band of rows against all columns is linked on the device, nothing but the count of links comes back per band; the labels
      * (smallest member of every sequence's cluster) come back once, and are numbered here by first member */
     const size_t band = band_rows ? (size_t) band_rows : 4096;
@@ -476,10 +549,22 @@ main (int argc, char **argv)
 
   double ms[3] = {0., 0., 0.};
   uvaia_gpu_pairs_ms (gpu, ms, 0);
-  fprintf (stderr, want_clusters ? "Wrote the %s clusters of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n"
+  fprintf (stderr, want_mst ? "Wrote the %s minimum spanning tree of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n"
+                 : want_nearest ? "Wrote the %s nearest sequence of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n"
+                 : want_clusters ? "Wrote the %s clusters of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n"
                                  : "Wrote the %s distances of %zu of %zu sequences (%d sites, trim %ld) to %s in %.3lf secs.\n", metric_name, n, rows.count, rows.nchar, trim,
            out ? out : "standard output", biomcmc_update_elapsed_time (time0));
-  if (want_clusters) {
+  if (want_mst) {
+    double near_ms = 0.;
+    uvaia_gpu_near_ms (gpu, &near_ms, 0);
+    fprintf (stderr, "dist report: {\"sequences\": %zu, \"edges\": %zu, \"trees\": %zu, \"rounds\": %d, \"weight\": %lld, \"tiles_walked\": %llu, \"tiles_skipped\": %llu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",
+             n, n_edges, n - n_edges, n_rounds, weight, tiles[0], tiles[1], rows.load_ms, ms[0] + near_ms, format_ms, snk.write_ms);
+  } else if (want_nearest) {
+    double near_ms = 0.;
+    uvaia_gpu_near_ms (gpu, &near_ms, 0);
+    fprintf (stderr, "dist report: {\"sequences\": %zu, \"nearest\": %zu, \"rounds\": %d, \"weight\": %lld, \"tiles_walked\": %llu, \"tiles_skipped\": %llu, \"bands\": %zu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",
+             n, n_edges, n_rounds, weight, tiles[0], tiles[1], n_bands, rows.load_ms, ms[0] + near_ms, format_ms, snk.write_ms);
+  } else if (want_clusters) {
     double link_ms = 0.;
     uvaia_gpu_link_ms (gpu, &link_ms, 0);
     fprintf (stderr, "dist report: {\"sequences\": %zu, \"links\": %llu, \"clusters\": %zu, \"largest\": %zu, \"bands\": %zu, \"load_ms\": %.3f, \"kernel_ms\": %.3f, \"format_ms\": %.3f, \"write_ms\": %.3f}\n",

@@ -219,6 +219,13 @@ struct uvaia_gpu_ctx {
     // `begin` was given, and the database it was given for (links are refused once db_gen has moved on)
     DevBuf<uint32_t> d_parent, d_labels; double link_ms = 0.;      // device time of the link and label kernels
     struct { bool begun = false; unsigned long long db_gen = 0; size_t n = 0, trim = 0; int metric = 0, max_dist = 0, min_compared = 0; } link;
+    // closest reference of another component (uvaia_gpu_db_near_*, uvaia_gpu_db_mst): 12 bytes per reference resident at `begin` -- the
+    // packed keys and the components -- the two counters of tile pairs, and the host's copy of the components (it decides which launches
+    // are skipped whole)
+    DevBuf<unsigned long long> d_best, d_near_stats; DevBuf<uint32_t> d_comp; double near_ms = 0.;  // device time of the near kernels
+    unsigned long long near_tiles[2] = {0, 0};         // tile pairs walked, skipped since the last reset
+    std::vector<uint32_t> h_comp;
+    struct { bool begun = false; unsigned long long db_gen = 0; size_t n = 0, trim = 0; int metric = 0, min_compared = 0; } near;
   } pairs;
   // last batch (introspection)
   struct { const TileStore *store = nullptr; long long tile_first = 0; int n_tiles = 0, n = 0, rbegin = 0, ppad = 0; const int4 *rt = nullptr; } last;

@@ -1,4 +1,4 @@
-// kernels_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within): pairs_rows_kernel builds the row-side operand records of a band of rows, pairs_snp_kernel and pairs_counts_kernel count every (row, column) pair of a rectangle, the latter also into a list of the pairs within a distance; pairs_link_snp_kernel and the link mode of pairs_counts_kernel unite the pairs within a distance in a union-find forest instead (uvaia_gpu_db_link), pairs_labels_kernel reads the cluster labels off it.
+// kernels_pairs.inc -- part of uvaia_gpu.hip (included there, not a translation unit of its own): all pairs of the resident database against each other (uvaia_gpu_db_pairs, uvaia_gpu_db_pairs_within): pairs_rows_kernel builds the row-side operand records of a band of rows, pairs_snp_kernel and pairs_counts_kernel count every (row, column) pair of a rectangle, the latter also into a list of the pairs within a distance; pairs_link_snp_kernel and the link mode of pairs_counts_kernel unite the pairs within a distance in a union-find forest instead (uvaia_gpu_db_link), pairs_labels_kernel reads the cluster labels off it; pairs_near_snp_kernel and the near mode of pairs_counts_kernel keep every reference's closest reference of another component instead (uvaia_gpu_db_near, uvaia_gpu_db_mst).
 
 // ------------------------------------------------------------------------------------------------------------
 // device: all-pairs counters over the resident four-plane tiles
@@ -257,6 +257,143 @@ __global__ __launch_bounds__(256) void pairs_link_snp_kernel(const uint4 *__rest
   pairs_link_hits(parent, n_links, (uint32_t)(row0 + rt * RT), (uint32_t)col, hits, total, lane);
 }
 
+// ---- every reference's closest reference of another component (uvaia_gpu_db_near_* / uvaia_gpu_db_mst)
+// comp[] holds one dword per resident reference, written by a copy or by pairs_near_init_kernel BEFORE the launch and only read by it: plain
+// loads.  best[] holds one packed key (dist << 32 | other position) per reference, UVAIA_GPU_NEAR_NONE at the start.  While near kernels run
+// the ONLY stores to best[] are agent-scope 64-bit atomicMins; nothing waits for another wave, no flag is spun on, no fence is issued.
+// Why that is enough where the per-XCD L2s and per-CU L1s are not coherent within a launch:
+//   - best[x] only ever decreases, and every value it holds is NONE or the key of a counting pair of x, so whatever order the atomicMins
+//     of the waves, launches and calls arrive in, the cell ends as the minimum of the keys offered: a function of the rows and comp[] alone;
+//   - the guard in front of an atomicMin is a relaxed agent-scope load; a stale value is one the cell held EARLIER, that is a larger one:
+//     the guard then lets an atomicMin through that changes nothing.  It can never hold one back that would have lowered the cell;
+//   - the host reads best[] behind the stream, after the last kernel has ended.
+// Ties: the key orders by (dist, other position), and a candidate is already the smallest of its wave under that order -- the column side
+// keeps the first of ascending rows by a strict <, the row side takes the lowest lane of the ballot of the wave's minimum.
+constexpr uint32_t PAIRS_NEAR_NO = 0xFFFFFFFFu;        // no counting pair yet: above every distance (a distance is a number of sites)
+
+static __device__ __forceinline__ uint32_t pairs_wave_umin(uint32_t v)
+{ // the minimum over the 64 lanes, wave-uniform (every lane is active where this is called)
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) v = min(v, (uint32_t)__shfl_xor((int)v, s));
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+static __device__ __forceinline__ void pairs_near_lower(unsigned long long *p, unsigned long long key)
+{ // (a stale, larger value costs an atomic and never the answer)
+  if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(p, key);
+}
+
+// What a wave carries from the prologue to the epilogue, and the epilogue's running minima.  RT rows x 64 columns: lane = column, lanes
+// 0 .. RT - 1 also hold the row side (comp of row `lane` of the tile, and at the end that row's candidate).
+template <int RT> struct PairsNear {
+  uint32_t cc, rc;                                     // comp[col] of this lane; comp[row_first + lane] in lanes below RT
+  uint32_t cd = PAIRS_NEAR_NO, crow = 0;               // column side: the smallest (dist, row) of this lane's column
+  uint32_t rd = PAIRS_NEAR_NO, rcol = 0;               // row side, lane r: the smallest (dist, lane of the column) of row r
+  long long row_first, col; int rows_here, lane; bool col_ok;
+
+  // Prologue.  true: every row and column of the tile pair that is in range carries one comp (rows and columns out of range count as
+  // "same"), so no pair of it can count and the wave returns before the loop.  Wave-uniform: ballots and a readlane.  One lane adds the
+  // tile pair to stats[0] (walked) or stats[1] (skipped) by one vector atomicAdd.
+  __device__ __forceinline__ bool same(const uint32_t *__restrict__ comp, unsigned long long *__restrict__ stats)
+  {
+    const bool row_ok = lane < RT && lane < rows_here;
+    cc = col_ok ? comp[col] : 0u;
+    rc = row_ok ? comp[row_first + lane] : 0u;
+    const unsigned long long vc = __ballot(col_ok), vr = __ballot(row_ok);
+    bool one = true;
+    if (vc && vr) {
+      const uint32_t ref = (uint32_t)__builtin_amdgcn_readlane((int)cc, __ffsll((long long)vc) - 1);
+      one = __ballot((col_ok && cc != ref) || (row_ok && rc != ref)) == 0ull;
+    }
+    if (lane == 0) atomicAdd(stats + (one ? 1 : 0), 1ull);
+    return one;
+  }
+
+  // Epilogue, row r of the tile (r a constant of the unrolled loop, rows ascend): a pair counts when row and column are in range,
+  // row < col (database positions), the two comp differ and `floor_ok`.
+  __device__ __forceinline__ void row(int r, int dist, bool floor_ok)
+  {
+    const uint32_t rcr = (uint32_t)__builtin_amdgcn_readlane((int)rc, r);
+    const bool counts = col_ok && r < rows_here && row_first + r < col && rcr != cc && floor_ok;
+    const uint32_t key = counts ? (uint32_t)dist : PAIRS_NEAR_NO;
+    if (key < cd) { cd = key; crow = (uint32_t)(row_first + r); }
+    const uint32_t m = pairs_wave_umin(key);
+    if (m != PAIRS_NEAR_NO) {                          // (wave-uniform)
+      const unsigned long long holders = __ballot(key == m);      // lanes ascend with the column: the lowest bit is the smallest column
+      if (lane == r) { rd = m; rcol = (uint32_t)(__ffsll((long long)holders) - 1); }
+    }
+  }
+
+  __device__ __forceinline__ void flush(unsigned long long *best)
+  {
+    if (cd != PAIRS_NEAR_NO) pairs_near_lower(best + col, ((unsigned long long)cd << 32) | crow);
+    if (lane < RT && rd != PAIRS_NEAR_NO) pairs_near_lower(best + row_first + lane, ((unsigned long long)rd << 32) | (uint32_t)(col - lane + rcol));
+  }
+};
+
+// best[i] = NONE for the references resident at uvaia_gpu_db_near_begin, and with `identity` every reference a component of its own
+__global__ __launch_bounds__(256) void pairs_near_init_kernel(unsigned long long *__restrict__ best, uint32_t *__restrict__ comp, uint32_t n, int identity)
+{
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  best[i] = ~0ull;
+  if (identity) comp[i] = i;
+}
+
+// Every row's and column's closest reference of another component among RT = 32 rows x 64 columns per wave under the snp metric: the loop of
+// pairs_link_snp_kernel -- same operand records, same grid order, row operands in SGPRs, 4 vector instructions per pair-word, 6 with
+// FLOOR -- between the prologue and the epilogue of PairsNear.  Nothing dense is written.
+template <bool FLOOR>
+__global__ __launch_bounds__(256) void pairs_near_snp_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, long long row0, int n_rows, int n_rtiles,
+                                                              long long ctile0, int n_ctiles, long long col0, int n_cols, int min_compared,
+                                                              const uint32_t *__restrict__ comp, unsigned long long *best, unsigned long long *__restrict__ stats)
+{
+  constexpr int RT = 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rt = blockIdx.x % n_rtiles, ct = (blockIdx.x / n_rtiles) * 4 + wave;
+  if (ct >= n_ctiles) return;
+  PairsNear<RT> near;
+  near.col = (ctile0 + ct) * 64 + lane; near.col_ok = near.col >= col0 && near.col - col0 < n_cols;
+  near.row_first = row0 + (long long)rt * RT; near.rows_here = n_rows - rt * RT; near.lane = lane;
+  if (near.same(comp, stats)) return;
+  int acc[RT], cmp[FLOOR ? RT : 1];
+#pragma unroll
+  for (int r = 0; r < RT; r++) { acc[r] = 0; if (FLOOR) cmp[r] = 0; }
+  const uint4 *t = db + (size_t)(ctile0 + ct) * W4 * 4 * 64 + lane;
+  const size_t rstride = (size_t)W4 * PAIRS_SNP_DW;
+  const uint32_t *rb = rec + (size_t)rt * RT * rstride;
+  for (int w4 = 0; w4 < W4; w4++) {
+    const uint4 pA = t[(size_t)(w4 * 4 + 0) * 64], pC = t[(size_t)(w4 * 4 + 1) * 64], pG = t[(size_t)(w4 * 4 + 2) * 64], pT = t[(size_t)(w4 * 4 + 3) * 64];
+    uint32_t cL[4], cH[4], cI[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t a = u4c(pA, j), cc = u4c(pC, j), g = u4c(pG, j), tt = u4c(pT, j);
+      const uint32_t par = a ^ cc ^ g ^ tt, three = (a & cc & (g | tt)) | (g & tt & (a | cc));
+      cI[j] = par & ~three; cL[j] = (cc | tt) & cI[j]; cH[j] = (g | tt) & cI[j];
+    }
+    const uint32_t *s0 = rb + (size_t)w4 * PAIRS_SNP_DW;
+    QWords<PAIRS_SNP_DW> cur, nxt;
+    load_qwords(cur, s0);
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      if (r + 1 < RT) load_qwords(nxt, s0 + (size_t)(r + 1) * rstride);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t x = cL[j] ^ cur.v[j];
+        const uint32_t y = B3(cH[j], cur.v[4 + j], x, (TT_A ^ TT_B) | TT_C);          // codes differ
+        acc[r] = bcnt_acc(B3(y, cI[j], cur.v[8 + j], TT_A & TT_B & TT_C), acc[r]);
+        if (FLOOR) cmp[r] = bcnt_acc(cI[j] & cur.v[8 + j], cmp[r]);                   // both ACGT
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (r + 1 < RT) cur = nxt;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RT; r++) near.row(r, acc[r], !FLOOR || cmp[r] >= min_compared);
+  near.flush(best);
+}
+
 // The five counters of PAIRS_CNT_RT rows x 64 columns per wave, same mapping and grid order as pairs_snp_kernel; the plane-equality and
 // intersect chains of scan_iupac_kernel plus one `single & single'` count: 17 vector instructions per pair-word.
 // MODE = PAIRS_DENSE: out[(i * ld_out + (col - col0)) * 5 + c].
@@ -265,17 +402,25 @@ __global__ __launch_bounds__(256) void pairs_link_snp_kernel(const uint4 *__rest
 // many slots by one vector atomicAdd on *n_list, and every store is bounded by list_cap -- *n_list ends as the number of hits, whatever fitted.
 // MODE = PAIRS_LINK: nothing dense and no list; the pairs row < col with distance <= max_dist and, under the same metric, compared
 // (count[4] under metric 1, count[3] under metric 2) >= min_compared are united in parent[] and counted into *n_list (pairs_link_hits).
-enum { PAIRS_DENSE = 0, PAIRS_LIST = 1, PAIRS_LINK = 2 };
+// MODE = PAIRS_NEAR: nothing dense, no list, no forest; the prologue and epilogue of PairsNear around the same loop, over that distance and
+// that compared: `parent` is comp[] (only read), `n_list` the two counters of tile pairs walked and skipped, `best` the keys.
+enum { PAIRS_DENSE = 0, PAIRS_LIST = 1, PAIRS_LINK = 2, PAIRS_NEAR = 3 };
 template <int MODE>
 __global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restrict__ db, int W4, const uint32_t *__restrict__ rec, long long row0, int n_rows, int n_rtiles,
                                                             long long ctile0, int n_ctiles, long long col0, int n_cols, int *__restrict__ out, size_t ld_out,
                                                             int metric, int max_dist, int upper, uvaia_gpu_pair *__restrict__ list, unsigned long long list_cap,
-                                                            unsigned long long *__restrict__ n_list, int min_compared, uint32_t *parent)
+                                                            unsigned long long *__restrict__ n_list, int min_compared, uint32_t *parent, unsigned long long *best)
 {
   constexpr int RT = PAIRS_CNT_RT;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int rt = blockIdx.x % n_rtiles, ct = (blockIdx.x / n_rtiles) * 4 + wave;
   if (ct >= n_ctiles) return;
+  PairsNear<RT> near;
+  if (MODE == PAIRS_NEAR) {
+    near.col = (ctile0 + ct) * 64 + lane; near.col_ok = near.col >= col0 && near.col - col0 < n_cols;
+    near.row_first = row0 + (long long)rt * RT; near.rows_here = n_rows - rt * RT; near.lane = lane;
+    if (near.same(parent, n_list)) return;
+  }
   int acc[RT][5];
 #pragma unroll
   for (int r = 0; r < RT; r++) { acc[r][0] = acc[r][1] = acc[r][2] = acc[r][3] = acc[r][4] = 0; }
@@ -347,6 +492,14 @@ __global__ __launch_bounds__(256) void pairs_counts_kernel(const uint4 *__restri
       hits |= (uint32_t)h << r;
     }
     pairs_link_hits(parent, n_list, (uint32_t)(row0 + rt * RT), (uint32_t)col, hits, total, lane);
+  } else if (MODE == PAIRS_NEAR) {
+#pragma unroll
+    for (int r = 0; r < RT; r++) {
+      const bool snp = metric == UVAIA_GPU_DIST_SNP;
+      const int c0 = acc[r][0], c2 = acc[r][2], c3 = acc[r][3], c4 = acc[r][4];      // (read first, as the link mode does)
+      near.row(r, snp ? c4 - c0 : c3 - c2, (snp ? c4 : c3) >= min_compared);
+    }
+    near.flush(best);
   } else {
     auto hit = [&](int r) {
       const int i = rt * RT + r;

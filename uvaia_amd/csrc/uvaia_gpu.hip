@@ -26,8 +26,10 @@
 #include <cstring>
 #include <functional>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/uvaia_gpu.h"
